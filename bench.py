@@ -2,6 +2,7 @@
 """Headline benchmark: AAE training docs/sec at |items|=100k, hidden=200 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--items N] [--hidden H] [--dtype f32|bf16]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one AdversarialAutoEncoder.partial_fit (ae_step + disc_step + gen_step with all four optimiser
 updates, reference aaerec/aae.py:745-766) over one batch of B synthetic docs per GPU, driven by the epoch loop of
@@ -14,7 +15,14 @@ N > 1: one process per GPU over RCCL.  Either the caller launches the ranks
 them itself (before anything touches the GPU) and relays rank 0's line.  Every rank processes B docs per step (weak
 scaling): the global batch of N * B rows is sharded over the ranks by AdversarialAutoEncoder(data_parallel=...).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the kernel that takes the most time in the step, from hipEvent
+A plain run sets up, runs W warm-up steps, times K steps (one timed region, `ms_per_step` = its time / K) and prints
+the result line; nothing else is measured.  Everything below comes with `--full` only (which also times the default
+repeats of K steps, see --repeats, and reports their median).  `--dump-outputs DIR` writes what the timed path hands
+its caller after its last timed step (the step's losses and the model's parameters, see dump_outputs) as DIR/*.npy;
+the corpus, the initial weights, the epoch permutations and the device generator are seeded, so that the same
+arguments give the same inputs on every run.
+
+Rank 0 prints ONE JSON line.  With --full: `roofline` is for the kernel that takes the most time in the step, from hipEvent
 pairs recorded around its launches inside the timed region; `cpu_baseline` is the PyTorch-CPU dense port of the
 reference step (oracle/dense_torch_port.py) timed on this box's host cores over a bounded sample of the same
 workload (N = 1 only); `extra.b512` is the MFMA-bound batch-512 variant of the same configuration (N = 1, f32),
@@ -55,8 +63,16 @@ def parse():
                          "with fp32 accumulation, fp32 master weights and fp32 Adam (config C2)")
     ap.add_argument("--cond-inc", type=int, default=0, help="width of a constant concatenated condition block (config C4: 300)")
     ap.add_argument("--median-len", type=int, default=20, help="median items per synthetic doc")
-    ap.add_argument("--repeats", type=int, default=0, help="timed repeats of K steps, the median is reported (0 = auto: 15 for a region under 20 ms, 5 when "
-                                                           "K steps take well under a second, else 1)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed repeats of K steps, the median is reported (0 = auto: 1 in a plain run; with "
+                                                           "--full 15 for a region under 20 ms, 5 when K steps take well under a second, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: per-kernel timings and rooflines, raw_step, the extra "
+                         "configurations (b512, C2 bf16, C4, C5 on one GPU, predict top-k), the CPU baseline; N > 1: the "
+                         "collectives breakdown and the other data-parallel scheme")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's losses and the model's parameters (vocabulary-wide "
+                         "layers: a fixed sample of items) as DIR/<name>.npy, float32 (with --full, give --repeats as well: "
+                         "its default follows the time of the first repeat, and so would the number of steps before the dump)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the batch-512 extra line")
@@ -211,6 +227,39 @@ def timed_steps(it, k, barrier):
     return time.perf_counter() - t0
 
 
+DUMP_ITEMS = 2048            # --dump-outputs: items of the fixed sample of the vocabulary-wide layers
+DUMP_MAX_ELEMS = 1 << 19     # ... and of any other array (a fixed sample of its elements beyond that): 18 arrays, < 40 MB
+VOCAB_WIDE = ("enc.lin1.weight", "dec.lin3.weight", "dec.lin3.bias")
+
+
+def dump_outputs(path, model, losses, n_items, rank):
+    """--dump-outputs: what the timed path hands its caller after its last step - the step's losses (recon, disc, gen) and
+    the model partial_fit returns, i.e. its parameters - as <path>/<name>.npy in float32.  The vocabulary-wide layers are
+    written for a fixed, seeded sample of DUMP_ITEMS items (their rows / columns), any other array over DUMP_MAX_ELEMS
+    elements as a fixed, seeded sample of its elements.  Under a vocabulary-sharded scheme (N > 1) the vocabulary-wide
+    layers live in item slices on the ranks and are left out, and the hidden layers come from the handle that trains them
+    (the one _losses() reads).  Every rank calls this; rank 0 writes."""
+    model._dp_settle()
+    sliced = model._slice is not None
+    params = (model._slice if sliced and model.dp_mode == "shard" else model.hip).state_dict()
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    items = np.sort(np.random.default_rng(0).choice(n_items, size=min(n_items, DUMP_ITEMS), replace=False))
+    out = {"losses": np.asarray(losses, dtype=np.float32)}
+    for k, v in params.items():
+        if k in VOCAB_WIDE:
+            if sliced:
+                continue
+            v = np.take(v, items, axis=list(v.shape).index(n_items))
+        v = np.asarray(v, dtype=np.float32)
+        if v.size > DUMP_MAX_ELEMS:
+            v = v.reshape(-1)[np.sort(np.random.default_rng(1).choice(v.size, size=DUMP_MAX_ELEMS, replace=False))]
+        out[k] = v
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+
+
 def collective_breakdown(model, it, extra_steps, barrier, dist, world, dev):
     """N > 1: what the step spends in its collectives (event pairs on the step's stream around every call of the collectives
     table, a pass of its own behind the timed region): per rank the time from "this rank reaches the collective" to "it has
@@ -279,7 +328,7 @@ def main():
 
     from aaerec import _hip
     from aaerec.condition import ConditionList, PretrainedWordEmbeddingCondition
-    from tools.synth import init_params, throughput_corpus
+    from tools.synth import throughput_corpus
 
     N, h, c, B = a.items, a.hidden, a.code, a.batch
     Bg = B * world
@@ -292,6 +341,7 @@ def main():
         conditions = ConditionList([("title", PretrainedWordEmbeddingCondition(_ConstVectors(a.cond_inc), use_cuda=True))])
         cond_data = [torch.randn(n_batches * Bg, a.cond_inc, device=dev) * 0.1]
     model = make_model(a, Bg, dist if use_dp else None, conditions=conditions)
+    np.random.seed(4321)         # fit()'s epoch permutations come from np.random's global state: the same batches every run
     with contextlib.redirect_stdout(sys.stderr):
         it = model.fit_steps(X, condition_data=cond_data)
         next(it)                                          # construction + corpus upload + first step
@@ -311,15 +361,17 @@ def main():
     # step) are timed in a short pass AFTER the timed region; that pass does not enter `value`.
     # The event pairs ride in the FIRST timed repeat of K steps only (`profiled_repeat`): they cost that repeat ~4 % (a
     # timing event carries a system-scope release the plain launch does not), the other repeats run as production does and
-    # the median over all of them is `value`.
-    if os.environ.get("AAE_BENCH_NO_PROF") is None:          # (debugging aid: a kernel trace of the loop without the timing events)
+    # the median over all of them is `value`.  A plain run (no --full) times its K steps once, without the event pairs.
+    profiled = a.full and os.environ.get("AAE_BENCH_NO_PROF") is None   # (debugging aid: a kernel trace of the loop without the timing events)
+    if profiled:
         out_model.profile_enable(True, kernels=K_OUT)
     dts = [timed_steps(it, a.steps, barrier)]
-    out_model.profile_enable(False)
+    if profiled:
+        out_model.profile_enable(False)
     # (a region of 20 steps - the driver's K - is 5 ms: the first three such regions behind the warm-up run 3-4 % slower than the
     #  ones after them (the chip settles its clocks over the first ~15 ms of the loop; region_profile.py), so a median of five sat
     #  on the settling ones.  Fifteen repeats of so short a region cost 70 ms and every one is listed in config.repeat_ms_per_step)
-    repeats = a.repeats or (15 if dts[0] < 0.02 else 5 if dts[0] < 0.25 else 1)
+    repeats = a.repeats or ((15 if dts[0] < 0.02 else 5 if dts[0] < 0.25 else 1) if a.full else 1)
     for _ in range(repeats - 1):
         dts.append(timed_steps(it, a.steps, barrier))
     dt = float(np.median(dts))
@@ -329,6 +381,52 @@ def main():
         dt = float(t.item())
     losses = model._losses()
     docs_per_s = a.steps * Bg / dt
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, losses, N, rank)
+    peak_tf = MFMA_BF16_PEAK_TF if a.dtype == "bf16" else MFMA_F32_PEAK_TF
+    # The whole step against its own floor (VERDICT r3): ALGORITHMIC bytes and flops of one partial_fit - the output layer's
+    # parameter + optimiser stream (24 B per element of dec.lin3, read once / written once), the first layer's touched rows
+    # (3 forward gathers + 2 optimisers of 32 B per element), the hidden layers' Adam (28 B per element, the encoder's twice) -
+    # against max(bytes / HBM peak, flops / matrix peak of the line's dtype); per rank: its documents, its share of the layer
+    Nr = out_model.N if vocab else N
+    step_roofline = step_floor(Nr, h, c, a.cond_inc, (Bg if vocab else B), B, nnz_per_batch, peak_tf, dt / a.steps * 1e3)
+    dp_desc = None
+    if use_dp:          # (what the output says about the MAIN line's scheme: read before --full's other scheme closes its handles)
+        dp_desc = dict(shard_first=bool(getattr(model._dp, "shard_first", False)),
+                       comm=model._dp.comm_stats() if hasattr(model._dp, "comm_stats") else None,
+                       native=getattr(model._dp, "_native", None) is not None)
+    if a.full:
+        kstats, roofline, roofline_critical, dp_breakdown, raw, extra, cpu, dp_other = full_measurements(
+            a, model, it, out_model, vocab, X, cond_data, conditions, dts, repeats, barrier, dist, use_dp, world, rank, dev,
+            N, h, c, B, Bg, n_batches, nnz_per_batch, peak_tf)
+    else:
+        kstats = roofline = roofline_critical = dp_breakdown = raw = cpu = dp_other = None
+        extra = {}
+    result_line = None
+    if rank == 0:
+        result_line = json.dumps(result(a, N, h, c, B, Bg, world, use_dp, vocab, dist, docs_per_s, dt, dts, nnz_per_batch, profiled,
+                                        losses, step_roofline, kstats, roofline, roofline_critical, dp_breakdown, raw, extra, cpu,
+                                        dp_other, dp_desc))
+    if dist is not None:
+        dist.destroy_process_group()
+    if rank == 0:
+        # RCCL writes a version banner through C stdio, which is block-buffered when stdout is a pipe and
+        # would otherwise land after the result: flush it first so the JSON is the last line
+        try:
+            import ctypes
+            ctypes.CDLL(None).fflush(None)
+        except OSError:
+            pass
+        sys.stdout.flush()
+        print(result_line, flush=True)
+
+
+def full_measurements(a, model, it, out_model, vocab, X, cond_data, conditions, dts, repeats, barrier, dist, use_dp, world, rank,
+                      dev, N, h, c, B, Bg, n_batches, nnz_per_batch, peak_tf):
+    """--full: everything besides the headline, behind its timed steps - per-kernel timings and the rooflines, raw_step, the
+    extra configurations, the CPU baseline, the collectives breakdown and the other data-parallel scheme (N > 1)."""
+    from aaerec.condition import ConditionList, PretrainedWordEmbeddingCondition
+    from tools.synth import init_params, throughput_corpus
 
     km = kernel_models(N, h, B, nnz_per_batch, c)
     if vocab:       # the output-layer kernels' algorithmic work on this rank: its item slice x the global batch
@@ -358,7 +456,6 @@ def main():
 
     dp_breakdown = collective_breakdown(model, it, extra_steps, barrier, dist, world, dev) if use_dp else None
 
-    peak_tf = MFMA_BF16_PEAK_TF if a.dtype == "bf16" else MFMA_F32_PEAK_TF
     roofline = roofline_critical = None
 
     def roof(name):
@@ -408,13 +505,6 @@ def main():
                             r["traffic_in_run"] = False      # (a counter pass cannot share a run with the timed region)
             except (OSError, ValueError, KeyError):
                 pass
-
-    # The whole step against its own floor (VERDICT r3): ALGORITHMIC bytes and flops of one partial_fit - the output layer's
-    # parameter + optimiser stream (24 B per element of dec.lin3, read once / written once), the first layer's touched rows
-    # (3 forward gathers + 2 optimisers of 32 B per element), the hidden layers' Adam (28 B per element, the encoder's twice) -
-    # against max(bytes / HBM peak, flops / matrix peak of the line's dtype); per rank: its documents, its share of the layer
-    Nr = out_model.N if vocab else N
-    step_roofline = step_floor(Nr, h, c, a.cond_inc, (Bg if vocab else B), B, nnz_per_batch, peak_tf, dt / a.steps * 1e3)
 
     raw = None
     extra = {}
@@ -635,11 +725,6 @@ def main():
     # all-reduces of partial sums), the north star's wording is `replicated` (full replicas, RCCL reduce-scatter / all-gather of
     # the decoder gradient overlapped with backward): the first multi-GPU run measures both.  Same steps, same bracketing
     # (barrier + synchronize, MAX over ranks), a full dp_breakdown; AAE_BENCH_EXTRAS without "dp_other" skips it.
-    dp_desc = None
-    if use_dp:          # (what the output says about the MAIN line's scheme: read before its model goes)
-        dp_desc = dict(shard_first=bool(getattr(model._dp, "shard_first", False)),
-                       comm=model._dp.comm_stats() if hasattr(model._dp, "comm_stats") else None,
-                       native=getattr(model._dp, "_native", None) is not None)
     dp_other = None
     if use_dp and world > 1 and not a.no_extra and "dp_other" in os.environ.get("AAE_BENCH_EXTRAS", "dp_other").split(","):
         try:
@@ -704,72 +789,69 @@ def main():
         except Exception as e:       # noqa: BLE001 - the main line is measured already: it is printed whatever happens to this one
             dp_other = dict(dp_other or {}, error=f"{type(e).__name__}: {e}")
 
-    if rank == 0:
-        cfg_name = ("C2 RCV1-scale" if a.dtype == "bf16" else "C4 EconBiz-scale + 300-d title condition" if a.cond_inc
-                    else "C3 PubMed-scale")
-        cfg_id = ("C3" if (N, h, a.dtype, a.cond_inc) == (100000, 200, "f32", 0) else
-                  "C2" if (N, h, a.dtype, a.cond_inc) == (47000, 100, "bf16", 0) else
-                  "C4" if a.cond_inc else "custom")
-        kitems = f"{N // 1000}k" if N % 1000 == 0 else str(N)
-        out = {
-            # (BASELINE.json's metric names the headline shape; any other shape names its own so that two lines are never
-            #  compared across configurations)
-            "metric": f"train docs/sec at |items|={kitems} h={h}" + ("" if a.dtype == "f32" else f" {a.dtype}"),
-            "config_id": cfg_id,
-            "value": round(docs_per_s, 1), "unit": "docs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"{cfg_name} synthetic Bags: |items|={N}, hidden={h}, code={c}, "
-                                   f"{'fp32' if a.dtype == 'f32' else 'bf16 MFMA inputs / fp32 accumulate, master weights and Adam'}, "
-                                   f"batch={B} docs/GPU/step, full partial_fit (ae+disc+gen, 4 Adam) inside the "
-                                   f"AdversarialAutoEncoder.fit epoch loop (permutation batches of a corpus resident in HBM)",
-                       "n_items": N, "n_hidden": h, "n_code": c, "batch_per_gpu": B, "global_batch": Bg,
-                       "cond_inc": a.cond_inc, "nnz_per_batch": round(nnz_per_batch, 1), "rng": "device",
-                       "timed_repeats": len(dts), "repeat_ms_per_step": [round(d / a.steps * 1e3, 4) for d in dts],
-                       "profiled_repeat": 0,
-                       "parallelism": (f"dp{world}" if not use_dp else
-                                       (f"dp{world}, item slices of both vocabulary-wide layers + replicated hidden stacks on the global batch, "
-                                        f"3 all-reduces of partial sums per step" if a.dp == "shard" else
-                                        f"dp{world}, decoder output layer and encoder first layer sharded over the vocabulary"
-                                        if dp_desc["shard_first"] else
-                                        f"dp{world}, decoder output layer sharded over the vocabulary") if vocab else
-                                       f"dp{world}, replicated decoder")},
-            "roofline": roofline, "step_roofline": step_roofline, "cpu_baseline": cpu, "kernels": kstats,
-            **({"roofline_critical": roofline_critical} if roofline_critical else {}),
-            "losses_last_step": [round(float(x), 5) for x in losses],
-        }
-        if raw:
-            out["raw_step"] = raw
-        if extra:
-            out["extra"] = extra
-        if dp_breakdown:
-            out["dp_breakdown"] = dp_breakdown
-        if use_dp:
-            out["dp"] = a.dp
-        if dp_other:
-            out["dp_other"] = dp_other
-        if use_dp and dp_desc["comm"] is not None:
-            out["collectives_per_step"] = dp_desc["comm"]
-            native = dp_desc["native"]
-            rccl = dist is not None and str(dist.get_backend()).lower() == "nccl"
-            out["dp_step_driver"] = (("library call (" + ("aae_shard_step" if a.dp == "shard" else "aae_dp_step") + "), " + ("RCCL communicator of the library" if rccl else
-                                                                         "collectives through host-staged callbacks (functional check)"))
-                                     if native else "python phases over torch.distributed")
-        if cpu:
-            out["speedup_vs_cpu_baseline"] = round(docs_per_s / cpu["value"], 1)
-        result_line = json.dumps(out)
-    if dist is not None:
-        dist.destroy_process_group()
-    if rank == 0:
-        # RCCL writes a version banner through C stdio, which is block-buffered when stdout is a pipe and
-        # would otherwise land after the result: flush it first so the JSON is the last line
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except OSError:
-            pass
-        sys.stdout.flush()
-        print(result_line, flush=True)
+    return kstats, roofline, roofline_critical, dp_breakdown, raw, extra, cpu, dp_other
+
+
+def result(a, N, h, c, B, Bg, world, use_dp, vocab, dist, docs_per_s, dt, dts, nnz_per_batch, profiled, losses, step_roofline,
+           kstats, roofline, roofline_critical, dp_breakdown, raw, extra, cpu, dp_other, dp_desc):
+    """The result line (rank 0).  A plain run leaves out what --full measures (kernels, roofline, cpu_baseline, raw_step, extra,
+    dp_breakdown, dp_other)."""
+    cfg_name = ("C2 RCV1-scale" if a.dtype == "bf16" else "C4 EconBiz-scale + 300-d title condition" if a.cond_inc
+                else "C3 PubMed-scale")
+    cfg_id = ("C3" if (N, h, a.dtype, a.cond_inc) == (100000, 200, "f32", 0) else
+              "C2" if (N, h, a.dtype, a.cond_inc) == (47000, 100, "bf16", 0) else
+              "C4" if a.cond_inc else "custom")
+    kitems = f"{N // 1000}k" if N % 1000 == 0 else str(N)
+    out = {
+        # (BASELINE.json's metric names the headline shape; any other shape names its own so that two lines are never
+        #  compared across configurations)
+        "metric": f"train docs/sec at |items|={kitems} h={h}" + ("" if a.dtype == "f32" else f" {a.dtype}"),
+        "config_id": cfg_id,
+        "value": round(docs_per_s, 1), "unit": "docs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": f"{cfg_name} synthetic Bags: |items|={N}, hidden={h}, code={c}, "
+                               f"{'fp32' if a.dtype == 'f32' else 'bf16 MFMA inputs / fp32 accumulate, master weights and Adam'}, "
+                               f"batch={B} docs/GPU/step, full partial_fit (ae+disc+gen, 4 Adam) inside the "
+                               f"AdversarialAutoEncoder.fit epoch loop (permutation batches of a corpus resident in HBM)",
+                   "n_items": N, "n_hidden": h, "n_code": c, "batch_per_gpu": B, "global_batch": Bg,
+                   "cond_inc": a.cond_inc, "nnz_per_batch": round(nnz_per_batch, 1), "rng": "device",
+                   "timed_repeats": len(dts), "repeat_ms_per_step": [round(d / a.steps * 1e3, 4) for d in dts],
+                   "profiled_repeat": 0 if profiled else None,
+                   "parallelism": (f"dp{world}" if not use_dp else
+                                   (f"dp{world}, item slices of both vocabulary-wide layers + replicated hidden stacks on the global batch, "
+                                    f"3 all-reduces of partial sums per step" if a.dp == "shard" else
+                                    f"dp{world}, decoder output layer and encoder first layer sharded over the vocabulary"
+                                    if dp_desc["shard_first"] else
+                                    f"dp{world}, decoder output layer sharded over the vocabulary") if vocab else
+                                   f"dp{world}, replicated decoder")},
+        "step_roofline": step_roofline,
+        "losses_last_step": [round(float(x), 5) for x in losses],
+    }
+    if a.full:
+        out.update(roofline=roofline, cpu_baseline=cpu, kernels=kstats)
+        if roofline_critical:
+            out["roofline_critical"] = roofline_critical
+    if raw:
+        out["raw_step"] = raw
+    if extra:
+        out["extra"] = extra
+    if dp_breakdown:
+        out["dp_breakdown"] = dp_breakdown
+    if use_dp:
+        out["dp"] = a.dp
+    if dp_other:
+        out["dp_other"] = dp_other
+    if use_dp and dp_desc["comm"] is not None:
+        out["collectives_per_step"] = dp_desc["comm"]
+        native = dp_desc["native"]
+        rccl = dist is not None and str(dist.get_backend()).lower() == "nccl"
+        out["dp_step_driver"] = (("library call (" + ("aae_shard_step" if a.dp == "shard" else "aae_dp_step") + "), " + ("RCCL communicator of the library" if rccl else
+                                                                     "collectives through host-staged callbacks (functional check)"))
+                                 if native else "python phases over torch.distributed")
+    if cpu:
+        out["speedup_vs_cpu_baseline"] = round(docs_per_s / cpu["value"], 1)
+    return out
 
 
 if __name__ == "__main__":

@@ -290,21 +290,47 @@ def test_embedded_vectorizer_host_side_matches_reference_fixture():
 
 
 # ---- boundary: the reference's drivers keep importing what this build does not restate ----------
-REFERENCE = "/root/reference"
+# The module names of the reference's aaerec/ package: the ones this build mirrors, and the out-of-scope ones it leaves
+# to the user's checkout
+_MIRRORED = ["aae", "base", "condition", "dae", "datasets", "evaluation", "rank_metrics_with_std", "transforms", "ub", "vae"]
+_OUT_OF_SCOPE = {
+    "baselines": "from .base import Recommender\n\n\nclass RandomBaseline(Recommender):\n    pass\n\n\n"
+                 "class Countbased(Recommender):\n    pass\n\n\nclass MostPopular(Recommender):\n    pass\n",
+    "svd": "from .base import Recommender\nfrom .ub import AutoEncoderMixin\n\n\n"
+           "class SVDRecommender(Recommender, AutoEncoderMixin):\n    pass\n",
+    "utils": "",
+}
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "aaerec")), reason="the reference checkout exists in the build container only")
-def test_driver_import_lines_resolve_with_this_package_in_front_of_the_reference():
+def _stand_in_checkout(root):
+    """A stand-in of the user's reference checkout under `root`, laid out as the reference's is: aaerec/ with every module
+    name of the reference.  The out-of-scope modules define the classes the drivers import, on top of aaerec.base as the
+    reference's do; the mirrored ones refuse to be imported (this package must shadow them)."""
+    pkg = os.path.join(root, "aaerec")
+    os.makedirs(pkg)
+    open(os.path.join(pkg, "__init__.py"), "w").close()
+    for m in _MIRRORED:
+        with open(os.path.join(pkg, m + ".py"), "w") as f:
+            f.write(f"raise ImportError('aaerec.{m} was taken from the checkout behind the package')\n")
+    for m, text in _OUT_OF_SCOPE.items():
+        with open(os.path.join(pkg, m + ".py"), "w") as f:
+            f.write(text)
+    return root
+
+
+def test_driver_import_lines_resolve_with_this_package_in_front_of_the_reference(tmp_path):
     """sys.path = [aae-recommender_amd, <the user's reference checkout>].  The import lines of the
     reference's main.py:11-20 must all resolve - the modules this build mirrors from HERE, the out-of-scope ones
     (aaerec.baselines, aaerec.svd: main.py:14-15) from the user's checkout through aaerec.__path__ - in a fresh
-    interpreter (gensim, main.py:18, is not part of either package and not in this image)."""
+    interpreter (gensim, main.py:18, is not part of either package).  The checkout is a stand-in with the reference's
+    layout (_stand_in_checkout)."""
     import subprocess
     import sys
     pkg = os.path.join(ROOT, "aae-recommender_amd")
+    reference = _stand_in_checkout(str(tmp_path / "reference"))
     code = (
         "import sys, os\n"
-        f"sys.path[:0] = [{pkg!r}, {REFERENCE!r}]\n"
+        f"sys.path[:0] = [{pkg!r}, {reference!r}]\n"
         "from aaerec.datasets import Bags\n"
         "from aaerec.evaluation import Evaluation\n"
         "from aaerec.aae import AAERecommender, DecodingRecommender\n"
@@ -320,7 +346,7 @@ def test_driver_import_lines_resolve_with_this_package_in_front_of_the_reference
         "assert not here('aaerec.svd') and not here('aaerec.baselines')\n"
         "assert issubclass(SVDRecommender, aaerec.base.Recommender) and issubclass(Countbased, aaerec.base.Recommender)\n"
         "print('ok')\n")
-    out = subprocess.run([sys.executable, "-c", code, pkg], capture_output=True, text=True, timeout=300, cwd="/tmp")
+    out = subprocess.run([sys.executable, "-c", code, pkg], capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 

@@ -963,7 +963,7 @@ def test_bench_spawns_its_own_ranks(dp):
     env = dict(os.environ, AAE_BENCH_GLOO_ONE_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu", "--items", "6000", "--hidden", "64", "--dp", dp], env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -974,6 +974,37 @@ def test_bench_spawns_its_own_ranks(dp):
     assert np.all(np.isfinite(out["losses_last_step"]))
     if dp == "shard":            # the default scheme: three all-reduces per step, the library's step driver
         assert out["collectives_per_step"]["collectives"] == 3 and "3 all-reduces" in out["config"]["parallelism"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): ONE timed region of exactly --steps steps, the headline fields, none of what
+    --full measures; --dump-outputs writes the last timed step's losses and parameters (float32), and a second run with
+    the same arguments trains on the same inputs (seeded corpus, permutations, device generator): the same outputs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--items", "6000", "--hidden", "64", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 7 and out["config"]["timed_repeats"] == 1 and out["unit"] == "docs/s" and out["higher_is_better"]
+        assert out["ms_per_step"] == pytest.approx(out["config"]["repeat_ms_per_step"][0], rel=1e-3)
+        assert out["value"] == pytest.approx(7 * 100 / (out["ms_per_step"] * 7e-3), rel=2e-3)
+        assert not {"kernels", "roofline", "cpu_baseline", "raw_step", "extra"} & set(out)
+        files = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert {"losses", "enc.lin1.weight", "dec.lin3.weight", "dec.lin3.bias", "disc.lin3.weight"} <= set(files)
+        assert all(v.dtype == np.float32 and np.all(np.isfinite(v)) for v in files.values())
+        assert files["dec.lin3.weight"].shape == (2048, 64) and files["enc.lin1.weight"].shape == (64, 2048)
+        np.testing.assert_allclose(files["losses"], out["losses_last_step"], rtol=1e-4, atol=1e-5)
+        outs.append(files)
+    for k, v in outs[0].items():
+        np.testing.assert_allclose(outs[1][k], v, rtol=1e-4, atol=1e-5, err_msg=k)
 
 
 def test_dense_batches_are_compacted_on_the_device():

@@ -1,19 +1,21 @@
 #!/bin/bash
-# Round evidence, run on the GPU box from the repo root:  bash tools/collect_profiles.sh <tag>
-# Leaves under gpurun_out/: <tag>_bench.json (default bench.py run), <tag>_kernel_stats.csv (rocprofv3 --kernel-trace
-# --stats of the same command), <tag>_bf16_* (the C2 line), pmc_fetch.txt / pmc_write.txt / pmc_mfma.txt (separate
-# --pmc passes).  Progress lines go to stdout (a silent run is taken to be hung).
+# Round evidence, run on a machine with the GPU from the repo root:  bash tools/collect_profiles.sh <tag>
+# Leaves in $PROFILE_OUT (default: profile_out/ in the repo root): <tag>_bench.json (a `bench.py --full` run),
+# <tag>_kernel_stats.csv (rocprofv3 --kernel-trace --stats of the headline loop), <tag>_bf16_* (the C2 line); the
+# separate --pmc passes of tools/pmc_pass.sh leave their pmc_<tag>.txt where that script writes them.
+# Progress lines go to stdout (a silent run is taken to be hung).
 tag=${1:-r4}
 root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-cd "$root" && mkdir -p gpurun_out
-echo "[collect] bench f32"; python3 bench.py > gpurun_out/${tag}_bench.log 2>&1; tail -1 gpurun_out/${tag}_bench.log > gpurun_out/${tag}_bench.json
-echo "[collect] bench bf16"; python3 bench.py --dtype bf16 --no-cpu > gpurun_out/${tag}_bf16_bench.log 2>&1; tail -1 gpurun_out/${tag}_bf16_bench.log > gpurun_out/${tag}_bf16_bench.json
+out=${PROFILE_OUT:-$root/profile_out}
+cd "$root" && mkdir -p "$out"
+echo "[collect] bench f32"; python3 bench.py --full > "$out/${tag}_bench.log" 2>&1; tail -1 "$out/${tag}_bench.log" > "$out/${tag}_bench.json"
+echo "[collect] bench bf16"; python3 bench.py --full --dtype bf16 --no-cpu > "$out/${tag}_bf16_bench.log" 2>&1; tail -1 "$out/${tag}_bf16_bench.log" > "$out/${tag}_bf16_bench.json"
 for v in f32 bf16; do
   echo "[collect] rocprofv3 kernel stats $v"
   extra=""; [ $v = bf16 ] && extra="--dtype bf16"
-  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$root/gpurun_out/${tag}_prof" -o run -- python3 "$root/bench.py" --no-cpu --no-extra $extra > "$root/gpurun_out/${tag}_prof_$v.log" 2>&1 )
-  find gpurun_out/${tag}_prof -name "*kernel_stats.csv" -exec cp {} gpurun_out/${tag}_${v}_kernel_stats.csv \;
-  rm -rf gpurun_out/${tag}_prof
+  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_prof" -o run -- python3 "$root/bench.py" --no-cpu --no-extra $extra > "$out/${tag}_prof_$v.log" 2>&1 )
+  find "$out/${tag}_prof" -name "*kernel_stats.csv" -exec cp {} "$out/${tag}_${v}_kernel_stats.csv" \;
+  rm -rf "$out/${tag}_prof"
 done
 echo "[collect] pmc fetch"; bash tools/pmc_pass.sh fetch FETCH_SIZE
 echo "[collect] pmc write"; bash tools/pmc_pass.sh write WRITE_SIZE

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Short single-GPU runs of bench.py at the shapes of BASELINE.json's configs (numbers quoted in DESIGN.md).
 set -u
-run() { echo "== $1"; shift; timeout 600 python bench.py --no-cpu --no-extra "$@" 2>/dev/null | tail -1 | python -c "
+run() { echo "== $1"; shift; timeout 600 python bench.py --full --no-cpu --no-extra "$@" 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print(' docs/s', d['value'], ' ms/step', d['ms_per_step'], ' dominant', d['roofline']['kernel'], d['roofline']['avg_us'], 'us', d['roofline']['bound'], d['roofline']['frac'])"; }

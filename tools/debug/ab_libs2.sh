@@ -1,7 +1,7 @@
 # same-box A/B of two builds of the library: tools/debug/ab_libs2.sh <nameA> <nameB> [bench args] (libaaerec_hip_<name>.so), alternating runs
 A=$1; B=$2; shift; shift
 for i in 1 2 3; do for v in $A $B; do
-  AAE_HIP_LIB=$PWD/aae-recommender_amd/aaerec/libaaerec_hip_$v.so python bench.py --no-cpu --no-extra "$@" 2>/dev/null | tail -1 | V=$v python -c "
+  AAE_HIP_LIB=$PWD/aae-recommender_amd/aaerec/libaaerec_hip_$v.so python bench.py --full --no-cpu --no-extra "$@" 2>/dev/null | tail -1 | V=$v python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read()); k=d['kernels']; print(os.environ['V'], d['value'], d['ms_per_step'], {n: round(v['avg_us'],1) for n,v in k.items()})"
 done; done
