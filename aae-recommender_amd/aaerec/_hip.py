@@ -29,6 +29,7 @@ FINALS = {"linear": 0, "softmax": 1, "sigmoid": 2}
 OPTIMIZERS = {"adam": 0, "sgd": 1}
 PRIORS = {"gauss": 0, "categorical": 1, "bernoulli": 2}
 RNG_INJECT, RNG_DEVICE = 0, 1
+RANK_K_MAX = 1024         # longest list of predict_topk / decode_topk (aaerec_hip.h; beyond 32: csrc/rank_long.h)
 GRAD_FUSED, GRAD_EXPORT = 0, 1
 
 
@@ -126,6 +127,7 @@ _PROTOS = {
     "aae_predict": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_predict_topk": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_rank_max_rows": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "aae_rank_long_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "aae_decode_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "aae_encode": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
@@ -211,6 +213,13 @@ def load_library():
         raise ImportError("libaaerec_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def set_option(name, value):
+    """A switch of the library for the handles created from now on (aae_set_option; names: struct aae_options,
+    csrc/abi_model.h - e.g. 'RANK_COLLECT_CAP', the entries of a row's collect list in the k > 32 ranking path).
+    value None hands the name back to the environment variable AAE_<name>."""
+    _check(load_library().aae_set_option(str(name).encode(), None if value is None else str(value).encode()))
 
 
 def _check(rc):
@@ -1061,8 +1070,16 @@ class HipAAE:
             self._rank_rows[key] = int(out.value)
         return self._rank_rows[key]
 
+    def rank_long_stats(self):
+        """The fused k > 32 ranking calls since the last read (aae_rank_long_stats): calls, rows, rows whose collect list
+        overflowed, entries collected, the most entries of any row.  Resets the counters."""
+        out = (C.c_int64 * 5)()
+        _check(self.lib.aae_rank_long_stats(self.handle, out))
+        return dict(zip(("calls", "rows", "overflow_rows", "entries", "max_entries"), (int(v) for v in out)))
+
     def predict_topk(self, csr, row_start, n_rows, k, cond=None, exclude_known=True):
-        """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors.  n_rows <= rank_max_rows(k).
+        """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors.  n_rows <= rank_max_rows(k),
+        1 <= k <= RANK_K_MAX (k > 32: the long-list kernels, csrc/rank_long.h; equal logits go to the smaller item id).
         Ties: the reference leaves items of equal fp32 score in np.argpartition's order (evaluation.py:20-58).  Calls within
         the fused path's row limit order such items by their LOGIT (saturated sigmoids included), the dense fallback by the
         smaller item id: the k scores are the same either way, the items named may differ exactly where scores tie

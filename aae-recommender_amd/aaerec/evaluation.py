@@ -210,13 +210,14 @@ class Evaluation:
         return self
 
     def _bounded_k(self):
-        """The largest k of the requested metrics when ALL of them are bounded names (<= 32: what predict_topk ranks), else None."""
+        """The largest k of the requested metrics when ALL of them are bounded names (<= RANK_K_MAX: what predict_topk ranks), else None."""
+        from ._hip import RANK_K_MAX
         ks = []
         for m in self.metrics:
             if not isinstance(m, str) or m not in BOUNDED_METRICS:
                 return None
             ks.append(BOUNDED_METRICS[m].k)
-        return max(ks) if ks and max(ks) <= 32 else None
+        return max(ks) if ks and max(ks) <= RANK_K_MAX else None
 
     def __call__(self, recommenders, batch_size=None):
         if any(v is None for v in (self.train_set, self.test_set, self.x_test, self.y_test)):

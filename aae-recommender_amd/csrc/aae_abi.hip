@@ -32,6 +32,7 @@
 #include "dec_fused_bf16.h"
 #include "dec_crit_x3.h"
 #include "rank_x3.h"
+#include "rank_long.h"
 #include "chain.h"
 #include "chain4.h"
 #include "chain16x3.h"
@@ -61,10 +62,16 @@ int aae_abi_version(void) { return AAE_ABI_VERSION; }
 int aae_set_option(const char* name, const char* value) {
     if (!name || !*name) return fail(AAE_EINVAL, "option name is empty");
     static const char* known[] = {"NO_CHAIN", "CHAIN16", "SPLIT_ANY", "BLOCKED_ANY", "EARLY_ANY", "NO_LATE_JOIN", "NO_ITEM_COUNT", "W1_SERIAL",
-                                  "NO_RANK_FUSED", "CHAIN_KSLICES", "X16_ROWS", "DW_KSPLIT_ROWS", "DEC_TS", "CHAIN_TS", "DW_TS", "DEC_SKIP", "CHAIN_SKIP", "RANK_SKIP"};
+                                  "NO_RANK_FUSED", "CHAIN_KSLICES", "X16_ROWS", "DW_KSPLIT_ROWS", "DEC_TS", "CHAIN_TS", "DW_TS", "DEC_SKIP", "CHAIN_SKIP", "RANK_SKIP",
+                                  "RANK_COLLECT_CAP"};
     bool ok = false;
     for (const char* k : known) ok = ok || strcmp(k, name) == 0;
     if (!ok) return fail(AAE_EINVAL, "unknown option (aae_options, csrc/abi_model.h, lists them)");
+    if (value && strcmp(name, "RANK_COLLECT_CAP") == 0) {      // (a whole number of list entries the LDS sort can hold)
+        char* end = nullptr;
+        const long v = strtol(value, &end, 10);
+        if (end == value || *end || v < 1 || v > kLongCap) return fail(AAE_EINVAL, "RANK_COLLECT_CAP must be a whole number in [1, 4096]");
+    }
     if (value) g_options[name] = value; else g_options.erase(name);
     return AAE_OK;
 }

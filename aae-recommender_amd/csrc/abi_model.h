@@ -53,6 +53,8 @@ struct aae_options {
     bool chain_kslices;     // CHAIN_KSLICES: the 4-row chain kernel's linear ops in the k-slice form at every batch size (bf16 mode takes the
                             // column-owner form for batches of one fused launch: chain4.h)
     int x16_rows;           // X16_ROWS: programs of at least this many rows run on the wide-batch chain kernel (default 1024)
+    int rank_collect_cap;   // RANK_COLLECT_CAP: entries of a row's collect list in the long-list rank path (rank_long.h; 1 .. 4096, default 4096:
+                            // a small value sends rows through the overflow path - the result is the same, the tests use it)
     int dw_ksplit_rows;     // DW_KSPLIT_ROWS: weight-gradient tiles take the k-split form from this many rows on (default 256; -1: unset)
     // diagnostics (debug runs: tools/debug/*)
     char dec_ts[8];         // DEC_TS: in-kernel timeline of the output layer ("1", "x3", "obk")
@@ -68,6 +70,7 @@ inline void read_options(aae_options& o) {
     o.early_any = on("EARLY_ANY"); o.no_late_join = on("NO_LATE_JOIN"); o.no_item_count = on("NO_ITEM_COUNT");
     o.w1_serial = on("W1_SERIAL"); o.no_rank_fused = on("NO_RANK_FUSED"); o.chain_kslices = on("CHAIN_KSLICES");
     o.x16_rows = num("X16_ROWS", 1024); o.dw_ksplit_rows = num("DW_KSPLIT_ROWS", -1);
+    o.rank_collect_cap = std::max(0, std::min(num("RANK_COLLECT_CAP", 0), 4096));
     const char* ts = option_value("DEC_TS");
     snprintf(o.dec_ts, sizeof(o.dec_ts), "%s", ts ? ts : "");
     o.chain_ts = on("CHAIN_TS"); o.dw_ts = num("DW_TS", -1);
@@ -186,6 +189,7 @@ struct aae_model {
     // optimiser table's entry of the coming step was written a step early and no host call has touched the scalars since
     hipEvent_t ev_end = nullptr; bool end_marked = false, spec_tab_ok = false, pf_this_step = false, early_enabled = false, early_any = false;
     long long flushed_hstep = -1;                          // hstep at the last whole-matrix deferred-Adam flush of a rank call (abi_rank.h)
+    int64_t long_stats[5] = {0, 0, 0, 0, 0};               // aae_rank_long_stats: fused k > 32 calls, rows, rows that overflowed, entries collected, most per row
     bool rank_ok = false;                                  // rank_x3.h: predict -> rank fused (aae_predict_topk / aae_decode_topk), abi_rank.h
     bool side_ordered = false;                             // ... or put its dV3 GEMM there: the side stream is in order behind that step's output layer
 };

@@ -63,18 +63,15 @@ int aae_predict(aae_handle m, const aae_batch* batch, const float* cond_dev, flo
 
 // predict + on-device remove_non_missing / argtopk (evaluation.py:183-199, 20-58): only the k best
 // items per row (ids and min-max-scaled scores) leave the GPU
-int aae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev, int32_t k, int32_t exclude_known,
-                     int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    if (k < 1 || k > 32 || k > m->N) return fail(AAE_EINVAL, "k must be in [1, min(32, n_items)]");
-    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
-    TRY(rank_check_batch(batch));
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {   // fused: no [rows][N] matrix (abi_rank.h)
-        m->phase = 0;
-        return rank_predict(m, batch, cond_dev, k, exclude_known, idx_out_dev, val_out_dev, S(stream));
-    }
-    TRY(aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream));      // scores into the [rows][N] scratch
-    hipStream_t s = S(stream);
+}  // extern "C"
+namespace {
+int check_topk_k(const aae_model* m, int k) {
+    if (k < 1 || k > kLongKMax || k > m->N) return fail(AAE_EINVAL, "k must be in [1, min(1024, n_items)]");
+    return AAE_OK;
+}
+// the [rows][N] scores in the scratch -> [rows][k]: register lists up to k = 32 (kernels.h), the long-list kernel beyond
+int topk_from_scores(aae_model* m, int k, int exclude_known, int32_t* idx_out_dev, float* val_out_dev, hipStream_t s) {
+    if (rank_long(k)) return rank_long_dense(m, k, exclude_known, idx_out_dev, val_out_dev, s);
     if (k <= 10)
         hipLaunchKernelGGL(topk_rows_kernel<10>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
                            exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
@@ -87,11 +84,43 @@ int aae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev
     LAUNCHCHK("topk_rows");
     return AAE_OK;
 }
+}  // namespace
+extern "C" {
+
+int aae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev, int32_t k, int32_t exclude_known,
+                     int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    TRY(check_topk_k(m, k));
+    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
+    TRY(rank_check_batch(batch));
+    hipStream_t s = S(stream);
+    if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {   // fused: no [rows][N] matrix (abi_rank.h)
+        m->phase = 0;
+        TRY(rank_predict(m, batch, cond_dev, k, exclude_known, idx_out_dev, val_out_dev, s));
+        if (!rank_long(k)) return AAE_OK;
+        std::vector<std::pair<int, int>> spans;        // rows whose collect list overflowed: through the score matrix
+        TRY(rank_long_overflow(m, batch, k, s, spans));
+        for (const auto& sp : spans) {
+            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
+            TRY(aae_predict(m, &sub, cond_dev ? cond_dev + (size_t)sp.first * m->cfg.cond_inc : nullptr, m->G.p, m->ldn, stream));
+            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + (size_t)sp.first * k, val_out_dev + (size_t)sp.first * k, s));
+        }
+        return AAE_OK;
+    }
+    TRY(aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream));      // scores into the [rows][N] scratch
+    return topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s);
+}
 
 int aae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
     if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
-    if (k < 1 || k > 32 || k > m->N) return fail(AAE_EINVAL, "k must be in [1, min(32, n_items)]");
+    TRY(check_topk_k(m, k));
     *rows_out = std::max(m->R, rank_rows_cap(m, k));
+    return AAE_OK;
+}
+
+int aae_rank_long_stats(aae_handle m, int64_t out[5]) {
+    if (!m || !out) return fail(AAE_EINVAL, "NULL argument");
+    for (int i = 0; i < 5; ++i) { out[i] = m->long_stats[i]; m->long_stats[i] = 0; }
     return AAE_OK;
 }
 
@@ -100,26 +129,27 @@ int aae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
 int aae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k,
                     int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
     if (!m || !zc_dev || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    if (k < 1 || k > 32 || k > m->N) return fail(AAE_EINVAL, "k must be in [1, min(32, n_items)]");
+    TRY(check_topk_k(m, k));
     if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
     TRY(rank_check_batch(batch));
+    hipStream_t s = S(stream);
     if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {
         m->phase = 0;
-        return rank_decode(m, zc_dev, zc_ld, batch, k, exclude_known, idx_out_dev, val_out_dev, S(stream));
+        TRY(rank_decode(m, zc_dev, zc_ld, batch, k, exclude_known, idx_out_dev, val_out_dev, s));
+        if (!rank_long(k)) return AAE_OK;
+        std::vector<std::pair<int, int>> spans;
+        TRY(rank_long_overflow(m, batch, k, s, spans));
+        for (const auto& sp : spans) {
+            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
+            TRY(set_batch(m, &sub));
+            TRY(aae_decode(m, zc_dev + (size_t)sp.first * zc_ld, zc_ld, m->rows, m->G.p, m->ldn, stream));
+            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + (size_t)sp.first * k, val_out_dev + (size_t)sp.first * k, s));
+        }
+        return AAE_OK;
     }
     TRY(set_batch(m, batch));
     TRY(aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream));   // scores into the [rows][N] scratch
-    hipStream_t s = S(stream);
-    if (k <= 10)
-        hipLaunchKernelGGL(topk_rows_kernel<10>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
-                           exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    else if (k <= 20)
-        hipLaunchKernelGGL(topk_rows_kernel<20>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
-                           exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    else
-        hipLaunchKernelGGL(topk_rows_kernel<32>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
-                           exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    LAUNCHCHK("topk_rows");
+    TRY(topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s));
     m->phase = 0;
     return AAE_OK;
 }

@@ -8,7 +8,10 @@
 //   dh2      [rows][ldh]    the decoder's last hidden activations (ONE chain program: encoder tail -> code -> condition
 //                           block -> decoder hidden layers, 4 rows per workgroup)
 //   known    [rows][kw]     bitmap of the rows' input items        cand [rows][wgs][K] x (score, id), mm [rows][wgs][2]
+//   k > 32 (rank_long.h):   tau [rows], count [rows], list [rows][cap] x 64 bits
 // Launches per call: (deferred-Adam flush of enc.lin1 when rows are behind) gather, chain, known-item mask, rank, merge.
+// k > 32: ... rank (K = 32), floor, rank again with the collect epilogue, sort; then the rows' counts are read back (the call
+// synchronises its stream) and a row whose list overflowed is ranked through the score matrix (rank_long_dense).
 #pragma once
 
 namespace {
@@ -25,8 +28,12 @@ constexpr int kRankMaxRows = 4096;
 struct RankPlan {
     int rows, K, nblk, wgs, kw, bb;
     float *a1, *eh1, *dh2, *rscale, *cand_v, *mm; int* cand_i; unsigned* known;
+    int cap; float* tau; int* count; unsigned long long* list;      // k > 32 (rank_long.h)
     size_t floats;
 };
+
+inline bool rank_long(int k) { return k > 32; }
+inline int rank_collect_cap(const aae_model* m) { return m->opt.rank_collect_cap > 0 ? m->opt.rank_collect_cap : kLongCap; }
 
 inline int rank_K(int k) { return k <= 10 ? 10 : k <= 20 ? 20 : 32; }
 
@@ -47,6 +54,11 @@ RankPlan rank_plan(const aae_model* m, int rows, int k, float* base) {
     p.cand_v = take((size_t)rows * p.wgs * p.K);
     p.cand_i = reinterpret_cast<int*>(take((size_t)rows * p.wgs * p.K));
     p.mm = take((size_t)rows * p.wgs * 2);
+    if (rank_long(k)) {
+        p.cap = rank_collect_cap(m);
+        p.tau = take(rows); p.count = reinterpret_cast<int*>(take(rows));
+        p.list = reinterpret_cast<unsigned long long*>(take((size_t)rows * p.cap * 2));
+    }
     p.floats = off;
     return p;
 }
@@ -60,12 +72,16 @@ size_t rank_ws_floats(const aae_model* m) {
 
 // most rows one fused call can rank (0: the fused path does not apply to this handle)
 int rank_rows_cap(const aae_model* m, int k) {
-    if (!m->rank_ok || k < 1 || k > 32) return 0;
+    if (!m->rank_ok || k < 1 || k > kLongKMax) return 0;
     const size_t have = rank_ws_floats(m);
+    const int ntiles = (m->N + kTI - 1) / kTI;
     int lo = 0, hi = kRankMaxRows;          // (the plan's size is monotone in rows up to rounding: bisect)
     while (lo < hi) {
         const int mid = (lo + hi + 1) / 2;
-        if (rank_plan(m, mid, k, nullptr).floats <= have) lo = mid; else hi = mid - 1;
+        const RankPlan p = rank_plan(m, mid, k, nullptr);
+        // (k > 32: the floor needs k candidates per row - fewer workgroups per row block than that and every row would overflow)
+        const bool floor_ok = !rank_long(k) || p.wgs * 32 >= k || p.wgs == ntiles;
+        if (p.floats <= have && floor_ok) lo = mid; else hi = mid - 1;
     }
     return lo;
 }
@@ -93,6 +109,16 @@ int launch_rank_nb(const RankArgs& a, int K, int grid, hipStream_t s) {
     return AAE_OK;
 }
 
+// the K = 32 kernel's front end with the collect epilogue (rank_long.h)
+template <int NB>
+int launch_collect_nb(const RankArgs& a, int grid, hipStream_t s) {
+    const uint32_t lds = (uint32_t)rank_x3_lds_bytes(NB);
+    if (x3_big_span(a.N, a.ldv)) hipLaunchKernelGGL((rank_x3_kernel<NB, 1, true, true>), dim3(grid), dim3(kNT), lds, s, a);
+    else hipLaunchKernelGGL((rank_x3_kernel<NB, 1, false, true>), dim3(grid), dim3(kNT), lds, s, a);
+    LAUNCHCHK("rank_x3 (collect)");
+    return AAE_OK;
+}
+
 bool rank_set_attributes() {
     bool ok = true;
     auto set = [&](const void* f, int NB) {
@@ -103,6 +129,9 @@ bool rank_set_attributes() {
     set(reinterpret_cast<const void*>(rank_x3_kernel<7, 20>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 20, true>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 32>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 32, true>), 7);
     set(reinterpret_cast<const void*>(rank_x3_kernel<13, 10>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 10, true>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 20>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 20, true>), 13);
     set(reinterpret_cast<const void*>(rank_x3_kernel<13, 32>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 32, true>), 13);
+    set(reinterpret_cast<const void*>(rank_x3_kernel<4, 1, false, true>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<4, 1, true, true>), 4);
+    set(reinterpret_cast<const void*>(rank_x3_kernel<7, 1, false, true>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 1, true, true>), 7);
+    set(reinterpret_cast<const void*>(rank_x3_kernel<13, 1, false, true>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 1, true, true>), 13);
     auto set2 = [&](const void* f, int NB) {
         ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_x3v2_lds_bytes(NB)) == hipSuccess;
     };
@@ -134,6 +163,23 @@ int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, i
             case 7: TRY(launch_rank_nb<7>(a, p.K, grid, s)); break;
             default: TRY(launch_rank_nb<13>(a, p.K, grid, s)); break;
         }
+    }
+    if (rank_long(k)) {
+        ProfScope ps(m, AAE_K_RANK, s);
+        hipLaunchKernelGGL(rank_floor_kernel, dim3(p.rows), dim3(256), 0, s, p.cand_v, p.cand_i, p.wgs * p.K, k, p.tau, p.count);
+        LAUNCHCHK("rank_floor");
+        a.tau = p.tau; a.count = p.count; a.list = p.list; a.cap = p.cap;
+        switch (m->fused_nb) {
+            case 4: TRY(launch_collect_nb<4>(a, grid, s)); break;
+            case 7: TRY(launch_collect_nb<7>(a, grid, s)); break;
+            default: TRY(launch_collect_nb<13>(a, grid, s)); break;
+        }
+        int P = 2;
+        while (P < p.cap) P <<= 1;
+        hipLaunchKernelGGL(rank_long_sort_kernel, dim3(p.rows), dim3(kLongNT), (uint32_t)(P * sizeof(unsigned long long)), s,
+                           p.list, p.count, p.cap, p.mm, p.wgs, k, reinterpret_cast<int*>(idx_out), val_out);
+        LAUNCHCHK("rank_long_sort");
+        return AAE_OK;
     }
     switch (p.K) {
         case 10: hipLaunchKernelGGL(rank_merge_kernel<10>, dim3((p.rows + 3) / 4), dim3(256), 0, s, p.cand_v, p.cand_i, p.mm, p.rows, p.wgs, k, reinterpret_cast<int*>(idx_out), val_out); break;
@@ -218,6 +264,45 @@ int rank_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batc
     rank_dec_hidden(m, cb, 2, 5, rows, p, s);
     TRY(launch_chain(m, cb, s));
     return rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out, val_out, s);
+}
+
+// k > 32, the dense form: [rows][ldn] scores in the scratch -> [rows][k]
+int rank_long_dense(aae_model* m, int k, int exclude_known, int32_t* idx_out, float* val_out, hipStream_t s) {
+    ProfScope ps(m, AAE_K_RANK, s);
+    hipLaunchKernelGGL(rank_long_dense_kernel, dim3(m->rows), dim3(kLongNT), 0, s, m->G.p, m->ldn, m->N, m->bv, exclude_known, k,
+                       reinterpret_cast<int*>(idx_out), val_out);
+    LAUNCHCHK("rank_long_dense");
+    return AAE_OK;
+}
+
+// After a fused k > 32 call: the rows' entry counts (synchronises `s`), the handle's statistics, and the spans of at most
+// max_batch rows that hold a row whose list overflowed - the caller ranks those through the score matrix.
+int rank_long_overflow(aae_model* m, const aae_batch* b, int k, hipStream_t s, std::vector<std::pair<int, int>>& spans) {
+    const int rows = b->n_rows;
+    // (a span keeps to the dense path's per-batch bounds: max_batch rows, max_nnz entries)
+    const int span = std::max(1, std::min(m->R, b->max_row_nnz > 0 ? m->cfg.max_nnz / b->max_row_nnz : m->R));
+    const RankPlan p = rank_plan(m, rows, k, m->G.p);
+    std::vector<int> cnt(rows);
+    HIPCHK(hipMemcpyAsync(cnt.data(), p.count, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    m->long_stats[0] += 1; m->long_stats[1] += rows;
+    spans.clear();
+    for (int r = 0; r < rows; ++r) {
+        m->long_stats[3] += cnt[r]; m->long_stats[4] = std::max<int64_t>(m->long_stats[4], cnt[r]);
+        if (cnt[r] <= p.cap) continue;
+        m->long_stats[2] += 1;
+        if (spans.empty() || r >= spans.back().first + spans.back().second) spans.push_back({r, std::min(span, rows - r)});
+    }
+    return AAE_OK;
+}
+
+// rows [off, off + n) of a batch as a batch of their own, within the per-batch bounds of the dense path
+aae_batch rank_sub_batch(const aae_model* m, const aae_batch* b, int off, int n) {
+    aae_batch c = *b;
+    if (c.rows_dev) c.rows_dev += off; else c.row_start += off;
+    c.n_rows = n; c.generation = 0;
+    if (b->max_row_nnz > 0) c.nnz_bound = (int32_t)std::min<int64_t>((int64_t)n * b->max_row_nnz, b->nnz_bound);
+    return c;
 }
 
 int rank_check_batch(const aae_batch* b) {

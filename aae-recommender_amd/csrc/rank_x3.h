@@ -31,6 +31,9 @@ struct RankArgs {
     float* mm;                          // [B][wgs][2] per-workgroup (min, max) over all cells
     int one_term;                       // bf16 mode: operands rounded to bf16 (first term of the split only)
     int dbg;                            // timing-only ablation mask (AAE_RANK_SKIP), 0 in production
+    // the COLLECT epilogue of rank_x3_kernel (long lists, rank_long.h): cells >= tau[row] appended to the row's list
+    const float* tau; int* count;       // [B] the row's floor; its entries so far (may run beyond cap: the overflow mark)
+    unsigned long long* list; int cap;  // [B][cap] (order-preserving key of the logit << 32) | ~item
 };
 
 // One workgroup per row: the row's known items -> its bitmap (known != NULL), and the bias input of the output layer: column
@@ -69,7 +72,9 @@ inline size_t rank_x3_lds_bytes(int NB) {          // (128-row blocks as well: i
     return sizeof(float) * ((size_t)3 * kTI * S1 + (size_t)2 * kRankGR2 * kRRS + (size_t)lsteps * kRankMB2 * 3 * 64 * 4);
 }
 
-template <int NB, int K, bool WIN = false>      // WIN: dec.lin3 beyond 2^31 bytes (dec_fused.h X3WindowT)
+// COLLECT (rank_long.h): the same products with another epilogue - no lists, no extremes: every rankable cell at or above the
+// row's floor goes to the row's list in the workspace
+template <int NB, int K, bool WIN = false, bool COLLECT = false>      // WIN: dec.lin3 beyond 2^31 bytes (dec_fused.h X3WindowT)
 __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
     const bool one = a.one_term != 0;
     constexpr int KC1 = (NB + 1) / 2, NKS = (KC1 + 1) / 2;
@@ -159,6 +164,10 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
 #pragma unroll
     for (int j = 0; j < K; ++j) { tv[j] = -INFINITY; ti[j] = -1; }
     float vmin = INFINITY, vmax = -INFINITY;
+    const int crow = erow0 + min(eb, B - 1);
+    const float c_tau = COLLECT ? a.tau[crow] : 0.f;
+    int* const c_count = COLLECT ? a.count + crow : nullptr;
+    unsigned long long* const c_list = COLLECT ? a.list + (size_t)crow * a.cap : nullptr;
 
     // the epilogue of one finished tile: the thread's four cells
     auto epilogue = [&](int i0, unsigned kword) {
@@ -169,7 +178,15 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
         for (int j = 0; j < 4; ++j) {
             const int n = 4 * eq + j, item = i0 + n;
             const float v = (&lA.x)[j] + (&lB.x)[j];       // the LOGIT: sigmoid is monotone - applied to the winners only (merge)
-            if (item < N) {
+            if constexpr (COLLECT) {
+                if (item < N && !((kword >> n) & 1u) && v >= c_tau) {
+                    const int pos = atomicAdd(c_count, 1);
+                    if (pos < a.cap) {
+                        const unsigned u = __float_as_uint(v);
+                        c_list[pos] = ((unsigned long long)(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | (unsigned)~item;
+                    }
+                }
+            } else if (item < N) {
                 vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
                 if (!((kword >> n) & 1u) && v > tv[K - 1] && !(a.dbg & 1)) {
                     tv[K - 1] = v; ti[K - 1] = item;
@@ -243,6 +260,7 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
     }
     lds_barrier();
     if (prev_i0 >= 0) epilogue(prev_i0, kw_prev);
+    if constexpr (COLLECT) return;
 
     // ---- the 8 threads of a row merge their lists (K rounds of an 8-lane argmax, ties to the smaller item) -> K candidates
     // of this workgroup for the row; its minimum / maximum

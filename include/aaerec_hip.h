@@ -177,7 +177,7 @@ int aae_abi_version(void);
 const char* aae_last_error(void);
 /* A switch of the library for the handles created FROM NOW ON (value NULL: back to the environment variable AAE_<name>, which
    is what a handle reads otherwise).  Names: struct aae_options, csrc/abi_model.h - paths the parity suites force (NO_CHAIN,
-   SPLIT_ANY, BLOCKED_ANY, X16_ROWS, DW_KSPLIT_ROWS ...) and the diagnostics of debug runs (DEC_TS ...).  No counterpart in
+   SPLIT_ANY, BLOCKED_ANY, X16_ROWS, DW_KSPLIT_ROWS, RANK_COLLECT_CAP ...) and the diagnostics of debug runs (DEC_TS ...).  No counterpart in
    the reference (it has no switches: one eager path); a handle reads its switches once, in aae_create. */
 int aae_set_option(const char* name, const char* value);
 
@@ -381,18 +381,31 @@ int aae_predict(aae_handle h, const aae_batch* batch, const float* cond_dev, flo
 /* predict followed on the device by what Evaluation does on the host with the dense matrix:
  * remove_non_missing (row-wise min-max scaling; items present in the input row excluded when
  * exclude_known != 0; evaluation.py:183-199) and argtopk (evaluation.py:20-58).  Writes the k
- * (<= 32) best item ids per row, best first, and their scaled scores: [rows][k].
+ * (1 <= k <= min(1024, n_items)) best item ids per row, best first, and their scaled scores: [rows][k].
  * Items of EQUAL fp32 score (saturated sigmoids of a trained model, collisions near 1) are in np.argpartition's arbitrary
  * order in the reference; here the fused form (aae_rank_max_rows) orders them by logit, the dense form by the smaller item
- * id - the k scores are identical, the named items may differ exactly at ties. */
+ * id - the k scores are identical, the named items may differ exactly at ties.
+ * k > 32 (the reference's MPD driver ranks 500 items per row) takes the long-list kernels (csrc/rank_long.h): the fused form
+ * orders by logit, items of equal LOGIT by the smaller id; the dense form by score, then the smaller id.  The output does not
+ * vary from run to run.  A row with fewer than k rankable items (exclude_known on a row that names most of the vocabulary)
+ * lists its items, then id -1 with score 0 - at every k.  A fused call with k > 32 reads its rows' entry counts back before
+ * it returns (it synchronises `stream`; not for stream capture), and ranks a row whose collect list overflowed
+ * (RANK_COLLECT_CAP entries, default 4096) through the score matrix in the [max_batch][n_items] scratch: the result is exact
+ * either way. */
 int aae_predict_topk(aae_handle h, const aae_batch* batch, const float* cond_dev, int32_t k,
                      int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream);
 /* Rows ONE aae_predict_topk / aae_decode_topk call may rank (>= max_batch).  Where the fused form applies (r4: the output
  * layer, its sigmoid, the row minimum / maximum, the known-item mask and the top-k selection in one pass over dec.lin3 -
  * the [rows, n_items] score matrix never exists in HBM; hidden widths of the layer-chain kernels) a call takes far more
  * rows than a training batch - the parameter stream is then read once per call, not once per max_batch rows - and such a
- * batch is exempt from the max_batch / max_nnz bounds of aae_batch.  Otherwise *rows_out = max_batch. */
+ * batch is exempt from the max_batch / max_nnz bounds of aae_batch.  Otherwise *rows_out = max_batch.
+ * k > 32 adds a list of 2 x RANK_COLLECT_CAP words per row to the call's workspace and keeps enough workgroups per row block
+ * for the floor (32 candidates each, k in all): fewer rows per call than at k <= 32, never fewer than max_batch. */
 int aae_rank_max_rows(aae_handle h, int32_t k, int32_t* rows_out);
+/* The fused k > 32 calls of this handle since the last read: out[0] calls, [1] rows, [2] rows whose collect list overflowed
+ * (ranked through the score matrix instead), [3] entries collected over all rows, [4] the most entries of any row.  Resets
+ * the counters.  (How tight the floor is: [3] / [1] against k.) */
+int aae_rank_long_stats(aae_handle h, int64_t out[5]);
 /* The same behind a decoder input the caller built (AdversarialAutoEncoder.predict's second half, aae.py:855-866:
  * `z = conditions.encode_impose(z, c_batch)` with plugins of any kind, then dec): zc_dev [batch->n_rows][zc_ld],
  * zc_ld >= n_code + cond_inc; `batch` names the input rows (their items are the ones exclude_known removes). */
@@ -509,7 +522,8 @@ enum { AAE_K_ENC_GATHER = 0,   /* sparse row gather of the first encoder layer *
        AAE_K_CHAIN,            /* a layer-chain program: the hidden stacks of one phase (5 launches per step) */
        AAE_K_DEC_CRIT,         /* split form of the fused output layer, critical launch: logits + BCE + dA2 (+ dL/dlogits tiles) */
        AAE_K_DEC_OPT,          /* ... deferred launch on the library's side stream: dV3 + dec_optim behind the rest of the step */
-       AAE_K_RANK,             /* fused predict -> rank: output layer + sigmoid + min/max + known-item mask + per-workgroup top-k */
+       AAE_K_RANK,             /* fused predict -> rank: output layer + sigmoid + min/max + known-item mask + per-workgroup top-k;
+                                * k > 32: also floor + collect + sort, and the dense form's long-list kernel */
        AAE_K_COLLECTIVE,       /* a collective of aae_dp_step / aae_shard_step: event pair on the step's stream around the table's call
                                 * (what the rank waits: the transfer AND the slowest rank's arrival) */
        AAE_K_N };
