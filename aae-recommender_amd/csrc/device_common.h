@@ -8,6 +8,10 @@ namespace aae {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float kTiny = 1e-12f;                       // TINY, reference aaerec/aae.py:28
+// The logit from which the reference's fp32 sigmoid 1 / (1 + exp(-l)) IS 1.0f: fl(1 + e) == 1 iff e <= 2^-24 (a tie rounds to
+// the even 1.0), i.e. l >= 24 ln 2 = 16.635532.  From there on a zero-target cell of F.binary_cross_entropy costs the clamped
+// 100 and its s (1 - s) factor zeroes the gradient (aae.py:176-177, 693-695); below it 1 - sigmoid moves in steps of 2^-23.
+constexpr float kBceSatLogit = 16.635532f;
 constexpr float kSeluAlpha = 1.6732632423543772848170429916717f;
 constexpr float kSeluScale = 1.0507009873554804934193349852946f;
 

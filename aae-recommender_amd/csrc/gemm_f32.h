@@ -324,8 +324,8 @@ __device__ __forceinline__ void bce_elem(float logit, float t_raw, float gscale,
     const float x = s + kTiny, t = t_raw + kTiny;
     const float lx = fmaxf(__logf(x), -100.f);
     const float lp = e < 0.01f ? e * (1.f - e * (0.5f - e * 0.33333334f)) : __logf(1.f + e);
-    // max(log1p(-x), -100) = -softplus(logit) until sigmoid rounds to 1.0f (logit > 17.33), then -100
-    const float l1x = logit > 17.32868f ? -100.f : -(fmaxf(logit, 0.f) + lp);
+    // max(log1p(-x), -100) = -softplus(logit) until sigmoid rounds to 1.0f (logit >= 24 ln 2 = 16.64, kBceSatLogit), then -100
+    const float l1x = logit >= kBceSatLogit ? -100.f : -(fmaxf(logit, 0.f) + lp);
     loss = -(t * lx + (1.f - t) * l1x);
     g = (x - t) * __builtin_amdgcn_rcpf(fmaxf((1.f - x) * x, 1e-12f)) * (s * (1.f - s)) * gscale;
 }
@@ -333,7 +333,7 @@ __device__ __forceinline__ void bce_elem(float logit, float t_raw, float gscale,
 // The same for target == 0 (every element the GEMM epilogue sees), simplified analytically:
 //   x - t = s and (1-x)x = s(1-s) up to 1e-12, so dL/dl = s * gscale;
 //   loss = -log1p(-x) = softplus(l) = max(l,0) + log1p(exp(-|l|))  (the t*log(x) term is <= 1e-10).
-// fp32 saturation of the reference is kept: for l > 17.33 sigmoid rounds to exactly 1.0f, the
+// fp32 saturation of the reference is kept: for l >= 24 ln 2 = 16.64 (kBceSatLogit) sigmoid rounds to exactly 1.0f, the
 // reference's log1p(-1) = -inf is clamped to -100 and its s(1-s) factor zeroes the gradient.
 // log(x) for 1 <= x <= 2 with the bits of __logf(x): OCML's log_f32 is v_log_f32 (log2) times ln 2 in two-term
 // arithmetic, wrapped in a scaling of denormal arguments and a test for infinities - neither can occur here, and the
@@ -354,7 +354,7 @@ __device__ __forceinline__ void bce_elem_t0(float l, float gscale, float& g, flo
     float lp = e < 0.01f ? lp_series : lp_log;
     g = s * gscale;
     loss = fmaxf(l, 0.f) + lp;
-    if (l > 17.32868f) { g = 0.f; loss = 100.f; }
+    if (l >= kBceSatLogit) { g = 0.f; loss = 100.f; }
 }
 
 // The zero-target form in PARTS, for an epilogue that only needs the SUM of its cells' losses (dec_crit_x3.h): loss = add +
@@ -371,7 +371,7 @@ __device__ __forceinline__ void bce_elem_t0_parts(float l, float gscale, float& 
     g = s * gscale;
     add = fmaxf(l, 0.f) + (small ? lp_series : 0.f);
     fac = small ? 1.f : 1.f + e;
-    if (l > 17.32868f) { g = 0.f; add = 100.f; fac = 1.f; }
+    if (l >= kBceSatLogit) { g = 0.f; add = 100.f; fac = 1.f; }
 }
 // log(x) for a positive normal x, the arithmetic of log_1_to_2 (v_log_f32 times ln 2 in two terms)
 __device__ __forceinline__ float log_pos(float x) { return log_1_to_2(x); }

@@ -532,7 +532,7 @@ class OracleAAE:
         self.opt_dec.step(self.p, Gd)
         for cond in self.conditions:
             cond.step()
-        self.last = dict(enc_a1=ec["a1"], z=z, xhat=xhat)
+        self.last = dict(enc_a1=ec["a1"], z=z, xhat=xhat, logits=logits)
         return loss
 
     def disc_step(self, indptr, indices, values, z_real, masks):

@@ -11,7 +11,7 @@ STEP_CASES = [
     "step_nodrop_gauss", "step_masks", "step_masks_uneven", "step_cond_concat",
     "step_cond_categorical", "step_cond_concat_bias", "step_selu", "step_categorical_prior",
     "step_bernoulli_prior", "step_prior_scale", "step_sgd", "step_nonorm", "step_ragged",
-    "step_tanh", "step_lrs", "step_wide", "step_headline", "step_c4",
+    "step_tanh", "step_lrs", "step_wide", "step_headline", "step_c4", "step_saturated",
 ]
 
 # trainable CategoricalCondition variants (SparseAdam / mean / single index / behind a constant block)
@@ -34,8 +34,16 @@ class Fixture:
         self.steps = self.cfg["steps"]
 
     def init_params(self):
-        return {k[len("init."):]: self.z[k] for k in self.z.files
-                if k.startswith("init.") and not k.startswith("init.cond")}
+        out = {k[len("init."):]: self.z[k] for k in self.z.files
+               if k.startswith("init.") and not k.startswith("init.cond")}
+        if "init_from" in self.cfg:
+            # a fixture that starts from another one's initial parameters, some of them rescaled in fp32 (the generator
+            # asserts that this restatement gives the reference's own arrays bit for bit): the arrays are stored once
+            base = Fixture(self.cfg["init_from"]).init_params()
+            for k, f in self.cfg.get("init_scale", {}).items():
+                base[k] = (base[k] * np.float32(f)).astype(np.float32)
+            out = dict(base, **out)
+        return out
 
     def model_kwargs(self):
         c = self.cfg
@@ -67,9 +75,17 @@ class Fixture:
         return out or None
 
     def has_state(self, s):
+        if "state_keys" in self.cfg:
+            return True
         return f"step{s}.enc.lin1.weight" in self.z.files
 
     def expected_params(self, s):
+        """Every parameter after step s - or, for a fixture whose config names them (state_keys: the arrays recorded after
+        every step and those recorded after the last one only), exactly the named ones: a missing array is an error."""
+        if "state_keys" in self.cfg:
+            sk = self.cfg["state_keys"]
+            keys = sk["every"] + (sk["last"] if s == self.steps - 1 else [])
+            return {k: self.z[f"step{s}.{k}"] for k in keys}
         out = {}
         for net in ("enc", "dec", "disc"):
             for k in NET_KEYS:
@@ -80,7 +96,7 @@ class Fixture:
         """{(optimiser, 'net.key'): (m, v, t)}"""
         out = {}
         for tag, net in (("A_enc", "enc"), ("A_dec", "dec"), ("A_gen", "enc"), ("A_disc", "disc")):
-            if f"step{s}.{tag}.0.m" not in self.z.files and f"step{s}.{tag}.2.m" not in self.z.files:
+            if not any(f"step{s}.{tag}.{i}.m" in self.z.files for i in range(len(NET_KEYS))):
                 continue
             for i, k in enumerate(NET_KEYS):
                 key = f"step{s}.{tag}.{i}.m"
@@ -88,6 +104,29 @@ class Fixture:
                     out[(tag, f"{net}.{k}")] = (self.z[key], self.z[f"step{s}.{tag}.{i}.v"],
                                                 float(self.z[f"step{s}.{tag}.{i}.t"]))
         return out
+
+
+BCE_CUT = 24.0 * np.log(2.0)    # fp32: 1 / (1 + exp(-l)) == 1.0f from here on (fl(1 + e) == 1 iff e <= 2^-24)
+
+
+def bce_quantisation_bound(logits, indptr, indices, values=None):
+    """How far the reconstruction loss of an exact zero-target form (softplus(l), the kernels') may lie from the reference's
+    mean of -log(1 - fl(sigmoid(l))), from the logits alone.  Below the cut-off the reference's q = 1 - fl(sigmoid(l)) carries
+    an absolute error of at most d = 1.5 * 2^-24 (half a step of 1 + e, half a step of the quotient; 1 - s is exact) and is
+    at least 2^-24; the exact form has none to speak of.  A zero-target cell's term therefore differs by at most
+    max(log((q + d) / q), log(q / max(q - d, 2^-24))), q = 1 / (1 + exp(l)) in fp64.  From the cut-off on both charge the
+    clamped 100.  Summed over the zero-target cells, divided by B N.  (values: the targets of the CSR entries where they are
+    not all 1 - a cell of target t carries the term with the weight 1 - t.)"""
+    L = np.asarray(logits, dtype=np.float64)
+    B, N = L.shape
+    weight = np.ones((B, N))
+    rows = np.repeat(np.arange(B), np.diff(indptr))
+    weight[rows, indices] = 0.0 if values is None else 1.0 - np.asarray(values, dtype=np.float64)
+    below = L < BCE_CUT
+    q = 1.0 / (1.0 + np.exp(L[below]))
+    d = 1.5 * 2.0 ** -24
+    per_cell = np.maximum(np.log((q + d) / q), np.log(q / np.maximum(q - d, 2.0 ** -24)))
+    return float((per_cell * weight[below]).sum() / (B * N))
 
 
 # Errors of the rendezvous itself - the port a probe socket read back was taken before the ranks bound it, or the store was

@@ -3,7 +3,7 @@ real reference (tools/gen_golden.py).  Runs without a GPU."""
 import numpy as np
 import pytest
 
-from golden_util import ACT_CASES, CAT_CASES, STEP_CASES, Fixture
+from golden_util import ACT_CASES, BCE_CUT, CAT_CASES, STEP_CASES, Fixture, bce_quantisation_bound
 from oracle import aae_oracle as O
 
 TOL_LOSS = 2e-6     # relative, fp32 summation order only
@@ -62,6 +62,82 @@ def test_oracle_reproduces_reference_steps(name):
                 assert cat.opt.t == float(fx.z[f"step{s}.cond.t"])
                 np.testing.assert_allclose(cat.opt.m, fx.z[f"step{s}.cond.m"], atol=1e-9, rtol=2e-5)
                 np.testing.assert_allclose(cat.opt.v, fx.z[f"step{s}.cond.v"], atol=1e-13, rtol=5e-5)
+
+
+def test_fp32_sigmoid_is_one_from_24_ln_2_on():
+    """The cut-off every output-layer kernel carries (csrc/device_common.h kBceSatLogit), stated against torch itself: the
+    reference's fp32 sigmoid 1 / (1 + exp(-l)) is < 1 just below 24 ln 2 = 16.6355 and == 1 from there on (fl(1 + e) == 1 iff
+    e <= 2^-24) - not from 25 ln 2 = 17.3287 on, where 1 + e would round to 1 in a format with one more bit.  From there a
+    zero-target cell of F.binary_cross_entropy(sigmoid(l) + 1e-12, .) costs the clamped 100 and its gradient is 0 (aae.py:176-177,
+    693-695).  The oracle's sigmoid saturates on the same side for a sweep of logits outside step_saturated's guard, and the
+    fixture's own record says that no zero-target cell of its steps lies inside it."""
+    import torch
+    import torch.nn.functional as F
+    sat = Fixture("step_saturated").cfg["saturation"]
+    guard = sat["guard"]
+    assert abs(sat["cut"] - BCE_CUT) < 1e-12 and 1e-4 <= guard < sat["nearest_zero_target_cell"]
+    f32 = np.float32
+    cut = f32(BCE_CUT)
+    below = np.nextafter(cut, f32(0), dtype=f32)
+    for _ in range(8):                      # a few fp32 steps clear of the tie e == 2^-24 itself (1 ulp of l is 1.9e-6)
+        below = np.nextafter(below, f32(0), dtype=f32)
+    above = cut
+    for _ in range(8):
+        above = np.nextafter(above, f32(100), dtype=f32)
+    assert BCE_CUT - below < 2e-5 and above - BCE_CUT < 2e-5
+    sweep = np.concatenate([np.linspace(8.0, BCE_CUT - guard, 4001), [below, above], np.linspace(BCE_CUT + guard, 18.0, 2001),
+                            [25 * np.log(2.0) - 1e-3, 25 * np.log(2.0) + 1e-3, 30.0, 88.0, 104.0, 500.0]]).astype(f32)
+    want_one = sweep.astype(np.float64) >= BCE_CUT
+    for x in (torch.from_numpy(sweep), torch.from_numpy(sweep[:5]), torch.from_numpy(sweep[-9:])):     # vector and scalar paths
+        s = torch.sigmoid(x).numpy()
+        w = (x.numpy().astype(np.float64) >= BCE_CUT)
+        assert np.array_equal(s == 1.0, w), x.numpy()[(s == 1.0) != w]
+    assert np.array_equal(O.sigmoid(sweep) == 1.0, want_one), sweep[(O.sigmoid(sweep) == 1.0) != want_one]
+    # below the cut-off 1 - sigmoid moves in whole steps of 2^-24 and is never 0; what BCE makes of a zero target
+    q = (f32(1) - O.sigmoid(sweep[~want_one])).astype(np.float64) * 2.0 ** 24
+    assert np.array_equal(q, np.round(q)) and q.min() >= 1.0
+    x = torch.from_numpy(sweep).requires_grad_(True)
+    loss = F.binary_cross_entropy(torch.sigmoid(x) + 1e-12, torch.zeros_like(x) + 1e-12, reduction="none")
+    loss.sum().backward()
+    assert np.array_equal(loss.detach().numpy() == 100.0, want_one)
+    assert np.array_equal(x.grad.numpy() == 0.0, want_one)
+    assert float(loss.detach().numpy()[~want_one].max()) < 17.0
+
+
+def test_quantisation_bound_holds_for_the_reference_arithmetic_on_the_saturated_fixture():
+    """golden_util.bce_quantisation_bound is what the GPU tests allow the kernels' exact softplus against the reference's
+    quantised log(1 - sigmoid) - checked here cell by cell against torch's own fp32 BCE on the oracle's logits of
+    step_saturated (no zero-target cell below the cut-off is further from softplus than its bound), and in the sum: the
+    reference's recorded loss lies within the bound of the loss with exact zero-target terms, and the bound is far below
+    what a cut-off at 25 ln 2 would cost (the cells of the band at ~83 each)."""
+    import torch
+    import torch.nn.functional as F
+    fx = Fixture("step_saturated")
+    m = build_oracle(fx)
+    for s in range(fx.steps):
+        ip, idx, val = fx.batch(s)
+        m.partial_fit(ip, idx, val, fx.z[f"step{s}.z_real"], fx.masks(s), None)
+        L = m.last["logits"]
+        B, N = L.shape
+        zero = np.ones((B, N), dtype=bool)
+        zero[np.repeat(np.arange(B), np.diff(ip)), idx] = False
+        T = torch.from_numpy((~zero).astype(np.float32))
+        ref = F.binary_cross_entropy(torch.sigmoid(torch.from_numpy(L)) + 1e-12, T + 1e-12, reduction="none").numpy().astype(np.float64)
+        l64 = L.astype(np.float64)
+        exact = np.where(zero & (l64 < BCE_CUT), np.logaddexp(0.0, l64), ref)          # softplus on the quantised cells
+        below = zero & (l64 < BCE_CUT)
+        q = 1.0 / (1.0 + np.exp(l64[below]))
+        d = 1.5 * 2.0 ** -24
+        per_cell = np.maximum(np.log((q + d) / q), np.log(q / np.maximum(q - d, 2.0 ** -24)))
+        assert np.all(np.abs(ref[below] - exact[below]) <= per_cell + 1e-6 * np.abs(exact[below])), s
+        bound = bce_quantisation_bound(L, ip, idx)
+        assert abs(per_cell.sum() / (B * N) - bound) < 1e-12
+        want = fx.z[f"step{s}.losses"][0]
+        band = fx.cfg["saturation"]["steps"][s]["zero_in_band"]
+        print(f"step {s}: reference loss {want:.6f}, exact-softplus loss {exact.mean():.6f}, bound {bound:.6f}, "
+              f"a cut-off at 25 ln 2 would cost {band * (100 - 17.33) / (B * N):.4f}")
+        assert abs(exact.mean() - want) <= bound + TOL_LOSS * want
+        assert bound < band * (100 - 17.33) / (B * N) / 10
 
 
 @pytest.mark.parametrize("name", ["step_nodrop_gauss", "step_cond_concat", "step_cond_concat_bias",

@@ -4,12 +4,19 @@ and compare losses, parameters and Adam states after every step.
 
 Tolerances (fp32): losses 1e-5 relative; parameters 1e-5 absolute (Adam turns an fp32
 summation-order difference of a ~1e-8 gradient into a few 1e-6 of parameter, see
-tests/test_oracle_golden.py); reconstructions 1e-5 absolute (north star: 1e-4)."""
+tests/test_oracle_golden.py); reconstructions 1e-5 absolute (north star: 1e-4).
+
+step_saturated (dec.lin3 x 400: a thousand zero-target logits beyond 24 ln 2, where the reference's fp32 sigmoid is exactly
+1.0 - loss 100, gradient 0 - and thousands just below, where its 1 - sigmoid is quantised in steps of 2^-24) is replayed at
+the same tolerances on every quantity but the reconstruction loss, whose bound is DERIVED from the reference-side logits
+(golden_util.bce_quantisation_bound) - the kernels' softplus is exact where the reference's logarithm is not."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from golden_util import ACT_CASES, STEP_CASES, Fixture
+from golden_util import ACT_CASES, STEP_CASES, Fixture, bce_quantisation_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +59,35 @@ def check_state(fx, m, s, name):
         np.testing.assert_allclose(gv, ev, atol=1e-12, rtol=2e-4, err_msg=f"{name} {tag} v {k}")
 
 
+@functools.lru_cache(maxsize=None)
+def recon_loss_bounds(name):
+    """Per step of a fixture in the saturated regime: the derived bound on |kernels' reconstruction loss - reference's| from
+    the REFERENCE-side logits - the CPU oracle's replay of the fixture (pinned to the reference by tests/test_oracle_golden.py),
+    never the device's."""
+    from test_oracle_golden import build_oracle
+    fx = Fixture(name)
+    ora = build_oracle(fx)
+    out = []
+    for s in range(fx.steps):
+        ip, idx, val = fx.batch(s)
+        ora.partial_fit(ip, idx, val, fx.z[f"step{s}.z_real"], fx.masks(s), fx.cond_inputs(s))
+        out.append(bce_quantisation_bound(ora.last["logits"], ip, idx))
+    return tuple(out)
+
+
+def check_losses(fx, s, got, name):
+    want = fx.z[f"step{s}.losses"]
+    if "saturation" not in fx.cfg:
+        np.testing.assert_allclose(got, want, rtol=TOL_LOSS, atol=1e-6, err_msg=f"{name} step {s} losses")
+        return
+    np.testing.assert_allclose(got[1:], want[1:], rtol=TOL_LOSS, atol=1e-6, err_msg=f"{name} step {s} adversarial losses")
+    bound = recon_loss_bounds(name)[s]
+    tol = bound + TOL_LOSS * abs(want[0])
+    print(f"{name} step {s}: reconstruction loss {got[0]:.6f}, reference {want[0]:.6f}, difference {got[0] - want[0]:+.6f}, "
+          f"derived bound {bound:.6f} + {TOL_LOSS:g} relative")
+    assert abs(got[0] - want[0]) <= tol, (name, s, got[0], want[0], tol)
+
+
 @pytest.mark.parametrize("name", FUSED_CASES + ACT_CASES)
 def test_step_matches_reference(name):
     fx = Fixture(name)
@@ -62,9 +98,7 @@ def test_step_matches_reference(name):
         cond = fx.cond_inputs(s)
         cond_t = torch.as_tensor(cond[0], device=m.device) if cond else None
         m.step(csr, 0, B, cond=cond_t, masks=fx.masks(s), z_real=fx.z[f"step{s}.z_real"])
-        got = m.losses()
-        np.testing.assert_allclose(got, fx.z[f"step{s}.losses"], rtol=TOL_LOSS, atol=1e-6,
-                                   err_msg=f"{name} step {s} losses")
+        check_losses(fx, s, m.losses(), name)
         if fx.has_state(s):
             check_state(fx, m, s, name)
     # predict with the trained weights (ragged last predict batch is the host's job: one call here)
@@ -76,7 +110,7 @@ def test_step_matches_reference(name):
 
 
 @pytest.mark.parametrize("name", ["step_headline", "step_masks", "step_wide", "step_ragged", "step_cond_concat", "step_sgd",
-                                  "step_lrs", "step_selu", "step_nonorm"])
+                                  "step_lrs", "step_selu", "step_nonorm", "step_saturated"])
 def test_step_matches_reference_through_the_split_output_layer(name, monkeypatch):
     """The same replay with the output layer in the form the benchmark's shapes take (AAE_SPLIT_ANY lifts the size rule
     that keeps small layers on the single launch): the CRITICAL launch with its fp32 products emulated on the bf16 matrix
@@ -112,19 +146,26 @@ def test_step_matches_reference_on_the_k_split_weight_gradient_tiles(name, monke
 
 
 def test_saturated_logits_cost_the_same_on_both_forms_of_the_output_layer(monkeypatch):
-    """F.binary_cross_entropy clamps its logarithms at -100, and sigmoid rounds to exactly 1.0f from a logit of 17.33 on: such a
-    cell of a zero target costs 100 and its s (1 - s) factor zeroes its gradient (aae.py:176-177, 693-695) - the output-layer
-    kernels keep both (csrc/gemm_f32.h bce_elem_t0).  Since r6 the CRITICAL launch takes the loss of a cell in parts - one
-    logarithm per thread and tile, of the product of its cells' 1 + e (bce_elem_t0_parts) -, where a saturated cell, a target's
-    exact form and the series for small e each leave the product alone.  dec.lin3 scaled until hundreds of logits saturate (and
-    as many lie far below zero): the reconstruction loss of the first step - a function of the initial parameters alone - on
-    the single launch (the per-cell form) and on the critical + deferred launches (the form in parts), to 1e-6; the saturated
-    cells' 100s are in it.  (Against the reference such a model's loss is a matter of fp32's 1 - sigmoid(l) between logits of
-    ~10 and 17.33 - the zero-target form is exact there where the reference's log(1 - x) is quantised, DESIGN.md 3.5 -, which
-    is why this compares the two forms with each other; every fixture compares both with the reference.)"""
+    """F.binary_cross_entropy clamps its logarithms at -100, and the fp32 sigmoid rounds to exactly 1.0f from a logit of
+    24 ln 2 = 16.64 on: such a cell of a zero target costs 100 and its s (1 - s) factor zeroes its gradient (aae.py:176-177,
+    693-695) - the output-layer kernels keep both (csrc/gemm_f32.h bce_elem_t0, device_common.h kBceSatLogit).  Since r6 the
+    CRITICAL launch takes the loss of a cell in parts - one logarithm per thread and tile, of the product of its cells' 1 + e
+    (bce_elem_t0_parts) -, where a saturated cell, a target's exact form and the series for small e each leave the product
+    alone.  dec.lin3 scaled until hundreds of logits saturate (and as many lie far below zero): the reconstruction loss of
+    the first step - a function of the initial parameters alone - on the single launch (the per-cell form) and on the
+    critical + deferred launches (the form in parts), to 1e-6; the saturated cells' 100s are in it.  Both are also held to
+    the CPU oracle's loss of the same step (the reference's arithmetic, cut-off included) within the derived bound of the
+    quantisation of its 1 - sigmoid(l) below the cut-off (golden_util.bce_quantisation_bound on the oracle's logits) plus
+    TOL_LOSS relative: two forms that are wrong the same way do not pass."""
+    from test_oracle_golden import build_oracle
     fx = Fixture("step_headline")
     params = fx.init_params()
     params["dec.lin3.weight"] = (params["dec.lin3.weight"] * np.float32(400.0)).astype(np.float32)
+    ora = build_oracle(fx)
+    ora.p.update({k: v.copy() for k, v in params.items()})
+    ip, idx, val = fx.batch(0)
+    want = ora.partial_fit(ip, idx, val, fx.z["step0.z_real"], fx.masks(0), None)[0]
+    bound = bce_quantisation_bound(ora.last["logits"], ip, idx)
     losses, nsat = [], 0
     for split in (False, True):
         if split:
@@ -136,10 +177,13 @@ def test_saturated_logits_cost_the_same_on_both_forms_of_the_output_layer(monkey
         nsat = int((full == 1.0).sum())
         m.step(csr, 0, csr.shape[0], masks=fx.masks(0), z_real=fx.z["step0.z_real"])
         losses.append(np.asarray(m.losses(), dtype=np.float64))
+    print("saturated scores of the batch:", nsat, "of", full.size, "| reconstruction loss, single launch | critical launch | oracle:",
+          losses[0][0], losses[1][0], want, "| derived bound", bound)
     assert nsat >= 200, ("the case is meant to saturate", nsat)
     assert losses[0][0] > 100.0 * nsat / full.size, ("the saturated cells' 100s are missing from the loss", losses[0], nsat, full.size)
     np.testing.assert_allclose(losses[1][0], losses[0][0], rtol=1e-6)
-    print("saturated scores of the batch:", nsat, "of", full.size, "| reconstruction loss, single launch | critical launch:", losses[0][0], losses[1][0])
+    for got in (losses[0][0], losses[1][0]):
+        assert abs(got - want) <= bound + TOL_LOSS * want, (got, want, bound)
 
 
 def test_plain_autoencoder_matches_reference():
