@@ -41,6 +41,8 @@
 
 using namespace aae;
 
+#include "kernel_pick.h"
+
 #include <map>
 static std::map<std::string, std::string> g_options;      // aae_set_option: name -> value (wins over the environment)
 const char* option_value(const char* name) {
@@ -107,6 +109,10 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     m->noise_next = nullptr; m->noise_ld = 0; m->dense_step = false;
     m->ae_only = cfg->model_kind == 1 || m->vae;
     m->lazy = true;    // deferred Adam on W1T in both gradient modes (export mode exchanges packed rows)
+    // the dynamic-LDS limit of a kernel family (kernel_pick.h each_*): a failure clears the capability flag it belongs to.
+    // Every output-layer family gets the chip's whole LDS (a launch asks for its family's own *_lds_bytes)
+    auto limit = [](bool& ok, size_t bytes) { return [&ok, bytes](auto kernel) { ok = ok && raise_lds_limit(kernel, bytes); }; };
+    const int maxlds = 160 * 1024;
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
@@ -120,30 +126,13 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         // (a decoder input [z | condition | 1] of up to 2 x 208 columns: two k-parts on the 4-row kernel; the VAE's programs keep 208)
         m->use_chain = (m->h + 1 <= 208) && (m->c + 1 <= 208) && (m->cp + 1 <= (cfg->model_kind == 3 ? 208 : 2 * 208)) &&
                        !m->opt.no_chain;      // (the code itself has to fit a slot: only the condition block may exceed it)
-        if (m->use_chain && (hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 kCSlots * kCR * kCL * (int)sizeof(float)) != hipSuccess ||
-                             hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 kCSlots * kCR * kCL * (int)sizeof(float)) != hipSuccess))
-            m->use_chain = false;
+        const size_t chain_lds = kCSlots * kCR * kCL * sizeof(float);
+        if (m->use_chain) each_chain(false, limit(m->use_chain, chain_lds));
         // (the r6 activation classes live in chain_kernel<.., true> alone: device_common.h act_fwd)
         m->act_nm = cfg->activation > AAE_ACT_LEAKYRELU;
-        if (m->use_chain && m->act_nm &&
-            (hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kCSlots * kCR * kCL * (int)sizeof(float)) != hipSuccess ||
-             hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kCSlots * kCR * kCL * (int)sizeof(float)) != hipSuccess))
-            m->use_chain = false;
-        m->use_chain4 = m->use_chain && !m->act_nm && !m->opt.chain16 &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(chain4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            kCSlots * kCR * kCL * (int)sizeof(float)) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(chain4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            kCSlots * kCR * kCL * (int)sizeof(float)) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(chain4_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            kCSlots * kCR * kCL * (int)sizeof(float)) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(chain4_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            kCSlots * kCR * kCL * (int)sizeof(float)) == hipSuccess;
+        if (m->use_chain && m->act_nm) each_chain(true, limit(m->use_chain, chain_lds));
+        m->use_chain4 = m->use_chain && !m->act_nm && !m->opt.chain16;
+        if (m->use_chain4) each_chain4(limit(m->use_chain4, chain_lds));
         if (m->use_chain && m->cp + 1 > 208 && !m->use_chain4) m->use_chain = false;
         m->x16_rows = m->opt.x16_rows;
         m->dw_ksplit_rows = 256;                       // (the handle is zero-filled after construction: no default member values)
@@ -154,18 +143,14 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
                 m->cnt_host = static_cast<int*>(hp); m->cnt_host_dev = static_cast<int*>(dp); *m->cnt_host = 0;
             } else { if (hp) (void)hipHostFree(hp); (void)hipGetLastError(); }
         }
-        m->x16_ok = m->use_chain4 && m->FXi[P_W2] != nullptr &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(chain16x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kX16Lds) == hipSuccess &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(chain16x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kX16Lds) == hipSuccess &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(chain16x3_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kX16Lds) == hipSuccess;
+        m->x16_ok = m->use_chain4 && m->FXi[P_W2] != nullptr;
+        if (m->x16_ok) each_chain16x3(limit(m->x16_ok, kX16Lds));
         m->force_unfused = cfg->unfused_decoder == 1;   // debugging / A-B switch: unfused_decoder = 1 keeps the 3-kernel path
         if (m->fused_ok) {
-            const int maxlds = 160 * 1024;
-            hipError_t e1 = aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<4>), reinterpret_cast<const void*>(dec_fused_kernel<4, kDecFused, true>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds);
-            hipError_t e2 = aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<7>), reinterpret_cast<const void*>(dec_fused_kernel<7, kDecFused, true>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds);
-            hipError_t e3 = aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<13>), reinterpret_cast<const void*>(dec_fused_kernel<13, kDecFused, true>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds);
-            hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(tile_bucket_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds - 2048);
-            m->bucket_wide_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(tile_bucket_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds - 16384) == hipSuccess;
+            each_dec_fused(kDecFused, limit(m->fused_ok, maxlds));
+            if (m->bf16) each_dec_fused_bf16(kDecFused, limit(m->fused_ok, maxlds));
+            if (!raise_lds_limit(tile_bucket_kernel, maxlds - 2048)) m->fused_ok = false;
+            m->bucket_wide_ok = raise_lds_limit(tile_bucket_wide_kernel, maxlds - 16384);
             {   //  the wide bucket builder keeps other workgroups off its CU by its register count (buckets.h: a clobber of
                 // v127) on top of its LDS claim: say so once if a compiler stops honouring the clobber - results do not depend on it
                 hipFuncAttributes fa;
@@ -176,20 +161,15 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
                 }
                 (void)hipGetLastError();
             }
-            if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) m->fused_ok = false;
-            if (m->bf16 &&
-                (hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds) != hipSuccess ||
-                 hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds) != hipSuccess ||
-                 hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<13>), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds) != hipSuccess))
-                m->fused_ok = false;
         }
     }
     m->late_enabled = !m->opt.no_late_join;
     m->early_enabled = true;
     m->early_any = m->opt.early_any;        // (tests: the early prefetch at every batch size)
-    m->rank_ok = m->fused_ok && m->use_chain4 && !m->vae && !m->opt.no_rank_fused && rank_set_attributes();
-    m->w1_big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(w1_item_update_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(sizeof(int) * w1_items_lds_words(16384))) == hipSuccess;
+    m->rank_ok = m->fused_ok && m->use_chain4 && !m->vae && !m->opt.no_rank_fused;      // (the rank kernels' limit: what they launch with)
+    if (m->rank_ok) each_rank_x3([&](RankKernel k, int nb) { m->rank_ok = m->rank_ok && raise_lds_limit(k, rank_x3_lds_bytes(nb)); });
+    if (m->rank_ok) each_rank_x3v2([&](RankKernel k, int nb) { m->rank_ok = m->rank_ok && raise_lds_limit(k, rank_x3v2_lds_bytes(nb)); });
+    m->w1_big_lds = raise_lds_limit(w1_item_update_kernel, sizeof(int) * w1_items_lds_words(16384));
     (void)hipGetLastError();
     m->grad_scale = 1.f;
     m->rng_row0 = 0; m->rng_global = 0;
@@ -226,12 +206,8 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     }
     if (side_ok && m->fused_ok && m->bf16 && m->split_wgs > 0 &&
         (size_t)((m->N + kBU - 1) / kBU) * kBU * bf_stride(4) <= (size_t)m->R * m->ldn) {      // (room for the stored gT images in the G scratch)
-        m->split_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<4, kDecCrit>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<7, kDecCrit>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<13, kDecCrit>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<4, kDecOpt>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<7, kDecOpt>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fused_bf16_kernel<13, kDecOpt>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+        m->split_ok = true;
+        for (int mode : {kDecCrit, kDecOpt}) each_dec_fused_bf16(mode, limit(m->split_ok, maxlds));
         (void)hipGetLastError();
     }
     // (bf16 mode too: its output layer runs the same kernels with every operand rounded to bf16 - DecFusedArgs::one_term - when
@@ -239,28 +215,15 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     if (side_ok && m->fused_ok && m->split_wgs > 0 && 
         (size_t)((m->N + kTI - 1) / kTI) * kTI * (size_t)std::min(m->R, 16 * kMB) * sizeof(float) < (size_t)0x7FFFFFF0u) {
         bool ok = true;
-        ok = ok && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<4, kDecCrit>), reinterpret_cast<const void*>(dec_fused_kernel<4, kDecCrit, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<7, kDecCrit>), reinterpret_cast<const void*>(dec_fused_kernel<7, kDecCrit, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<13, kDecCrit>), reinterpret_cast<const void*>(dec_fused_kernel<13, kDecCrit, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<4, kDecOpt>), reinterpret_cast<const void*>(dec_fused_kernel<4, kDecOpt, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<7, kDecOpt>), reinterpret_cast<const void*>(dec_fused_kernel<7, kDecOpt, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<13, kDecOpt>), reinterpret_cast<const void*>(dec_fused_kernel<13, kDecOpt, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<4, kDecOptAcc>), reinterpret_cast<const void*>(dec_fused_kernel<4, kDecOptAcc, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<7, kDecOptAcc>), reinterpret_cast<const void*>(dec_fused_kernel<7, kDecOptAcc, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_fused_kernel<13, kDecOptAcc>), reinterpret_cast<const void*>(dec_fused_kernel<13, kDecOptAcc, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_opt_blocks_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_opt_blocks_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_opt_blocks_kernel<13>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+        for (int mode : {kDecCrit, kDecOpt, kDecOptAcc}) each_dec_fused(mode, limit(ok, maxlds));
+        each_dec_opt_blocks(limit(ok, maxlds));
         if (!m->bf16) m->split_ok = ok;
-        m->x3_ok = ok
-                && aae_attr2(reinterpret_cast<const void*>(dec_crit_x3_kernel<4>), reinterpret_cast<const void*>(dec_crit_x3_kernel<4, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_crit_x3_kernel<7>), reinterpret_cast<const void*>(dec_crit_x3_kernel<7, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_crit_x3_kernel<13>), reinterpret_cast<const void*>(dec_crit_x3_kernel<13, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_crit_x3_kernel<13, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<4>), reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<7>), reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<7, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<13>), reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<13, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_opt_blocks_x3_kernel<13, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+        m->x3_ok = ok;
+        each_dec_crit_x3(false, limit(m->x3_ok, maxlds));
+        each_dec_opt_blocks_x3(limit(m->x3_ok, maxlds));
+        // (dec_opt_x3_kernel: the deferred launch of the fp32 step too.  Its 58 112 bytes fit the default limit today, and
+        //  raising the limit of a kernel that already fits is harmless - a wider kXGS then does not fail at the launch)
+        each_dec_opt_x3(false, limit(m->x3_ok, maxlds));
         (void)hipGetLastError();
         if (m->bf16) {
             m->bf16_x3 = m->x3_ok && ok;
@@ -275,16 +238,9 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
             // LDS (abi_output_layer.h), which no other workgroup of the step fits beside: 0.1648 ms at the old width, 0.162-0.164
             // on 48-64 workgroups (tools/debug/bf16_one_sweep.sh; a claim of 120 KB leaves the 24 KB weight-gradient workgroups
             // in: 0.1865).
-            m->bf16_one = m->bf16_x3
-                && aae_attr2(reinterpret_cast<const void*>(dec_crit_x3_kernel<4, false, true>), reinterpret_cast<const void*>(dec_crit_x3_kernel<4, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_crit_x3_kernel<7, false, true>), reinterpret_cast<const void*>(dec_crit_x3_kernel<7, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_crit_x3_kernel<13, false, true>), reinterpret_cast<const void*>(dec_crit_x3_kernel<13, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_x3_kernel<4, true>), reinterpret_cast<const void*>(dec_opt_x3_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_x3_kernel<7, true>), reinterpret_cast<const void*>(dec_opt_x3_kernel<7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_x3_kernel<13, true>), reinterpret_cast<const void*>(dec_opt_x3_kernel<13, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_x3_kernel<4>), reinterpret_cast<const void*>(dec_opt_x3_kernel<4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_x3_kernel<7>), reinterpret_cast<const void*>(dec_opt_x3_kernel<7, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess
-                && aae_attr2(reinterpret_cast<const void*>(dec_opt_x3_kernel<13>), reinterpret_cast<const void*>(dec_opt_x3_kernel<13, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+            m->bf16_one = m->bf16_x3;
+            each_dec_crit_x3(true, limit(m->bf16_one, maxlds));
+            each_dec_opt_x3(true, limit(m->bf16_one, maxlds));
             (void)hipGetLastError();
         }
         if (m->x3_ok) {
@@ -345,12 +301,7 @@ int aae_destroy(aae_handle h) {
     }
     if (h->dp_scratch) (void)hipFree(h->dp_scratch);
     if (h->cnt_host) (void)hipHostFree(h->cnt_host);
-    if (h->ev_crit) (void)hipEventDestroy(h->ev_crit);
-    if (h->ev_opt) (void)hipEventDestroy(h->ev_opt);
-    if (h->ev_head) (void)hipEventDestroy(h->ev_head);
-    if (h->ev_pf) (void)hipEventDestroy(h->ev_pf);
-    if (h->ev_bk) (void)hipEventDestroy(h->ev_bk);
-    if (h->ev_end) (void)hipEventDestroy(h->ev_end);
+    for (hipEvent_t e : {h->ev_crit, h->ev_opt, h->ev_head, h->ev_pf, h->ev_bk, h->ev_end}) if (e) (void)hipEventDestroy(e);
     if (h->prof_ev) {
         for (int k = 0; k < AAE_K_N; ++k)
             for (auto& pr : h->prof_ev[k]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }

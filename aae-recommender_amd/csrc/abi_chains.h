@@ -207,15 +207,51 @@ static bool x16_program_ok(const ChainProgram& P) {
     return true;
 }
 
+// debug (AAE_CHAIN_TS): the per-op timeline workgroup 0 of a chain launch left in `ts_dev`.  x16: chain16x3_kernel's three
+// stamps per op; else chain_kernel / chain4_kernel's one (four: + the matrix phase of op 2, chain4.h)
+int print_chain_timeline(const ChainProgram& P, const unsigned long long* ts_dev, bool x16, bool four, hipStream_t s) {
+    static const char* names[] = {"LOAD", "LINEAR", "LINEAR_DX", "FINAL_FWD", "FINAL_BWD", "ADV", "DROPACT", "SLABSUM", "ACTBWD", "STORE", "REPARAM", "REPARAM_BWD", "DISC_HEAD", "PRIOR"};
+    unsigned long long h[128];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h, ts_dev, sizeof(h), hipMemcpyDeviceToHost));
+    if (x16) {
+        fprintf(stderr, "[chain16x3 rows=%d nops=%d total=%.2fus; per op: whole (products | epilogue | barrier)]", P.rows, P.nops, (h[3 * P.nops] - h[0]) * 0.01);
+        for (int i = 0; i < P.nops; ++i) {
+            const bool lin = P.ops[i].kind == COP_LINEAR || P.ops[i].kind == COP_LINEAR_DX;
+            fprintf(stderr, " %s(K%d,N%d)=%.2f", names[P.ops[i].kind], P.ops[i].K, P.ops[i].N, (h[3 * i + 3] - h[3 * i]) * 0.01);
+            if (lin) fprintf(stderr, "(%.2f|%.2f|%.2f)", (h[3 * i + 1] - h[3 * i]) * 0.01, (h[3 * i + 2] - h[3 * i + 1]) * 0.01, (h[3 * i + 3] - h[3 * i + 2]) * 0.01);
+        }
+        fprintf(stderr, "\n");
+        return AAE_OK;
+    }
+    fprintf(stderr, "[chain rows=%d nops=%d total=%.2fus]", P.rows, P.nops, (h[P.nops] - h[0]) * 0.01);
+    for (int i = 0; i < P.nops; ++i)
+        fprintf(stderr, " %s(K%d,N%d%s%s)=%.2f", names[P.ops[i].kind], P.ops[i].K, P.ops[i].N,
+                P.ops[i].out ? ",st" : "", P.ops[i].out2 ? ",st2" : "", (h[i + 1] - h[i]) * 0.01);
+    fprintf(stderr, "\n");
+    if (P.nops <= 2) return AAE_OK;
+    fprintf(stderr, "   [op 2, wave 0 of workgroup 0] loads+mfma+partials=%.2f wait-barrier=%.2f epi-ctx=%.2f epilogue=%.2f barrier=%.2f (us)\n",
+            (h[21] - h[20]) * 0.01, (h[22] - h[21]) * 0.01, (h[23] - h[22]) * 0.01, (h[24] - h[23]) * 0.01, (h[25] - h[24]) * 0.01);
+    if (!four) return AAE_OK;
+    fprintf(stderr, "   [op 2: matrix phase %.2f us = %.0f shader clocks -> %.2f GHz]\n", (h[64 + 50] - h[64 + 48]) * 0.01,
+            (double)(h[64 + 51] - h[64 + 49]), (double)(h[64 + 51] - h[64 + 49]) / ((h[64 + 50] - h[64 + 48]) * 10.0));
+    for (int k = 0; k < 3; ++k) {
+        fprintf(stderr, "   [op 2, every wave, us after the op's start: %s]", k == 0 ? "loads issued" : k == 1 ? "first chunk multiplied" : "partial sums stored");
+        for (int w = 0; w < 16; ++w) fprintf(stderr, " %.2f", ((double)h[64 + 16 * k + w] - (double)h[64 + 48]) * 0.01);
+        fprintf(stderr, "\n");
+    }
+    return AAE_OK;
+}
+
 int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
     if (cb.P.nops > kCMaxOps) return fail(AAE_ESTATE, "chain program too long");
-    const int grid = (cb.P.rows + kCR - 1) / kCR + (cb.P.bk.enabled ? 1 : 0);
     const bool want_ts = m->opt.chain_ts;      // debug: per-op timeline of workgroup 0
     static unsigned long long* ts_dev = nullptr;
     if (want_ts) {
         if (!ts_dev && hipMalloc(&ts_dev, 128 * sizeof(unsigned long long)) != hipSuccess) return fail(AAE_EHIP, "ts alloc");
         cb.P.ts = ts_dev;
     }
+    const bool ts_kernel = want_ts && !m->bf16;      // (the 4-row and 16-row kernels' timeline instantiations are fp32 ones)
     ProfScope ps(m, AAE_K_CHAIN, s);
     // 4-row workgroups (chain4.h) whenever every linear op of the program has its k-major matrix (all but the VAE's)
     bool four = m->use_chain4;
@@ -242,63 +278,20 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
                 }
                 X.x16_first_lin[cls] = nxt;
             }
-            const int grid16 = (X.rows + kX16R - 1) / kX16R;
-            if (want_ts && !m->bf16) hipLaunchKernelGGL((chain16x3_kernel<false, true>), dim3(grid16), dim3(kX16T), kX16Lds, s, X);
-            else if (m->bf16) hipLaunchKernelGGL(chain16x3_kernel<true>, dim3(grid16), dim3(kX16T), kX16Lds, s, X);
-            else hipLaunchKernelGGL(chain16x3_kernel<false>, dim3(grid16), dim3(kX16T), kX16Lds, s, X);
+            const ChainKernel kernel = pick_chain16x3(m->bf16, ts_kernel);
+            if (!kernel) return fail(AAE_ESTATE, "no chain16x3 kernel is compiled for this mode");
+            hipLaunchKernelGGL(kernel, dim3((X.rows + kX16R - 1) / kX16R), dim3(kX16T), kX16Lds, s, X);
             LAUNCHCHK("chain16x3_kernel");
-            if (want_ts && !m->bf16) {
-                unsigned long long h[128];
-                HIPCHK(hipStreamSynchronize(s));
-                HIPCHK(hipMemcpy(h, ts_dev, sizeof(h), hipMemcpyDeviceToHost));
-                static const char* names[] = {"LOAD", "LINEAR", "LINEAR_DX", "FINAL_FWD", "FINAL_BWD", "ADV", "DROPACT", "SLABSUM", "ACTBWD", "STORE", "REPARAM", "REPARAM_BWD", "DISC_HEAD", "PRIOR"};
-                fprintf(stderr, "[chain16x3 rows=%d nops=%d total=%.2fus; per op: whole (products | epilogue | barrier)]", X.rows, X.nops, (h[3 * X.nops] - h[0]) * 0.01);
-                for (int i = 0; i < X.nops; ++i) {
-                    const bool lin = X.ops[i].kind == COP_LINEAR || X.ops[i].kind == COP_LINEAR_DX;
-                    fprintf(stderr, " %s(K%d,N%d)=%.2f", names[X.ops[i].kind], X.ops[i].K, X.ops[i].N, (h[3 * i + 3] - h[3 * i]) * 0.01);
-                    if (lin) fprintf(stderr, "(%.2f|%.2f|%.2f)", (h[3 * i + 1] - h[3 * i]) * 0.01, (h[3 * i + 2] - h[3 * i + 1]) * 0.01, (h[3 * i + 3] - h[3 * i + 2]) * 0.01);
-                }
-                fprintf(stderr, "\n");
-            }
-            return AAE_OK;
+            return ts_kernel ? print_chain_timeline(X, ts_dev, true, four, s) : AAE_OK;
         }
     }
-    if (four) {
-        const int grid4 = (cb.P.rows + kR4 - 1) / kR4 + (cb.P.bk.enabled ? 1 : 0);
-        if (want_ts && !m->bf16) hipLaunchKernelGGL((chain4_kernel<false, true>), dim3(grid4), dim3(kC4T), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-        else if (m->bf16 && !cb.P.kslices) hipLaunchKernelGGL((chain4_kernel<true, false, true>), dim3(grid4), dim3(kC4T), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-        else if (m->bf16) hipLaunchKernelGGL(chain4_kernel<true>, dim3(grid4), dim3(kC4T), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-        else hipLaunchKernelGGL(chain4_kernel<false>, dim3(grid4), dim3(kC4T), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-    } else if (m->act_nm) {
-        if (m->bf16) hipLaunchKernelGGL((chain_kernel<true, true>), dim3(grid), dim3(kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-        else hipLaunchKernelGGL((chain_kernel<false, true>), dim3(grid), dim3(kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-    } else if (m->bf16) hipLaunchKernelGGL(chain_kernel<true>, dim3(grid), dim3(kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
-    else hipLaunchKernelGGL(chain_kernel<false>, dim3(grid), dim3(kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
+    // (chain4: bf16 programs without k-slices take the column form)
+    const ChainKernel kernel = four ? pick_chain4(m->bf16, ts_kernel, m->bf16 && !cb.P.kslices) : pick_chain(m->bf16, m->act_nm);
+    if (!kernel) return fail(AAE_ESTATE, "no chain kernel is compiled for this mode");
+    const int grid = (cb.P.rows + (four ? kR4 : kCR) - 1) / (four ? kR4 : kCR) + (cb.P.bk.enabled ? 1 : 0);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(four ? kC4T : kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
     LAUNCHCHK("chain_kernel");
-    if (want_ts) {
-        unsigned long long h[128];
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(h, ts_dev, sizeof(h), hipMemcpyDeviceToHost));
-        static const char* names[] = {"LOAD", "LINEAR", "LINEAR_DX", "FINAL_FWD", "FINAL_BWD", "ADV", "DROPACT", "SLABSUM", "ACTBWD", "STORE", "REPARAM", "REPARAM_BWD", "DISC_HEAD", "PRIOR"};
-        fprintf(stderr, "[chain rows=%d nops=%d total=%.2fus]", cb.P.rows, cb.P.nops, (h[cb.P.nops] - h[0]) * 0.01);
-        for (int i = 0; i < cb.P.nops; ++i)
-            fprintf(stderr, " %s(K%d,N%d%s%s)=%.2f", names[cb.P.ops[i].kind], cb.P.ops[i].K, cb.P.ops[i].N,
-                    cb.P.ops[i].out ? ",st" : "", cb.P.ops[i].out2 ? ",st2" : "", (h[i + 1] - h[i]) * 0.01);
-        fprintf(stderr, "\n");
-        if (cb.P.nops > 2)
-            fprintf(stderr, "   [op 2, wave 0 of workgroup 0] loads+mfma+partials=%.2f wait-barrier=%.2f epi-ctx=%.2f epilogue=%.2f barrier=%.2f (us)\n",
-                    (h[21] - h[20]) * 0.01, (h[22] - h[21]) * 0.01, (h[23] - h[22]) * 0.01, (h[24] - h[23]) * 0.01, (h[25] - h[24]) * 0.01);
-        if (cb.P.nops > 2 && four)
-            fprintf(stderr, "   [op 2: matrix phase %.2f us = %.0f shader clocks -> %.2f GHz]\n", (h[64 + 50] - h[64 + 48]) * 0.01,
-                    (double)(h[64 + 51] - h[64 + 49]), (double)(h[64 + 51] - h[64 + 49]) / ((h[64 + 50] - h[64 + 48]) * 10.0));
-        if (cb.P.nops > 2 && four)
-            for (int k = 0; k < 3; ++k) {
-                fprintf(stderr, "   [op 2, every wave, us after the op's start: %s]", k == 0 ? "loads issued" : k == 1 ? "first chunk multiplied" : "partial sums stored");
-                for (int w = 0; w < 16; ++w) fprintf(stderr, " %.2f", ((double)h[64 + 16 * k + w] - (double)h[64 + 48]) * 0.01);
-                fprintf(stderr, "\n");
-            }
-    }
-    return AAE_OK;
+    return want_ts ? print_chain_timeline(cb.P, ts_dev, false, four, s) : AAE_OK;
 }
 
 // up to 4 weight-gradient jobs in one launch

@@ -16,13 +16,6 @@
 
 namespace {
 
-constexpr int kRankBb = 16 * kMB;          // (r1-r4: rows per row block of the rank kernels - the training kernels' 7 MFMA row blocks; now kRankGR2, rank_x3.h)
-// which of the two rank kernels a call takes (rank_x3.h) and its rows per row block
-inline bool rank_v2_nb(int NB, int K) {
-    constexpr bool v1 = false;       // (rank_x3_kernel, the r4 wave mapping: kept for K != 10, rank_x3.h)
-    return !v1 && (K == 10 || (K == 20 && NB < 13));                 // (the other list sizes spill registers in the v2 mapping: they keep v1)
-}
-inline int rank_bb(const aae_model*, int) { return kRankGR2; }      // (both kernels: 128-row blocks)
 constexpr int kRankMaxRows = 4096;
 
 struct RankPlan {
@@ -42,7 +35,7 @@ RankPlan rank_plan(const aae_model* m, int rows, int k, float* base) {
     RankPlan p; memset(&p, 0, sizeof(p));
     p.rows = rows; p.K = rank_K(k);
     const int ntiles = (m->N + kTI - 1) / kTI;
-    p.bb = rank_bb(m, p.K);
+    p.bb = kRankGR2;          // (both rank kernels: 128-row blocks, rank_x3.h)
     p.nblk = (rows + p.bb - 1) / p.bb;
     p.wgs = std::max(1, std::min(m->n_cu / std::max(1, p.nblk), ntiles));
     p.kw = (m->N + 31) / 32;
@@ -86,62 +79,17 @@ int rank_rows_cap(const aae_model* m, int k) {
     return lo;
 }
 
-template <int NB>
-int launch_rank_nb(const RankArgs& a, int K, int grid, hipStream_t s) {
+// one launch of a rank kernel: rank_x3v2 / rank_x3 by rank_v2_nb (kernel_pick.h), or the K = 32 kernel's front end with
+// the collect epilogue (rank_long.h)
+int launch_rank(const RankArgs& a, int nb, int K, bool collect, int grid, hipStream_t s) {
     const bool win = x3_big_span(a.N, a.ldv);      // (dec.lin3 beyond 2^31 bytes: the moving-window instantiations, dec_fused.h)
-    if (rank_v2_nb(NB, K)) {
-        const uint32_t lds2 = (uint32_t)rank_x3v2_lds_bytes(NB);
-        switch (K) {
-            case 10: { if (win) hipLaunchKernelGGL((rank_x3v2_kernel<NB, 10, true>), dim3(grid), dim3(kNT), lds2, s, a); else hipLaunchKernelGGL((rank_x3v2_kernel<NB, 10>), dim3(grid), dim3(kNT), lds2, s, a); } break;
-            case 20: { if (win) hipLaunchKernelGGL((rank_x3v2_kernel<NB, 20, true>), dim3(grid), dim3(kNT), lds2, s, a); else hipLaunchKernelGGL((rank_x3v2_kernel<NB, 20>), dim3(grid), dim3(kNT), lds2, s, a); } break;
-            default: { if (win) hipLaunchKernelGGL((rank_x3v2_kernel<NB, 32, true>), dim3(grid), dim3(kNT), lds2, s, a); else hipLaunchKernelGGL((rank_x3v2_kernel<NB, 32>), dim3(grid), dim3(kNT), lds2, s, a); } break;
-        }
-        LAUNCHCHK("rank_x3v2");
-        return AAE_OK;
-    }
-    const uint32_t lds = (uint32_t)rank_x3_lds_bytes(NB);
-    switch (K) {
-        case 10: { if (win) hipLaunchKernelGGL((rank_x3_kernel<NB, 10, true>), dim3(grid), dim3(kNT), lds, s, a); else hipLaunchKernelGGL((rank_x3_kernel<NB, 10>), dim3(grid), dim3(kNT), lds, s, a); } break;
-        case 20: { if (win) hipLaunchKernelGGL((rank_x3_kernel<NB, 20, true>), dim3(grid), dim3(kNT), lds, s, a); else hipLaunchKernelGGL((rank_x3_kernel<NB, 20>), dim3(grid), dim3(kNT), lds, s, a); } break;
-        default: { if (win) hipLaunchKernelGGL((rank_x3_kernel<NB, 32, true>), dim3(grid), dim3(kNT), lds, s, a); else hipLaunchKernelGGL((rank_x3_kernel<NB, 32>), dim3(grid), dim3(kNT), lds, s, a); } break;
-    }
-    LAUNCHCHK("rank_x3");
+    const bool v2 = !collect && rank_v2_nb(nb, K);
+    const RankKernel kernel = v2 ? pick_rank_x3v2(nb, K, win) : pick_rank_x3(nb, collect ? 1 : K, win, collect);
+    if (!kernel) return fail(AAE_ESTATE, "no rank kernel is compiled for this hidden width and list size");
+    const uint32_t lds = (uint32_t)(v2 ? rank_x3v2_lds_bytes(nb) : rank_x3_lds_bytes(nb));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kNT), lds, s, a);
+    LAUNCHCHK(v2 ? "rank_x3v2" : collect ? "rank_x3 (collect)" : "rank_x3");
     return AAE_OK;
-}
-
-// the K = 32 kernel's front end with the collect epilogue (rank_long.h)
-template <int NB>
-int launch_collect_nb(const RankArgs& a, int grid, hipStream_t s) {
-    const uint32_t lds = (uint32_t)rank_x3_lds_bytes(NB);
-    if (x3_big_span(a.N, a.ldv)) hipLaunchKernelGGL((rank_x3_kernel<NB, 1, true, true>), dim3(grid), dim3(kNT), lds, s, a);
-    else hipLaunchKernelGGL((rank_x3_kernel<NB, 1, false, true>), dim3(grid), dim3(kNT), lds, s, a);
-    LAUNCHCHK("rank_x3 (collect)");
-    return AAE_OK;
-}
-
-bool rank_set_attributes() {
-    bool ok = true;
-    auto set = [&](const void* f, int NB) {
-        ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_x3_lds_bytes(NB)) == hipSuccess;
-    };
-    set(reinterpret_cast<const void*>(rank_x3_kernel<4, 10>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<4, 10, true>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<4, 20>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<4, 20, true>), 4);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<4, 32>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<4, 32, true>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 10>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 10, true>), 7);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<7, 20>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 20, true>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 32>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 32, true>), 7);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<13, 10>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 10, true>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 20>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 20, true>), 13);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<13, 32>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 32, true>), 13);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<4, 1, false, true>), 4); set(reinterpret_cast<const void*>(rank_x3_kernel<4, 1, true, true>), 4);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<7, 1, false, true>), 7); set(reinterpret_cast<const void*>(rank_x3_kernel<7, 1, true, true>), 7);
-    set(reinterpret_cast<const void*>(rank_x3_kernel<13, 1, false, true>), 13); set(reinterpret_cast<const void*>(rank_x3_kernel<13, 1, true, true>), 13);
-    auto set2 = [&](const void* f, int NB) {
-        ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_x3v2_lds_bytes(NB)) == hipSuccess;
-    };
-    set2(reinterpret_cast<const void*>(rank_x3v2_kernel<4, 10>), 4); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<4, 10, true>), 4); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<4, 20>), 4); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<4, 20, true>), 4);
-    set2(reinterpret_cast<const void*>(rank_x3v2_kernel<4, 32>), 4); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<4, 32, true>), 4); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<7, 10>), 7); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<7, 10, true>), 7);
-    set2(reinterpret_cast<const void*>(rank_x3v2_kernel<7, 20>), 7); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<7, 20, true>), 7); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<7, 32>), 7); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<7, 32, true>), 7);
-    set2(reinterpret_cast<const void*>(rank_x3v2_kernel<13, 10>), 13); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<13, 10, true>), 13); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<13, 20>), 13); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<13, 20, true>), 13);
-    set2(reinterpret_cast<const void*>(rank_x3v2_kernel<13, 32>), 13); set2(reinterpret_cast<const void*>(rank_x3v2_kernel<13, 32, true>), 13);
-    (void)hipGetLastError();
-    return ok;
 }
 
 // dh2 (workspace) of `rows` rows -> [rows][k] ids and scaled scores
@@ -158,22 +106,14 @@ int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, i
     const int grid = p.wgs * p.nblk;
     {
         ProfScope ps(m, AAE_K_RANK, s);
-        switch (m->fused_nb) {
-            case 4: TRY(launch_rank_nb<4>(a, p.K, grid, s)); break;
-            case 7: TRY(launch_rank_nb<7>(a, p.K, grid, s)); break;
-            default: TRY(launch_rank_nb<13>(a, p.K, grid, s)); break;
-        }
+        TRY(launch_rank(a, m->fused_nb, p.K, false, grid, s));
     }
     if (rank_long(k)) {
         ProfScope ps(m, AAE_K_RANK, s);
         hipLaunchKernelGGL(rank_floor_kernel, dim3(p.rows), dim3(256), 0, s, p.cand_v, p.cand_i, p.wgs * p.K, k, p.tau, p.count);
         LAUNCHCHK("rank_floor");
         a.tau = p.tau; a.count = p.count; a.list = p.list; a.cap = p.cap;
-        switch (m->fused_nb) {
-            case 4: TRY(launch_collect_nb<4>(a, grid, s)); break;
-            case 7: TRY(launch_collect_nb<7>(a, grid, s)); break;
-            default: TRY(launch_collect_nb<13>(a, grid, s)); break;
-        }
+        TRY(launch_rank(a, m->fused_nb, p.K, true, grid, s));
         int P = 2;
         while (P < p.cap) P <<= 1;
         hipLaunchKernelGGL(rank_long_sort_kernel, dim3(p.rows), dim3(kLongNT), (uint32_t)(P * sizeof(unsigned long long)), s,
@@ -181,11 +121,10 @@ int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, i
         LAUNCHCHK("rank_long_sort");
         return AAE_OK;
     }
-    switch (p.K) {
-        case 10: hipLaunchKernelGGL(rank_merge_kernel<10>, dim3((p.rows + 3) / 4), dim3(256), 0, s, p.cand_v, p.cand_i, p.mm, p.rows, p.wgs, k, reinterpret_cast<int*>(idx_out), val_out); break;
-        case 20: hipLaunchKernelGGL(rank_merge_kernel<20>, dim3((p.rows + 3) / 4), dim3(256), 0, s, p.cand_v, p.cand_i, p.mm, p.rows, p.wgs, k, reinterpret_cast<int*>(idx_out), val_out); break;
-        default: hipLaunchKernelGGL(rank_merge_kernel<32>, dim3((p.rows + 3) / 4), dim3(256), 0, s, p.cand_v, p.cand_i, p.mm, p.rows, p.wgs, k, reinterpret_cast<int*>(idx_out), val_out); break;
-    }
+    const MergeKernel merge = pick_rank_merge(p.K);
+    if (!merge) return fail(AAE_ESTATE, "no rank_merge kernel is compiled for this list size");
+    hipLaunchKernelGGL(merge, dim3((p.rows + 3) / 4), dim3(256), 0, s, p.cand_v, p.cand_i, p.mm, p.rows, p.wgs, k,
+                       reinterpret_cast<int*>(idx_out), val_out);
     LAUNCHCHK("rank_merge");
     return AAE_OK;
 }

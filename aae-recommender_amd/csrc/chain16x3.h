@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                         v = acc[q];
                         if (acc_in) v += x16_get(dst, lr, col);           // the layer's earlier k-part: this lane's own cell
                         if (ec.epi == CEPI_ACTBWD) {
-                            v *= act_grad_from_y(ec.act, ygp ? yv[q] : x16_get(ys, lr, col));
+                            v *= act_grad_from_y<false>(ec.act, ygp ? yv[q] : x16_get(ys, lr, col));
                             if (ec.den) v *= chain_keep(ec, r0 + lr, col) ? ec.mk : 0.f;
                         } else {
                             v = chain_epi<false>(ec, r0 + lr, lr, col, v);
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                     if (epi_k == CEPI_ACTBWD) {
                         const float y = qaux_ptr[(size_t)(r0 + rowc) * qaux_ld + cc];
                         const float kp = (sec.den && cell) ? (chain_keep(sec, r0 + wave, ecol) ? sec.mk : 0.f) : 1.f;
-                        acc *= act_grad_from_y(sec.act, y) * kp;
+                        acc *= act_grad_from_y<false>(sec.act, y) * kp;
                     }
                     acc = cell ? acc : 0.f;
                     store(wave, ecol, acc);
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                 if (k < kX16Kp) {
                     float v = 0.f;
                     if (lrow < nrows && k < Nn) {
-                        v = gv * wv[j] * act_grad_from_y(ec.act, x16_get(ys, lrow, k));
+                        v = gv * wv[j] * act_grad_from_y<false>(ec.act, x16_get(ys, lrow, k));
                         if (ec.den) v *= chain_keep(ec, grow, k) ? ec.mk : 0.f;
                         store(lrow, k, v);
                     }

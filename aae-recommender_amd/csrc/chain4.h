@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                         v = crow == 0 ? cs[0] : crow == 1 ? cs[1] : crow == 2 ? cs[2] : cs[3];
                         if (acc_in) v += dst[crow * kCL + ccol];
                         if (ec.epi == CEPI_ACTBWD) {
-                            v *= act_grad_from_y(ec.act, ygp ? yv1 : (slots + yslot_k * kR4 * kCL)[crow * kCL + ccol]);
+                            v *= act_grad_from_y<false>(ec.act, ygp ? yv1 : (slots + yslot_k * kR4 * kCL)[crow * kCL + ccol]);
                             if (ec.den) v *= chain_keep(ec, r0 + crow, ccol) ? ec.mk : 0.f;
                         } else {
                             v = chain_epi<false>(ec, r0 + crow, crow, ccol, v);
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     if (acc_in) v += dst[erow * kCL + ecol];          // (uniform) the layer's earlier k-part: this thread's own cell
                     // (the epilogue's y slot holds 4-row blocks here: index it with this kernel's row stride)
                     if (ec.epi == CEPI_ACTBWD) {
-                        v *= act_grad_from_y(ec.act, ygp ? yv[eh] : (slots + yslot_k * kR4 * kCL)[erow * kCL + ecol]);
+                        v *= act_grad_from_y<false>(ec.act, ygp ? yv[eh] : (slots + yslot_k * kR4 * kCL)[erow * kCL + ecol]);
                         if (ec.den) v *= chain_keep(ec, r0 + erow, ecol) ? ec.mk : 0.f;
                     } else {
                         v = chain_epi<false>(ec, r0 + erow, erow, ecol, v);
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     const float y = qaux_ptr[(size_t)(r0 + rowc) * qaux_ld + cc];
                     const bool cell = erow < nrows && ecol < opN;
                     const float kp = (sec.den && cell) ? (chain_keep(sec, r0 + erow, ecol) ? sec.mk : 0.f) : 1.f;
-                    acc *= act_grad_from_y(sec.act, y) * kp;
+                    acc *= act_grad_from_y<false>(sec.act, y) * kp;
                 }
                 dst[erow * kCL + ecol] = (erow < nrows && ecol < opN) ? acc : 0.f;
             }
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     v = src[erow * kCL + ecol];
                     if (kind == COP_DROPACT) v = chain_epi<false>(ec, r0 + erow, erow, ecol, v);
                     else {
-                        v *= act_grad_from_y(ec.act, (slots + qyslot * kR4 * kCL)[erow * kCL + ecol]);
+                        v *= act_grad_from_y<false>(ec.act, (slots + qyslot * kR4 * kCL)[erow * kCL + ecol]);
                         if (ec.den) v *= chain_keep(ec, r0 + erow, ecol) ? ec.mk : 0.f;
                     }
                 }
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     if (k < kCL) {
                         float v = 0.f;
                         if (lrow < nrows && k < Nn) {
-                            v = gv * wv[j] * act_grad_from_y(ec.act, ys[lrow * kCL + k]);
+                            v = gv * wv[j] * act_grad_from_y<false>(ec.act, ys[lrow * kCL + k]);
                             if (ec.den) v *= chain_keep(ec, grow, k) ? ec.mk : 0.f;
                         }
                         dst[lrow * kCL + k] = v;

@@ -89,7 +89,7 @@ __device__ float nm_grad_from_y(int act, float ym) {
 // EXT = false (the 4-row and 16-row chain kernels, at their 128-register cap): r1-r5's six classes only - the r6 classes inlined
 // there cost the 16-row kernel 74 spilled registers on EVERY activation's path.  A model with one of the r6 classes runs its
 // layer programs on chain_kernel<.., true> (16-row blocks on the fp32 pipe), the instantiation that carries them all.
-template <bool EXT = true>
+template <bool EXT>      // (no default: every call site says which set of activation classes it carries)
 __device__ __forceinline__ float act_fwd(int act, float x) {
     if (!EXT && act > ACT_LEAKY) return x;
     switch (act) {
@@ -120,7 +120,7 @@ __device__ __forceinline__ float act_fwd(int act, float x) {
 // (the monotone ones directly; GELU / SiLU / Mish / Hardswish through the branch bit, above).
 // EXT = false (the 4-row / 16-row chain kernels): r1-r5's six classes, as act_fwd<false>; the per-layer epilogues and
 // chain_kernel<.., true> carry all of them.
-template <bool EXT = false>
+template <bool EXT>
 __device__ __forceinline__ float act_grad_from_y(int act, float y) {
     if (EXT && act >= ACT_GELU) return nm_grad_from_y(act, y);
     if (!EXT) {

@@ -277,7 +277,7 @@ struct EpiDropAct {
         for (int i = 0; i < 4 && gn + i < N; ++i) {
             float a = (&v.x)[i];
             if (d.enabled) a = drop_fwd(d, drop_keep(d, st.key, gm, gn + i), a);
-            o[i] = act_fwd(act, a);
+            o[i] = act_fwd<true>(act, a);
         }
     }
 };

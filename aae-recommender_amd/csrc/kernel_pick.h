@@ -1,0 +1,124 @@
+// Every templated kernel family of the library, spelled ONCE: pick_*() maps run-time values to a typed kernel pointer,
+// each_*() hands out the members a handle may launch (aae_create raises their dynamic-LDS limit through it).
+// (one of the parts of aae_abi.hip's translation unit: included there behind the kernel headers, not on its own)
+// A picker returns nullptr for a combination that is not compiled (`if constexpr`: asking for it does not instantiate it) and
+// its caller fails with AAE_ESTATE - nothing falls through to another member.  An enumeration walks its picker over the whole
+// run-time domain, so a new template flag is one more argument here and nowhere else.
+#pragma once
+
+#include <type_traits>
+
+namespace {
+
+using DecKernel = void (*)(DecFusedArgs);
+using RankKernel = void (*)(RankArgs);
+using ChainKernel = void (*)(ChainProgram);
+using MergeKernel = void (*)(const float*, const int*, const float*, int, int, int, int*, float*);
+
+// run-time x -> f(integral_constant<V>) for the V of the list that equals x; nullptr for any other x
+template <class R, int... Vs, class F>
+R pick_of(int x, F&& f) {
+    R r = nullptr;
+    (void)(... || (x == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)));
+    return r;
+}
+// run-time bools -> f(bool_constant...), in the order given
+template <class R, bool... Bs, class F>
+R pick_flags(F&& f) { return f(std::bool_constant<Bs>{}...); }
+template <class R, bool... Bs, class F, class... Rest>
+R pick_flags(F&& f, bool b, Rest... rest) {
+    return b ? pick_flags<R, Bs..., true>(f, rest...) : pick_flags<R, Bs..., false>(f, rest...);
+}
+// NB = ceil((h + 1) / 16) column blocks of the hidden width (aae_model::fused_nb); K = list entries per workgroup (rank_K)
+template <class R, class F> R pick_nb(int nb, F&& f) { return pick_of<R, 4, 7, 13>(nb, f); }
+template <class R, class F> R pick_k(int k, F&& f) { return pick_of<R, 10, 20, 32>(k, f); }
+constexpr int kPickNb[] = {4, 7, 13}, kPickK[] = {10, 20, 32};
+#define NB_ decltype(NB)::value      // (an enclosing lambda's constant, named without capturing it)
+
+template <class K>
+bool raise_lds_limit(K kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+
+// ---- dec_fused.h: every MODE with its moving-window form; dec_fused_bf16.h: no kDecOptAcc, no window form
+inline DecKernel pick_dec_fused(int nb, int mode, bool win) {
+    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_of<DecKernel, kDecFused, kDecCrit, kDecOpt, kDecOptAcc>(mode, [&](auto MODE) {
+        return pick_flags<DecKernel>([](auto WIN) -> DecKernel { return dec_fused_kernel<NB_, decltype(MODE)::value, WIN()>; }, win); }); });
+}
+inline DecKernel pick_dec_fused_bf16(int nb, int mode) {
+    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_of<DecKernel, kDecFused, kDecCrit, kDecOpt>(mode, [](auto MODE) -> DecKernel {
+        return dec_fused_bf16_kernel<NB_, MODE()>; }); });
+}
+inline DecKernel pick_dec_opt_blocks(int nb) {
+    return pick_nb<DecKernel>(nb, [](auto NB) -> DecKernel { return dec_opt_blocks_kernel<NB_>; });
+}
+template <class F> void each_dec_fused(int mode, F&& f) { for (int nb : kPickNb) for (int win = 0; win < 2; ++win) f(pick_dec_fused(nb, mode, win)); }
+template <class F> void each_dec_fused_bf16(int mode, F&& f) { for (int nb : kPickNb) f(pick_dec_fused_bf16(nb, mode)); }
+template <class F> void each_dec_opt_blocks(F&& f) { for (int nb : kPickNb) f(pick_dec_opt_blocks(nb)); }
+
+// ---- dec_crit_x3.h.  TS (the debug timelines) exists for NB == 13 alone, three-term, no window
+inline DecKernel pick_dec_crit_x3(int nb, bool ts, bool one, bool win) {
+    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_flags<DecKernel>([](auto TS, auto ONE, auto WIN) -> DecKernel {
+        if constexpr (TS() && (NB_ != 13 || ONE() || WIN())) return nullptr; else return dec_crit_x3_kernel<NB_, TS(), ONE(), WIN()>; }, ts, one, win); });
+}
+inline DecKernel pick_dec_opt_x3(int nb, bool one, bool win) {
+    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_flags<DecKernel>([](auto ONE, auto WIN) -> DecKernel {
+        return dec_opt_x3_kernel<NB_, ONE(), WIN()>; }, one, win); });
+}
+inline DecKernel pick_dec_opt_blocks_x3(int nb, bool ts, bool win) {
+    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_flags<DecKernel>([](auto TS, auto WIN) -> DecKernel {
+        if constexpr (TS() && (NB_ != 13 || WIN())) return nullptr; else return dec_opt_blocks_x3_kernel<NB_, TS(), WIN()>; }, ts, win); });
+}
+// (ONE: the one-term members are a bf16 handle's, prepared apart from the three-term ones)
+template <class F> void each_dec_crit_x3(bool one, F&& f) {
+    for (int nb : kPickNb) for (int i = 0; i < 4; ++i) if (DecKernel k = pick_dec_crit_x3(nb, i & 1, one, i & 2)) f(k);
+}
+template <class F> void each_dec_opt_x3(bool one, F&& f) { for (int nb : kPickNb) for (int win = 0; win < 2; ++win) f(pick_dec_opt_x3(nb, one, win)); }
+template <class F> void each_dec_opt_blocks_x3(F&& f) {
+    for (int nb : kPickNb) for (int i = 0; i < 4; ++i) if (DecKernel k = pick_dec_opt_blocks_x3(nb, i & 1, i & 2)) f(k);
+}
+
+// ---- rank_x3.h.  Which of the two rank kernels a call takes: the v2 wave mapping where its registers do not spill (the
+// other list sizes keep rank_x3_kernel, the r4 mapping).  Both are compiled for every (NB, K).
+inline bool rank_v2_nb(int nb, int K) { return K == 10 || (K == 20 && nb < 13); }
+// K = 1 is the collect epilogue's front end (rank_long.h): COLLECT exists with it alone, and it not without COLLECT
+inline RankKernel pick_rank_x3(int nb, int K, bool win, bool collect) {
+    return pick_nb<RankKernel>(nb, [&](auto NB) { return pick_of<RankKernel, 1, 10, 20, 32>(K, [&](auto KK) {
+        return pick_flags<RankKernel>([](auto WIN, auto COLLECT) -> RankKernel {
+            constexpr int K_ = decltype(KK)::value;
+            if constexpr ((K_ == 1) != COLLECT()) return nullptr; else return rank_x3_kernel<NB_, K_, WIN(), COLLECT()>; }, win, collect); }); });
+}
+inline RankKernel pick_rank_x3v2(int nb, int K, bool win) {
+    return pick_nb<RankKernel>(nb, [&](auto NB) { return pick_k<RankKernel>(K, [&](auto KK) {
+        return pick_flags<RankKernel>([](auto WIN) -> RankKernel { return rank_x3v2_kernel<NB_, decltype(KK)::value, WIN()>; }, win); }); });
+}
+inline MergeKernel pick_rank_merge(int K) {
+    return pick_k<MergeKernel>(K, [](auto KK) -> MergeKernel { return rank_merge_kernel<KK()>; });
+}
+// f(kernel, nb): the LDS of a rank kernel goes with its NB (rank_x3_lds_bytes / rank_x3v2_lds_bytes)
+template <class F> void each_rank_x3(F&& f) {
+    for (int nb : kPickNb) for (int win = 0; win < 2; ++win) for (int K : {1, 10, 20, 32}) f(pick_rank_x3(nb, K, win, K == 1), nb);
+}
+template <class F> void each_rank_x3v2(F&& f) {
+    for (int nb : kPickNb) for (int win = 0; win < 2; ++win) for (int K : kPickK) f(pick_rank_x3v2(nb, K, win), nb);
+}
+
+// ---- chain.h (NM: the r6 activation classes, device_common.h act_fwd); chain4.h: the timeline in fp32 alone, the column
+// form (a program without k-slices) in bf16 alone; chain16x3.h: the timeline in fp32 alone
+inline ChainKernel pick_chain(bool bf, bool nm) {
+    return pick_flags<ChainKernel>([](auto BF, auto NM) -> ChainKernel { return chain_kernel<BF(), NM()>; }, bf, nm);
+}
+inline ChainKernel pick_chain4(bool bf, bool ts, bool cols) {
+    return pick_flags<ChainKernel>([](auto BF, auto TS, auto COLS) -> ChainKernel {
+        if constexpr ((TS() && (BF() || COLS())) || (COLS() && !BF())) return nullptr; else return chain4_kernel<BF(), TS(), COLS()>; }, bf, ts, cols);
+}
+inline ChainKernel pick_chain16x3(bool bf, bool ts) {
+    return pick_flags<ChainKernel>([](auto BF, auto TS) -> ChainKernel {
+        if constexpr (BF() && TS()) return nullptr; else return chain16x3_kernel<BF(), TS()>; }, bf, ts);
+}
+template <class F> void each_chain(bool nm, F&& f) { f(pick_chain(false, nm)); f(pick_chain(true, nm)); }
+template <class F> void each_chain4(F&& f) { for (int i = 0; i < 8; ++i) if (ChainKernel k = pick_chain4(i & 1, i & 2, i & 4)) f(k); }
+template <class F> void each_chain16x3(F&& f) { for (int i = 0; i < 4; ++i) if (ChainKernel k = pick_chain16x3(i & 1, i & 2)) f(k); }
+
+#undef NB_
+}  // namespace

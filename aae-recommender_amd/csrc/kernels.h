@@ -213,7 +213,7 @@ __global__ __launch_bounds__(64 * NW) void enc_gather_kernel_t(BatchView bv, con
         a1[(size_t)b * ld + c] = v;
         if (y) {
             if (d.enabled) v = drop_fwd(d, drop_keep(d, key, b, c), v);
-            y[(size_t)b * ld + c] = act_fwd(act, v);
+            y[(size_t)b * ld + c] = act_fwd<true>(act, v);
         }
     }
 }
@@ -228,7 +228,7 @@ __global__ void drop_act_kernel(const float* __restrict__ a, float* __restrict__
         int r = i / h, c = i - r * h;
         float v = a[(size_t)r * ld + c];
         if (d.enabled) v = drop_fwd(d, drop_keep(d, key, r, c), v);
-        y[(size_t)r * ld + c] = act_fwd(act, v);
+        y[(size_t)r * ld + c] = act_fwd<true>(act, v);
     }
 }
 
@@ -499,7 +499,7 @@ __global__ void slab_reduce_fwd_kernel(const float* __restrict__ slabs, int nsla
         v += b1[c];
         a1[(size_t)r * ld + c] = v;
         if (d.enabled) v = drop_fwd(d, drop_keep(d, key, r, c), v);
-        y[(size_t)r * ld + c] = act_fwd(act, v);
+        y[(size_t)r * ld + c] = act_fwd<true>(act, v);
     }
 }
 
