@@ -128,6 +128,10 @@ _PROTOS = {
     "aae_predict_topk": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_rank_max_rows": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "aae_rank_long_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "aae_predict_ranks": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.POINTER(AaeBatch), C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_decode_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    "aae_rank_full_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "aae_decode_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "aae_encode": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
@@ -1105,6 +1109,65 @@ class HipAAE:
             _check(self.lib.aae_decode_topk(self.handle, _ptr(zc), zc.shape[1], C.byref(b), int(k), int(bool(exclude_known)),
                                             _ptr(idx), _ptr(val), self._stream()))
         return idx, val
+
+    # ---- full ranking: the rank of every held-out item (csrc/rank_full.h) ------------------------
+    def rank_full_max_rows(self):
+        """Rows one aae_predict_ranks / aae_decode_ranks call may take (aae_rank_full_max_rows)."""
+        if "full" not in self._rank_rows:
+            out = C.c_int32()
+            _check(self.lib.aae_rank_full_max_rows(self.handle, C.byref(out)))
+            self._rank_rows["full"] = int(out.value)
+        return self._rank_rows["full"]
+
+    def _truth_span(self, truth_csr, row_start, n_rows):
+        """(entries of truth rows [row_start, row_start + n_rows), the batch naming them); indptr is read on the host once."""
+        gen, ip = getattr(truth_csr, "_indptr_host", (None, None))
+        if ip is None or gen != getattr(truth_csr, "generation", 0):
+            gen, ip = getattr(truth_csr, "generation", 0), truth_csr.indptr.cpu().numpy()
+            truth_csr._indptr_host = (gen, ip)
+        if truth_csr.shape[1] != self.N:
+            raise ValueError(f"the ground truth has {truth_csr.shape[1]} columns, the model {self.N} items")
+        return int(ip[row_start + n_rows] - ip[row_start]), self._batch(truth_csr, row_start, n_rows, bounded=False)
+
+    def predict_ranks(self, csr, row_start, n_rows, truth_csr, cond=None, exclude_known=True):
+        """int32 device tensor: for every stored entry of truth_csr[row_start : row_start + n_rows], in CSR order, the
+        1-based rank of that item among its row's items in predict_topk's ordering (known items excluded from the ranking
+        with exclude_known; better score first, equal logits to the smaller id; a truth item that is itself a known item
+        ranks behind every rankable one: n_rankable + 1 + #{known ids < it}).  Any number of rows: chunked by
+        rank_full_max_rows().  Row i of truth_csr belongs to row i of csr."""
+        if cond is not None:
+            cond = upload(cond, self.device, torch.float32).contiguous()
+        out, chunk = [], self.rank_full_max_rows()
+        for s0 in range(row_start, row_start + n_rows, chunk):
+            n = min(chunk, row_start + n_rows - s0)
+            nnz, tb = self._truth_span(truth_csr, s0, n)
+            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            if nnz:
+                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
+                c = None if cond is None else cond[s0 - row_start:s0 - row_start + n]
+                with self._on_device():
+                    _check(self.lib.aae_predict_ranks(self.handle, C.byref(b), _ptr(c), C.byref(tb), int(bool(exclude_known)),
+                                                      _ptr(ranks), self._stream()))
+            out.append(ranks)
+        return torch.cat(out) if len(out) != 1 else out[0]
+
+    def decode_ranks(self, zc, csr, row_start, truth_csr, exclude_known=True):
+        """The same for decode(zc): the input rows csr[row_start : row_start + len(zc)] (aae_decode_ranks)."""
+        zc = zc.detach().to(self.device, torch.float32).contiguous()
+        n_rows = zc.shape[0]
+        out, chunk = [], self.rank_full_max_rows()
+        for s0 in range(row_start, row_start + n_rows, chunk):
+            n = min(chunk, row_start + n_rows - s0)
+            nnz, tb = self._truth_span(truth_csr, s0, n)
+            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            if nnz:
+                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
+                z = zc[s0 - row_start:s0 - row_start + n]
+                with self._on_device():
+                    _check(self.lib.aae_decode_ranks(self.handle, _ptr(z), z.shape[1], C.byref(b), C.byref(tb),
+                                                     int(bool(exclude_known)), _ptr(ranks), self._stream()))
+            out.append(ranks)
+        return torch.cat(out) if len(out) != 1 else out[0]
 
     def encode(self, csr, row_start, n_rows):
         b = self._batch(csr, row_start, n_rows)

@@ -670,6 +670,54 @@ def _predict_topk(self, X, k=10, condition_data=None, exclude_known=True):
 AdversarialAutoEncoder.predict_topk = _predict_topk
 
 
+def _predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
+    """The rank of every held-out item in the full ranking of its row, without the [n, N] score matrix leaving the device
+    or being sorted anywhere: a scipy CSR with Y's pattern (canonical: duplicates summed, indices sorted) whose data are
+    the int32 1-based ranks of those items among the row's items - predict_topk's ordering (the items of X's row are not
+    rankable with exclude_known).  Everything evaluation.METRICS needs follows from them (evaluation.evaluate_ranks); only
+    nnz(Y) integers cross PCIe.  Conditions as in predict_topk()."""
+    self.eval()
+    use_condition = _check_conditions(self.conditions, condition_data)
+    if self.conditions:
+        self.conditions.eval()
+    fused = (not use_condition) or self._is_constant_concat()
+    native = use_condition and not fused and self._is_device_native()
+    Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+    Ys = sp.csr_matrix(Y, copy=True) if not sp.issparse(Y) else Y.tocsr(copy=True)
+    if Ys.shape != Xs.shape:
+        raise ValueError("the ground truth has shape {}, the inputs {}".format(Ys.shape, Xs.shape))
+    Ys.sum_duplicates()
+    Ys.sort_indices()
+    csr = _hip.DeviceCSR(Xs, self.hip.device)
+    truth = _hip.DeviceCSR(Ys, self.hip.device)
+    self._dp_settle()
+    if self._slice is not None:
+        self._dp.gather_output_layer()
+    ranks = []
+    chunk = max(self.batch_size, min(self.hip.rank_full_max_rows(), 2048))
+    for start in range(0, Xs.shape[0], chunk):
+        n = min(chunk, Xs.shape[0] - start)
+        cond = None
+        c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
+        if use_condition and fused:
+            cond = torch.cat([_hip.upload(c.encode(x), self.hip.device) for c, x in zip(self.conditions.values(), c_batch)], 1)
+        elif native:
+            cond = self._native_cond_block(c_batch, n)
+        if fused or native:
+            ranks.append(self.hip.predict_ranks(csr, start, n, truth, cond=cond, exclude_known=exclude_known))
+        else:
+            with torch.no_grad():
+                z = torch.cat([self.hip.encode(csr, s0, min(self.batch_size, start + n - s0))
+                               for s0 in range(start, start + n, self.batch_size)])
+                ranks.append(self.hip.decode_ranks(self.conditions.encode_impose(z, c_batch), csr, start, truth,
+                                                   exclude_known=exclude_known))
+    data = torch.cat(ranks).cpu().numpy().astype(np.int32, copy=False) if ranks else np.zeros(0, dtype=np.int32)
+    return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+
+
+AdversarialAutoEncoder.predict_ranks = _predict_ranks
+
+
 def _take(c, idx, rows_dev=None):
     """Row selection on whatever a condition's transform produced (ndarray, sparse, list, tensor).  rows_dev: the same
     selection as a device tensor - condition data that already lives in HBM is then selected there (indexing a device
@@ -899,3 +947,11 @@ class AAERecommender(Recommender):
         if self.conditions:
             condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
         return self.model.predict_topk(X, k=k, condition_data=condition_data)
+
+    def predict_ranks(self, test_set, y_true):
+        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag."""
+        X = test_set.tocsr()
+        condition_data = None
+        if self.conditions:
+            condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
+        return self.model.predict_ranks(X, y_true, condition_data=condition_data)

@@ -1,4 +1,4 @@
-"""PyTorch custom ops over the C ABI: ``torch.ops.aaerec.{step, encode, predict, predict_topk}``.
+"""PyTorch custom ops over the C ABI: ``torch.ops.aaerec.{step, encode, predict, predict_topk, predict_ranks}``.
 
 The product is ``libaaerec_hip.so`` (``include/aaerec_hip.h``); these ops are the thin torch-facing
 surface BASELINE.json's north star names ("exposed to Python through PyTorch-ROCm custom ops over a
@@ -28,6 +28,9 @@ _LIB.define(f"encode(int model, {_CSR}, int row_start, int n_rows, int max_row_n
 _LIB.define(f"predict(int model, {_CSR}, int row_start, int n_rows, int max_row_nnz, Tensor? cond) -> Tensor")
 _LIB.define(f"predict_topk(int model, {_CSR}, int row_start, int n_rows, int max_row_nnz, Tensor? cond, int k, "
             "bool exclude_known) -> (Tensor, Tensor)")
+# the rank of every stored entry of the truth CSR's rows (same row window as the input CSR) in the full ranking: int32, CSR order
+_LIB.define(f"predict_ranks(int model, {_CSR}, int row_start, int n_rows, int max_row_nnz, Tensor? cond, "
+            "Tensor truth_indptr, Tensor truth_indices, int truth_max_row_nnz, bool exclude_known) -> Tensor")
 
 _MODELS = weakref.WeakValueDictionary()
 _IDS = itertools.count(1)
@@ -99,5 +102,16 @@ def _predict_topk(model, indptr, indices, values, row_start, n_rows, max_row_nnz
                           exclude_known=exclude_known)
 
 
-for _name, _fn in (("step", _step), ("encode", _encode), ("predict", _predict), ("predict_topk", _predict_topk)):
+def _predict_ranks(model, indptr, indices, values, row_start, n_rows, max_row_nnz, cond, truth_indptr, truth_indices,
+                   truth_max_row_nnz, exclude_known):
+    m = _model(model)
+    # (the library does not read a truth matrix's values: any float32 device tensor stands in for them)
+    truth = _CsrView(truth_indptr, truth_indices, values, truth_max_row_nnz, m.N)
+    truth.shape = (truth_indptr.numel() - 1, m.N)
+    return m.predict_ranks(_CsrView(indptr, indices, values, max_row_nnz, m.N), row_start, n_rows, truth, cond=cond,
+                           exclude_known=exclude_known)
+
+
+for _name, _fn in (("step", _step), ("encode", _encode), ("predict", _predict), ("predict_topk", _predict_topk),
+                   ("predict_ranks", _predict_ranks)):
     _LIB.impl(_name, _fn, "CUDA")

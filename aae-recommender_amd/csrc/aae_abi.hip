@@ -33,6 +33,7 @@
 #include "dec_crit_x3.h"
 #include "rank_x3.h"
 #include "rank_long.h"
+#include "rank_full.h"
 #include "chain.h"
 #include "chain4.h"
 #include "chain16x3.h"

@@ -154,5 +154,44 @@ int aae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_
     return AAE_OK;
 }
 
+// ---- the rank of every held-out item in the full ranking of its row (rank_full.h) ------------------------------------
+int aae_rank_full_max_rows(aae_handle m, int32_t* rows_out) {
+    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
+    *rows_out = std::max(m->R, rank_full_rows_cap(m));
+    return AAE_OK;
+}
+
+int aae_predict_ranks(aae_handle m, const aae_batch* batch, const float* cond_dev, const aae_batch* truth, int32_t exclude_known,
+                      int32_t* ranks_out_dev, void* stream) {
+    if (!m || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
+    TRY(rank_check_batch(batch));
+    TRY(rank_check_truth(batch, truth));
+    hipStream_t s = S(stream);
+    if (batch->n_rows >= 1 && batch->n_rows <= rank_full_rows_cap(m)) {     // fused: no [rows][N] matrix (abi_rank.h)
+        m->phase = 0;
+        return rank_full_predict(m, batch, cond_dev, truth, exclude_known, ranks_out_dev, s);
+    }
+    TRY(aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream));           // scores into the [rows][N] scratch
+    return rank_full_dense(m, rank_view(batch), rank_view(truth), 0, exclude_known, ranks_out_dev, s);
+}
+
+int aae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
+                     int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
+    if (!m || !zc_dev || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
+    TRY(rank_check_batch(batch));
+    TRY(rank_check_truth(batch, truth));
+    hipStream_t s = S(stream);
+    if (batch->n_rows >= 1 && batch->n_rows <= rank_full_rows_cap(m)) {
+        m->phase = 0;
+        return rank_full_decode(m, zc_dev, zc_ld, batch, truth, exclude_known, ranks_out_dev, s);
+    }
+    TRY(set_batch(m, batch));
+    TRY(aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream));     // scores into the [rows][N] scratch
+    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), 0, exclude_known, ranks_out_dev, s));
+    m->phase = 0;
+    return AAE_OK;
+}
 
 }  // extern "C"

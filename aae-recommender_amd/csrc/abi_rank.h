@@ -12,6 +12,9 @@
 // Launches per call: (deferred-Adam flush of enc.lin1 when rows are behind) gather, chain, known-item mask, rank, merge.
 // k > 32: ... rank (K = 32), floor, rank again with the collect epilogue, sort; then the rows' counts are read back (the call
 // synchronises its stream) and a row whose list overflowed is ranked through the score matrix (rank_long_dense).
+// Full ranking (rank_full.h; aae_predict_ranks / aae_decode_ranks): no candidate lists; instead
+//   tgt_i, tgt_v, tcount [rows][kFullSlots]   the held-out items of this round, their logits, the cells ranked before them
+// Launches: gather, chain, known-item mask, then per round of 8 held-out items a row: setup, rank (pick), rank (count), finish.
 #pragma once
 
 namespace {
@@ -22,6 +25,7 @@ struct RankPlan {
     int rows, K, nblk, wgs, kw, bb;
     float *a1, *eh1, *dh2, *rscale, *cand_v, *mm; int* cand_i; unsigned* known;
     int cap; float* tau; int* count; unsigned long long* list;      // k > 32 (rank_long.h)
+    int* tgt_i; float* tgt_v; int* tcount;                          // full ranking (rank_full.h)
     size_t floats;
 };
 
@@ -31,7 +35,7 @@ inline int rank_collect_cap(const aae_model* m) { return m->opt.rank_collect_cap
 inline int rank_K(int k) { return k <= 10 ? 10 : k <= 20 ? 20 : 32; }
 
 // lays the workspace out for `rows` rows (base == NULL: measures only)
-RankPlan rank_plan(const aae_model* m, int rows, int k, float* base) {
+RankPlan rank_plan(const aae_model* m, int rows, int k, float* base, bool full = false) {
     RankPlan p; memset(&p, 0, sizeof(p));
     p.rows = rows; p.K = rank_K(k);
     const int ntiles = (m->N + kTI - 1) / kTI;
@@ -44,6 +48,13 @@ RankPlan rank_plan(const aae_model* m, int rows, int k, float* base) {
     p.a1 = take((size_t)rows * m->ldh); p.eh1 = take((size_t)rows * m->ldh); p.dh2 = take((size_t)rows * m->ldh);
     p.rscale = take(rows);
     p.known = reinterpret_cast<unsigned*>(take((size_t)rows * p.kw));
+    if (full) {     // (no lists: the pick / count epilogues leave no candidates)
+        p.tgt_i = reinterpret_cast<int*>(take((size_t)rows * kFullSlots));
+        p.tgt_v = take((size_t)rows * kFullSlots);
+        p.tcount = reinterpret_cast<int*>(take((size_t)rows * kFullSlots));
+        p.floats = off;
+        return p;
+    }
     p.cand_v = take((size_t)rows * p.wgs * p.K);
     p.cand_i = reinterpret_cast<int*>(take((size_t)rows * p.wgs * p.K));
     p.mm = take((size_t)rows * p.wgs * 2);
@@ -79,16 +90,29 @@ int rank_rows_cap(const aae_model* m, int k) {
     return lo;
 }
 
+// most rows one fused full-ranking call can take (0: the fused path does not apply to this handle)
+int rank_full_rows_cap(const aae_model* m) {
+    if (!m->rank_ok) return 0;
+    const size_t have = rank_ws_floats(m);
+    int lo = 0, hi = kRankMaxRows;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        if (rank_plan(m, mid, 32, nullptr, true).floats <= have) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // one launch of a rank kernel: rank_x3v2 / rank_x3 by rank_v2_nb (kernel_pick.h), or the K = 32 kernel's front end with
-// the collect epilogue (rank_long.h)
-int launch_rank(const RankArgs& a, int nb, int K, bool collect, int grid, hipStream_t s) {
+// another epilogue: collect (rank_long.h), pick / count (rank_full.h)
+int launch_rank(const RankArgs& a, int nb, int K, int epi, int grid, hipStream_t s) {
     const bool win = x3_big_span(a.N, a.ldv);      // (dec.lin3 beyond 2^31 bytes: the moving-window instantiations, dec_fused.h)
-    const bool v2 = !collect && rank_v2_nb(nb, K);
-    const RankKernel kernel = v2 ? pick_rank_x3v2(nb, K, win) : pick_rank_x3(nb, collect ? 1 : K, win, collect);
+    const bool v2 = epi == kRankLists && rank_v2_nb(nb, K);
+    const RankKernel kernel = v2 ? pick_rank_x3v2(nb, K, win) : pick_rank_x3(nb, epi != kRankLists ? 1 : K, win, epi);
     if (!kernel) return fail(AAE_ESTATE, "no rank kernel is compiled for this hidden width and list size");
     const uint32_t lds = (uint32_t)(v2 ? rank_x3v2_lds_bytes(nb) : rank_x3_lds_bytes(nb));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kNT), lds, s, a);
-    LAUNCHCHK(v2 ? "rank_x3v2" : collect ? "rank_x3 (collect)" : "rank_x3");
+    LAUNCHCHK(v2 ? "rank_x3v2" : epi == kRankCollect ? "rank_x3 (collect)" : epi == kRankPick ? "rank_x3 (pick)"
+                 : epi == kRankCount ? "rank_x3 (count)" : "rank_x3");
     return AAE_OK;
 }
 
@@ -106,14 +130,14 @@ int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, i
     const int grid = p.wgs * p.nblk;
     {
         ProfScope ps(m, AAE_K_RANK, s);
-        TRY(launch_rank(a, m->fused_nb, p.K, false, grid, s));
+        TRY(launch_rank(a, m->fused_nb, p.K, kRankLists, grid, s));
     }
     if (rank_long(k)) {
         ProfScope ps(m, AAE_K_RANK, s);
         hipLaunchKernelGGL(rank_floor_kernel, dim3(p.rows), dim3(256), 0, s, p.cand_v, p.cand_i, p.wgs * p.K, k, p.tau, p.count);
         LAUNCHCHK("rank_floor");
         a.tau = p.tau; a.count = p.count; a.list = p.list; a.cap = p.cap;
-        TRY(launch_rank(a, m->fused_nb, p.K, true, grid, s));
+        TRY(launch_rank(a, m->fused_nb, p.K, kRankCollect, grid, s));
         int P = 2;
         while (P < p.cap) P <<= 1;
         hipLaunchKernelGGL(rank_long_sort_kernel, dim3(p.rows), dim3(kLongNT), (uint32_t)(P * sizeof(unsigned long long)), s,
@@ -126,6 +150,41 @@ int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, i
     hipLaunchKernelGGL(merge, dim3((p.rows + 3) / 4), dim3(256), 0, s, p.cand_v, p.cand_i, p.mm, p.rows, p.wgs, k,
                        reinterpret_cast<int*>(idx_out), val_out);
     LAUNCHCHK("rank_merge");
+    return AAE_OK;
+}
+
+// dh2 (workspace) of `rows` rows -> the rank of every stored entry of the rows' truth, CSR order (rank_full.h)
+int rank_full_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, const BatchView& tv, int max_truth, int exclude_known,
+                       int32_t* ranks_out, hipStream_t s) {
+    hipLaunchKernelGGL(known_mask_kernel, dim3(p.rows), dim3(256), 0, s, bv, exclude_known ? p.known : (unsigned*)nullptr, p.kw,
+                       p.dh2, m->ldh, m->h);
+    LAUNCHCHK("known_mask");
+    RankArgs a; memset(&a, 0, sizeof(a));
+    a.dh2 = p.dh2; a.ldh = m->ldh; a.V3a = m->P[P_V3].p; a.ldv = m->ldh; a.N = m->N; a.B = p.rows;
+    a.nblk = p.nblk; a.Bb = p.bb; a.known = exclude_known ? p.known : nullptr; a.kw = p.kw;
+    a.one_term = m->bf16 ? 1 : 0;
+    a.tgt_i = p.tgt_i; a.tgt_v = p.tgt_v; a.tcount = p.tcount;
+    const int grid = p.wgs * p.nblk;
+    ProfScope ps(m, AAE_K_RANK, s);
+    for (int g = 0; g * kFullSlots < max_truth; ++g) {      // 8 held-out items a row and round
+        hipLaunchKernelGGL(rank_full_setup_kernel, dim3(p.rows), dim3(64), 0, s, tv, m->N, g, p.tgt_i, p.tgt_v, p.tcount);
+        LAUNCHCHK("rank_full_setup");
+        TRY(launch_rank(a, m->fused_nb, 1, kRankPick, grid, s));
+        TRY(launch_rank(a, m->fused_nb, 1, kRankCount, grid, s));
+        hipLaunchKernelGGL(rank_full_finish_kernel, dim3(p.rows), dim3(256), 0, s, tv, g, p.tgt_i, p.tcount,
+                           reinterpret_cast<int*>(ranks_out));
+        LAUNCHCHK("rank_full_finish");
+    }
+    return AAE_OK;
+}
+
+// the dense form: rows [row0, row0 + m->rows) of the call, their scores in the [max_batch][n_items] scratch
+int rank_full_dense(aae_model* m, const BatchView& bv, const BatchView& tv, int row0, int exclude_known, int32_t* ranks_out,
+                    hipStream_t s) {
+    ProfScope ps(m, AAE_K_RANK, s);
+    hipLaunchKernelGGL(rank_full_dense_kernel, dim3(m->rows), dim3(kFullNT), 0, s, m->G.p, m->ldn, m->N, bv, tv, row0, exclude_known,
+                       reinterpret_cast<int*>(ranks_out));
+    LAUNCHCHK("rank_full_dense");
     return AAE_OK;
 }
 
@@ -146,16 +205,14 @@ BatchView rank_view(const aae_batch* b) {
     return bv;
 }
 
-// predict -> rank for batch->n_rows <= rank_rows_cap rows (eval mode: no dropout; aae.py:840-870)
-int rank_predict(aae_model* m, const aae_batch* batch, const float* cond_dev, int k, int exclude_known, int32_t* idx_out,
-                 float* val_out, hipStream_t s) {
+// the rows' forward pass up to the decoder's last hidden layer -> p.dh2 (eval mode: no dropout; aae.py:840-870)
+int rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* cond_dev, const RankPlan& p, hipStream_t s) {
     const int rows = batch->n_rows, h = m->h, c = m->c, cp = m->cp;
     TRY(join_deferred(m, s));
     if (m->flushed_hstep != m->hstep) {     // every row of enc.lin1 through the current step: once after the last training step
         TRY(lazy_flush(m, s));               // (rows fall behind only when a step opens: hstep counts them)
         m->flushed_hstep = m->hstep;
     }
-    const RankPlan p = rank_plan(m, rows, k, m->G.p);
     const BatchView bv = rank_view(batch);
     {
         DropSpec d1 = make_drop(m, 0, false, nullptr, nullptr, rows, h, 0);
@@ -183,16 +240,21 @@ int rank_predict(aae_model* m, const aae_batch* batch, const float* cond_dev, in
         f.one_col = cp;
     }
     rank_dec_hidden(m, cb, 2, 5, rows, p, s);
-    TRY(launch_chain(m, cb, s));
-    return rank_from_dh2(m, p, bv, k, exclude_known, idx_out, val_out, s);
+    return launch_chain(m, cb, s);
 }
 
-// the same from a decoder input the caller built: zc_dev [rows][zc_ld]
-int rank_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int k, int exclude_known,
-                int32_t* idx_out, float* val_out, hipStream_t s) {
-    const int rows = batch->n_rows, cp = m->cp;
+// predict -> rank for batch->n_rows <= rank_rows_cap rows
+int rank_predict(aae_model* m, const aae_batch* batch, const float* cond_dev, int k, int exclude_known, int32_t* idx_out,
+                 float* val_out, hipStream_t s) {
+    const RankPlan p = rank_plan(m, batch->n_rows, k, m->G.p);
+    TRY(rank_predict_hidden(m, batch, cond_dev, p, s));
+    return rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out, val_out, s);
+}
+
+// the same from a decoder input the caller built: zc_dev [rows][zc_ld] -> p.dh2
+int rank_decode_hidden(aae_model* m, const float* zc_dev, int64_t zc_ld, int rows, const RankPlan& p, hipStream_t s) {
+    const int cp = m->cp;
     TRY(join_deferred(m, s));
-    const RankPlan p = rank_plan(m, rows, k, m->G.p);
     ChainBuilder cb(m, rows);
     if (wide_dec_in(m)) {
         cb.add(cop_load(zc_dev, (int)zc_ld, 2, kCWide));
@@ -201,8 +263,28 @@ int rank_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batc
         ChainOp& l = cb.add(cop_load(zc_dev, (int)zc_ld, 2, cp)); l.one_col = cp;
     }
     rank_dec_hidden(m, cb, 2, 5, rows, p, s);
-    TRY(launch_chain(m, cb, s));
+    return launch_chain(m, cb, s);
+}
+
+int rank_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int k, int exclude_known,
+                int32_t* idx_out, float* val_out, hipStream_t s) {
+    const RankPlan p = rank_plan(m, batch->n_rows, k, m->G.p);
+    TRY(rank_decode_hidden(m, zc_dev, zc_ld, batch->n_rows, p, s));
     return rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out, val_out, s);
+}
+
+// full ranking of batch->n_rows <= rank_full_rows_cap rows against their truth rows
+int rank_full_predict(aae_model* m, const aae_batch* batch, const float* cond_dev, const aae_batch* truth, int exclude_known,
+                      int32_t* ranks_out, hipStream_t s) {
+    const RankPlan p = rank_plan(m, batch->n_rows, 32, m->G.p, true);
+    TRY(rank_predict_hidden(m, batch, cond_dev, p, s));
+    return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out, s);
+}
+int rank_full_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
+                     int exclude_known, int32_t* ranks_out, hipStream_t s) {
+    const RankPlan p = rank_plan(m, batch->n_rows, 32, m->G.p, true);
+    TRY(rank_decode_hidden(m, zc_dev, zc_ld, batch->n_rows, p, s));
+    return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out, s);
 }
 
 // k > 32, the dense form: [rows][ldn] scores in the scratch -> [rows][k]
@@ -246,6 +328,14 @@ aae_batch rank_sub_batch(const aae_model* m, const aae_batch* b, int off, int n)
 
 int rank_check_batch(const aae_batch* b) {
     if (!b || !b->indptr_dev || !b->indices_dev || !b->values_dev) return fail(AAE_EINVAL, "batch pointers are NULL");
+    return AAE_OK;
+}
+
+// the ground truth of a full-ranking call: the rows of `batch`, one for one (its values are not read)
+int rank_check_truth(const aae_batch* batch, const aae_batch* truth) {
+    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, "truth pointers are NULL");
+    if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, "truth names another number of rows than batch");
+    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "truth needs max_row_nnz: the entries of its longest row (an upper bound)");
     return AAE_OK;
 }
 

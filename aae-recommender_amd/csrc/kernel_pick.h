@@ -81,12 +81,14 @@ template <class F> void each_dec_opt_blocks_x3(F&& f) {
 // ---- rank_x3.h.  Which of the two rank kernels a call takes: the v2 wave mapping where its registers do not spill (the
 // other list sizes keep rank_x3_kernel, the r4 mapping).  Both are compiled for every (NB, K).
 inline bool rank_v2_nb(int nb, int K) { return K == 10 || (K == 20 && nb < 13); }
-// K = 1 is the collect epilogue's front end (rank_long.h): COLLECT exists with it alone, and it not without COLLECT
-inline RankKernel pick_rank_x3(int nb, int K, bool win, bool collect) {
+// K = 1 is the front end of the epilogues that keep no lists - collect (rank_long.h), pick and count (rank_full.h): they exist
+// with it alone, and it not without one of them
+inline RankKernel pick_rank_x3(int nb, int K, bool win, int epi) {
     return pick_nb<RankKernel>(nb, [&](auto NB) { return pick_of<RankKernel, 1, 10, 20, 32>(K, [&](auto KK) {
-        return pick_flags<RankKernel>([](auto WIN, auto COLLECT) -> RankKernel {
-            constexpr int K_ = decltype(KK)::value;
-            if constexpr ((K_ == 1) != COLLECT()) return nullptr; else return rank_x3_kernel<NB_, K_, WIN(), COLLECT()>; }, win, collect); }); });
+        return pick_of<RankKernel, kRankLists, kRankCollect, kRankPick, kRankCount>(epi, [&](auto EPI) {
+            return pick_flags<RankKernel>([](auto WIN) -> RankKernel {
+                constexpr int K_ = decltype(KK)::value, EPI_ = decltype(EPI)::value;
+                if constexpr ((K_ == 1) != (EPI_ != kRankLists)) return nullptr; else return rank_x3_kernel<NB_, K_, WIN(), EPI_>; }, win); }); }); });
 }
 inline RankKernel pick_rank_x3v2(int nb, int K, bool win) {
     return pick_nb<RankKernel>(nb, [&](auto NB) { return pick_k<RankKernel>(K, [&](auto KK) {
@@ -97,7 +99,10 @@ inline MergeKernel pick_rank_merge(int K) {
 }
 // f(kernel, nb): the LDS of a rank kernel goes with its NB (rank_x3_lds_bytes / rank_x3v2_lds_bytes)
 template <class F> void each_rank_x3(F&& f) {
-    for (int nb : kPickNb) for (int win = 0; win < 2; ++win) for (int K : {1, 10, 20, 32}) f(pick_rank_x3(nb, K, win, K == 1), nb);
+    for (int nb : kPickNb) for (int win = 0; win < 2; ++win) {
+        for (int K : kPickK) f(pick_rank_x3(nb, K, win, kRankLists), nb);
+        for (int epi : {kRankCollect, kRankPick, kRankCount}) f(pick_rank_x3(nb, 1, win, epi), nb);
+    }
 }
 template <class F> void each_rank_x3v2(F&& f) {
     for (int nb : kPickNb) for (int win = 0; win < 2; ++win) for (int K : kPickK) f(pick_rank_x3v2(nb, K, win), nb);

@@ -34,7 +34,15 @@ struct RankArgs {
     // the COLLECT epilogue of rank_x3_kernel (long lists, rank_long.h): cells >= tau[row] appended to the row's list
     const float* tau; int* count;       // [B] the row's floor; its entries so far (may run beyond cap: the overflow mark)
     unsigned long long* list; int cap;  // [B][cap] (order-preserving key of the logit << 32) | ~item
+    // the PICK / COUNT epilogues of rank_x3_kernel (full ranking, rank_full.h): kFullSlots held-out items per row and launch
+    const int* tgt_i;                   // [B][kFullSlots] their item ids, -1: slot unused
+    float* tgt_v;                       // [B][kFullSlots] their logits (PICK writes, COUNT reads); -inf: the item is a known one
+    int* tcount;                        // [B][kFullSlots] cells that rank before the item (COUNT adds)
 };
+
+// the epilogues of rank_x3_kernel
+constexpr int kRankLists = 0, kRankCollect = 1, kRankPick = 2, kRankCount = 3;
+constexpr int kFullSlots = 8;       // held-out items per row one PICK + COUNT pair of launches answers (rank_full.h)
 
 // One workgroup per row: the row's known items -> its bitmap (known != NULL), and the bias input of the output layer: column
 // h of the row's dh2 = 1, the padding columns behind it = 0 (the chain program stores the layer's h outputs only; the
@@ -72,10 +80,12 @@ inline size_t rank_x3_lds_bytes(int NB) {          // (128-row blocks as well: i
     return sizeof(float) * ((size_t)3 * kTI * S1 + (size_t)2 * kRankGR2 * kRRS + (size_t)lsteps * kRankMB2 * 3 * 64 * 4);
 }
 
-// COLLECT (rank_long.h): the same products with another epilogue - no lists, no extremes: every rankable cell at or above the
-// row's floor goes to the row's list in the workspace
-template <int NB, int K, bool WIN = false, bool COLLECT = false>      // WIN: dec.lin3 beyond 2^31 bytes (dec_fused.h X3WindowT)
+// EPI = kRankCollect (rank_long.h): the same products with another epilogue - no lists, no extremes: every rankable cell at or
+// above the row's floor goes to the row's list in the workspace.  kRankPick / kRankCount (rank_full.h): the cells that ARE the
+// row's held-out items store their logit; every cell is compared with the row's held-out logits and counted where it ranks first.
+template <int NB, int K, bool WIN = false, int EPI = kRankLists>      // WIN: dec.lin3 beyond 2^31 bytes (dec_fused.h X3WindowT)
 __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
+    constexpr bool COLLECT = EPI == kRankCollect, FULL = EPI == kRankPick || EPI == kRankCount;
     const bool one = a.one_term != 0;
     constexpr int KC1 = (NB + 1) / 2, NKS = (KC1 + 1) / 2;
     constexpr int NKR = NKS > kXRegSteps ? kXRegSteps : NKS, NKL = NKS - NKR;
@@ -168,6 +178,14 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
     const float c_tau = COLLECT ? a.tau[crow] : 0.f;
     int* const c_count = COLLECT ? a.count + crow : nullptr;
     unsigned long long* const c_list = COLLECT ? a.list + (size_t)crow * a.cap : nullptr;
+    constexpr int TS = FULL ? kFullSlots : 1;
+    int f_t[TS], f_c[TS]; float f_l[TS];       // the row's held-out items, their logits, this thread's cells ranked before them
+#pragma unroll
+    for (int s = 0; s < TS; ++s) {
+        f_t[s] = FULL ? a.tgt_i[(size_t)crow * TS + s] : -1;
+        f_l[s] = EPI == kRankCount ? a.tgt_v[(size_t)crow * TS + s] : INFINITY;
+        f_c[s] = 0;
+    }
 
     // the epilogue of one finished tile: the thread's four cells
     auto epilogue = [&](int i0, unsigned kword) {
@@ -184,6 +202,16 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
                     if (pos < a.cap) {
                         const unsigned u = __float_as_uint(v);
                         c_list[pos] = ((unsigned long long)(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | (unsigned)~item;
+                    }
+                }
+            } else if constexpr (FULL) {
+                // a known item counts as a cell at -inf: it ranks behind every rankable item, among its like by id
+                const float w = ((kword >> n) & 1u) ? -INFINITY : v;
+                if (item < N) {
+#pragma unroll
+                    for (int s = 0; s < TS; ++s) {
+                        if constexpr (EPI == kRankPick) { if (item == f_t[s]) a.tgt_v[(size_t)crow * TS + s] = w; }
+                        else f_c[s] += (w > f_l[s] || (w == f_l[s] && item < f_t[s])) ? 1 : 0;
                     }
                 }
             } else if (item < N) {
@@ -260,7 +288,18 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
     }
     lds_barrier();
     if (prev_i0 >= 0) epilogue(prev_i0, kw_prev);
-    if constexpr (COLLECT) return;
+    if constexpr (COLLECT || EPI == kRankPick) return;
+    if constexpr (EPI == kRankCount) {
+        // the 8 threads of a row add their counts up; one integer atomic per (row, slot, workgroup): the sum does not depend on order
+#pragma unroll
+        for (int s = 0; s < TS; ++s) {
+            int c = f_c[s];
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) c += __shfl_xor(c, o, 64);
+            if (erow && eq == 0 && f_t[s] >= 0 && c > 0) atomicAdd(a.tcount + (size_t)crow * TS + s, c);
+        }
+        return;
+    }
 
     // ---- the 8 threads of a row merge their lists (K rounds of an 8-lane argmax, ties to the smaller item) -> K candidates
     // of this workgroup for the row; its minimum / maximum

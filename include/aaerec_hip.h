@@ -411,6 +411,30 @@ int aae_rank_long_stats(aae_handle h, int64_t out[5]);
  * zc_ld >= n_code + cond_inc; `batch` names the input rows (their items are the ones exclude_known removes). */
 int aae_decode_topk(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k,
                     int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream);
+/* The rank of every held-out item in the FULL ranking of its row - what the unbounded metrics need (mrr, map: RR = 1 / the
+ * best rank, AP = mean_j j / r_j over the row's sorted ranks), and everything a metric bounded at k needs as well.  `truth`
+ * is a batch over the ground-truth CSR with the row addressing of `batch` (row i of the one belongs to row i of the other;
+ * values_dev is not read; max_row_nnz must be given: an upper bound of its longest row).  ranks_out_dev: int32, one entry per
+ * stored truth entry of the call's rows, in CSR order (row after row, a row's entries in their stored order): its 1-based
+ * rank among the row's items, 0 for an id outside [0, n_items).
+ * Tie rule - the ordering of aae_predict_topk: with exclude_known the row's input items are not rankable; the better score
+ * first; the fused form (aae_rank_full_max_rows) orders by LOGIT and items of equal logit by the smaller id, exactly the order
+ * of aae_predict_topk's lists of k > 20 on the same handle (a truth entry of rank r <= k IS position r - 1 of that list; the
+ * lists of k <= 20 may come from another summation order of the same products and differ where two logits are within a
+ * rounding of each other); the dense form orders by score, then the smaller id.  A held-out item that is itself a known item
+ * ranks behind every rankable item, among the known ones by id: n_rankable + 1 + #{known ids < t}.
+ * The fused form answers 8 held-out items per row in two passes over dec.lin3 and repeats them for longer truth rows
+ * (csrc/rank_full.h).  Nothing synchronises; the result does not vary from run to run.  As with aae_predict_topk, the hidden
+ * layers of a call of more than 224 rows are summed in another order than those of a smaller call: ranks at near-ties may
+ * differ between the two (bf16 handles: visibly); calls on one side of 224 rows agree exactly however the rows are chunked. */
+int aae_predict_ranks(aae_handle h, const aae_batch* batch, const float* cond_dev, const aae_batch* truth,
+                      int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
+/* The same behind a decoder input the caller built (as aae_decode_topk): zc_dev [batch->n_rows][zc_ld]. */
+int aae_decode_ranks(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
+                     int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
+/* Rows ONE aae_predict_ranks / aae_decode_ranks call may take (>= max_batch; aae_rank_max_rows is about the list calls and
+ * keeps its values): the fused form keeps [rows][8] targets and counters instead of candidate lists. */
+int aae_rank_full_max_rows(aae_handle h, int32_t* rows_out);
 /* split form for generic conditions */
 int aae_encode(aae_handle h, const aae_batch* batch, float* z_out_dev, void* stream);
 int aae_decode(aae_handle h, const float* zc_dev, int64_t zc_ld, int32_t n_rows,

@@ -6,7 +6,10 @@ AAE_NO_RANK_FUSED=1 in a second process, the r1-r3 two-kernel path.  Per-call HI
 (AAE_K_RANK) against its floors: 2 rows N (h+1) flop on the matrix cores, 4 N (h+1) bytes of dec.lin3 from HBM.
 RR_K=500 (any k up to 1024) ranks long lists (csrc/rank_long.h) and adds, per rows-per-call, the median of RR_REPEATS timed
 regions of that call, of the k = 32 call on the same rows, and of the only other way to the same lists: predict() per
-max_batch rows, the dense matrix copied to the host, remove_non_missing + argtopk there."""
+max_batch rows, the dense matrix copied to the host, remove_non_missing + argtopk there.
+RR_MODE=ranks times the full ranking instead (csrc/rank_full.h): predict_ranks with RR_TRUTH held-out items per row (default
+1), ranks on the host, per rows-per-call against the k = 32 list call and the dense route to the same ranks (predict() per
+max_batch rows, remove_non_missing, a full argsort on the host); it fails unless the new call is 10x faster than that route."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aae-recommender_amd"))
@@ -29,6 +32,36 @@ csr = DeviceCSR(X, hip.device)
 cap = hip.rank_max_rows(K)
 print(f"rank_max_rows({K}) = {cap}", flush=True)
 ROWS = [int(x) for x in os.environ.get("RR_ROWS", "100,256,512,1024,2048").split(",")]
+if os.environ.get("RR_MODE") == "ranks":
+    from aaerec.evaluation import remove_non_missing
+    T = int(os.environ.get("RR_TRUTH", 1))
+    r = np.random.default_rng(0)
+    tr = [np.sort(r.choice(N, size=T, replace=False)) for _ in range(DOCS)]
+    truth = DeviceCSR.from_arrays(np.arange(DOCS + 1, dtype=np.int64) * T, np.concatenate(tr), np.ones(DOCS * T, dtype=np.float32), N, hip.device)
+    print(f"rank_full_max_rows = {hip.rank_full_max_rows()}, {T} held-out item(s) per row", flush=True)
+
+    def region(fn, n):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+    med = lambda t: sorted(t)[len(t) // 2]                                                          # noqa: E731
+    reps_ = int(os.environ.get("RR_REPEATS", 5))
+    for rows in ROWS:
+        def dense_route():
+            full = np.concatenate([hip.predict(csr, s, min(B, rows - s)).cpu().numpy() for s in range(0, rows, B)])
+            return np.argsort(remove_non_missing(full, X[:rows], copy=False), axis=1)
+        hip.predict_ranks(csr, 0, rows, truth).cpu()
+        t_full = [region(lambda: hip.predict_ranks(csr, 0, rows, truth).cpu(), 5) for _ in range(reps_)]
+        t_32 = [region(lambda: hip.predict_topk(csr, 0, min(rows, cap), 32)[0].cpu(), 5) for _ in range(reps_)] if rows <= cap else [float("nan")]
+        dense_route()
+        t_host = [region(dense_route, 1) for _ in range(reps_)]
+        print(f"rows/call {rows:5d}: predict_ranks median {med(t_full):.3f} ms (repeats {[round(x, 3) for x in sorted(t_full)]}) | predict_topk k=32: "
+              f"{med(t_32):.3f} ms -> {med(t_full) / med(t_32):.2f}x | dense route (predict + host argsort): {med(t_host):.1f} ms "
+              f"({[round(x, 1) for x in sorted(t_host)]}) -> {med(t_host) / med(t_full):.1f}x slower", flush=True)
+        assert med(t_host) >= 10.0 * med(t_full), "predict_ranks is not 10x faster than the dense route"
+    sys.exit(0)
 for rows in [r for r in ROWS if r <= cap]:
     reps = max(3, 4096 // rows)
     for timed in (False, True):
