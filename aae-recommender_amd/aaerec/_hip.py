@@ -134,6 +134,16 @@ _PROTOS = {
     "aae_rank_full_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "aae_decode_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "aae_vae_predict_topk": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "aae_vae_predict_ranks": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p, C.POINTER(AaeBatch), C.c_int32,
+                                        C.c_void_p, C.c_void_p]),
+    "aae_vae_decode_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "aae_vae_decode_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32,
+                                       C.c_void_p, C.c_void_p]),
+    "aae_vae_rank_max_rows": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "aae_vae_rank_full_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "aae_encode": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
     "aae_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_apply_updates": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -1166,6 +1176,97 @@ class HipAAE:
                 with self._on_device():
                     _check(self.lib.aae_decode_ranks(self.handle, _ptr(z), z.shape[1], C.byref(b), C.byref(tb),
                                                      int(bool(exclude_known)), _ptr(ranks), self._stream()))
+            out.append(ranks)
+        return torch.cat(out) if len(out) != 1 else out[0]
+
+    # ---- the VAE's predict -> rank (aae_vae_predict_topk / ...; csrc/abi_rank.h, the VAE's form) ----------
+    def vae_rank_max_rows(self, k=10):
+        """Rows one vae_predict_topk / vae_decode_topk call may rank (aae_vae_rank_max_rows)."""
+        key = ("vae", int(k))
+        if key not in self._rank_rows:
+            out = C.c_int32()
+            _check(self.lib.aae_vae_rank_max_rows(self.handle, int(k), C.byref(out)))
+            self._rank_rows[key] = int(out.value)
+        return self._rank_rows[key]
+
+    def vae_rank_full_max_rows(self):
+        """Rows one aae_vae_predict_ranks / aae_vae_decode_ranks call may take (aae_vae_rank_full_max_rows)."""
+        if "vae_full" not in self._rank_rows:
+            out = C.c_int32()
+            _check(self.lib.aae_vae_rank_full_max_rows(self.handle, C.byref(out)))
+            self._rank_rows["vae_full"] = int(out.value)
+        return self._rank_rows["vae_full"]
+
+    def _eps_rows(self, eps, n_rows):
+        if eps is None:
+            return None
+        eps = torch.as_tensor(eps, dtype=torch.float32).to(self.device).contiguous()
+        if tuple(eps.shape) != (n_rows, self.c):
+            raise ValueError(f"eps has shape {tuple(eps.shape)}, the call {(n_rows, self.c)}: one row of draws per row")
+        return eps
+
+    def vae_predict_topk(self, csr, row_start, n_rows, k, cond=None, eps=None, exclude_known=True):
+        """predict_topk of a VAE handle: the scores of vae_predict for the same rows and eps ([n_rows, n_code]; None: the
+        device generator), ranked as predict_topk ranks.  n_rows <= vae_rank_max_rows(k)."""
+        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
+        idx = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
+        val = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
+        if cond is not None:
+            cond = upload(cond, self.device, torch.float32).contiguous()
+        eps = self._eps_rows(eps, n_rows)
+        with self._on_device():
+            _check(self.lib.aae_vae_predict_topk(self.handle, C.byref(b), _ptr(cond), _ptr(eps), int(k), int(bool(exclude_known)),
+                                                 _ptr(idx), _ptr(val), self._stream()))
+        return idx, val
+
+    def vae_decode_topk(self, zc, csr, row_start, k, exclude_known=True):
+        """Top-k of the VAE's decode(zc) for the input rows csr[row_start : row_start + len(zc)] (aae_vae_decode_topk)."""
+        zc = zc.detach().to(self.device, torch.float32).contiguous()
+        n_rows = zc.shape[0]
+        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
+        idx = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
+        val = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
+        with self._on_device():
+            _check(self.lib.aae_vae_decode_topk(self.handle, _ptr(zc), zc.shape[1], C.byref(b), int(k), int(bool(exclude_known)),
+                                                _ptr(idx), _ptr(val), self._stream()))
+        return idx, val
+
+    def vae_predict_ranks(self, csr, row_start, n_rows, truth_csr, cond=None, eps=None, exclude_known=True):
+        """predict_ranks of a VAE handle (aae_vae_predict_ranks).  Any number of rows: chunked by vae_rank_full_max_rows(),
+        every chunk with its rows of cond and eps."""
+        if cond is not None:
+            cond = upload(cond, self.device, torch.float32).contiguous()
+        eps = self._eps_rows(eps, n_rows)
+        out, chunk = [], self.vae_rank_full_max_rows()
+        for s0 in range(row_start, row_start + n_rows, chunk):
+            n = min(chunk, row_start + n_rows - s0)
+            nnz, tb = self._truth_span(truth_csr, s0, n)
+            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            if nnz:
+                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
+                c = None if cond is None else cond[s0 - row_start:s0 - row_start + n]
+                e = None if eps is None else eps[s0 - row_start:s0 - row_start + n]
+                with self._on_device():
+                    _check(self.lib.aae_vae_predict_ranks(self.handle, C.byref(b), _ptr(c), _ptr(e), C.byref(tb),
+                                                          int(bool(exclude_known)), _ptr(ranks), self._stream()))
+            out.append(ranks)
+        return torch.cat(out) if len(out) != 1 else out[0]
+
+    def vae_decode_ranks(self, zc, csr, row_start, truth_csr, exclude_known=True):
+        """The same for the VAE's decode(zc) (aae_vae_decode_ranks)."""
+        zc = zc.detach().to(self.device, torch.float32).contiguous()
+        n_rows = zc.shape[0]
+        out, chunk = [], self.vae_rank_full_max_rows()
+        for s0 in range(row_start, row_start + n_rows, chunk):
+            n = min(chunk, row_start + n_rows - s0)
+            nnz, tb = self._truth_span(truth_csr, s0, n)
+            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            if nnz:
+                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
+                z = zc[s0 - row_start:s0 - row_start + n]
+                with self._on_device():
+                    _check(self.lib.aae_vae_decode_ranks(self.handle, _ptr(z), z.shape[1], C.byref(b), C.byref(tb),
+                                                         int(bool(exclude_known)), _ptr(ranks), self._stream()))
             out.append(ranks)
         return torch.cat(out) if len(out) != 1 else out[0]
 

@@ -885,6 +885,43 @@ class DecodingRecommender(Recommender):
         condition_data = self.conditions.transform(condition_data_raw)
         return self._predict_conditions(condition_data, n_users)
 
+    def _rank_chunks(self, test_set, chunk, call):
+        """call(inputs, csr, start) over the test bags, `chunk` at a time: the decoder input of predict() (self._inputs of the
+        chunk's condition data), the test set's own rows as the known items."""
+        condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
+        X = test_set.tocsr()
+        csr = _hip.DeviceCSR(X, self.hip.device)
+        self.conditions.eval()
+        out = []
+        with torch.no_grad():
+            for start in range(0, X.shape[0], chunk):
+                c_batch = [_take(c, slice(start, min(start + chunk, X.shape[0]))) for c in condition_data]
+                out.append(call(self._inputs(c_batch), csr, start))
+        return out
+
+    def predict_topk(self, test_set, k=10):
+        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag: predict -> remove_non_missing ->
+        argtopk on the device (aae_decode_topk), only [n, k] crosses PCIe."""
+        chunk = max(self.batch_size, min(self.hip.rank_max_rows(k), 2048))
+        parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_topk(zc, csr, start, k))
+        if not parts:
+            return np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32)
+        return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
+
+    def predict_ranks(self, test_set, y_true):
+        """CSR with y_true's (canonical) pattern: the rank of every held-out item in the full ranking of its test bag
+        (aae_decode_ranks)."""
+        Ys = sp.csr_matrix(y_true, copy=True) if not sp.issparse(y_true) else y_true.tocsr(copy=True)
+        if Ys.shape != (test_set.size(0), self.hip.N):
+            raise ValueError("the ground truth has shape {}, the test set {}".format(Ys.shape, (test_set.size(0), self.hip.N)))
+        Ys.sum_duplicates()
+        Ys.sort_indices()
+        truth = _hip.DeviceCSR(Ys, self.hip.device)
+        chunk = max(self.batch_size, min(self.hip.rank_full_max_rows(), 2048))
+        ranks = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_ranks(zc, csr, start, truth))
+        data = torch.cat(ranks).cpu().numpy().astype(np.int32, copy=False) if ranks else np.zeros(0, dtype=np.int32)
+        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+
 
 def _validate_targets(X):
     """The reference's F.binary_cross_entropy rejects targets outside [0,1] (duplicate items in a

@@ -177,3 +177,16 @@ class DAERecommender(Recommender):
         else:
             condition_data = None
         return self.dae.predict(X, condition_data=condition_data)
+
+    def _conditions_of(self, test_set):
+        if not self.conditions:
+            return None
+        return self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
+
+    def predict_topk(self, test_set, k=10):
+        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag (AdversarialAutoEncoder.predict_topk)."""
+        return self.dae.predict_topk(test_set.tocsr(), k=k, condition_data=self._conditions_of(test_set))
+
+    def predict_ranks(self, test_set, y_true):
+        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag."""
+        return self.dae.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set))

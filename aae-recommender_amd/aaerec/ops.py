@@ -1,4 +1,5 @@
-"""PyTorch custom ops over the C ABI: ``torch.ops.aaerec.{step, encode, predict, predict_topk, predict_ranks}``.
+"""PyTorch custom ops over the C ABI: ``torch.ops.aaerec.{step, encode, predict, predict_topk, predict_ranks,
+vae_predict_topk, vae_predict_ranks}``.
 
 The product is ``libaaerec_hip.so`` (``include/aaerec_hip.h``); these ops are the thin torch-facing
 surface BASELINE.json's north star names ("exposed to Python through PyTorch-ROCm custom ops over a
@@ -30,6 +31,11 @@ _LIB.define(f"predict_topk(int model, {_CSR}, int row_start, int n_rows, int max
             "bool exclude_known) -> (Tensor, Tensor)")
 # the rank of every stored entry of the truth CSR's rows (same row window as the input CSR) in the full ranking: int32, CSR order
 _LIB.define(f"predict_ranks(int model, {_CSR}, int row_start, int n_rows, int max_row_nnz, Tensor? cond, "
+            "Tensor truth_indptr, Tensor truth_indices, int truth_max_row_nnz, bool exclude_known) -> Tensor")
+# the same for a VAE handle (HipAAE(..., vae=True)): eps = [n_rows, n_code] draws of reparametrize(), None = the device generator
+_LIB.define(f"vae_predict_topk(int model, {_CSR}, int row_start, int n_rows, int max_row_nnz, Tensor? cond, Tensor? eps, int k, "
+            "bool exclude_known) -> (Tensor, Tensor)")
+_LIB.define(f"vae_predict_ranks(int model, {_CSR}, int row_start, int n_rows, int max_row_nnz, Tensor? cond, Tensor? eps, "
             "Tensor truth_indptr, Tensor truth_indices, int truth_max_row_nnz, bool exclude_known) -> Tensor")
 
 _MODELS = weakref.WeakValueDictionary()
@@ -112,6 +118,22 @@ def _predict_ranks(model, indptr, indices, values, row_start, n_rows, max_row_nn
                            exclude_known=exclude_known)
 
 
+def _vae_predict_topk(model, indptr, indices, values, row_start, n_rows, max_row_nnz, cond, eps, k, exclude_known):
+    m = _model(model)
+    return m.vae_predict_topk(_CsrView(indptr, indices, values, max_row_nnz, m.N), row_start, n_rows, k, cond=cond, eps=eps,
+                              exclude_known=exclude_known)
+
+
+def _vae_predict_ranks(model, indptr, indices, values, row_start, n_rows, max_row_nnz, cond, eps, truth_indptr, truth_indices,
+                       truth_max_row_nnz, exclude_known):
+    m = _model(model)
+    truth = _CsrView(truth_indptr, truth_indices, values, truth_max_row_nnz, m.N)
+    truth.shape = (truth_indptr.numel() - 1, m.N)
+    return m.vae_predict_ranks(_CsrView(indptr, indices, values, max_row_nnz, m.N), row_start, n_rows, truth, cond=cond, eps=eps,
+                               exclude_known=exclude_known)
+
+
 for _name, _fn in (("step", _step), ("encode", _encode), ("predict", _predict), ("predict_topk", _predict_topk),
-                   ("predict_ranks", _predict_ranks)):
+                   ("predict_ranks", _predict_ranks), ("vae_predict_topk", _vae_predict_topk),
+                   ("vae_predict_ranks", _vae_predict_ranks)):
     _LIB.impl(_name, _fn, "CUDA")

@@ -204,6 +204,70 @@ class VAE:
                 pred.put(start, self.hip.vae_predict(csr, start, n, cond=cond, eps=self._eps(n)))
         return pred.numpy()
 
+    # ---- ranking on the device (aae_vae_predict_topk / aae_vae_predict_ranks) ----------------------------------
+    def _rank_chunks(self, Xs, condition_data, chunk, fused, decode):
+        """The rows of Xs, `chunk` at a time, through fused(start, n, cond, eps) - conditions the kernels take ride in the
+        call - or, behind any other plugin, decode(start, zc): aae_vae_encode -> encode_impose as predict() cuts it.  In
+        rng_mode='reference' eps is drawn as predict() draws it - torch.randn per batch_size rows, in row order - so the
+        same torch seed gives the scores of predict()."""
+        use_condition = _check_conditions(self.conditions, condition_data)
+        self.eval()
+        if self.conditions:
+            self.conditions.eval()
+        csr = _hip.DeviceCSR(Xs, self.device)
+        n_rows, bs = Xs.shape[0], self.batch_size
+        eps_all = None
+        if self.rng_mode == "reference":
+            draws = [self._eps(min(bs, n_rows - s)) for s in range(0, n_rows, bs)]
+            eps_all = torch.cat(draws).to(self.device) if draws else None
+        out = []
+        with torch.no_grad():
+            for start in range(0, n_rows, chunk):
+                n = min(chunk, n_rows - start)
+                eps = None if eps_all is None else eps_all[start:start + n]
+                c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
+                if use_condition and not self._cond_native:
+                    z = torch.cat([self.hip.vae_encode(csr, s0, min(bs, start + n - s0), train=False,
+                                                       eps=None if eps is None else eps[s0 - start:s0 - start + bs])
+                                   for s0 in range(start, start + n, bs)])
+                    out.append(decode(csr, start, self.conditions.encode_impose(z, c_batch)))
+                else:
+                    out.append(fused(csr, start, n, self._cond(c_batch) if use_condition else None, eps))
+        return out
+
+    def predict_topk(self, X, k=10, condition_data=None, exclude_known=True):
+        """(item ids [n, k], scaled scores [n, k]) of predict -> remove_non_missing -> argtopk (vae.py:229-266,
+        evaluation.py:183-199, 20-58) without the [n, N] score matrix: see AdversarialAutoEncoder.predict_topk."""
+        Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+        chunk = max(self.batch_size, min(self.hip.vae_rank_max_rows(k), 2048))
+        parts = self._rank_chunks(
+            Xs, condition_data, chunk,
+            lambda csr, start, n, cond, eps: self.hip.vae_predict_topk(csr, start, n, k, cond=cond, eps=eps,
+                                                                       exclude_known=exclude_known),
+            lambda csr, start, zc: self.hip.vae_decode_topk(zc, csr, start, k, exclude_known=exclude_known))
+        if not parts:
+            return np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32)
+        return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
+
+    def predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
+        """A scipy CSR with Y's (canonical) pattern whose data are the int32 1-based ranks of the held-out items in the full
+        ranking of their rows: see AdversarialAutoEncoder.predict_ranks."""
+        Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+        Ys = sp.csr_matrix(Y, copy=True) if not sp.issparse(Y) else Y.tocsr(copy=True)
+        if Ys.shape != Xs.shape:
+            raise ValueError("the ground truth has shape {}, the inputs {}".format(Ys.shape, Xs.shape))
+        Ys.sum_duplicates()
+        Ys.sort_indices()
+        truth = _hip.DeviceCSR(Ys, self.device)
+        chunk = max(self.batch_size, min(self.hip.vae_rank_full_max_rows(), 2048))
+        ranks = self._rank_chunks(
+            Xs, condition_data, chunk,
+            lambda csr, start, n, cond, eps: self.hip.vae_predict_ranks(csr, start, n, truth, cond=cond, eps=eps,
+                                                                        exclude_known=exclude_known),
+            lambda csr, start, zc: self.hip.vae_decode_ranks(zc, csr, start, truth, exclude_known=exclude_known))
+        data = torch.cat(ranks).cpu().numpy().astype(np.int32, copy=False) if ranks else np.zeros(0, dtype=np.int32)
+        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+
 
 class VAERecommender(Recommender):
     """
@@ -246,3 +310,16 @@ class VAERecommender(Recommender):
         else:
             condition_data = None
         return self.model.predict(X, condition_data=condition_data)
+
+    def _conditions_of(self, test_set):
+        if not self.conditions:
+            return None
+        return self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
+
+    def predict_topk(self, test_set, k=10):
+        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag."""
+        return self.model.predict_topk(test_set.tocsr(), k=k, condition_data=self._conditions_of(test_set))
+
+    def predict_ranks(self, test_set, y_true):
+        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag."""
+        return self.model.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set))

@@ -73,6 +73,7 @@ struct ChainBuilder {
     }
     ChainOp& add(const ChainOp& o) { P.ops[P.nops] = o; return P.ops[P.nops++]; }
     int x16_rows = 0;      // > 0: this program's own row threshold for the wide-batch kernel (beside_deferred)
+    bool vae4 = false;     // the program's COP_REPARAM runs on the 4-row kernel's VAE member (the VAE's rank programs, abi_rank.h)
     // The discriminator and generator programs of a row-blocked step over a LARGE vocabulary run beside its deferred launch,
     // which holds 3/4 of the chip for most of the step's tail: a 4-row launch of 128 workgroups (512 rows) then takes two
     // rounds on the CUs that are left - there the 16-row kernel pays from 512 rows on (C3 at batch 512: generator program 64 ->
@@ -245,7 +246,7 @@ int print_chain_timeline(const ChainProgram& P, const unsigned long long* ts_dev
 
 int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
     if (cb.P.nops > kCMaxOps) return fail(AAE_ESTATE, "chain program too long");
-    const bool want_ts = m->opt.chain_ts;      // debug: per-op timeline of workgroup 0
+    const bool want_ts = m->opt.chain_ts && !cb.vae4;      // debug: per-op timeline of workgroup 0 (the VAE member carries no stamps)
     static unsigned long long* ts_dev = nullptr;
     if (want_ts) {
         if (!ts_dev && hipMalloc(&ts_dev, 128 * sizeof(unsigned long long)) != hipSuccess) return fail(AAE_EHIP, "ts alloc");
@@ -258,7 +259,8 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
     for (int i = 0; i < cb.P.nops && four; ++i)
         if ((cb.P.ops[i].kind == COP_LINEAR || cb.P.ops[i].kind == COP_LINEAR_DX) && !cb.P.ops[i].Wkn && !cb.P.ops[i].W4) four = false;
     for (int i = 0; i < cb.P.nops && four; ++i)
-        if (cb.P.ops[i].kind == COP_ADV || cb.P.ops[i].kind == COP_REPARAM || cb.P.ops[i].kind == COP_REPARAM_BWD) four = false;
+        if (cb.P.ops[i].kind == COP_ADV || (cb.P.ops[i].kind == COP_REPARAM && !cb.vae4) || cb.P.ops[i].kind == COP_REPARAM_BWD) four = false;
+    if (cb.vae4 && !four) return fail(AAE_ESTATE, "a VAE rank program needs the 4-row chain kernel");
     for (int i = 0; i < cb.P.nops; ++i)
         if ((cb.P.ops[i].row_lo > 0 || cb.P.ops[i].acc_in || cb.P.ops[i].y_glb) && !four)
             return fail(AAE_ESTATE, "a program prefix for the upper rows / a layer in two k-parts needs the 4-row chain kernel");
@@ -286,7 +288,7 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
         }
     }
     // (chain4: bf16 programs without k-slices take the column form)
-    const ChainKernel kernel = four ? pick_chain4(m->bf16, ts_kernel, m->bf16 && !cb.P.kslices) : pick_chain(m->bf16, m->act_nm);
+    const ChainKernel kernel = four ? pick_chain4(m->bf16, ts_kernel, m->bf16 && !cb.P.kslices, cb.vae4) : pick_chain(m->bf16, m->act_nm);
     if (!kernel) return fail(AAE_ESTATE, "no chain kernel is compiled for this mode");
     const int grid = (cb.P.rows + (four ? kR4 : kCR) - 1) / (four ? kR4 : kCR) + (cb.P.bk.enabled ? 1 : 0);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(four ? kC4T : kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);

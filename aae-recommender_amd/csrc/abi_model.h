@@ -191,6 +191,7 @@ struct aae_model {
     long long flushed_hstep = -1;                          // hstep at the last whole-matrix deferred-Adam flush of a rank call (abi_rank.h)
     int64_t long_stats[5] = {0, 0, 0, 0, 0};               // aae_rank_long_stats: fused k > 32 calls, rows, rows that overflowed, entries collected, most per row
     bool rank_ok = false;                                  // rank_x3.h: predict -> rank fused (aae_predict_topk / aae_decode_topk), abi_rank.h
+    bool vae_rank_ok = false;                              // ... of a VAE handle (aae_vae_predict_topk / _ranks: chain4.h's COP_REPARAM member)
     bool side_ordered = false;                             // ... or put its dV3 GEMM there: the side stream is in order behind that step's output layer
 };
 

@@ -195,3 +195,125 @@ int aae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae
 }
 
 }  // extern "C"
+
+// ---- the VAE: predict -> rank (reference vae.py:229-266 + evaluation.py:183-199, 20-58; abi_rank.h, the VAE's form) -------------------
+namespace {
+int vae_rank_check(const aae_model* m, const float* cond_dev, const float* eps_dev, bool decode) {
+    if (!m->vae || !m->use_chain) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
+    if (decode) return AAE_OK;
+    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
+    if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
+    return AAE_OK;
+}
+// the dense form's scores: rows of `batch` (<= max_batch) into the [max_batch][n_items] scratch
+int vae_scores_to_scratch(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev,
+                          int64_t zc_ld, void* stream) {
+    if (!zc_dev) return aae_vae_predict(m, batch, cond_dev, eps_dev, m->G.p, m->ldn, stream);
+    TRY(set_batch(m, batch));
+    return aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream);
+}
+// zc_dev != NULL: the decode form (cond_dev / eps_dev are not read)
+int vae_topk(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld,
+             int k, int exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    hipStream_t s = S(stream);
+    const int nc = m->c, ci = m->cfg.cond_inc;
+    if (batch->n_rows >= 1 && batch->n_rows <= vae_rank_rows_cap(m, k)) {      // fused: no [rows][N] matrix
+        const int rows = batch->n_rows;
+        const VaeRankCopies c = vae_rank_copies(m, m->G.p);
+        float* base = m->G.p + c.floats;
+        const RankPlan p = rank_plan(m, rows, k, base);
+        m->phase = 0;
+        if (zc_dev) TRY(vae_rank_decode_hidden(m, zc_dev, zc_ld, rows, c, p.dh2, s));
+        else TRY(vae_rank_predict_hidden(m, batch, cond_dev, eps_dev, 0, c, p.a1, p.eh1, p.rscale, p.dh2, s));
+        TRY(rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out_dev, val_out_dev, s));
+        if (!rank_long(k)) return AAE_OK;
+        std::vector<std::pair<int, int>> spans;        // rows whose collect list overflowed: through the score matrix
+        TRY(rank_long_overflow(m, batch, k, s, spans, base));
+        for (const auto& sp : spans) {
+            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
+            const size_t r0 = (size_t)sp.first;
+            TRY(vae_rank_long_span(m, &sub, cond_dev ? cond_dev + r0 * ci : nullptr, eps_dev ? eps_dev + r0 * nc : nullptr,
+                                   zc_dev ? zc_dev + r0 * zc_ld : nullptr, zc_ld, sp.first, k, exclude_known, idx_out_dev + r0 * k,
+                                   val_out_dev + r0 * k, s));
+        }
+        return AAE_OK;
+    }
+    TRY(vae_scores_to_scratch(m, batch, cond_dev, eps_dev, zc_dev, zc_ld, stream));
+    TRY(topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s));
+    m->phase = 0;
+    return AAE_OK;
+}
+int vae_ranks(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld,
+              const aae_batch* truth, int exclude_known, int32_t* ranks_out_dev, void* stream) {
+    hipStream_t s = S(stream);
+    if (batch->n_rows >= 1 && batch->n_rows <= vae_rank_full_rows_cap(m)) {
+        const int rows = batch->n_rows;
+        const VaeRankCopies c = vae_rank_copies(m, m->G.p);
+        const RankPlan p = rank_plan(m, rows, 32, m->G.p + c.floats, true);
+        m->phase = 0;
+        if (zc_dev) TRY(vae_rank_decode_hidden(m, zc_dev, zc_ld, rows, c, p.dh2, s));
+        else TRY(vae_rank_predict_hidden(m, batch, cond_dev, eps_dev, 0, c, p.a1, p.eh1, p.rscale, p.dh2, s));
+        return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out_dev, s);
+    }
+    TRY(vae_scores_to_scratch(m, batch, cond_dev, eps_dev, zc_dev, zc_ld, stream));
+    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), 0, exclude_known, ranks_out_dev, s));
+    m->phase = 0;
+    return AAE_OK;
+}
+}  // namespace
+extern "C" {
+
+int aae_vae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, int32_t k,
+                         int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    TRY(vae_rank_check(m, cond_dev, eps_dev, false));
+    TRY(check_topk_k(m, k));
+    TRY(rank_check_batch(batch));
+    return vae_topk(m, batch, cond_dev, eps_dev, nullptr, 0, k, exclude_known, idx_out_dev, val_out_dev, stream);
+}
+
+int aae_vae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k, int32_t exclude_known,
+                        int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    if (!m || !zc_dev || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    TRY(vae_rank_check(m, nullptr, nullptr, true));
+    TRY(check_topk_k(m, k));
+    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
+    TRY(rank_check_batch(batch));
+    return vae_topk(m, batch, nullptr, nullptr, zc_dev, zc_ld, k, exclude_known, idx_out_dev, val_out_dev, stream);
+}
+
+int aae_vae_predict_ranks(aae_handle m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const aae_batch* truth,
+                          int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
+    if (!m || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    TRY(vae_rank_check(m, cond_dev, eps_dev, false));
+    TRY(rank_check_batch(batch));
+    TRY(rank_check_truth(batch, truth));
+    return vae_ranks(m, batch, cond_dev, eps_dev, nullptr, 0, truth, exclude_known, ranks_out_dev, stream);
+}
+
+int aae_vae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
+                         int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
+    if (!m || !zc_dev || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
+    TRY(vae_rank_check(m, nullptr, nullptr, true));
+    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
+    TRY(rank_check_batch(batch));
+    TRY(rank_check_truth(batch, truth));
+    return vae_ranks(m, batch, nullptr, nullptr, zc_dev, zc_ld, truth, exclude_known, ranks_out_dev, stream);
+}
+
+int aae_vae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
+    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
+    TRY(vae_rank_check(m, nullptr, nullptr, true));
+    TRY(check_topk_k(m, k));
+    *rows_out = std::max(m->R, vae_rank_rows_cap(m, k));
+    return AAE_OK;
+}
+
+int aae_vae_rank_full_max_rows(aae_handle m, int32_t* rows_out) {
+    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
+    TRY(vae_rank_check(m, nullptr, nullptr, true));
+    *rows_out = std::max(m->R, vae_rank_full_rows_cap(m));
+    return AAE_OK;
+}
+
+}  // extern "C"

@@ -74,10 +74,9 @@ size_t rank_ws_floats(const aae_model* m) {
     return m->G.floats();
 }
 
-// most rows one fused call can rank (0: the fused path does not apply to this handle)
-int rank_rows_cap(const aae_model* m, int k) {
-    if (!m->rank_ok || k < 1 || k > kLongKMax) return 0;
-    const size_t have = rank_ws_floats(m);
+// most rows one fused call can rank in `have` floats of workspace
+int rank_rows_fit(const aae_model* m, int k, size_t have) {
+    if (k < 1 || k > kLongKMax) return 0;
     const int ntiles = (m->N + kTI - 1) / kTI;
     int lo = 0, hi = kRankMaxRows;          // (the plan's size is monotone in rows up to rounding: bisect)
     while (lo < hi) {
@@ -89,11 +88,8 @@ int rank_rows_cap(const aae_model* m, int k) {
     }
     return lo;
 }
-
-// most rows one fused full-ranking call can take (0: the fused path does not apply to this handle)
-int rank_full_rows_cap(const aae_model* m) {
-    if (!m->rank_ok) return 0;
-    const size_t have = rank_ws_floats(m);
+// ... one fused full-ranking call
+int rank_full_rows_fit(const aae_model* m, size_t have) {
     int lo = 0, hi = kRankMaxRows;
     while (lo < hi) {
         const int mid = (lo + hi + 1) / 2;
@@ -101,6 +97,9 @@ int rank_full_rows_cap(const aae_model* m) {
     }
     return lo;
 }
+// (0: the fused path does not apply to this handle)
+int rank_rows_cap(const aae_model* m, int k) { return m->rank_ok ? rank_rows_fit(m, k, rank_ws_floats(m)) : 0; }
+int rank_full_rows_cap(const aae_model* m) { return m->rank_ok ? rank_full_rows_fit(m, rank_ws_floats(m)) : 0; }
 
 // one launch of a rank kernel: rank_x3v2 / rank_x3 by rank_v2_nb (kernel_pick.h), or the K = 32 kernel's front end with
 // another epilogue: collect (rank_long.h), pick / count (rank_full.h)
@@ -205,24 +204,28 @@ BatchView rank_view(const aae_batch* b) {
     return bv;
 }
 
-// the rows' forward pass up to the decoder's last hidden layer -> p.dh2 (eval mode: no dropout; aae.py:840-870)
-int rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* cond_dev, const RankPlan& p, hipStream_t s) {
-    const int rows = batch->n_rows, h = m->h, c = m->c, cp = m->cp;
+// the first layer of a rank call: a1 / eh1 [rows][ldh] = (act of) enc.lin1 of the rows, eval mode; every deferred launch joined
+int rank_first_layer(aae_model* m, const aae_batch* batch, float* a1, float* eh1, float* rscale, hipStream_t s) {
+    const int rows = batch->n_rows, h = m->h;
     TRY(join_deferred(m, s));
     if (m->flushed_hstep != m->hstep) {     // every row of enc.lin1 through the current step: once after the last training step
         TRY(lazy_flush(m, s));               // (rows fall behind only when a step opens: hstep counts them)
         m->flushed_hstep = m->hstep;
     }
-    const BatchView bv = rank_view(batch);
-    {
-        DropSpec d1 = make_drop(m, 0, false, nullptr, nullptr, rows, h, 0);
-        ProfScope ps(m, AAE_K_ENC_GATHER, s);
-        hipLaunchKernelGGL(enc_gather_kernel, dim3(rows), dim3(1024), (uint32_t)((size_t)16 * r4(h) * sizeof(float)), s, bv,
-                           (const float*)m->P[P_W1T].p, m->ldw1, (const float*)m->P[P_B1].p, h, (int)m->cfg.normalize_inputs,
-                           p.a1, p.eh1, m->ldh, (int)m->cfg.activation, d1, (uint64_t)m->cfg.seed, (const long long*)m->step_ctr,
-                           p.rscale, (const float*)nullptr, AdvanceJob{nullptr, nullptr, nullptr, nullptr, 0}, (long long)-1);
-        LAUNCHCHK("enc_gather (rank)");
-    }
+    DropSpec d1 = make_drop(m, 0, false, nullptr, nullptr, rows, h, 0);
+    ProfScope ps(m, AAE_K_ENC_GATHER, s);
+    hipLaunchKernelGGL(enc_gather_kernel, dim3(rows), dim3(1024), (uint32_t)((size_t)16 * r4(h) * sizeof(float)), s, rank_view(batch),
+                       (const float*)m->P[P_W1T].p, m->ldw1, (const float*)m->P[P_B1].p, h, (int)m->cfg.normalize_inputs,
+                       a1, eh1, m->ldh, (int)m->cfg.activation, d1, (uint64_t)m->cfg.seed, (const long long*)m->step_ctr,
+                       rscale, (const float*)nullptr, AdvanceJob{nullptr, nullptr, nullptr, nullptr, 0}, (long long)-1);
+    LAUNCHCHK("enc_gather (rank)");
+    return AAE_OK;
+}
+
+// the rows' forward pass up to the decoder's last hidden layer -> p.dh2 (eval mode: no dropout; aae.py:840-870)
+int rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* cond_dev, const RankPlan& p, hipStream_t s) {
+    const int rows = batch->n_rows, h = m->h, c = m->c, cp = m->cp;
+    TRY(rank_first_layer(m, batch, p.a1, p.eh1, p.rscale, s));
     ChainBuilder cb(m, rows);
     ChainOp& l = cb.add(cop_load(p.eh1, m->ldh, 0, h)); l.one_col = h;
     ChainOp& w2 = cb.add(cop_fwd(m, P_W2, 0, 1, h + 1, h, CEPI_DROPACT, s));
@@ -298,11 +301,12 @@ int rank_long_dense(aae_model* m, int k, int exclude_known, int32_t* idx_out, fl
 
 // After a fused k > 32 call: the rows' entry counts (synchronises `s`), the handle's statistics, and the spans of at most
 // max_batch rows that hold a row whose list overflowed - the caller ranks those through the score matrix.
-int rank_long_overflow(aae_model* m, const aae_batch* b, int k, hipStream_t s, std::vector<std::pair<int, int>>& spans) {
+int rank_long_overflow(aae_model* m, const aae_batch* b, int k, hipStream_t s, std::vector<std::pair<int, int>>& spans,
+                       float* base = nullptr) {
     const int rows = b->n_rows;
     // (a span keeps to the dense path's per-batch bounds: max_batch rows, max_nnz entries)
     const int span = std::max(1, std::min(m->R, b->max_row_nnz > 0 ? m->cfg.max_nnz / b->max_row_nnz : m->R));
-    const RankPlan p = rank_plan(m, rows, k, m->G.p);
+    const RankPlan p = rank_plan(m, rows, k, base ? base : m->G.p);      // (base: a workspace that starts behind the scratch's head)
     std::vector<int> cnt(rows);
     HIPCHK(hipMemcpyAsync(cnt.data(), p.count, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -337,6 +341,109 @@ int rank_check_truth(const aae_batch* batch, const aae_batch* truth) {
     if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, "truth names another number of rows than batch");
     if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "truth needs max_row_nnz: the entries of its longest row (an upper bound)");
     return AAE_OK;
+}
+
+// ---- the VAE's form (aae_vae_predict_topk / _ranks / _decode_topk / _decode_ranks; reference vae.py:229-266) -------------
+// The same workspace, the same ranking passes over dec.lin3 (= fc4); the hidden half is the VAE's forward in ONE program on the
+// 4-row kernel: eh1 -> [mu | logvar] = [fc21; fc22] eh1 -> z = mu + eps * exp(logvar / 2) -> condition block -> dh2 = act(fc3 zc).
+// A VAE handle keeps no k-major copies of its layers (its training programs run on chain.h, whose optimiser epilogues would
+// have to keep them in step): a rank call derives the F4 copies of the two small matrices into the head of its workspace -
+// ~60 k floats at the headline widths, two launches - and lays its plan out behind them.
+struct VaeRankCopies { float* w3; float* v1; float* d4; size_t floats; };
+
+VaeRankCopies vae_rank_copies(const aae_model* m, float* base) {
+    auto f4 = [](const Ten& W) { return (size_t)((W.cols + 3) / 4 + kW4Pad) * 4 * W.rows; };          // (+ the zero k-chunk rows, chain4.h)
+    auto d4 = [](const Ten& W) { return (size_t)((W.rows + 3) / 4) * 4 * W.cols; };
+    const Ten &W3 = m->P[P_W3], &V1 = m->P[P_V1];
+    VaeRankCopies c;
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return base ? base + o : nullptr; };
+    c.w3 = take(f4(W3)); c.v1 = take(f4(V1));
+    c.d4 = take(std::max(d4(W3), d4(V1)));       // (interleave4_kernel writes the dX copy too: nobody reads it)
+    c.floats = off;
+    return c;
+}
+
+int vae_rank_rows_cap(const aae_model* m, int k) {
+    const size_t have = rank_ws_floats(m), head = vae_rank_copies(m, nullptr).floats;
+    return m->vae_rank_ok && have > head ? rank_rows_fit(m, k, have - head) : 0;
+}
+int vae_rank_full_rows_cap(const aae_model* m) {
+    const size_t have = rank_ws_floats(m), head = vae_rank_copies(m, nullptr).floats;
+    return m->vae_rank_ok && have > head ? rank_full_rows_fit(m, have - head) : 0;
+}
+
+// the F4 copies from the parameters as they stand (behind join_deferred: nothing else writes or reads the scratch)
+int vae_rank_derive(aae_model* m, const VaeRankCopies& c, hipStream_t s) {
+    HIPCHK(hipMemsetAsync(c.w3, 0, c.floats * sizeof(float), s));      // (the k-chunks beyond a matrix read as zero, not as what a step left)
+    for (int pid : {P_W3, P_V1}) {
+        const Ten& W = m->P[pid];
+        hipLaunchKernelGGL(interleave4_kernel, dim3(grid1d((size_t)W.rows * ((W.cols + 3) / 4))), dim3(256), 0, s, W.p, (int)W.ld,
+                           W4Copies{pid == P_W3 ? c.w3 : c.v1, c.d4, (int)W.rows, (int)W.cols, nullptr, nullptr, nullptr, kCWide});
+        LAUNCHCHK("interleave4 (vae rank)");
+    }
+    return AAE_OK;
+}
+
+// a forward layer of the VAE's rank program: cop_fwd with the workspace's F4 copy
+ChainOp vae_cop_fwd(const aae_model* m, int pid, const float* w4, int src, int dst, int K, int N, int epi) {
+    ChainOp o = cop_linear(COP_LINEAR, src, dst, m->P[pid], K, N, epi);
+    o.W4 = w4; o.ns4 = (int)m->P[pid].rows;
+    return o;
+}
+
+// the decoder half: slot 2 holds [z | condition | 1] -> dh2 = act(fc3 zc) (no dropout in the VAE: the DropSpec stays disabled)
+void vae_rank_dec_hidden(aae_model* m, ChainBuilder& cb, const VaeRankCopies& c, float* dh2) {
+    ChainOp& v1 = cb.add(vae_cop_fwd(m, P_V1, c.v1, 2, 3, m->cp + 1, m->h, CEPI_DROPACT));
+    v1.one_col = m->h; cop_out(v1, dh2, m->ldh);
+}
+
+// rows of `batch` -> dh2 [rows][ldh].  eps_dev: row 0 of the batch (NULL: the counter generator, rows counted from grow0);
+// a1 / eh1 / rscale: [rows] scratch of the first layer
+int vae_rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, int grow0,
+                            const VaeRankCopies& c, float* a1, float* eh1, float* rscale, float* dh2, hipStream_t s) {
+    const int rows = batch->n_rows, h = m->h, nc = m->c, cp = m->cp;
+    TRY(rank_first_layer(m, batch, a1, eh1, rscale, s));
+    TRY(vae_rank_derive(m, c, s));
+    ChainBuilder cb(m, rows);
+    cb.vae4 = true;
+    ChainOp& l = cb.add(cop_load(eh1, m->ldh, 0, h)); l.one_col = h;
+    cb.add(vae_cop_fwd(m, P_W3, c.w3, 0, 1, h + 1, 2 * nc, CEPI_NONE));
+    ChainOp& rp = cb.add(cop(COP_REPARAM, 1, 2, nc));
+    rp.W = eps_dev; rp.ldw = nc; rp.aux = 12; rp.grow0 = grow0;        // (stream id 12: chain_vae_forward's draws)
+    if (m->cfg.cond_inc > 0) {
+        ChainOp& cl = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, m->cfg.cond_inc)); cl.dst_col0 = nc; cl.one_col = cp;
+    } else {
+        rp.one_col = cp;
+    }
+    vae_rank_dec_hidden(m, cb, c, dh2);
+    return launch_chain(m, cb, s);
+}
+
+// the same from a decoder input the caller built: zc_dev [rows][zc_ld] -> dh2
+int vae_rank_decode_hidden(aae_model* m, const float* zc_dev, int64_t zc_ld, int rows, const VaeRankCopies& c, float* dh2, hipStream_t s) {
+    TRY(join_deferred(m, s));
+    TRY(vae_rank_derive(m, c, s));
+    ChainBuilder cb(m, rows);
+    cb.vae4 = true;
+    ChainOp& l = cb.add(cop_load(zc_dev, (int)zc_ld, 2, m->cp)); l.one_col = m->cp;
+    vae_rank_dec_hidden(m, cb, c, dh2);
+    return launch_chain(m, cb, s);
+}
+
+// A row of a fused k > 32 call whose collect list overflowed: rows [0, sub->n_rows) of `sub` (<= max_batch) through the score
+// matrix.  The hidden half runs the fused call's own program on the handle's per-batch buffers - the same eps rows (eps_dev /
+// generator rows from grow0), the same dh2 bits - then fc4 + sigmoid into the scratch, which the copies' head is part of: they
+// are derived again per span.
+int vae_rank_long_span(aae_model* m, const aae_batch* sub, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld,
+                       int grow0, int k, int exclude_known, int32_t* idx_out, float* val_out, hipStream_t s) {
+    TRY(set_batch(m, sub));
+    const VaeRankCopies c = vae_rank_copies(m, m->G.p);
+    if (zc_dev) TRY(vae_rank_decode_hidden(m, zc_dev, zc_ld, m->rows, c, m->dh2.p, s));
+    else TRY(vae_rank_predict_hidden(m, sub, cond_dev, eps_dev, grow0, c, m->a1.p, m->eh1.p, m->rscale, m->dh2.p, s));
+    EpiSigmoid e; e.out = m->G.p; e.ld = m->ldn;
+    TRY(linear_fwd(m->dh2.p, m->ldh, m->rows, m->P[P_V3], e, s, gmode(m)));
+    return rank_long_dense(m, k, exclude_known, idx_out, val_out, s);
 }
 
 }  // namespace

@@ -236,7 +236,9 @@ __device__ __forceinline__ f32x4 chain4_cols(const float* W4, int ns4, int N, in
 // k-slice form sits at its 128-register cap: compiled beside the other form it keeps one of its thirteen weight chunks in scratch
 // memory (and waits for all of them before its first product: C4's shape in bf16 0.312 -> 0.321 ms/step) - so wide batches are
 // launched on the instantiation without it.
-template <bool BF, bool TS = false, bool COLS = false>
+// VAE: the instantiation that carries the forward COP_REPARAM op - the VAE's predict -> rank programs (abi_rank.h) alone run on
+// it.  The op is compiled into no other member: every program of the AAE's step keeps the code it had.
+template <bool BF, bool TS = false, bool COLS = false, bool VAE = false>
 __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
     extern __shared__ __attribute__((aligned(16))) float slots[];     // [kCSlots][4][kCL], then the partial-sum scratch
     if (P.bk.enabled && blockIdx.x == gridDim.x - 1) {                // (uniform) the piggy-backed bucket builder
@@ -542,7 +544,37 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     }
                 }
             }
-        }   // COP_STORE: only the stores below.  (COP_ADV / COP_REPARAM*: VAE programs stay on chain.h's kernel)
+        }   // COP_STORE: only the stores below.  (COP_ADV / COP_REPARAM_BWD: the VAE's training programs stay on chain.h's kernel)
+        // VAE (vae.py:115-118): src = [mu | logvar] (2N columns) -> dst[:, 0:N) = mu + eps * exp(logvar / 2), one cell per thread.
+        // eps: qW (injected, [rows][qldw]) or the counter generator - the draw of chain.h's op for the same (seed, step, row
+        // qgrow0 + r, column) - kept in qaux_ptr where the caller wants it.  src != dst.  (A statement of its own, not one more
+        // branch of the chain above: the other members then compile to exactly what they were.)
+        if constexpr (VAE) {
+            if (kind == COP_REPARAM) {
+                if (ecol < kCL)
+                for (int eh = 0; eh < kC4E; ++eh) {
+                    const int erow = erow0 + kC4ER * eh;
+                    float zv = 0.f;
+                    if (erow < nrows && ecol < opN) {
+                        float eps;
+                        if (qW) eps = qW[(size_t)(r0 + erow) * qldw + ecol];
+                        else {      // Box-Muller on two words of the counter generator (stream id = qaux)
+                            const uint64_t k = key ^ ((uint64_t)(uint32_t)qaux * 0xA0761D6478BD642Full);
+                            const uint32_t u1 = hash_cell(k, (uint32_t)(r0 + erow + qgrow0), (uint32_t)(2 * ecol));
+                            const uint32_t u2 = hash_cell(k, (uint32_t)(r0 + erow + qgrow0), (uint32_t)(2 * ecol + 1));
+                            const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
+                            const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
+                            eps = sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2);
+                        }
+                        if (qaux_ptr) qaux_ptr[(size_t)(r0 + erow) * qaux_ld + ecol] = eps;
+                        const float mu = src[erow * kCL + ecol], lv = src[erow * kCL + opN + ecol];
+                        zv = mu + eps * expf(0.5f * lv);
+                    }
+                    dst[erow * kCL + ecol] = ecol == one_col ? (erow < nrows ? 1.f : 0.f) : zv;
+                }
+                one_done = true;
+            }
+        }
         if (TS && tsp && oi == 2 && tid == 0) tsp[64 + 53] = wall_clock64();
         chain_barrier();
         if (TS && tsp && oi == 2 && tid == 0) tsp[64 + 54] = wall_clock64();

@@ -109,13 +109,15 @@ template <class F> void each_rank_x3v2(F&& f) {
 }
 
 // ---- chain.h (NM: the r6 activation classes, device_common.h act_fwd); chain4.h: the timeline in fp32 alone, the column
-// form (a program without k-slices) in bf16 alone; chain16x3.h: the timeline in fp32 alone
+// form (a program without k-slices) in bf16 alone, the VAE's reparametrisation op in plain fp32 alone; chain16x3.h: the
+// timeline in fp32 alone
 inline ChainKernel pick_chain(bool bf, bool nm) {
     return pick_flags<ChainKernel>([](auto BF, auto NM) -> ChainKernel { return chain_kernel<BF(), NM()>; }, bf, nm);
 }
-inline ChainKernel pick_chain4(bool bf, bool ts, bool cols) {
-    return pick_flags<ChainKernel>([](auto BF, auto TS, auto COLS) -> ChainKernel {
-        if constexpr ((TS() && (BF() || COLS())) || (COLS() && !BF())) return nullptr; else return chain4_kernel<BF(), TS(), COLS()>; }, bf, ts, cols);
+inline ChainKernel pick_chain4(bool bf, bool ts, bool cols, bool vae = false) {
+    return pick_flags<ChainKernel>([](auto BF, auto TS, auto COLS, auto VAE) -> ChainKernel {
+        if constexpr ((TS() && (BF() || COLS())) || (COLS() && !BF()) || (VAE() && (BF() || TS() || COLS()))) return nullptr;
+        else return chain4_kernel<BF(), TS(), COLS(), VAE()>; }, bf, ts, cols, vae);
 }
 inline ChainKernel pick_chain16x3(bool bf, bool ts) {
     return pick_flags<ChainKernel>([](auto BF, auto TS) -> ChainKernel {
@@ -123,6 +125,7 @@ inline ChainKernel pick_chain16x3(bool bf, bool ts) {
 }
 template <class F> void each_chain(bool nm, F&& f) { f(pick_chain(false, nm)); f(pick_chain(true, nm)); }
 template <class F> void each_chain4(F&& f) { for (int i = 0; i < 8; ++i) if (ChainKernel k = pick_chain4(i & 1, i & 2, i & 4)) f(k); }
+template <class F> void each_chain4_vae(F&& f) { f(pick_chain4(false, false, false, true)); }      // (a VAE handle's rank programs)
 template <class F> void each_chain16x3(F&& f) { for (int i = 0; i < 4; ++i) if (ChainKernel k = pick_chain16x3(i & 1, i & 2)) f(k); }
 
 #undef NB_

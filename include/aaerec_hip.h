@@ -435,6 +435,31 @@ int aae_decode_ranks(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae
 /* Rows ONE aae_predict_ranks / aae_decode_ranks call may take (>= max_batch; aae_rank_max_rows is about the list calls and
  * keeps its values): the fused form keeps [rows][8] targets and counters instead of candidate lists. */
 int aae_rank_full_max_rows(aae_handle h, int32_t* rows_out);
+/* The VAE's predict -> rank (reference vae.py:229-266 behind evaluation.py:183-199, 20-58): aae_predict_topk /
+ * aae_predict_ranks / aae_decode_topk / aae_decode_ranks / aae_rank_max_rows / aae_rank_full_max_rows for a handle created with
+ * cfg.model_kind = AAE_MODEL_VAE (any other handle: AAE_ESTATE; the AAE calls keep what they did on a VAE handle).  Arguments,
+ * ordering, tie rules, padding and the rank of a known held-out item are those of the AAE calls; the scores are those of
+ * aae_vae_predict for the same rows and the same eps.
+ *   eps_dev   [batch->n_rows][n_code] draws of reparametrize(), row i for row i of the batch however the call is carried out
+ *             (a k > 32 row that is ranked again through the score matrix reuses its row); NULL = the counter generator
+ *             (required when cfg.rng_mode == AAE_RNG_INJECT), whose draw depends on (seed, step, row of the call, column).
+ * The fused form (aae_vae_rank_max_rows / aae_vae_rank_full_max_rows rows per call, far more than max_batch) computes the
+ * hidden half - fc1, [fc21; fc22], the reparametrisation, the condition block, fc3 - in the call's workspace, 4 rows per
+ * workgroup, and ranks over fc4 as the AAE calls do; the [rows, n_items] score matrix never exists.  Its hidden layers are
+ * summed in another order than aae_vae_predict's (scores agree to rounding, ids may differ at such near-ties).  A call beyond
+ * those rows (<= max_batch then) or on a handle without the rank kernels takes the dense form: aae_vae_predict / aae_decode
+ * into the [max_batch][n_items] scratch, ranked there.  The decode calls take a decoder input the caller built
+ * (aae_vae_encode(train = 0) -> conditions of any plugin kind), zc_dev [batch->n_rows][zc_ld]. */
+int aae_vae_predict_topk(aae_handle h, const aae_batch* batch, const float* cond_dev, const float* eps_dev, int32_t k,
+                         int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_vae_predict_ranks(aae_handle h, const aae_batch* batch, const float* cond_dev, const float* eps_dev,
+                          const aae_batch* truth, int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
+int aae_vae_decode_topk(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k,
+                        int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_vae_decode_ranks(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
+                         int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
+int aae_vae_rank_max_rows(aae_handle h, int32_t k, int32_t* rows_out);
+int aae_vae_rank_full_max_rows(aae_handle h, int32_t* rows_out);
 /* split form for generic conditions */
 int aae_encode(aae_handle h, const aae_batch* batch, float* z_out_dev, void* stream);
 int aae_decode(aae_handle h, const float* zc_dev, int64_t zc_ld, int32_t n_rows,

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""The VAE's predict -> rank at the headline shape (C3: 100 000 items, hidden 200, VR_DOCS = 10 000 test rows).
+1. VAERecommender through Evaluation, topk=True (predict_topk on the device: aae_vae_predict_topk) against topk=False (the
+   reference's dense pipeline: the [n, items] matrix to the host, minmax_scale / argpartition there) - the same build, the
+   same trained model, bounded metrics; whole-call wall time, median of VR_REPEATS.
+2. The fused call alone (aae_vae_predict_topk, rows per call = what the handle takes, ids on the host) against aae_vae_predict
+   per max_batch rows + remove_non_missing + argtopk on the host, and against the AAE's aae_predict_topk at the same shape.
+3. The hidden half's chain program on the 4-row kernel (chain4.h, the rank calls) against the same layers on the 16-row kernel
+   (chain.h, aae_vae_predict's program, which also stores mu / logvar / eps / zc) at 128 / 1024 / 4096 rows: HIP-event time of
+   the chain launch (AAE_K_CHAIN), median of VR_REPEATS launches behind 3 warm-up launches.  The two launches do not do the
+   same work: chain.h's program has the four extra stores, and the rank call pays a memset and two interleave4 launches for
+   its weight copies OUTSIDE the timed launch - their cost is printed beside the pair (the same call's wall time with and
+   without them is not separable from the host; they are timed as the wall time of a decode-form call on ONE row, whose
+   chain program is a single 51 -> 200 layer, against the same call's chain launch).
+VR_PARTS=1,2,3 selects the parts."""
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aae-recommender_amd"))
+import numpy as np
+import scipy.sparse as sp
+import torch
+from aaerec._hip import DeviceCSR, HipAAE, K_CHAIN
+from aaerec.evaluation import Evaluation, argtopk, remove_non_missing
+from aaerec.vae import VAERecommender
+from tools.synth import throughput_corpus
+
+N, h, c, B = int(os.environ.get("VR_ITEMS", 100000)), int(os.environ.get("VR_HIDDEN", 200)), 50, 100
+DOCS, REPS = int(os.environ.get("VR_DOCS", 10000)), int(os.environ.get("VR_REPEATS", 3))
+PARTS = [int(x) for x in os.environ.get("VR_PARTS", "1,2,3").split(",")]
+med = lambda t: sorted(t)[len(t) // 2]                                                                  # noqa: E731
+
+
+def region(fn, n=1):
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e3
+
+
+class Set:
+    """What Evaluation and a recommender read of a Bags."""
+    def __init__(self, X):
+        self.X = X
+
+    def tocsr(self):
+        return self.X
+
+    def size(self, dim=0):
+        return self.X.shape[dim]
+
+    def clone(self):
+        return self
+
+    def get_attributes(self, keys):
+        return []
+
+
+class Trained(VAERecommender):
+    def train(self, training_set):          # (trained once: both Evaluation runs score the same model)
+        if self.model is None:
+            super().train(training_set)
+
+
+if 1 in PARTS or 2 in PARTS:
+    X = throughput_corpus(DOCS, N, seed=1234)
+    r = np.random.default_rng(0)
+    held = r.integers(0, N, DOCS)          # (one held-out item per row; one that the row names ranks behind the rankable ones)
+    Y = sp.csr_matrix((np.ones(DOCS, dtype=np.float32), (np.arange(DOCS), held)), shape=X.shape)
+    rec = Trained(n_hidden=h, n_code=c, n_epochs=1, batch_size=B, lr=0.001, verbose=False, seed=1)
+    rec.train(Set(X))
+    hip = rec.model.hip
+
+if 1 in PARTS:
+    metrics = ["mrr@10", "map@10", "p@5", "P@1"]
+    times = {}
+    for topk in (True, False):
+        ev = Evaluation(None, 0, metrics=metrics, logfile=os.devnull, topk=topk)
+        ev.train_set, ev.test_set, ev.x_test, ev.y_test = Set(X), Set(X), X, Y
+        if topk:
+            ev([rec], batch_size=1000)
+        times[topk] = [region(lambda: ev([rec], batch_size=1000)) for _ in range(REPS)]
+        print(f"Evaluation(topk={topk}) of VAERecommender, {DOCS} test rows x {N} items: median {med(times[topk]) / 1e3:.3f} s "
+              f"(repeats {[round(x / 1e3, 3) for x in sorted(times[topk])]})", flush=True)
+    print(f"  -> the dense pipeline takes {med(times[False]) / med(times[True]):.1f}x the device ranking", flush=True)
+
+if 2 in PARTS:
+    csr = DeviceCSR(X, hip.device)
+    rows = min(hip.vae_rank_max_rows(10), 2048, DOCS)
+    print(f"vae_rank_max_rows(10) = {hip.vae_rank_max_rows(10)}, vae_rank_full_max_rows = {hip.vae_rank_full_max_rows()}; {rows} rows per call", flush=True)
+
+    def host_route():
+        full = np.concatenate([hip.vae_predict(csr, s, min(B, rows - s)).cpu().numpy() for s in range(0, rows, B)])
+        return argtopk(remove_non_missing(full, X[:rows], copy=False), 10)
+    hip.vae_predict_topk(csr, 0, rows, 10)[0].cpu()
+    t_fused = [region(lambda: hip.vae_predict_topk(csr, 0, rows, 10)[0].cpu(), 5) for _ in range(REPS)]
+    host_route()
+    t_host = [region(host_route) for _ in range(REPS)]
+    print(f"aae_vae_predict_topk, {rows} rows, ids on the host: median {med(t_fused):.3f} ms (repeats {[round(x, 3) for x in sorted(t_fused)]}) | "
+          f"aae_vae_predict + host ranking: {med(t_host):.1f} ms ({[round(x, 1) for x in sorted(t_host)]}) -> {med(t_host) / med(t_fused):.1f}x", flush=True)
+    aae = HipAAE(N, h, c, max_batch=B, rng_mode="device", seed=1)
+    arows = min(rows, aae.rank_max_rows(10))
+    acsr = DeviceCSR(X, aae.device)
+    aae.predict_topk(acsr, 0, arows, 10)[0].cpu()
+    t_aae = [region(lambda: aae.predict_topk(acsr, 0, arows, 10)[0].cpu(), 5) for _ in range(REPS)]
+    print(f"aae_predict_topk (AAE handle, same shape), {arows} rows: median {med(t_aae):.3f} ms (repeats {[round(x, 3) for x in sorted(t_aae)]})"
+          f" -> the VAE call takes {med(t_fused) / rows / (med(t_aae) / arows):.3f}x per row", flush=True)
+
+if 3 in PARTS:
+    Ns, R = 4096, 4096
+    dev = HipAAE(Ns, h, c, max_batch=R, max_nnz=R * 64, rng_mode="device", seed=1, dropout=(0.0, 0.0), vae=True)
+    Xs = throughput_corpus(R, Ns, seed=5)
+    scsr = DeviceCSR(Xs, dev.device)
+    reps = max(REPS, 9)
+    print("part 3: the chain.h program also stores mu / logvar / eps / zc; the rank call derives its weight copies (a memset + two "
+          "interleave4 launches) outside the timed chain launch", flush=True)
+    zc1 = torch.zeros(1, c, device=dev.device)
+    dev.vae_decode_topk(zc1, scsr, 0, 10)
+    t_call = med([region(lambda: dev.vae_decode_topk(zc1, scsr, 0, 10), 20) for _ in range(reps)]) * 1e3
+    print(f"   a one-row decode-form call, launch to completion: {t_call:.1f} us wall (derive + chain + mask + rank + merge: the derive's three "
+          "launches are at most this)", flush=True)
+    for rows in (128, 1024, 4096):
+        if rows > dev.vae_rank_max_rows(10):
+            print(f"{rows} rows: beyond vae_rank_max_rows(10) = {dev.vae_rank_max_rows(10)} of this handle", flush=True)
+            continue
+        out = {}
+        for name, fn in (("chain4.h (4 rows per workgroup, rank call)", lambda: dev.vae_predict_topk(scsr, 0, rows, 10)),
+                         ("chain.h (16 rows per workgroup, aae_vae_predict)", lambda: dev.vae_predict(scsr, 0, rows))):
+            for _ in range(3):
+                fn()
+            t = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                dev.profile_enable(True, kernels=(K_CHAIN,))
+                fn()
+                torch.cuda.synchronize()
+                dev.profile_enable(False)
+                ms, n = dev.profile_read(K_CHAIN)
+                t.append(ms / max(n, 1) * 1e3)
+            out[name] = med(t)
+            print(f"{rows:5d} rows, hidden-half program on {name}: median {med(t):.1f} us (repeats {[round(x, 1) for x in sorted(t)]})", flush=True)
