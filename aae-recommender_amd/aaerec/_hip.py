@@ -30,6 +30,7 @@ OPTIMIZERS = {"adam": 0, "sgd": 1}
 PRIORS = {"gauss": 0, "categorical": 1, "bernoulli": 2}
 RNG_INJECT, RNG_DEVICE = 0, 1
 RANK_K_MAX = 1024         # longest list of predict_topk / decode_topk (aaerec_hip.h; beyond 32: csrc/rank_long.h)
+COOC_TILE = 16384         # items per LDS tile of the co-occurrence score kernel (AAE_COOC_TILE; csrc/cooc.h kCoocTile)
 GRAD_FUSED, GRAD_EXPORT = 0, 1
 
 
@@ -90,6 +91,10 @@ class AaeCollectives(C.Structure):
 
 class AaeTensor(C.Structure):
     _fields_ = [("byte_offset", C.c_size_t), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64)]
+
+
+class AaeCooc(C.Structure):
+    _fields_ = [("indptr_dev", C.c_void_p), ("indices_dev", C.c_void_p), ("values_dev", C.c_void_p), ("n_rows", C.c_int32)]
 
 
 _PROTOS = {
@@ -167,6 +172,11 @@ _PROTOS = {
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_void_p]),
     "aae_csr_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_cooc_scores": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_cooc_topk": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_cooc_ranks": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_void_p]),
     "aae_dense_to_csr": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.POINTER(C.c_int32 * 4), C.c_void_p]),
     "aae_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -427,6 +437,89 @@ class DeviceCSR:
         self.indices = upload(np.asarray(indices, dtype=np.int32) if len(indices) else np.zeros(1, dtype=np.int32), device)
         self.values = upload(np.asarray(values, dtype=np.float32) if len(values) else np.zeros(1, dtype=np.float32), device)
         return self
+
+
+# ---- the item co-occurrence baseline (aae_cooc_*; csrc/cooc.h) -----------------------------------------------------
+class DeviceCooc:
+    """A co-occurrence matrix resident in HBM as the kernels read it: int64 indptr, int32 indices (ascending within a
+    row), int32 values.  `C` is a scipy matrix [items, items] with whole-number values below 2^31 (aaerec.cooc checks)."""
+
+    def __init__(self, C, device):
+        C = C.tocsr()
+        C.sum_duplicates()
+        C.sort_indices()
+        self.shape = C.shape
+        self.device = torch.device(device)
+        self.indptr = upload(C.indptr.astype(np.int64), device)
+        self.indices = upload(C.indices.astype(np.int32) if C.nnz else np.zeros(1, dtype=np.int32), device)
+        self.values = upload(np.rint(C.data).astype(np.int32) if C.nnz else np.zeros(1, dtype=np.int32), device)
+
+    def struct(self):
+        c = AaeCooc()
+        c.indptr_dev, c.indices_dev, c.values_dev = self.indptr.data_ptr(), self.indices.data_ptr(), self.values.data_ptr()
+        c.n_rows = int(self.shape[0])
+        return c
+
+
+def _cooc_batch(csr, row_start, n_rows, rows=None):
+    b = AaeBatch()
+    b.indptr_dev, b.indices_dev, b.values_dev = csr.indptr.data_ptr(), csr.indices.data_ptr(), csr.values.data_ptr()
+    b.rows_dev = rows.data_ptr() if rows is not None else None
+    b.row_start, b.n_rows = int(row_start), int(n_rows)
+    b.max_row_nnz = int(csr.nnz_per_row_max)
+    b.nnz_bound = int(min(n_rows * max(1, csr.nnz_per_row_max), 2 ** 31 - 1))
+    return b
+
+
+def _cooc_scratch(cooc, n_rows, scratch):
+    """[n_rows, ld] float32 on cooc's device: the caller's (at least n_rows rows, unit column stride) or a new one."""
+    N = int(cooc.shape[1])
+    if scratch is None:
+        return torch.empty(n_rows, (N + 3) & ~3, dtype=torch.float32, device=cooc.device)
+    if not scratch.is_cuda or scratch.dtype != torch.float32 or scratch.dim() != 2 or scratch.stride(1) != 1 \
+            or scratch.shape[0] < n_rows or scratch.shape[1] < N:
+        raise TypeError("aaerec: scratch must be a float32 GPU matrix of at least [n_rows, n_items] with unit column stride")
+    return scratch
+
+
+def cooc_scores(cooc, csr, row_start, n_rows, rows=None, out=None):
+    """float32 device tensor [n_rows, items]: X[rows] @ C for rows [row_start, row_start + n_rows) of the DeviceCSR `csr`
+    (or the rows named by the int32 device tensor `rows`) - exact whole numbers while they stay below 2^24."""
+    out = _cooc_scratch(cooc, n_rows, out)
+    c, b = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows)
+    with torch.cuda.device(cooc.device):
+        _check(load_library().aae_cooc_scores(C.byref(c), int(cooc.shape[1]), C.byref(b), _ptr(out), out.stride(0),
+                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+    return out[:n_rows, :cooc.shape[1]]
+
+
+def cooc_topk(cooc, csr, row_start, n_rows, k, rows=None, exclude_known=True, scratch=None):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: predict -> remove_non_missing -> argtopk
+    of the co-occurrence scores, the better score first and the smaller id at equal scores (aae_cooc_topk)."""
+    scratch = _cooc_scratch(cooc, n_rows, scratch)
+    idx = torch.empty(n_rows, k, dtype=torch.int32, device=cooc.device)
+    val = torch.empty(n_rows, k, dtype=torch.float32, device=cooc.device)
+    c, b = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows)
+    with torch.cuda.device(cooc.device):
+        _check(load_library().aae_cooc_topk(C.byref(c), int(cooc.shape[1]), C.byref(b), int(k), int(bool(exclude_known)),
+                                            _ptr(scratch), scratch.stride(0), _ptr(idx), _ptr(val),
+                                            C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+    return idx, val
+
+
+def cooc_ranks(cooc, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, scratch=None):
+    """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with
+    the addressing of the input rows; n_truth = their stored entries), CSR order, in cooc_topk's ordering (aae_cooc_ranks)."""
+    scratch = _cooc_scratch(cooc, n_rows, scratch)
+    ranks = torch.empty(int(n_truth), dtype=torch.int32, device=cooc.device)
+    if not n_truth:
+        return ranks
+    c, b, t = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(truth_csr, row_start, n_rows, rows)
+    with torch.cuda.device(cooc.device):
+        _check(load_library().aae_cooc_ranks(C.byref(c), int(cooc.shape[1]), C.byref(b), C.byref(t), int(bool(exclude_known)),
+                                             _ptr(scratch), scratch.stride(0), _ptr(ranks),
+                                             C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+    return ranks
 
 
 # state_dict key <-> (net, layer)

@@ -34,6 +34,7 @@
 #include "rank_x3.h"
 #include "rank_long.h"
 #include "rank_full.h"
+#include "cooc.h"
 #include "chain.h"
 #include "chain4.h"
 #include "chain16x3.h"
@@ -465,6 +466,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_output_layer.h"
 #include "abi_step_phases.h"
 #include "abi_predict.h"
+#include "abi_cooc.h"
 #include "abi_data_parallel.h"
 
 #include "dp_step.h"

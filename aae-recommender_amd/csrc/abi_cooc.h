@@ -1,0 +1,75 @@
+// Entry points of the item co-occurrence baseline (cooc.h): scores alone, or scores into the caller's scratch followed by the
+// dense ranking kernels of rank_long.h / rank_full.h as they stand.  Handle-free: every buffer is the caller's, every launch
+// goes to the caller's stream, nothing synchronises.
+// (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
+#pragma once
+
+static_assert(kCoocTile == AAE_COOC_TILE, "include/aaerec_hip.h names the tile width of csrc/cooc.h");
+
+namespace {
+
+// everything a call can be refused for before anything touches the device
+int cooc_check(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const float* scores_dev, int64_t ld) {
+    const std::string w(who);
+    if (!cooc || !cooc->indptr_dev || !cooc->indices_dev || !cooc->values_dev) return fail(AAE_EINVAL, w + ": cooc or one of its pointers is NULL");
+    if (n_items <= 0) return fail(AAE_EINVAL, w + ": n_items must be positive");
+    if (cooc->n_rows < 0) return fail(AAE_EINVAL, w + ": cooc->n_rows is negative");
+    if (!batch || !batch->indptr_dev || !batch->indices_dev || !batch->values_dev) return fail(AAE_EINVAL, w + ": batch pointers are NULL");
+    if (batch->n_rows < 0) return fail(AAE_EINVAL, w + ": batch->n_rows is negative");
+    if (!scores_dev) return fail(AAE_EINVAL, w + ": the score matrix (scratch) is NULL");
+    if (ld < n_items) return fail(AAE_EINVAL, w + ": the score matrix's leading dimension (scratch_ld) is smaller than n_items");
+    if (ld > 0x7FFFFFFF) return fail(AAE_EINVAL, w + ": the score matrix's leading dimension does not fit 31 bits");
+    const int64_t ntiles = ((int64_t)n_items + kCoocTile - 1) / kCoocTile;
+    if (batch->n_rows * ntiles > 0x7FFFFFFF) return fail(AAE_EINVAL, w + ": rows x item tiles exceed one launch's grid");
+    return AAE_OK;
+}
+
+int cooc_launch(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, float* scores_dev, int64_t ld, hipStream_t s) {
+    const int ntiles = (n_items + kCoocTile - 1) / kCoocTile;
+    const CoocView C{cooc->indptr_dev, cooc->indices_dev, cooc->values_dev, cooc->n_rows};
+    hipLaunchKernelGGL(cooc_scores_kernel, dim3((unsigned)(batch->n_rows * ntiles)), dim3(kCoocNT), 0, s, C, (int)n_items, ntiles,
+                       rank_view(batch), scores_dev, (long long)ld);
+    LAUNCHCHK("cooc_scores");
+    return AAE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aae_cooc_scores(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, float* scores_dev, int64_t ld, void* stream) {
+    TRY(cooc_check("aae_cooc_scores", cooc, n_items, batch, scores_dev, ld));
+    if (batch->n_rows == 0) return AAE_OK;
+    return cooc_launch(cooc, n_items, batch, scores_dev, ld, S(stream));
+}
+
+int aae_cooc_topk(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
+                  float* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    TRY(cooc_check("aae_cooc_topk", cooc, n_items, batch, scratch_dev, scratch_ld));
+    if (k < 1 || k > kLongKMax || k > n_items) return fail(AAE_EINVAL, "aae_cooc_topk: k must be in [1, min(1024, n_items)]");
+    if (!idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "aae_cooc_topk: idx_out_dev / val_out_dev is NULL");
+    if (batch->n_rows == 0) return AAE_OK;
+    hipStream_t s = S(stream);
+    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
+    hipLaunchKernelGGL(rank_long_dense_kernel, dim3(batch->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
+                       rank_view(batch), (int)exclude_known, (int)k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
+    LAUNCHCHK("rank_long_dense (cooc)");
+    return AAE_OK;
+}
+
+int aae_cooc_ranks(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
+                   float* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream) {
+    TRY(cooc_check("aae_cooc_ranks", cooc, n_items, batch, scratch_dev, scratch_ld));
+    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, "aae_cooc_ranks: truth pointers are NULL");
+    if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, "aae_cooc_ranks: truth names another number of rows than batch");
+    if (!ranks_out_dev) return fail(AAE_EINVAL, "aae_cooc_ranks: ranks_out_dev is NULL");
+    if (batch->n_rows == 0) return AAE_OK;
+    hipStream_t s = S(stream);
+    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
+    hipLaunchKernelGGL(rank_full_dense_kernel, dim3(batch->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
+                       rank_view(batch), rank_view(truth), 0, (int)exclude_known, reinterpret_cast<int*>(ranks_out_dev));
+    LAUNCHCHK("rank_full_dense (cooc)");
+    return AAE_OK;
+}
+
+}  // extern "C"

@@ -460,6 +460,38 @@ int aae_vae_decode_ranks(aae_handle h, const float* zc_dev, int64_t zc_ld, const
                          int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
 int aae_vae_rank_max_rows(aae_handle h, int32_t k, int32_t* rows_out);
 int aae_vae_rank_full_max_rows(aae_handle h, int32_t* rows_out);
+/* The item co-occurrence baseline (reference baselines.py:22-43, Countbased: predict = X @ C, C = X^T X of the training set;
+ * csrc/cooc.h).  Handle-free like aae_cat_encode / aae_csr_embed: every buffer is the caller's, the launches go to `stream`,
+ * nothing synchronises.  `cooc` is C in CSR form with INTEGER values: indptr int64 [n_rows + 1], indices int32 with the columns
+ * ascending within a row, values int32.  `batch` names the input rows (values float32 holding whole numbers).
+ *   scores[r][j] = sum over the entries (i, x_i) of row r of x_i * C[i][j],   j < n_items
+ * summed in int32 and converted to fp32 once: exact (the caller keeps every sum below 2^24; beyond it the fp32 is the rounded
+ * integer, beyond 2^31 the sum wraps), identical from run to run and however the rows are chunked.  An input id outside
+ * [0, n_items) or >= cooc->n_rows is skipped; an empty input row is a row of zeros.  Columns [n_items, ld) are not written.
+ * aae_cooc_scores  the score matrix alone: scores_dev [batch->n_rows][ld], ld >= n_items.
+ * aae_cooc_topk    scores into scratch_dev [batch->n_rows][scratch_ld], then the dense form of aae_predict_topk over it
+ *                  (csrc/rank_long.h, every k in [1, min(1024, n_items)]): row-wise min-max scaling in which the known items
+ *                  still enter the minimum and maximum, known items masked (exclude_known; their ids must then lie in
+ *                  [0, n_items), as in every dense ranking call), the better score first and the smaller id at equal scores,
+ *                  id -1 / score 0 behind a row's last rankable item.  The scratch is left with the known items at -inf.
+ * aae_cooc_ranks   scores into the scratch, then the dense form of aae_predict_ranks (csrc/rank_full.h): one int32 per stored
+ *                  entry of the truth rows, CSR order; a truth entry that is a known item ranks behind every rankable item, an
+ *                  id outside [0, n_items) ranks 0.  truth->max_row_nnz is not read.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, n_items <= 0, k outside its range,
+ * scratch_ld < n_items (or beyond 2^31 - 1), negative row counts, truth->n_rows != batch->n_rows.  No rows: nothing is launched. */
+typedef struct aae_cooc {
+    const int64_t* indptr_dev;
+    const int32_t* indices_dev;
+    const int32_t* values_dev;
+    int32_t n_rows;           /* rows of C (= n_items for X^T X) */
+} aae_cooc;
+int aae_cooc_scores(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, float* scores_dev, int64_t ld, void* stream);
+int aae_cooc_topk(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
+                  float* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_cooc_ranks(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
+                   float* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
+/* items per LDS tile of the score kernel (csrc/cooc.h kCoocTile): tests place their shapes across its multiples */
+#define AAE_COOC_TILE 16384
 /* split form for generic conditions */
 int aae_encode(aae_handle h, const aae_batch* batch, float* z_out_dev, void* stream);
 int aae_decode(aae_handle h, const float* zc_dev, int64_t zc_ld, int32_t n_rows,
