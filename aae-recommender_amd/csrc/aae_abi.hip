@@ -439,7 +439,9 @@ int aae_tensor_info(aae_handle h, int id, aae_tensor* out) {
     else if (id == AAE_T_ACT_A1) t = &h->a1;
     else if (id == AAE_T_ACT_DH2) t = &h->dh2;
     else if (id == AAE_T_ACT_DA2) t = &h->da2;
-    else if (id == AAE_T_ACT_GA1) t = (h->ext_first && h->ga1x.p) ? &h->ga1x : &h->gb3;   // (ga1x: the LAST rows hold the batch)
+    // (ga1x: the LAST rows hold the batch; the per-layer path - NO_CHAIN, or a model too wide for the chain programs - leaves
+    //  dL/d(a1) in gb1: abi_layers.h encoder_backward)
+    else if (id == AAE_T_ACT_GA1) t = (h->ext_first && h->ga1x.p) ? &h->ga1x : h->use_chain ? &h->gb3 : &h->gb1;
     else if (id == AAE_T_ACT_DZC) { tmp = h->gzc; tmp.cols = h->cp; t = &tmp; }
     else if (id == AAE_T_ACT_LOSSES) {
         tmp.rows = 1; tmp.cols = 4; tmp.ld = 4; tmp.off = (size_t)((char*)h->losses - h->base); t = &tmp;

@@ -36,7 +36,18 @@ __device__ __forceinline__ float sigmoidf_(float x) {
 // The one missing bit - which side of x* the input was on - rides in the LEAST SIGNIFICANT BIT of the stored output (one unit
 // in the last place of y, 6e-8 relative: far inside the tolerances of this path), and the backward pass inverts f on that
 // branch (bracketed Newton steps; Hardswish in closed form) to evaluate f'(x).  Near x* the inverse is ill-conditioned but
-// f' is ~0 there: the error of f'(x) stays below 1e-4 absolute on the ~1e-3 wide neighbourhood of x*, 1e-6 elsewhere.
+// f' is ~0 there.  With eta the error of the stored output (its rounding, the stolen bit, the error of erff / tanhf / log1pf /
+// __expf) the inverse cannot tell x from x* within sqrt(2 eta / f''), and lands eta / (f'' |x - x*|) away beyond that: the
+// absolute error of f'(x) is bounded by  max(far, min(near, c / |x - x*|))  with
+//              near      c         far
+//   GELU       6.5e-4    5.5e-7    1.5e-4     (far: 1 + erf cancels on the left branch)
+//   SiLU       4e-4      3.5e-7    3e-5
+//   Mish       9.5e-4    1.8e-6    4.5e-5
+//   Hardswish  1.8e-4    1e-7      1.7e-6
+// These are 1.5 times the maxima of a float32 emulation of this code against float64 under the error bounds of those
+// functions (tests/act_sweep.py, held by tests/test_act_sweep_cpu.py); tests/test_act_sweep_gpu.py holds every kernel family
+// to them over the whole domain, and DESIGN.md 3.2 records what the device measured.
+// At Hardswish's kinks the flat pieces win, as in ATen: 0 at x = -3 (y = -0, left branch), 1 at x = 3.
 __device__ __forceinline__ float nm_xstar(int act) {        // argmin of f
     return act == ACT_GELU ? -0.75179160f : act == ACT_SILU ? -1.27846455f : act == ACT_MISH ? -1.19245934f : -1.5f;
 }
@@ -61,7 +72,7 @@ __device__ float nm_grad_from_y(int act, float ym) {
     const float y = __uint_as_float(__float_as_uint(ym) & ~1u);
     if (act == ACT_HARDSWISH) {             // x relu6(x + 3) / 6: 0 | x (x + 3) / 6 | x;  torch: 0 | x / 3 + 0.5 | 1
         if (y >= 3.f) return 1.f;
-        if (left && y == 0.f) return 0.f;   // x <= -3 (the one point x = -3 itself has measure zero)
+        if (left && y == 0.f) return 0.f;   // x <= -3 (torch's 0 holds at x = -3 itself too)
         const float r = sqrtf(fmaxf(9.f + 24.f * y, 0.f)) * (1.f / 6.f);
         return left ? -r : r;
     }

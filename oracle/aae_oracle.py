@@ -142,7 +142,8 @@ def act_bwd(name, x, y, g):
         t = np.tanh(act_fwd("Softplus", x))
         return (g * (t + x * sigmoid(x) * (f32(1) - t * t))).astype(f32)
     if name == "Hardswish":
-        return np.where(x < -3, f32(0), np.where(x <= 3, g * (x / f32(3) + f32(0.5)), g)).astype(f32)
+        # (ATen's hardswish_backward: the two kinks belong to the flat pieces - 0 at x = -3, 1 at x = 3)
+        return np.where(x <= -3, f32(0), np.where(x < 3, g * (x / f32(3) + f32(0.5)), g)).astype(f32)
     raise ValueError(name)
 
 
