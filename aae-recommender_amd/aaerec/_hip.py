@@ -31,6 +31,7 @@ PRIORS = {"gauss": 0, "categorical": 1, "bernoulli": 2}
 RNG_INJECT, RNG_DEVICE = 0, 1
 RANK_K_MAX = 1024         # longest list of predict_topk / decode_topk (aaerec_hip.h; beyond 32: csrc/rank_long.h)
 COOC_TILE = 16384         # items per LDS tile of the co-occurrence score kernel (AAE_COOC_TILE; csrc/cooc.h kCoocTile)
+LOWRANK_DIMS_MAX = 4096   # widest hidden vector of the truncated-SVD projection kernel (AAE_LOWRANK_DIMS_MAX; csrc/lowrank.h)
 GRAD_FUSED, GRAD_EXPORT = 0, 1
 
 
@@ -95,6 +96,10 @@ class AaeTensor(C.Structure):
 
 class AaeCooc(C.Structure):
     _fields_ = [("indptr_dev", C.c_void_p), ("indices_dev", C.c_void_p), ("values_dev", C.c_void_p), ("n_rows", C.c_int32)]
+
+
+class AaeLowRank(C.Structure):
+    _fields_ = [("vt_dev", C.c_void_p), ("ld", C.c_int64), ("n_features", C.c_int32), ("dims", C.c_int32)]
 
 
 _PROTOS = {
@@ -177,6 +182,12 @@ _PROTOS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_cooc_ranks": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p]),
+    "aae_lowrank_scores": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
+    "aae_lowrank_topk": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_lowrank_ranks": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.POINTER(AaeBatch),
+                                    C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "aae_dense_to_csr": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.POINTER(C.c_int32 * 4), C.c_void_p]),
     "aae_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -519,6 +530,87 @@ def cooc_ranks(cooc, csr, row_start, n_rows, truth_csr, n_truth, rows=None, excl
         _check(load_library().aae_cooc_ranks(C.byref(c), int(cooc.shape[1]), C.byref(b), C.byref(t), int(bool(exclude_known)),
                                              _ptr(scratch), scratch.stride(0), _ptr(ranks),
                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+    return ranks
+
+
+# ---- the truncated-SVD baseline (aae_lowrank_*; csrc/lowrank.h) -----------------------------------------------------
+class DeviceLowRank:
+    """TruncatedSVD.components_ [dims, features] resident in HBM as the kernels read it: ONE float32 table Vt
+    [features, ld], row f = column f of the components, ld = dims rounded up to 4 floats, the padding zero."""
+
+    def __init__(self, components, device):
+        V = np.asarray(components)
+        if V.ndim != 2 or not 1 <= V.shape[0] <= LOWRANK_DIMS_MAX or V.shape[1] < 1:
+            raise ValueError("aaerec: components must be [dims, features] with dims in [1, %d]" % LOWRANK_DIMS_MAX)
+        dims, features = V.shape
+        vt = np.zeros((features, (dims + 3) & ~3), dtype=np.float32)
+        vt[:, :dims] = V.T
+        self.shape = (features, dims)
+        self.device = torch.device(device)
+        self.table = upload(vt, device)
+
+    def struct(self):
+        s = AaeLowRank()
+        s.vt_dev, s.ld = self.table.data_ptr(), self.table.stride(0)
+        s.n_features, s.dims = int(self.shape[0]), int(self.shape[1])
+        return s
+
+
+def _lowrank_scratch(lr, n_rows, width, scratch, what):
+    """[n_rows, ld] float32 on lr's device, ld a multiple of 4 floats: the caller's (at least n_rows x width) or a new one."""
+    if scratch is None:
+        return torch.empty(n_rows, (width + 3) & ~3, dtype=torch.float32, device=lr.device)
+    if not scratch.is_cuda or scratch.dtype != torch.float32 or scratch.dim() != 2 or scratch.stride(1) != 1 \
+            or scratch.shape[0] < n_rows or scratch.shape[1] < width or scratch.stride(0) % 4 or scratch.data_ptr() % 16:
+        raise TypeError("aaerec: %s must be a 16-byte aligned float32 GPU matrix of at least [n_rows, %d] with unit column stride "
+                        "and a row stride that is a multiple of 4" % (what, width))
+    return scratch
+
+
+def lowrank_scores(lr, n_items, csr, row_start, n_rows, rows=None, out=None, hidden=None):
+    """float32 device tensor [n_rows, n_items]: (X[rows] Vt) Vt[:n_items]^T for rows [row_start, row_start + n_rows) of the
+    DeviceCSR `csr` of feature rows (or the rows named by the int32 device tensor `rows`) (aae_lowrank_scores)."""
+    out = _lowrank_scratch(lr, n_rows, int(n_items), out, "out")
+    hidden = _lowrank_scratch(lr, n_rows, lr.shape[1], hidden, "hidden")
+    v, b = lr.struct(), _cooc_batch(csr, row_start, n_rows, rows)
+    with torch.cuda.device(lr.device):
+        _check(load_library().aae_lowrank_scores(C.byref(v), int(n_items), C.byref(b), _ptr(hidden), hidden.stride(0), _ptr(out),
+                                                 out.stride(0), C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream)))
+    return out[:n_rows, :n_items]
+
+
+def lowrank_topk(lr, n_items, csr, items_csr, row_start, n_rows, k, rows=None, exclude_known=True, scratch=None, hidden=None):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: predict -> remove_non_missing -> argtopk of
+    the truncated-SVD scores of the feature rows `csr`; `items_csr` names the known items of the same rows (ids below
+    n_items).  The better score first, the smaller id at equal scores (aae_lowrank_topk)."""
+    scratch = _lowrank_scratch(lr, n_rows, int(n_items), scratch, "scratch")
+    hidden = _lowrank_scratch(lr, n_rows, lr.shape[1], hidden, "hidden")
+    idx = torch.empty(n_rows, k, dtype=torch.int32, device=lr.device)
+    val = torch.empty(n_rows, k, dtype=torch.float32, device=lr.device)
+    v, b, i = lr.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(items_csr, row_start, n_rows, rows)
+    with torch.cuda.device(lr.device):
+        _check(load_library().aae_lowrank_topk(C.byref(v), int(n_items), C.byref(b), C.byref(i), int(k), int(bool(exclude_known)),
+                                               _ptr(hidden), hidden.stride(0), _ptr(scratch), scratch.stride(0), _ptr(idx), _ptr(val),
+                                               C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream)))
+    return idx, val
+
+
+def lowrank_ranks(lr, n_items, csr, items_csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, scratch=None,
+                  hidden=None):
+    """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with
+    the addressing of the input rows; n_truth = their stored entries), CSR order, in lowrank_topk's ordering
+    (aae_lowrank_ranks)."""
+    scratch = _lowrank_scratch(lr, n_rows, int(n_items), scratch, "scratch")
+    hidden = _lowrank_scratch(lr, n_rows, lr.shape[1], hidden, "hidden")
+    ranks = torch.empty(int(n_truth), dtype=torch.int32, device=lr.device)
+    if not n_truth:
+        return ranks
+    v, b, i = lr.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(items_csr, row_start, n_rows, rows)
+    t = _cooc_batch(truth_csr, row_start, n_rows, rows)
+    with torch.cuda.device(lr.device):
+        _check(load_library().aae_lowrank_ranks(C.byref(v), int(n_items), C.byref(b), C.byref(i), C.byref(t), int(bool(exclude_known)),
+                                                _ptr(hidden), hidden.stride(0), _ptr(scratch), scratch.stride(0), _ptr(ranks),
+                                                C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream)))
     return ranks
 
 

@@ -1,0 +1,190 @@
+"""Truncated-SVD baseline with its ranking on the device (the reference's SVDRecommender, svd.py:15-57).
+
+    scores = (X_test V^T) V[:, :n_classes],   V = TruncatedSVD.components_  [dims, features]
+    features = items (+ the tf-idf vocabulary of the titles when use_title)
+
+`train` fits scikit-learn's TruncatedSVD on the host, as the reference does, and `predict` is the reference's host route
+(float64, transform then inverse_transform, sliced to the items).  `predict_topk` / `predict_ranks` are what `Evaluation` asks
+for where a recommender offers them: V is uploaded once as one fp32 table Vt [features, dims] (_hip.DeviceLowRank), csrc/lowrank.h
+projects the sparse feature rows onto it, the tiled fp32 GEMM of csrc/gemm_f32.h reconstructs the item scores into a
+[rows, items] scratch, and the dense kernels of csrc/rank_long.h / rank_full.h rank them there - row-wise min-max scaling with the
+known items still in the minimum and maximum, known ITEMS masked (the title columns are features, never candidates), the better
+score first, the smaller id at equal scores.  Only [n, k] ids or nnz(truth) ranks cross PCIe.
+
+The device computes in fp32 where the host route computes in float64: scores agree within the bound csrc/lowrank.h states,
+and two items closer than that may swap places.  The host answers, from predict() and with the same ordering rule, when
+device is None, for a list longer than min(1024, items), for more than 4096 dimensions and for a table that is not finite.
+
+This module is not `aaerec.svd`: that name keeps resolving to the user's checkout of the reference through the package path
+(aaerec/__init__.py), as `aaerec.baselines` does beside `aaerec.cooc`.
+"""
+import numpy as np
+import scipy.sparse as sp
+import torch
+from sklearn.decomposition import TruncatedSVD
+from sklearn.feature_extraction.text import TfidfVectorizer
+
+from . import _hip
+from .base import Recommender
+from .cooc import _order_row
+from .ub import AutoEncoderMixin
+
+
+def _canonical(M):
+    M = sp.csr_matrix(M, dtype=np.float64, copy=True)
+    M.sum_duplicates()
+    M.sort_indices()
+    return M
+
+
+class SVDRecommender(Recommender, AutoEncoderMixin):
+    """SVD baseline, capable of dealing with text.  dims, use_title, tfidf_params and the further keyword arguments
+    (TruncatedSVD's) are the reference's.  scratch_bytes: the [rows, items] fp32 scratch of one device call - the rows of a
+    predict_topk / predict_ranks call are chunked to it.  device: where Vt lives and the ranking runs; None keeps everything
+    on the host."""
+
+    def __init__(self, dims=1000, use_title=False, tfidf_params={}, scratch_bytes=256 << 20, device="cuda:0", **kwargs):
+        super().__init__()
+        if use_title:
+            self.tfidf = TfidfVectorizer(input="content", **tfidf_params)
+        self.svd = TruncatedSVD(dims, **kwargs)
+        self.use_title = use_title
+        self.scratch_bytes = int(scratch_bytes)
+        self.device = device
+        self._dev = self._dev_of = None
+
+    def __str__(self):
+        return str(self.svd)
+
+    def fit(self, X, y=None):
+        self._dev = self._dev_of = None
+        self.svd.fit(X)
+        return self
+
+    def transform(self, X, y=None):
+        return self.svd.transform(X)
+
+    def inverse_transform(self, X, y=None):
+        return self.svd.inverse_transform(X)
+
+    def train(self, training_set):
+        x_train = training_set.tocsr()
+        self.n_classes = x_train.shape[1]
+        if self.use_title:
+            titles = self.tfidf.fit_transform(training_set.get_single_attribute("title"))
+            x_train = sp.hstack([x_train, titles])
+        self.fit(x_train)
+        self._table()                     # one upload (a table the device route can take, and a device to take it)
+
+    def _features(self, test_set):
+        """The rows the model reads: the item columns, then the tf-idf block of the titles."""
+        x_test = test_set.tocsr()
+        if self.use_title:
+            titles = self.tfidf.transform(test_set.get_single_attribute("title"))
+            x_test = sp.hstack([x_test, titles]).tocsr()
+        return x_test
+
+    def predict(self, test_set):
+        return self.reconstruct(self._features(test_set))[:, :self.n_classes]
+
+    # ---- ranking ---------------------------------------------------------------------------------------------------
+    def _table(self):
+        """The device table of self.svd.components_ as they stand (built when first needed, again when the array is another
+        one), or None: no device, more dimensions than the projection kernel takes, values that are not finite."""
+        V = getattr(self.svd, "components_", None)
+        if self.device is None or V is None:
+            return None
+        if self._dev_of is not V:
+            self._dev_of = V
+            ok = V.shape[0] <= _hip.LOWRANK_DIMS_MAX and bool(np.isfinite(V).all()) and \
+                bool(np.isfinite(np.asarray(V, dtype=np.float32)).all())
+            self._dev = _hip.DeviceLowRank(V, self.device) if ok else None
+        return self._dev
+
+    def on_device(self, k=None):
+        """Whether a call (k: its list length) takes the device route."""
+        if k is not None and not 1 <= k <= min(_hip.RANK_K_MAX, self.n_classes):
+            return False
+        return self._table() is not None
+
+    def _inputs(self, test_set):
+        """(feature rows, their item columns) in canonical CSR form, float64."""
+        F = _canonical(self._features(test_set))
+        if F.shape[1] != self.svd.components_.shape[1]:
+            raise ValueError("the test set has {} feature columns, the model {}".format(F.shape[1], self.svd.components_.shape[1]))
+        return F, _canonical(F[:, :self.n_classes])
+
+    def _chunk_rows(self, n_items):
+        return max(1, self.scratch_bytes // (4 * ((n_items + 3) & ~3)))
+
+    def _host_rows(self, F, X):
+        """(row number, its scores float64 [items], its known item ids) over the rows, a bounded block at a time."""
+        step = max(1, (64 << 20) // (8 * max(1, F.shape[1])))
+        for r0 in range(0, F.shape[0], step):
+            S = np.asarray(self.reconstruct(F[r0:r0 + step]), dtype=np.float64)[:, :self.n_classes]
+            for j in range(S.shape[0]):
+                yield r0 + j, S[j], X.indices[X.indptr[r0 + j]:X.indptr[r0 + j + 1]]
+
+    def _scratch(self, n, n_items):
+        chunk = self._chunk_rows(n_items)
+        dev, dims = self._dev.device, self._dev.shape[1]
+        return chunk, torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=torch.float32, device=dev), \
+            torch.empty(min(chunk, n), (dims + 3) & ~3, dtype=torch.float32, device=dev)
+
+    def predict_topk(self, test_set, k=10):
+        """(item ids int32 [n, k], scaled scores float32 [n, k]) of the k best new items per test bag: predict ->
+        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item."""
+        F, X = self._inputs(test_set)
+        n, n_items = X.shape
+        if k < 1:
+            raise ValueError("k must be positive")
+        if self.on_device(k) and n:
+            lr = self._dev
+            feat, items = _hip.DeviceCSR(F, lr.device), _hip.DeviceCSR(X, lr.device)
+            chunk, scratch, hidden = self._scratch(n, n_items)
+            parts = [_hip.lowrank_topk(lr, n_items, feat, items, s0, min(chunk, n - s0), k, scratch=scratch, hidden=hidden)
+                     for s0 in range(0, n, chunk)]
+            return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
+        ids = np.full((n, k), -1, dtype=np.int32)
+        val = np.zeros((n, k), dtype=np.float32)
+        for r, s, known in self._host_rows(F, X):
+            best = _order_row(s, known)[:k]
+            span = s.max() - s.min()
+            ids[r, :best.size] = best
+            val[r, :best.size] = (s[best] - s.min()) / (span if span > 0 else 1.0)        # (float64, rounded to fp32 once)
+        return ids, val
+
+    def predict_ranks(self, test_set, y_true):
+        """CSR of int32 with y_true's (canonical) pattern: the 1-based rank of every held-out item in the full ranking of its
+        test bag, in predict_topk's ordering.  A held-out item that is a known item ranks behind every rankable one, among
+        the known items by id."""
+        F, X = self._inputs(test_set)
+        n, n_items = X.shape
+        Ys = sp.csr_matrix(y_true, copy=True) if not sp.issparse(y_true) else y_true.tocsr(copy=True)
+        if Ys.shape != X.shape:
+            raise ValueError("the ground truth has shape {}, the test set {}".format(Ys.shape, X.shape))
+        Ys.sum_duplicates()
+        Ys.sort_indices()
+        if self.on_device() and n:
+            lr = self._dev
+            feat, items, truth = (_hip.DeviceCSR(M, lr.device) for M in (F, X, Ys))
+            chunk, scratch, hidden = self._scratch(n, n_items)
+            parts = []
+            for s0 in range(0, n, chunk):
+                rows = min(chunk, n - s0)
+                nnz = int(Ys.indptr[s0 + rows] - Ys.indptr[s0])
+                parts.append(_hip.lowrank_ranks(lr, n_items, feat, items, s0, rows, truth, nnz, scratch=scratch, hidden=hidden))
+            data = torch.cat(parts).cpu().numpy().astype(np.int32, copy=False)
+        else:
+            data = np.zeros(Ys.nnz, dtype=np.int32)
+            ids = np.arange(n_items)
+            for r, s, known in self._host_rows(F, X):
+                lo, hi = Ys.indptr[r], Ys.indptr[r + 1]
+                if lo == hi:
+                    continue
+                s = s.copy()
+                s[known] = -np.inf
+                for e in range(lo, hi):
+                    t = Ys.indices[e]
+                    data[e] = 1 + np.count_nonzero((s > s[t]) | ((s == s[t]) & (ids < t)))
+        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)

@@ -492,6 +492,45 @@ int aae_cooc_ranks(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch
                    float* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
 /* items per LDS tile of the score kernel (csrc/cooc.h kCoocTile): tests place their shapes across its multiples */
 #define AAE_COOC_TILE 16384
+/* The truncated-SVD baseline (reference svd.py:15-57, SVDRecommender: predict = (X V^T) V[:, :n_items], V = TruncatedSVD's
+ * components_ [dims][n_features], n_features = items (+ the tf-idf vocabulary of the titles); csrc/lowrank.h).  Handle-free like
+ * the cooc calls.  `lowrank` is ONE fp32 table for both products: vt_dev [n_features][ld], row f = column f of V, ld a multiple
+ * of 4 floats >= dims rounded up to 4 (the padding zero), 16-byte aligned, dims in [1, AAE_LOWRANK_DIMS_MAX].
+ *   hidden[r][d] = sum over the entries (f, x_f) of row r of `features` of x_f * vt[f][d]     (CSR order, one fmaf per term)
+ *   scores[r][j] = sum over d of hidden[r][d] * vt[j][d],   j < n_items <= n_features           (fp32 matrix pipe, d ascending)
+ * Both are k-ordered fp32 fmaf chains that depend on the row alone: the same bits from run to run and however the rows are
+ * chunked.  |scores - exact| <= 2^-24 (dims + nnz_r + 4) sum_d (sum_f |x_f| |V_df|) |V_dj| to first order (csrc/lowrank.h).
+ * A feature id outside [0, n_features) is skipped; an empty row is a row of zeros.  hidden_dev [features->n_rows][hidden_ld]
+ * is the caller's scratch for the hidden vectors (hidden_ld >= dims, a multiple of 4 floats, 16-byte aligned; columns
+ * [dims, hidden_ld) are not written and not used).  Columns [n_items, ld) of the score matrix are not written.
+ * aae_lowrank_scores  the score matrix alone: scores_dev [features->n_rows][ld], ld >= n_items, a multiple of 4 floats, 16-byte
+ *                     aligned.
+ * aae_lowrank_topk    scores into scratch_dev [rows][scratch_ld] (as ld above), then the dense form of aae_predict_topk over it
+ *                     exactly as aae_cooc_topk: `items` names the known items of the same rows (ids in [0, n_items) when
+ *                     exclude_known, as in every dense ranking call; its values are not read), row-wise min-max scaling with
+ *                     the known items still in the extrema, the better score first and the smaller id at equal scores, id -1 /
+ *                     score 0 behind a row's last rankable item, k in [1, min(1024, n_items)].
+ * aae_lowrank_ranks   scores into the scratch, then the dense form of aae_predict_ranks as aae_cooc_ranks: one int32 per stored
+ *                     entry of the truth rows, CSR order.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, dims / n_features / n_items out of range,
+ * k outside its range, a leading dimension that is too small or not a multiple of 4 floats, a misaligned base, negative row
+ * counts, items->n_rows or truth->n_rows != features->n_rows.  No rows: nothing is launched. */
+typedef struct aae_lowrank {
+    const float* vt_dev;      /* [n_features][ld] */
+    int64_t ld;
+    int32_t n_features;
+    int32_t dims;
+} aae_lowrank;
+int aae_lowrank_scores(const aae_lowrank* lowrank, int32_t n_items, const aae_batch* features, float* hidden_dev, int64_t hidden_ld,
+                       float* scores_dev, int64_t ld, void* stream);
+int aae_lowrank_topk(const aae_lowrank* lowrank, int32_t n_items, const aae_batch* features, const aae_batch* items, int32_t k,
+                     int32_t exclude_known, float* hidden_dev, int64_t hidden_ld, float* scratch_dev, int64_t scratch_ld,
+                     int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_lowrank_ranks(const aae_lowrank* lowrank, int32_t n_items, const aae_batch* features, const aae_batch* items,
+                      const aae_batch* truth, int32_t exclude_known, float* hidden_dev, int64_t hidden_ld, float* scratch_dev,
+                      int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
+/* widest hidden vector of the projection kernel (csrc/lowrank.h kProjDimsMax) */
+#define AAE_LOWRANK_DIMS_MAX 4096
 /* split form for generic conditions */
 int aae_encode(aae_handle h, const aae_batch* batch, float* z_out_dev, void* stream);
 int aae_decode(aae_handle h, const float* zc_dev, int64_t zc_ld, int32_t n_rows,

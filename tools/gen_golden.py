@@ -1142,6 +1142,75 @@ def gen_saturated(ref_aae, ref_cond, scale=SAT_SCALE, seed=16, name="step_satura
                     state_keys=SAT_STATE_KEYS, predict_B=32, finish=finish)
 
 
+def svd_corpus(seed, n_docs=700, n_items=330, n_proto=30):
+    """A small citation-like corpus with titles: documents draw most of their items from one of n_proto item pools and
+    most of their title words from that pool's word list, over the years 2000-2009.  (tokens as int ids, titles as text)"""
+    rng = np.random.RandomState(seed)
+    pools = [rng.choice(n_items, size=14, replace=False) for _ in range(n_proto)]
+    words = [["w%dx%d" % (p, j) for j in range(6)] for p in range(n_proto)]
+    common = ["study", "analysis", "model", "data", "effect", "system", "method", "review"]
+    docs, titles, years = [], [], []
+    for i in range(n_docs):
+        p = rng.randint(n_proto)
+        own = rng.choice(pools[p], size=rng.randint(4, 9), replace=False).tolist()
+        stray = rng.choice(n_items, size=rng.randint(0, 3), replace=False).tolist()
+        docs.append(sorted(set(int(t) for t in own + stray)))
+        title = rng.choice(words[p], size=rng.randint(2, 5), replace=False).tolist() + \
+            rng.choice(common, size=rng.randint(1, 4), replace=False).tolist()
+        if rng.rand() < 0.15:
+            title += rng.choice(words[rng.randint(n_proto)], size=1).tolist()
+        titles.append(" ".join(title))
+        years.append(2000 + (i * 10) // n_docs)
+    return docs, titles, years
+
+
+def gen_svd():
+    """The reference's SVDRecommender (svd.py:15-57) on the CPU behind the reference's own Bags / Evaluation.setup split
+    (year 2009, min_elements 2, drop 1): svd_plain.npz (dims 12, items only) and svd_titles.npz (dims 20, use_title).
+    Data only: the corpus (token ids, title strings, years), the split as the reference made it (train / test / held-out CSR,
+    the titles of both sides, the item vocabulary), components_ (float64), the tf-idf vocabulary with its idf, str(model)
+    and the reference's predict() output."""
+    import_reference()
+    import aaerec.datasets as ref_ds
+    import aaerec.evaluation as ref_ev
+    import aaerec.svd as ref_svd
+    for name, seed, dims, use_title, random_state in (("svd_plain", 5, 12, False, 11), ("svd_titles", 6, 20, True, 12)):
+        docs, titles, years = svd_corpus(seed)
+        owners = ["d%d" % i for i in range(len(docs))]
+        bags = ref_ds.Bags([["i%d" % t for t in d] for d in docs], owners,
+                           {"year": dict(zip(owners, years)), "title": dict(zip(owners, titles))})
+        ev = ref_ev.Evaluation(bags, 2009, metrics=["mrr@10"], logfile=os.devnull)
+        ev.setup(seed=42, min_elements=2, drop=1)
+        train_set, test_set = ev.train_set.clone(), ev.test_set.clone()
+        rec = ref_svd.SVDRecommender(dims, use_title=use_title, random_state=random_state)
+        rec.train(train_set)
+        pred = np.asarray(rec.predict(test_set), dtype=np.float64)
+        Xtr, Xte, Yte = train_set.tocsr(), sp.csr_matrix(ev.x_test), sp.csr_matrix(ev.y_test)
+        for M in (Xtr, Xte, Yte):
+            M.sum_duplicates()
+            M.sort_indices()
+        out = dict(dims=np.asarray(dims), use_title=np.asarray(int(use_title)), random_state=np.asarray(random_state),
+                   split_year=np.asarray(2009), setup_seed=np.asarray(42), min_elements=np.asarray(2), drop=np.asarray(1),
+                   doc_indptr=np.concatenate([[0], np.cumsum([len(d) for d in docs])]).astype(np.int64),
+                   doc_tokens=np.asarray([t for d in docs for t in d], dtype=np.int32),
+                   doc_years=np.asarray(years, dtype=np.int32), doc_titles=np.asarray(titles),
+                   item_vocab=np.asarray([train_set.index2token[i] for i in range(len(train_set.index2token))]),
+                   train_indptr=Xtr.indptr.astype(np.int64), train_indices=Xtr.indices.astype(np.int32), train_data=Xtr.data.astype(np.float64),
+                   test_indptr=Xte.indptr.astype(np.int64), test_indices=Xte.indices.astype(np.int32), test_data=Xte.data.astype(np.float64),
+                   truth_indptr=Yte.indptr.astype(np.int64), truth_indices=Yte.indices.astype(np.int32),
+                   n_items=np.asarray(Xtr.shape[1]),
+                   train_titles=np.asarray(train_set.get_single_attribute("title")),
+                   test_titles=np.asarray(test_set.get_single_attribute("title")),
+                   components=np.asarray(rec.svd.components_, dtype=np.float64), model_str=np.asarray(str(rec)),
+                   pred=pred)
+        if use_title:
+            terms = sorted(rec.tfidf.vocabulary_, key=rec.tfidf.vocabulary_.get)
+            out.update(tfidf_terms=np.asarray(terms), tfidf_idf=np.asarray(rec.tfidf.idf_, dtype=np.float64))
+        path = os.path.join(OUT, name + ".npz")
+        np.savez_compressed(path, **out)
+        print(name, "train", Xtr.shape, "test", Xte.shape, "features", rec.svd.components_.shape[1], "bytes", os.path.getsize(path))
+
+
 ACT_NAMES = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink",
              "Identity", "GELU", "SiLU", "Mish", "Hardswish", "ELU", "LeakyReLU", "Sigmoid"]
 
@@ -1221,6 +1290,8 @@ def main():
         gen_vae(only="step_vae_cat")
     if want("vectorizer"):
         gen_embedded_vectorizer()
+    if want("svd"):
+        gen_svd()
     if want("metrics"):
         gen_metric_known_answers()
     if want("e2e"):
