@@ -31,6 +31,8 @@ PRIORS = {"gauss": 0, "categorical": 1, "bernoulli": 2}
 RNG_INJECT, RNG_DEVICE = 0, 1
 RANK_K_MAX = 1024         # longest list of predict_topk / decode_topk (aaerec_hip.h; beyond 32: csrc/rank_long.h)
 COOC_TILE = 16384         # items per LDS tile of the co-occurrence score kernel (AAE_COOC_TILE; csrc/cooc.h kCoocTile)
+SPGEMM_HASH_PRODUCTS = 4096   # most products of a row the sparse product keeps in an LDS hash table (AAE_SPGEMM_HASH_PRODUCTS; csrc/spgemm.h)
+SPGEMM_STAGE = 512        # entries of a row of A its tile kernel stages in LDS at a time (AAE_SPGEMM_STAGE)
 LOWRANK_DIMS_MAX = 4096   # widest hidden vector of the truncated-SVD projection kernel (AAE_LOWRANK_DIMS_MAX; csrc/lowrank.h)
 GRAD_FUSED, GRAD_EXPORT = 0, 1
 
@@ -182,6 +184,10 @@ _PROTOS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_cooc_ranks": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p]),
+    "aae_spgemm_i32_bound": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_spgemm_i32_count": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_spgemm_i32_fill": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     "aae_lowrank_scores": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
     "aae_lowrank_topk": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_int32,
@@ -460,10 +466,39 @@ class DeviceCooc:
         C.sum_duplicates()
         C.sort_indices()
         self.shape = C.shape
+        self.nnz = int(C.nnz)
         self.device = torch.device(device)
         self.indptr = upload(C.indptr.astype(np.int64), device)
         self.indices = upload(C.indices.astype(np.int32) if C.nnz else np.zeros(1, dtype=np.int32), device)
         self.values = upload(np.rint(C.data).astype(np.int32) if C.nnz else np.zeros(1, dtype=np.int32), device)
+
+    @classmethod
+    def from_device(cls, indptr, indices, values, shape, device):
+        """The matrix from device tensors as they stand - int64 indptr [rows + 1], int32 indices / values [>= max(1, nnz)], the
+        columns ascending within a row: no host round trip beyond the one number nnz = indptr[-1]."""
+        self = cls.__new__(cls)
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.device = torch.device(device)
+        for t, dt in ((indptr, torch.int64), (indices, torch.int32), (values, torch.int32)):
+            if not t.is_cuda or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() < 1:
+                raise TypeError("aaerec: from_device takes contiguous GPU vectors: int64 indptr, int32 indices, int32 values")
+        if indptr.numel() != self.shape[0] + 1:
+            raise ValueError("aaerec: indptr must hold rows + 1 offsets")
+        self.nnz = int(indptr[-1])
+        if indices.numel() < self.nnz or values.numel() < self.nnz:
+            raise ValueError("aaerec: indices / values are shorter than indptr[-1]")
+        self.indptr, self.indices, self.values = indptr, indices, values
+        return self
+
+    def to_scipy(self):
+        """The matrix on the host: a canonical scipy CSR with int64 values."""
+        import scipy.sparse as sp
+        return sp.csr_matrix((self.values[:self.nnz].cpu().numpy().astype(np.int64), self.indices[:self.nnz].cpu().numpy(),
+                              self.indptr.cpu().numpy()), shape=self.shape)
+
+    def abs_max(self):
+        """max |value| over the stored entries (0 without any): a device reduction, one number to the host."""
+        return int(self.values[:self.nnz].abs().max()) if self.nnz else 0
 
     def struct(self):
         c = AaeCooc()
@@ -531,6 +566,47 @@ def cooc_ranks(cooc, csr, row_start, n_rows, truth_csr, n_truth, rows=None, excl
                                              _ptr(scratch), scratch.stride(0), _ptr(ranks),
                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
     return ranks
+
+
+# ---- the exact int32 sparse product (aae_spgemm_i32_*; csrc/spgemm.h) -----------------------------------------------
+def _spgemm_operands(A, B):
+    if A.shape[1] != B.shape[0]:
+        raise ValueError("aaerec: spgemm_i32 of [{} x {}] and [{} x {}]".format(*A.shape, *B.shape))
+    if A.device != B.device:
+        raise ValueError("aaerec: the operands of spgemm_i32 live on different devices")
+    return A.struct(), B.struct(), C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+
+
+def spgemm_bound(A, B):
+    """int64 device tensor [rows of A]: u_i = the products of row i of A . B (aae_spgemm_i32_bound) - rows with
+    u_i <= SPGEMM_HASH_PRODUCTS take the hash kernel, longer ones the tile kernel."""
+    a, b, stream = _spgemm_operands(A, B)
+    u = torch.empty(max(1, A.shape[0]), dtype=torch.int64, device=A.device)
+    with torch.cuda.device(A.device):
+        _check(load_library().aae_spgemm_i32_bound(C.byref(a), C.byref(b), int(B.shape[0]), _ptr(u), stream))
+    return u[:A.shape[0]]
+
+
+def spgemm_i32(A, B):
+    """A . B as a DeviceCooc, exact in int32, the columns ascending in every row.  A, B: DeviceCooc-like (int32 CSR in HBM,
+    canonical, strictly positive values whose products' sums stay below 2^31 - the caller's guarantee, not checked).  Two
+    passes: Count, a cumsum, Fill; the one host read is nnz of the result, unknown until Count has run."""
+    a, b, stream = _spgemm_operands(A, B)
+    m, n, dev = int(A.shape[0]), int(B.shape[1]), A.device
+    lib = load_library()
+    u = torch.empty(max(1, m), dtype=torch.int64, device=dev)
+    row_nnz = torch.zeros(max(1, m), dtype=torch.int64, device=dev)
+    indptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.aae_spgemm_i32_bound(C.byref(a), C.byref(b), int(B.shape[0]), _ptr(u), stream))
+        _check(lib.aae_spgemm_i32_count(C.byref(a), C.byref(b), n, _ptr(u), _ptr(row_nnz), stream))
+        if m:
+            torch.cumsum(row_nnz[:m], 0, out=indptr[1:])
+        nnz = int(indptr[-1])
+        indices = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)
+        values = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)
+        _check(lib.aae_spgemm_i32_fill(C.byref(a), C.byref(b), n, _ptr(u), _ptr(indptr), _ptr(indices), _ptr(values), stream))
+    return DeviceCooc.from_device(indptr, indices, values, (m, n), dev)
 
 
 # ---- the truncated-SVD baseline (aae_lowrank_*; csrc/lowrank.h) -----------------------------------------------------

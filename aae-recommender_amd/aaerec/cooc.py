@@ -12,7 +12,15 @@ cross PCIe.
 The device is used only where it is exact (`device_route_ok`): whole-number values in X and C, max |C| < 2^31, and
 max_r (sum_i |x_ri|) * max |C| < 2^24, so that every score is a whole number fp32 represents.  Anything else - and a list
 longer than min(1024, items) - is answered on the host from predict() with the same ordering rule: callers see no difference
-beyond speed.  C itself is built on the host with scipy, as the reference builds it, and uploaded once by train().
+beyond speed.
+
+C is built where `build` says.  "host": scipy's product, as the reference builds it, uploaded once by train().  "device": X and
+X^T (transposed on the host) go up as int32 CSR and C = X^T . X is formed there by the exact int32 sparse product of
+csrc/spgemm.h (`_hip.spgemm_i32`), as is C . C for every further order; nothing is uploaded a second time, and `cooccurences`
+is downloaded only when somebody reads it.  The device builds only what it builds exactly (`device_build_ok`: a canonical X of
+strictly positive whole numbers with max_i sum_d x_di^2 < 2^31; before each further order max_i sum_j C_ij^2 < 2^31): the
+result has scipy's indptr, indices and values.  "auto" takes the device route when AUTO_BUILDS_ON_DEVICE says the measurement
+favoured it, a device is named and the guard passes, and continues on the host from the order at which a guard fails.
 
 This module is not `aaerec.baselines`: that name (MostPopular, RandomBaseline, the reference's own Countbased) keeps resolving
 to the user's checkout of the reference through the package path (aaerec/__init__.py).
@@ -26,6 +34,8 @@ from .base import Recommender
 
 EXACT_FP32 = 1 << 24          # every whole number up to here is an fp32
 INT32_LIMIT = 1 << 31
+# value types in which scipy's product of whole numbers below 2^31 is exact, so that both builds give the same matrix
+_EXACT_DTYPES = tuple(np.dtype(t) for t in (np.float64, np.int32, np.int64, np.uint32, np.uint64))
 
 
 def _abs_max(M):
@@ -36,18 +46,69 @@ def _whole(M):
     return bool(np.all(M.data == np.rint(M.data))) if M.nnz else True
 
 
+def _route_ok(X, c_whole, c_abs_max):
+    """The one rule of device_route_ok, from what is known of C: whether its values are whole, and max |C|."""
+    X = sp.csr_matrix(X)
+    if not (_whole(X) and c_whole):
+        return False
+    if c_abs_max >= INT32_LIMIT:
+        return False
+    row_sum = float(abs(X).sum(axis=1).max()) if X.nnz else 0.0
+    return row_sum * c_abs_max < EXACT_FP32
+
+
 def device_route_ok(X, C):
     """True when X @ C on the device is exact: X and C hold whole numbers, max |C| < 2^31 (its int32 upload), and the largest
     score any row can reach, max_r (sum_i |x_ri|) * max |C|, stays below 2^24 (the int32 sum is then a whole number that fp32
     represents).  X, C: scipy sparse matrices."""
-    X, C = sp.csr_matrix(X), sp.csr_matrix(C)
-    if not (_whole(X) and _whole(C)):
+    C = sp.csr_matrix(C)
+    return _route_ok(X, _whole(C), _abs_max(C))
+
+
+def _canonical(X):
+    """Columns strictly ascending within every row of the CSR matrix X (sorted, no duplicates) - looked at, not enforced."""
+    nnz = int(X.indptr[-1])
+    if nnz < 2:
+        return True
+    rising = np.diff(X.indices[:nnz]) > 0
+    starts = np.asarray(X.indptr[1:-1])
+    starts = starts[(starts > 0) & (starts < nnz)]
+    rising[starts - 1] = True                     # (the step from a row's last entry to the next row's first is free)
+    return bool(rising.all())
+
+
+def device_build_ok(X):
+    """True when the device builds C = X^T X exactly as scipy does (csrc/spgemm.h): X is a canonical CSR matrix of float64 or
+    of 32- / 64-bit integers (what scipy itself multiplies exactly below 2^31), every stored value a strictly positive whole number - scipy keeps a structural entry for an explicit zero and for a sum that cancels;
+    positive values rule both out, so the pattern is scipy's - and max_i sum_d x_di^2 < 2^31: for a Gram matrix
+    C_ij <= sqrt(C_ii C_jj) <= max_i C_ii, so every entry and, the terms being positive, every partial sum fits int32."""
+    if not sp.issparse(X) or X.format != "csr":
         return False
-    cmax = _abs_max(C)
-    if cmax >= INT32_LIMIT:
+    if X.shape[0] >= INT32_LIMIT or X.shape[1] >= INT32_LIMIT or not _canonical(X):
         return False
-    row_sum = float(abs(X).sum(axis=1).max()) if X.nnz else 0.0
-    return row_sum * cmax < EXACT_FP32
+    if not X.nnz:
+        return True
+    data = np.asarray(X.data)
+    if data.dtype not in _EXACT_DTYPES:           # (scipy's own product would round or wrap: the two builds would differ)
+        return False
+    if not (np.all(data > 0) and np.all(data == np.rint(data))):
+        return False
+    if float(data.max()) ** 2 >= INT32_LIMIT:     # (every square below is then an integer float64 holds)
+        return False
+    diag = np.bincount(X.indices, weights=data.astype(np.float64) ** 2, minlength=X.shape[1])
+    return bool(diag.max() < INT32_LIMIT)
+
+
+def _power_ok(C):
+    """Whether the device may form C . C for the symmetric DeviceCooc C: max_i sum_j C_ij^2 < 2^31 - the largest diagonal
+    entry of the Gram matrix C^T C, which bounds all of it.  An int64 reduction over the CSR values on the device."""
+    if not C.nnz:
+        return True
+    if C.abs_max() ** 2 >= INT32_LIMIT:           # (each square below is then < 2^31: no row sum can leave int64)
+        return False
+    sq = C.values[:C.nnz].to(torch.int64) ** 2
+    rows = torch.repeat_interleave(torch.arange(C.shape[0], device=C.device), C.indptr.diff())
+    return int(torch.zeros(C.shape[0], dtype=torch.int64, device=C.device).index_add_(0, rows, sq).max()) < INT32_LIMIT
 
 
 def _order_row(s, known):
@@ -56,34 +117,87 @@ def _order_row(s, known):
     return ids[~np.isin(ids, known)] if len(known) else ids
 
 
+BUILDS = ("auto", "host", "device")
+# What build="auto" does where the device route is open: decided by the one measurement of tools/cooc_build_rate.py in DESIGN 3.4d
+AUTO_BUILDS_ON_DEVICE = True
+
+
 class Countbased(Recommender):
     """Item Co-Occurrence.  order: 1 = C = X^T X; n = C <- C^T C repeated n - 1 times.  scratch_bytes: the [rows, items]
     fp32 scratch of one device call - the rows of a predict_topk / predict_ranks call are chunked to it.  device: where C
-    lives and the ranking runs; None keeps everything on the host."""
+    lives and the ranking runs; None keeps everything on the host.  build: where train() forms C - "host" (scipy), "device"
+    (csrc/spgemm.h; ValueError where there is no device or device_build_ok refuses) or "auto" (the module docstring)."""
 
-    def __init__(self, order=1, scratch_bytes=256 << 20, device="cuda:0"):
+    def __init__(self, order=1, scratch_bytes=256 << 20, device="cuda:0", build="auto"):
         super().__init__()
+        if build not in BUILDS:
+            raise ValueError("build must be one of {}, not {!r}".format(BUILDS, build))
+        if build == "device" and device is None:
+            raise ValueError('build="device" needs a device')
         self.order = order
         self.scratch_bytes = int(scratch_bytes)
         self.device = device
-        self.cooccurences = None        # (the reference's spelling: drivers and notebooks read this attribute)
+        self.build = build
+        self.built_on = None            # "host" / "device": where the last train() formed C (its last product)
+        self._cooc = None
+        self._shape = None
+        self._dtype = None
+        self._cmax = 0.0                # max |C| of the uploaded matrix: on_device() reads this, not the matrix
         self._dev = None
 
     def __str__(self):
         return "Count-based Predictor (order {})".format(self.order)
 
+    @property
+    def cooccurences(self):
+        """C as a scipy CSR (the reference's spelling: drivers and notebooks read this attribute).  After a device build it is
+        downloaded on first access and kept."""
+        if self._cooc is None and self._dev is not None and self.built_on == "device":
+            self._cooc = self._dev.to_scipy().astype(self._dtype)
+        return self._cooc
+
+    @cooccurences.setter
+    def cooccurences(self, C):
+        self._cooc = C
+
     def train(self, X):
         X = X.tocsr()
-        C = (X.T @ X).tocsr()
-        for _ in range(self.order - 1):
+        self._cooc, self._dev, self._cmax, self._shape, self._dtype = None, None, 0.0, (X.shape[1], X.shape[1]), X.dtype
+        self.built_on = None
+        if self.build == "device" and not device_build_ok(X):
+            raise ValueError('build="device": X is not a canonical CSR matrix of strictly positive whole numbers with '
+                             "max_i sum_d x_di^2 < 2^31 (device_build_ok)")
+        if self.build == "device" or (self.build == "auto" and AUTO_BUILDS_ON_DEVICE and self.device is not None and device_build_ok(X)):
+            C, done = self._train_device(X)
+            if C is None:
+                return
+        else:
+            C, done = (X.T @ X).tocsr(), 1
+        for _ in range(self.order - done):
             C = (C.T @ C).tocsr()
         C.sum_duplicates()
         C.sort_indices()
         self.cooccurences = C
-        self._dev = None
+        self.built_on = "host"
         # one upload, and only of a matrix the device route can ever take: whole numbers that fit int32
         if self.device is not None and _whole(C) and _abs_max(C) < INT32_LIMIT:
             self._dev = _hip.DeviceCooc(C, self.device)
+            self._cmax = _abs_max(C)
+
+    def _train_device(self, X):
+        """C on the device: (None, order) when every product was formed there - self._dev is the result - or (the scipy matrix
+        of the last order the device formed, that order) for train() to continue from on the host."""
+        Xt = _hip.DeviceCooc(X.T.tocsr(), self.device)      # (transposing on the device is out of scope)
+        C = _hip.spgemm_i32(Xt, _hip.DeviceCooc(X, self.device))
+        for done in range(1, self.order):
+            if not _power_ok(C):
+                if self.build == "device":
+                    raise ValueError('build="device": max_i sum_j C_ij^2 >= 2^31 at order {}: the next product leaves int32'.format(done))
+                return C.to_scipy().astype(X.dtype), done
+            # X^T X is symmetric and so is every power of it, so C^T C = C . C and no transpose is needed on the device
+            C = _hip.spgemm_i32(C, C)
+        self._dev, self._cmax, self.built_on = C, float(C.abs_max()), "device"
+        return None, self.order
 
     def predict(self, X):
         return X.tocsr() @ self.cooccurences
@@ -93,16 +207,16 @@ class Countbased(Recommender):
         X = test_set.tocsr().astype(np.float64)
         X.sum_duplicates()
         X.sort_indices()
-        if X.shape[1] != self.cooccurences.shape[0]:
-            raise ValueError("the test set has {} columns, the model {} items".format(X.shape[1], self.cooccurences.shape[0]))
+        if X.shape[1] != self._shape[0]:
+            raise ValueError("the test set has {} columns, the model {} items".format(X.shape[1], self._shape[0]))
         return X
 
     def on_device(self, X, k=None):
         """Whether a call over the rows X (k: its list length) takes the device route."""
-        n_items = self.cooccurences.shape[1]
+        n_items = self._shape[1]
         if self._dev is None or (k is not None and not 1 <= k <= min(_hip.RANK_K_MAX, n_items)):
             return False
-        return device_route_ok(X, self.cooccurences)
+        return _route_ok(X, True, self._cmax)      # (device_route_ok's rule: an uploaded C is whole, max |C| kept by train())
 
     def _chunk_rows(self, n_items):
         return max(1, self.scratch_bytes // (4 * ((n_items + 3) & ~3)))

@@ -35,6 +35,7 @@
 #include "rank_long.h"
 #include "rank_full.h"
 #include "cooc.h"
+#include "spgemm.h"
 #include "lowrank.h"
 #include "chain.h"
 #include "chain4.h"
@@ -470,6 +471,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_step_phases.h"
 #include "abi_predict.h"
 #include "abi_cooc.h"
+#include "abi_spgemm.h"
 #include "abi_lowrank.h"
 #include "abi_data_parallel.h"
 

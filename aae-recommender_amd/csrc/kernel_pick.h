@@ -133,5 +133,14 @@ template <class F> void each_chain16x3(F&& f) { for (int i = 0; i < 4; ++i) if (
 using LowRankGemmKernel = void (*)(GemmShape, EpiStore);
 inline LowRankGemmKernel pick_lowrank_gemm() { return gemm_f32_kernel<0, 1, 16, 64, EpiStore, false>; }
 
+// ---- spgemm.h: the Count / Fill pair of each path.  Static LDS: no limit to raise
+using SpgemmKernel = void (*)(SpgemmArgs);
+inline SpgemmKernel pick_spgemm_hash(bool fill) {
+    return pick_flags<SpgemmKernel>([](auto FILL) -> SpgemmKernel { return spgemm_hash_kernel<FILL()>; }, fill);
+}
+inline SpgemmKernel pick_spgemm_tile(bool fill) {
+    return pick_flags<SpgemmKernel>([](auto FILL) -> SpgemmKernel { return spgemm_tile_kernel<FILL()>; }, fill);
+}
+
 #undef NB_
 }  // namespace

@@ -492,6 +492,28 @@ int aae_cooc_ranks(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch
                    float* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
 /* items per LDS tile of the score kernel (csrc/cooc.h kCoocTile): tests place their shapes across its multiples */
 #define AAE_COOC_TILE 16384
+/* The exact sparse product behind the co-occurrence matrix (csrc/spgemm.h): C = A . B, A [A->n_rows x p], B [p x n] with
+ * p = B->n_rows, every matrix an `aae_cooc` (int64 indptr, int32 indices ascending within a row and without duplicates, int32
+ * values); C in the same layout, columns ascending in every row.  Handle-free like the cooc calls; the caller runs the three in
+ * this order on one stream and does the scan and the allocation between the last two:
+ * aae_spgemm_i32_bound  u_dev [A->n_rows] int64: u_i = sum over the entries (d, .) of A's row i of the stored entries of B's row
+ *                       d - the products of row i, an upper bound of its result entries that deals the rows to the two kernels
+ *                       (u_i <= AAE_SPGEMM_HASH_PRODUCTS: an LDS hash table; beyond: LDS tiles of AAE_COOC_TILE columns).
+ * aae_spgemm_i32_count  row_nnz_dev [A->n_rows] int64: the stored entries of every result row.
+ * aae_spgemm_i32_fill   indices_dev / values_dev [indptr[A->n_rows]] from indptr_dev [A->n_rows + 1], the exclusive scan of
+ *                       row_nnz_dev; u_dev as Count read it.  Nothing is stored outside a row's own range.
+ * Every sum is formed in int32 with integer adds: the same bits every run.  The calls do NOT check for int32 overflow, and the
+ * tile kernel takes a cell whose sum is 0 for untouched: the caller guarantees strictly positive values whose sums stay below
+ * 2^31 (aaerec/cooc.py device_build_ok).  A column id of A outside [0, p) or of B outside [0, n) is skipped; an empty row of A
+ * gives an empty row; A->n_rows = 0 launches nothing.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, a negative size, p > B->n_rows. */
+#define AAE_SPGEMM_HASH_PRODUCTS 4096
+/* entries of a row of A the tile kernel stages in LDS at a time (csrc/spgemm.h kSpgemmStage): tests give it a longer row */
+#define AAE_SPGEMM_STAGE 512
+int aae_spgemm_i32_bound(const aae_cooc* A, const aae_cooc* B, int32_t p, int64_t* u_dev, void* stream);
+int aae_spgemm_i32_count(const aae_cooc* A, const aae_cooc* B, int32_t n, const int64_t* u_dev, int64_t* row_nnz_dev, void* stream);
+int aae_spgemm_i32_fill(const aae_cooc* A, const aae_cooc* B, int32_t n, const int64_t* u_dev, const int64_t* indptr_dev,
+                        int32_t* indices_dev, int32_t* values_dev, void* stream);
 /* The truncated-SVD baseline (reference svd.py:15-57, SVDRecommender: predict = (X V^T) V[:, :n_items], V = TruncatedSVD's
  * components_ [dims][n_features], n_features = items (+ the tf-idf vocabulary of the titles); csrc/lowrank.h).  Handle-free like
  * the cooc calls.  `lowrank` is ONE fp32 table for both products: vt_dev [n_features][ld], row f = column f of V, ld a multiple
