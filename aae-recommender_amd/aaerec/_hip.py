@@ -33,6 +33,7 @@ RANK_K_MAX = 1024         # longest list of predict_topk / decode_topk (aaerec_h
 COOC_TILE = 16384         # items per LDS tile of the co-occurrence score kernel (AAE_COOC_TILE; csrc/cooc.h kCoocTile)
 SPGEMM_HASH_PRODUCTS = 4096   # most products of a row the sparse product keeps in an LDS hash table (AAE_SPGEMM_HASH_PRODUCTS; csrc/spgemm.h)
 SPGEMM_STAGE = 512        # entries of a row of A its tile kernel stages in LDS at a time (AAE_SPGEMM_STAGE)
+SPTRANS_LDS = 4096        # longest row of a transpose sorted in LDS in one go (AAE_SPTRANS_LDS; csrc/sptrans.h): longer ones merge through a scratch
 LOWRANK_DIMS_MAX = 4096   # widest hidden vector of the truncated-SVD projection kernel (AAE_LOWRANK_DIMS_MAX; csrc/lowrank.h)
 GRAD_FUSED, GRAD_EXPORT = 0, 1
 
@@ -188,6 +189,10 @@ _PROTOS = {
     "aae_spgemm_i32_count": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_spgemm_i32_fill": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "aae_csr_transpose_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_csr_transpose_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "aae_spmm_f32": (C.c_int, [C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_lowrank_scores": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
     "aae_lowrank_topk": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_int32,
@@ -607,6 +612,72 @@ def spgemm_i32(A, B):
         values = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)
         _check(lib.aae_spgemm_i32_fill(C.byref(a), C.byref(b), n, _ptr(u), _ptr(indptr), _ptr(indices), _ptr(values), stream))
     return DeviceCooc.from_device(indptr, indices, values, (m, n), dev)
+
+
+# ---- the device CSR transpose (aae_csr_transpose_*; csrc/sptrans.h) -------------------------------------------------
+def _transpose_arrays(indptr, indices, values, shape, device):
+    """(indptr int64 [cols + 1], indices int32, values of values.dtype) of the transpose of the canonical CSR arrays on
+    `device`: Count, a cumsum, Fill.  The values are moved as bits.  One host read: nnz of the result."""
+    m, n, dev = int(shape[0]), int(shape[1]), torch.device(device)
+    lib = load_library()
+    col_nnz = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+    t_indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib.aae_csr_transpose_count(_ptr(indptr), _ptr(indices), m, n, _ptr(col_nnz), stream))
+        if n:
+            torch.cumsum(col_nnz[:n], 0, out=t_indptr[1:])
+        nnz = int(t_indptr[-1])
+        t_indices = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)
+        t_values = torch.zeros(max(1, nnz), dtype=values.dtype, device=dev)
+        scratch = torch.empty(nnz, dtype=torch.int64, device=dev) if nnz > SPTRANS_LDS else None
+        _check(lib.aae_csr_transpose_fill(_ptr(indptr), _ptr(indices), _ptr(values), m, n, _ptr(t_indptr), _ptr(t_indices),
+                                          _ptr(t_values), _ptr(col_nnz), _ptr(scratch), nnz if scratch is not None else 0, nnz, stream))
+    return t_indptr, t_indices, t_values, nnz
+
+
+def csr_transpose(csr):
+    """The transpose of a canonical DeviceCSR (columns ascending and duplicate-free within a row) as a DeviceCSR: bit for bit
+    scipy's A.T.tocsr() after sort_indices() (aae_csr_transpose_count / _fill).  A column id outside [0, cols) is skipped."""
+    if csr.values.dtype != torch.float32 or csr.indices.dtype != torch.int32 or csr.indptr.dtype != torch.int64:
+        raise TypeError("aaerec: csr_transpose takes a DeviceCSR (int64 indptr, int32 indices, float32 values)")
+    dev = csr.indptr.device
+    indptr, indices, values, nnz = _transpose_arrays(csr.indptr, csr.indices, csr.values, csr.shape, dev)
+    out = DeviceCSR.__new__(DeviceCSR)
+    out.generation = next(_GENERATION)
+    out.shape = (int(csr.shape[1]), int(csr.shape[0]))
+    out.nnz = nnz
+    out.nnz_per_row_max = int(indptr.diff().max()) if out.shape[0] else 0
+    out.indptr, out.indices, out.values = indptr, indices, values
+    return out
+
+
+def cooc_transpose(cooc):
+    """The transpose of a DeviceCooc as a DeviceCooc: csr_transpose for the int32 operands of spgemm_i32."""
+    indptr, indices, values, _ = _transpose_arrays(cooc.indptr, cooc.indices, cooc.values, cooc.shape, cooc.device)
+    return DeviceCooc.from_device(indptr, indices, values, (cooc.shape[1], cooc.shape[0]), cooc.device)
+
+
+def spmm_f32(csr, dense, width=None, out=None):
+    """float32 device tensor [rows, width]: csr @ dense[:, :width] for the DeviceCSR `csr` [rows, cols] and the float32 GPU
+    matrix `dense` [cols, >= width] (unit column stride, a 16-byte aligned base, a row stride that is a multiple of 4 floats and
+    at least width rounded up to 4 - the padding is read) (aae_spmm_f32: the projection kernel of csrc/lowrank.h, one k-ordered
+    fmaf chain per element in CSR order).  out: a matrix of the same kind of at least [rows, width], or a new one."""
+    width = int(dense.shape[1] if width is None else width)
+    n_rows, n_cols = int(csr.shape[0]), int(csr.shape[1])
+    if not dense.is_cuda or dense.dtype != torch.float32 or dense.dim() != 2 or dense.stride(1) != 1 or dense.shape[0] < n_cols \
+            or dense.shape[1] < width:
+        raise TypeError("aaerec: dense must be a float32 GPU matrix of [cols of csr, >= width] with unit column stride")
+    dev = dense.device
+    if out is None:
+        out = torch.empty(n_rows, (max(width, 1) + 3) & ~3, dtype=torch.float32, device=dev)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_rows:
+        raise TypeError("aaerec: out must be a float32 GPU matrix of at least [rows of csr, width] with unit column stride")
+    b = _cooc_batch(csr, 0, n_rows)
+    with torch.cuda.device(dev):
+        _check(load_library().aae_spmm_f32(C.byref(b), _ptr(dense), dense.stride(0), n_cols, width, _ptr(out), out.stride(0),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out[:n_rows, :width]
 
 
 # ---- the truncated-SVD baseline (aae_lowrank_*; csrc/lowrank.h) -----------------------------------------------------

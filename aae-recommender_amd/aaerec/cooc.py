@@ -14,8 +14,8 @@ max_r (sum_i |x_ri|) * max |C| < 2^24, so that every score is a whole number fp3
 longer than min(1024, items) - is answered on the host from predict() with the same ordering rule: callers see no difference
 beyond speed.
 
-C is built where `build` says.  "host": scipy's product, as the reference builds it, uploaded once by train().  "device": X and
-X^T (transposed on the host) go up as int32 CSR and C = X^T . X is formed there by the exact int32 sparse product of
+C is built where `build` says.  "host": scipy's product, as the reference builds it, uploaded once by train().  "device": X goes
+up as int32 CSR, X^T is formed there by csrc/sptrans.h (`_hip.cooc_transpose`) and C = X^T . X by the exact int32 sparse product of
 csrc/spgemm.h (`_hip.spgemm_i32`), as is C . C for every further order; nothing is uploaded a second time, and `cooccurences`
 is downloaded only when somebody reads it.  The device builds only what it builds exactly (`device_build_ok`: a canonical X of
 strictly positive whole numbers with max_i sum_d x_di^2 < 2^31; before each further order max_i sum_j C_ij^2 < 2^31): the
@@ -187,8 +187,8 @@ class Countbased(Recommender):
     def _train_device(self, X):
         """C on the device: (None, order) when every product was formed there - self._dev is the result - or (the scipy matrix
         of the last order the device formed, that order) for train() to continue from on the host."""
-        Xt = _hip.DeviceCooc(X.T.tocsr(), self.device)      # (transposing on the device is out of scope)
-        C = _hip.spgemm_i32(Xt, _hip.DeviceCooc(X, self.device))
+        Xd = _hip.DeviceCooc(X, self.device)
+        C = _hip.spgemm_i32(_hip.cooc_transpose(Xd), Xd)
         for done in range(1, self.order):
             if not _power_ok(C):
                 if self.build == "device":

@@ -36,6 +36,7 @@
 #include "rank_full.h"
 #include "cooc.h"
 #include "spgemm.h"
+#include "sptrans.h"
 #include "lowrank.h"
 #include "chain.h"
 #include "chain4.h"
@@ -472,6 +473,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_predict.h"
 #include "abi_cooc.h"
 #include "abi_spgemm.h"
+#include "abi_sptrans.h"
 #include "abi_lowrank.h"
 #include "abi_data_parallel.h"
 

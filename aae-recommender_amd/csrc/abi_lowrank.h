@@ -44,7 +44,7 @@ int lowrank_launch(const aae_lowrank* lr, int32_t n_items, const aae_batch* feat
                    float* scores_dev, int64_t ld, hipStream_t s) {
     const int rows = features->n_rows;
     const LowRankView V{lr->vt_dev, (long long)lr->ld, lr->n_features, lr->dims};
-    hipLaunchKernelGGL(lowrank_project_kernel, dim3((unsigned)rows), dim3(lowrank_project_threads(lr->dims)), 0, s, V, rank_view(features),
+    hipLaunchKernelGGL(pick_lowrank_project(), dim3((unsigned)rows), dim3(lowrank_project_threads(lr->dims)), 0, s, V, rank_view(features),
                        hidden_dev, (long long)hidden_ld);
     LAUNCHCHK("lowrank_project");
     GemmShape g;
@@ -68,6 +68,27 @@ int aae_lowrank_scores(const aae_lowrank* lowrank, int32_t n_items, const aae_ba
     TRY(lowrank_check("aae_lowrank_scores", lowrank, n_items, features, hidden_dev, hidden_ld, scores_dev, ld));
     if (features->n_rows == 0) return AAE_OK;
     return lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scores_dev, ld, S(stream));
+}
+
+int aae_spmm_f32(const aae_batch* rows, const float* dense_dev, int64_t ld, int32_t n_cols, int32_t width, float* out_dev,
+                 int64_t ld_out, void* stream) {
+    const std::string w("aae_spmm_f32");
+    if (!rows || !rows->indptr_dev || !rows->indices_dev || !rows->values_dev) return fail(AAE_EINVAL, w + ": row batch pointers are NULL");
+    if (rows->n_rows < 0) return fail(AAE_EINVAL, w + ": rows->n_rows is negative");
+    if (width < 1 || width > kProjDimsMax) return fail(AAE_EINVAL, w + ": width must be in [1, 4096]");
+    if (n_cols < 1) return fail(AAE_EINVAL, w + ": n_cols must be positive");
+    if (!dense_dev || !out_dev) return fail(AAE_EINVAL, w + ": dense_dev / out_dev is NULL");
+    if (ld < (((int64_t)width + 3) & ~(int64_t)3) || (ld & 3) || ld > 0x7FFFFFFF || !aligned16(dense_dev))
+        return fail(AAE_EINVAL, w + ": the dense operand's leading dimension (ld) must be a multiple of 4 floats, at least width rounded up to 4, "
+                                    "and the operand 16-byte aligned");
+    if (ld_out < width || (ld_out & 3) || ld_out > 0x7FFFFFFF || !aligned16(out_dev))
+        return fail(AAE_EINVAL, w + ": the result's leading dimension (ld_out) is smaller than width, or not a multiple of 4 floats on a 16-byte aligned base");
+    if (rows->n_rows == 0) return AAE_OK;
+    const LowRankView V{dense_dev, (long long)ld, n_cols, width};
+    hipLaunchKernelGGL(pick_lowrank_project(), dim3((unsigned)rows->n_rows), dim3(lowrank_project_threads(width)), 0, S(stream), V,
+                       rank_view(rows), out_dev, (long long)ld_out);
+    LAUNCHCHK("spmm_f32 (lowrank_project)");
+    return AAE_OK;
 }
 
 int aae_lowrank_topk(const aae_lowrank* lowrank, int32_t n_items, const aae_batch* features, const aae_batch* items, int32_t k,

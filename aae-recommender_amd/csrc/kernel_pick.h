@@ -142,5 +142,15 @@ inline SpgemmKernel pick_spgemm_tile(bool fill) {
     return pick_flags<SpgemmKernel>([](auto FILL) -> SpgemmKernel { return spgemm_tile_kernel<FILL()>; }, fill);
 }
 
+// ---- sptrans.h: the Count pass, and the two launches of Fill (scatter, then the per-segment sort).  Static LDS: no limit to raise
+using SptransKernel = void (*)(SptransArgs);
+inline SptransKernel pick_sptrans_count() { return sptrans_count_kernel; }
+inline SptransKernel pick_sptrans_scatter() { return sptrans_scatter_kernel; }
+inline SptransKernel pick_sptrans_sort() { return sptrans_sort_kernel; }
+
+// ---- lowrank.h: the CSR x row-major-dense product - the projection of the ranking calls and aae_spmm_f32 alike
+using SpmmKernel = void (*)(LowRankView, BatchView, float*, long long);
+inline SpmmKernel pick_lowrank_project() { return lowrank_project_kernel; }
+
 #undef NB_
 }  // namespace

@@ -514,6 +514,26 @@ int aae_spgemm_i32_bound(const aae_cooc* A, const aae_cooc* B, int32_t p, int64_
 int aae_spgemm_i32_count(const aae_cooc* A, const aae_cooc* B, int32_t n, const int64_t* u_dev, int64_t* row_nnz_dev, void* stream);
 int aae_spgemm_i32_fill(const aae_cooc* A, const aae_cooc* B, int32_t n, const int64_t* u_dev, const int64_t* indptr_dev,
                         int32_t* indices_dev, int32_t* values_dev, void* stream);
+/* Transpose of a canonical CSR matrix (csrc/sptrans.h): T = A^T for A [n_rows x n_cols] - int64 indptr, int32 indices ascending
+ * within a row and without duplicates, 4-byte values that are moved as raw bits (int32 and float32 alike) - T in the same layout,
+ * its rows ascending and duplicate-free: the indptr, indices and value bits of scipy's A.T.tocsr() after sort_indices(), the same
+ * bits every run.  Handle-free like the spgemm calls; the caller runs the two in this order on one stream and does the scan and
+ * the allocation between them:
+ * aae_csr_transpose_count  col_nnz_dev [n_cols] int64 (zeroed by the call): the stored entries of every column of A.
+ * aae_csr_transpose_fill   t_indices_dev / t_values_dev [nnz] from t_indptr_dev [n_cols + 1], the exclusive scan of col_nnz_dev.
+ *                          cursor_dev [n_cols] int64 is scratch (zeroed by the call).  A row of T of more than AAE_SPTRANS_LDS
+ *                          entries is sorted through scratch_dev, `scratch_pairs` 8-byte (row, value) pairs: nnz > AAE_SPTRANS_LDS
+ *                          requires scratch_pairs >= nnz (nnz = t_indptr[n_cols], passed by the caller who sized the result).
+ * A column id outside [0, n_cols) is skipped; nothing is stored outside a row's own range [t_indptr[c], t_indptr[c + 1]); every
+ * loop is bounded, so a wrong t_indptr drops entries and does not hang.  n_rows = 0 or n_cols = 0 launches nothing.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, a negative size, a scratch that is too
+ * small or not 8-byte aligned. */
+#define AAE_SPTRANS_LDS 4096
+int aae_csr_transpose_count(const int64_t* indptr_dev, const int32_t* indices_dev, int32_t n_rows, int32_t n_cols,
+                            int64_t* col_nnz_dev, void* stream);
+int aae_csr_transpose_fill(const int64_t* indptr_dev, const int32_t* indices_dev, const void* values_dev, int32_t n_rows,
+                           int32_t n_cols, const int64_t* t_indptr_dev, int32_t* t_indices_dev, void* t_values_dev,
+                           int64_t* cursor_dev, void* scratch_dev, int64_t scratch_pairs, int64_t nnz, void* stream);
 /* The truncated-SVD baseline (reference svd.py:15-57, SVDRecommender: predict = (X V^T) V[:, :n_items], V = TruncatedSVD's
  * components_ [dims][n_features], n_features = items (+ the tf-idf vocabulary of the titles); csrc/lowrank.h).  Handle-free like
  * the cooc calls.  `lowrank` is ONE fp32 table for both products: vt_dev [n_features][ld], row f = column f of V, ld a multiple
@@ -553,6 +573,15 @@ int aae_lowrank_ranks(const aae_lowrank* lowrank, int32_t n_items, const aae_bat
                       int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
 /* widest hidden vector of the projection kernel (csrc/lowrank.h kProjDimsMax) */
 #define AAE_LOWRANK_DIMS_MAX 4096
+/* The projection of the calls above as a product of its own: out[r][0:width] = sum over the entries (f, x_f) of row r of `rows`
+ * of x_f * dense[f][0:width] - a tall CSR x row-major dense product, the same kernel, the same k-ordered fmaf chain in CSR order
+ * and the same bits however it is launched (the randomized range finder of aaerec/lowrank.py is built from it).  dense_dev
+ * [n_cols][ld] and out_dev [rows->n_rows][ld_out]: leading dimensions in multiples of 4 floats on 16-byte aligned bases,
+ * ld >= width rounded up to 4 (the padding is read, its products are not stored), ld_out >= width; width in
+ * [1, AAE_LOWRANK_DIMS_MAX].  An id outside [0, n_cols) is skipped; an empty row is a row of zeros; columns [width, ld_out) are
+ * not written.  AAE_EINVAL as above. */
+int aae_spmm_f32(const aae_batch* rows, const float* dense_dev, int64_t ld, int32_t n_cols, int32_t width, float* out_dev,
+                 int64_t ld_out, void* stream);
 /* split form for generic conditions */
 int aae_encode(aae_handle h, const aae_batch* batch, float* z_out_dev, void* stream);
 int aae_decode(aae_handle h, const float* zc_dev, int64_t zc_ld, int32_t n_rows,
