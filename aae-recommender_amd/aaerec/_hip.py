@@ -185,6 +185,11 @@ _PROTOS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_cooc_ranks": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p]),
+    "aae_cooc_scores_i32": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_cooc_topk_i32": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_cooc_ranks_i32": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p]),
     "aae_spgemm_i32_bound": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p]),
     "aae_spgemm_i32_count": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_spgemm_i32_fill": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -476,6 +481,7 @@ class DeviceCooc:
         self.indptr = upload(C.indptr.astype(np.int64), device)
         self.indices = upload(C.indices.astype(np.int32) if C.nnz else np.zeros(1, dtype=np.int32), device)
         self.values = upload(np.rint(C.data).astype(np.int32) if C.nnz else np.zeros(1, dtype=np.int32), device)
+        self._row_abs_max = np.asarray(abs(C).max(axis=1).toarray(), dtype=np.float64).ravel() if C.nnz else np.zeros(C.shape[0])
 
     @classmethod
     def from_device(cls, indptr, indices, values, shape, device):
@@ -493,6 +499,7 @@ class DeviceCooc:
         if indices.numel() < self.nnz or values.numel() < self.nnz:
             raise ValueError("aaerec: indices / values are shorter than indptr[-1]")
         self.indptr, self.indices, self.values = indptr, indices, values
+        self._row_abs_max = None
         return self
 
     def to_scipy(self):
@@ -504,6 +511,18 @@ class DeviceCooc:
     def abs_max(self):
         """max |value| over the stored entries (0 without any): a device reduction, one number to the host."""
         return int(self.values[:self.nnz].abs().max()) if self.nnz else 0
+
+    def row_abs_max(self):
+        """m_i = max_j |C_ij| per row (0 for an empty one): a host array of float64 [rows], kept.  From the scipy matrix the
+        object was made from; for a matrix made on the device one reduction over the CSR values there and rows numbers to the
+        host - never the matrix.  (aaerec.cooc.device_route bounds a row's scores by it.)"""
+        if self._row_abs_max is None:
+            m = torch.zeros(self.shape[0], dtype=torch.int64, device=self.device)
+            if self.nnz:
+                rows = torch.repeat_interleave(torch.arange(self.shape[0], device=self.device), self.indptr.diff())
+                m.scatter_reduce_(0, rows, self.values[:self.nnz].to(torch.int64).abs(), "amax")
+            self._row_abs_max = m.cpu().numpy().astype(np.float64)
+        return self._row_abs_max
 
     def struct(self):
         c = AaeCooc()
@@ -522,55 +541,87 @@ def _cooc_batch(csr, row_start, n_rows, rows=None):
     return b
 
 
-def _cooc_scratch(cooc, n_rows, scratch):
-    """[n_rows, ld] float32 on cooc's device: the caller's (at least n_rows rows, unit column stride) or a new one."""
+def _cooc_scratch(cooc, n_rows, scratch, dtype=torch.float32):
+    """[n_rows, ld] of `dtype` (float32; int32 for the _i32 calls) on cooc's device: the caller's (at least n_rows rows, unit
+    column stride) or a new one."""
     N = int(cooc.shape[1])
     if scratch is None:
-        return torch.empty(n_rows, (N + 3) & ~3, dtype=torch.float32, device=cooc.device)
-    if not scratch.is_cuda or scratch.dtype != torch.float32 or scratch.dim() != 2 or scratch.stride(1) != 1 \
+        return torch.empty(n_rows, (N + 3) & ~3, dtype=dtype, device=cooc.device)
+    if not scratch.is_cuda or scratch.dtype != dtype or scratch.dim() != 2 or scratch.stride(1) != 1 \
             or scratch.shape[0] < n_rows or scratch.shape[1] < N:
-        raise TypeError("aaerec: scratch must be a float32 GPU matrix of at least [n_rows, n_items] with unit column stride")
+        raise TypeError("aaerec: scratch must be a {} GPU matrix of at least [n_rows, n_items] with unit column stride".format(
+            "float32" if dtype == torch.float32 else "int32"))
     return scratch
 
 
-def cooc_scores(cooc, csr, row_start, n_rows, rows=None, out=None):
-    """float32 device tensor [n_rows, items]: X[rows] @ C for rows [row_start, row_start + n_rows) of the DeviceCSR `csr`
-    (or the rows named by the int32 device tensor `rows`) - exact whole numbers while they stay below 2^24."""
-    out = _cooc_scratch(cooc, n_rows, out)
+def _cooc_scores(entry, dtype, cooc, csr, row_start, n_rows, rows, out):
+    out = _cooc_scratch(cooc, n_rows, out, dtype)
     c, b = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows)
     with torch.cuda.device(cooc.device):
-        _check(load_library().aae_cooc_scores(C.byref(c), int(cooc.shape[1]), C.byref(b), _ptr(out), out.stride(0),
+        _check(getattr(load_library(), entry)(C.byref(c), int(cooc.shape[1]), C.byref(b), _ptr(out), out.stride(0),
                                               C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
     return out[:n_rows, :cooc.shape[1]]
 
 
-def cooc_topk(cooc, csr, row_start, n_rows, k, rows=None, exclude_known=True, scratch=None):
-    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: predict -> remove_non_missing -> argtopk
-    of the co-occurrence scores, the better score first and the smaller id at equal scores (aae_cooc_topk)."""
-    scratch = _cooc_scratch(cooc, n_rows, scratch)
+def _cooc_topk(entry, dtype, cooc, csr, row_start, n_rows, k, rows, exclude_known, scratch):
+    scratch = _cooc_scratch(cooc, n_rows, scratch, dtype)
     idx = torch.empty(n_rows, k, dtype=torch.int32, device=cooc.device)
     val = torch.empty(n_rows, k, dtype=torch.float32, device=cooc.device)
     c, b = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows)
     with torch.cuda.device(cooc.device):
-        _check(load_library().aae_cooc_topk(C.byref(c), int(cooc.shape[1]), C.byref(b), int(k), int(bool(exclude_known)),
-                                            _ptr(scratch), scratch.stride(0), _ptr(idx), _ptr(val),
-                                            C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+        _check(getattr(load_library(), entry)(C.byref(c), int(cooc.shape[1]), C.byref(b), int(k), int(bool(exclude_known)),
+                                              _ptr(scratch), scratch.stride(0), _ptr(idx), _ptr(val),
+                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
     return idx, val
 
 
-def cooc_ranks(cooc, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, scratch=None):
-    """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with
-    the addressing of the input rows; n_truth = their stored entries), CSR order, in cooc_topk's ordering (aae_cooc_ranks)."""
-    scratch = _cooc_scratch(cooc, n_rows, scratch)
+def _cooc_ranks(entry, dtype, cooc, csr, row_start, n_rows, truth_csr, n_truth, rows, exclude_known, scratch):
+    scratch = _cooc_scratch(cooc, n_rows, scratch, dtype)
     ranks = torch.empty(int(n_truth), dtype=torch.int32, device=cooc.device)
     if not n_truth:
         return ranks
     c, b, t = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(truth_csr, row_start, n_rows, rows)
     with torch.cuda.device(cooc.device):
-        _check(load_library().aae_cooc_ranks(C.byref(c), int(cooc.shape[1]), C.byref(b), C.byref(t), int(bool(exclude_known)),
-                                             _ptr(scratch), scratch.stride(0), _ptr(ranks),
-                                             C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+        _check(getattr(load_library(), entry)(C.byref(c), int(cooc.shape[1]), C.byref(b), C.byref(t), int(bool(exclude_known)),
+                                              _ptr(scratch), scratch.stride(0), _ptr(ranks),
+                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
     return ranks
+
+
+def cooc_scores(cooc, csr, row_start, n_rows, rows=None, out=None):
+    """float32 device tensor [n_rows, items]: X[rows] @ C for rows [row_start, row_start + n_rows) of the DeviceCSR `csr`
+    (or the rows named by the int32 device tensor `rows`) - exact whole numbers while they stay below 2^24."""
+    return _cooc_scores("aae_cooc_scores", torch.float32, cooc, csr, row_start, n_rows, rows, out)
+
+
+def cooc_topk(cooc, csr, row_start, n_rows, k, rows=None, exclude_known=True, scratch=None):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: predict -> remove_non_missing -> argtopk
+    of the co-occurrence scores, the better score first and the smaller id at equal scores (aae_cooc_topk)."""
+    return _cooc_topk("aae_cooc_topk", torch.float32, cooc, csr, row_start, n_rows, k, rows, exclude_known, scratch)
+
+
+def cooc_ranks(cooc, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, scratch=None):
+    """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with
+    the addressing of the input rows; n_truth = their stored entries), CSR order, in cooc_topk's ordering (aae_cooc_ranks)."""
+    return _cooc_ranks("aae_cooc_ranks", torch.float32, cooc, csr, row_start, n_rows, truth_csr, n_truth, rows, exclude_known, scratch)
+
+
+# The same three calls over an int32 score matrix / scratch (aae_cooc_*_i32): the scores are ranked as the integers they are, so
+# ids and ranks are exact while every row keeps sum_i |x_i| * max_j |C_ij| < 2^31 - the caller's guarantee (aaerec.cooc.device_route),
+# which the calls do not check.
+def cooc_scores_i32(cooc, csr, row_start, n_rows, rows=None, out=None):
+    """cooc_scores with an int32 result [n_rows, items]: the sums as they are."""
+    return _cooc_scores("aae_cooc_scores_i32", torch.int32, cooc, csr, row_start, n_rows, rows, out)
+
+
+def cooc_topk_i32(cooc, csr, row_start, n_rows, k, rows=None, exclude_known=True, scratch=None):
+    """cooc_topk ranked on the int32 scores (`scratch`: int32); the scaled scores are (float(v) - float(min)) / span in fp32."""
+    return _cooc_topk("aae_cooc_topk_i32", torch.int32, cooc, csr, row_start, n_rows, k, rows, exclude_known, scratch)
+
+
+def cooc_ranks_i32(cooc, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, scratch=None):
+    """cooc_ranks counted on the int32 scores (`scratch`: int32)."""
+    return _cooc_ranks("aae_cooc_ranks_i32", torch.int32, cooc, csr, row_start, n_rows, truth_csr, n_truth, rows, exclude_known, scratch)
 
 
 # ---- the exact int32 sparse product (aae_spgemm_i32_*; csrc/spgemm.h) -----------------------------------------------

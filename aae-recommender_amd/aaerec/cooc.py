@@ -3,16 +3,20 @@
     scores = X_test @ C,   C = X^T X of the training set   (order n: C <- C^T C, n - 1 times)
 
 `predict` is the reference's: the scipy product, the host route.  `predict_topk` / `predict_ranks` are what `Evaluation` asks
-for where a recommender offers them: the scores are formed by csrc/cooc.h in int32 (exact), written as fp32 into a
-[rows, items] scratch and ranked there by the dense kernels of csrc/rank_long.h / rank_full.h - row-wise min-max scaling with
-the known items still in the minimum and maximum, known items masked, the better score first, THE SMALLER ID AT EQUAL SCORES
-(the reference leaves ties to np.argpartition's order; co-occurrence counts tie often).  Only [n, k] ids or nnz(truth) ranks
-cross PCIe.
+for where a recommender offers them: the scores are formed by csrc/cooc.h in int32 (exact), written into a [rows, items]
+scratch and ranked there by the dense kernels of csrc/rank_long.h / rank_full.h - row-wise min-max scaling with the known items
+still in the minimum and maximum, known items masked, the better score first, THE SMALLER ID AT EQUAL SCORES (the reference
+leaves ties to np.argpartition's order; co-occurrence counts tie often).  Only [n, k] ids or nnz(truth) ranks cross PCIe.
 
-The device is used only where it is exact (`device_route_ok`): whole-number values in X and C, max |C| < 2^31, and
-max_r (sum_i |x_ri|) * max |C| < 2^24, so that every score is a whole number fp32 represents.  Anything else - and a list
-longer than min(1024, items) - is answered on the host from predict() with the same ordering rule: callers see no difference
-beyond speed.
+The device is used only where it is exact, and `device_route` says how (`Countbased.route` for a trained model).  X and C hold
+whole numbers and max |C| < 2^31 on both device routes.
+  "f32"  max_r (sum_i |x_ri|) * max |C| < 2^24 (`device_route_ok`): every score is a whole number fp32 represents; the scratch
+         is fp32 and the float rank kernels order it.
+  "i32"  otherwise, while max |x| < 2^24 and max_r sum_i |x_ri| * m_i < 2^31 with m_i = max_j |C_ij|: no sum leaves int32; the
+         scratch is int32 and the integer members of the same kernels order the scores themselves, so nothing ties that is
+         not equal.  The bound counts only the rows of C that a bag touches, each with its own maximum.
+  None   anything else - and a list longer than min(1024, items) - is answered on the host from predict() with the same
+         ordering rule and the same fp32 formula for the scaled scores: callers see no difference beyond speed.
 
 C is built where `build` says.  "host": scipy's product, as the reference builds it, uploaded once by train().  "device": X goes
 up as int32 CSR, X^T is formed there by csrc/sptrans.h (`_hip.cooc_transpose`) and C = X^T . X by the exact int32 sparse product of
@@ -63,6 +67,41 @@ def device_route_ok(X, C):
     represents).  X, C: scipy sparse matrices."""
     C = sp.csr_matrix(C)
     return _route_ok(X, _whole(C), _abs_max(C))
+
+
+def _route(X, c_whole, c_abs_max, row_abs_max):
+    """device_route's rule from what is known of an uploaded C: whether its values are whole, max |C|, and a function that
+    returns m_i = max_j |C_ij| as a host array [items] (called only when the "f32" rule fails)."""
+    X = sp.csr_matrix(X)
+    if _route_ok(X, c_whole, c_abs_max):
+        return "f32"
+    if not (c_whole and c_abs_max < INT32_LIMIT and _whole(X) and _abs_max(X) < EXACT_FP32):
+        return None
+    bound = abs(X).astype(np.float64) @ np.asarray(row_abs_max(), dtype=np.float64)
+    return "i32" if float(bound.max()) < INT32_LIMIT else None
+
+
+def device_route(X, C, device="cuda:0"):
+    """How the device answers X @ C exactly: "f32", "i32" or None (the host route).  X, C: scipy sparse matrices; device: None
+    when there is none to upload C to.
+      "f32"  exactly where device_route_ok(X, C) holds.
+      "i32"  otherwise, when X and C hold whole numbers, max |x| < 2^24 (the batch travels as fp32 and the kernel reads it
+             back with a round to nearest), max |C| < 2^31 (its int32 upload) and, with m_i = max_j |C_ij|,
+                 B = max_r sum_i |x_ri| * m_i < 2^31.
+             For row r and any column j, every partial sum of sum_i x_ri * C_ij, in any order, is at most
+             sum_i |x_ri| * |C_ij| <= B in magnitude: the int32 accumulation cannot wrap, every score lies in
+             [-(2^31 - 1), 2^31 - 1], and INT32_MIN - what the rank kernels mask a known item to - is never a score.
+      None   everything else.
+    B is computed as abs(X) @ m in float64.  All terms are non-negative whole numbers.  If the true sum of a row is below 2^31
+    then so is every product and partial sum, all of them are exact in float64 (whole numbers below 2^53), and the computed
+    value is the true one.  If it is not, take the first operation, in the order the products and sums are evaluated, whose
+    exact result reaches 2^31: its operands are still exact, rounding is monotone and 2^31 is a float64, so its rounded result
+    is >= 2^31, and adding non-negative terms never lowers a rounded sum below it.  Either way the comparison is the true one."""
+    if device is None:
+        return None
+    C = sp.csr_matrix(C)
+    return _route(X, _whole(C), _abs_max(C), lambda: np.asarray(abs(C).max(axis=1).toarray(), dtype=np.float64).ravel()
+                  if C.nnz else np.zeros(C.shape[0]))
 
 
 def _canonical(X):
@@ -117,6 +156,7 @@ def _order_row(s, known):
     return ids[~np.isin(ids, known)] if len(known) else ids
 
 
+_SCRATCH = {"f32": torch.float32, "i32": torch.int32}      # the score type of each device route
 BUILDS = ("auto", "host", "device")
 # What build="auto" does where the device route is open: decided by the one measurement of tools/cooc_build_rate.py in DESIGN 3.4d
 AUTO_BUILDS_ON_DEVICE = True
@@ -124,7 +164,7 @@ AUTO_BUILDS_ON_DEVICE = True
 
 class Countbased(Recommender):
     """Item Co-Occurrence.  order: 1 = C = X^T X; n = C <- C^T C repeated n - 1 times.  scratch_bytes: the [rows, items]
-    fp32 scratch of one device call - the rows of a predict_topk / predict_ranks call are chunked to it.  device: where C
+    scratch (fp32 or int32) of one device call - the rows of a predict_topk / predict_ranks call are chunked to it.  device: where C
     lives and the ranking runs; None keeps everything on the host.  build: where train() forms C - "host" (scipy), "device"
     (csrc/spgemm.h; ValueError where there is no device or device_build_ok refuses) or "auto" (the module docstring)."""
 
@@ -212,11 +252,25 @@ class Countbased(Recommender):
         return X
 
     def on_device(self, X, k=None):
-        """Whether a call over the rows X (k: its list length) takes the device route."""
+        """Whether a call over the rows X (k: its list length) takes the fp32 device route - the "f32" of route(), which also
+        names the int32 one."""
         n_items = self._shape[1]
         if self._dev is None or (k is not None and not 1 <= k <= min(_hip.RANK_K_MAX, n_items)):
             return False
         return _route_ok(X, True, self._cmax)      # (device_route_ok's rule: an uploaded C is whole, max |C| kept by train())
+
+    def _route_of(self, X, k=None):
+        """device_route for the rows X (a canonical CSR) of a call with list length k, from what train() kept of C: its
+        maximum and, through the uploaded matrix, its row maxima - C itself is never downloaded for this."""
+        n_items = self._shape[1]
+        if self._dev is None or (k is not None and not 1 <= k <= min(_hip.RANK_K_MAX, n_items)):
+            return None
+        return _route(X, True, self._cmax, self._dev.row_abs_max)
+
+    def route(self, test_set, k=None):
+        """Which route predict_topk(test_set, k) - or, without k, predict_ranks(test_set, ...) - takes: "f32" or "i32" on the
+        device (device_route), None on the host."""
+        return self._route_of(self._inputs(test_set), k)
 
     def _chunk_rows(self, n_items):
         return max(1, self.scratch_bytes // (4 * ((n_items + 3) & ~3)))
@@ -236,11 +290,13 @@ class Countbased(Recommender):
         n, n_items = X.shape
         if k < 1:
             raise ValueError("k must be positive")
-        if self.on_device(X, k) and n:
+        route = self._route_of(X, k) if n else None
+        if route:
+            topk, dtype = getattr(_hip, "cooc_topk" if route == "f32" else "cooc_topk_i32"), _SCRATCH[route]
             csr = _hip.DeviceCSR(X, self._dev.device)
             chunk = self._chunk_rows(n_items)
-            scratch = torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=torch.float32, device=self._dev.device)
-            parts = [_hip.cooc_topk(self._dev, csr, s0, min(chunk, n - s0), k, scratch=scratch) for s0 in range(0, n, chunk)]
+            scratch = torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=dtype, device=self._dev.device)
+            parts = [topk(self._dev, csr, s0, min(chunk, n - s0), k, scratch=scratch) for s0 in range(0, n, chunk)]
             return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
         ids = np.full((n, k), -1, dtype=np.int32)
         val = np.zeros((n, k), dtype=np.float32)
@@ -263,15 +319,17 @@ class Countbased(Recommender):
             raise ValueError("the ground truth has shape {}, the test set {}".format(Ys.shape, X.shape))
         Ys.sum_duplicates()
         Ys.sort_indices()
-        if self.on_device(X) and n:
+        route = self._route_of(X) if n else None
+        if route:
+            ranks, dtype = getattr(_hip, "cooc_ranks" if route == "f32" else "cooc_ranks_i32"), _SCRATCH[route]
             csr, truth = _hip.DeviceCSR(X, self._dev.device), _hip.DeviceCSR(Ys, self._dev.device)
             chunk = self._chunk_rows(n_items)
-            scratch = torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=torch.float32, device=self._dev.device)
+            scratch = torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=dtype, device=self._dev.device)
             parts = []
             for s0 in range(0, n, chunk):
                 rows = min(chunk, n - s0)
                 nnz = int(Ys.indptr[s0 + rows] - Ys.indptr[s0])
-                parts.append(_hip.cooc_ranks(self._dev, csr, s0, rows, truth, nnz, scratch=scratch))
+                parts.append(ranks(self._dev, csr, s0, rows, truth, nnz, scratch=scratch))
             data = torch.cat(parts).cpu().numpy().astype(np.int32, copy=False)
         else:
             data = np.zeros(Ys.nnz, dtype=np.int32)

@@ -1,6 +1,7 @@
 // Entry points of the item co-occurrence baseline (cooc.h): scores alone, or scores into the caller's scratch followed by the
-// dense ranking kernels of rank_long.h / rank_full.h as they stand.  Handle-free: every buffer is the caller's, every launch
-// goes to the caller's stream, nothing synchronises.
+// dense ranking kernels of rank_long.h / rank_full.h.  Each call exists for both score types of those kernels (SC: float, and
+// int32_t behind the _i32 names - the same checks, the same launches, the integer members of the three kernels).  Handle-free:
+// every buffer is the caller's, every launch goes to the caller's stream, nothing synchronises.
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
 #pragma once
 
@@ -9,7 +10,7 @@ static_assert(kCoocTile == AAE_COOC_TILE, "include/aaerec_hip.h names the tile w
 namespace {
 
 // everything a call can be refused for before anything touches the device
-int cooc_check(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const float* scores_dev, int64_t ld) {
+int cooc_check(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const void* scores_dev, int64_t ld) {
     const std::string w(who);
     if (!cooc || !cooc->indptr_dev || !cooc->indices_dev || !cooc->values_dev) return fail(AAE_EINVAL, w + ": cooc or one of its pointers is NULL");
     if (n_items <= 0) return fail(AAE_EINVAL, w + ": n_items must be positive");
@@ -24,12 +25,53 @@ int cooc_check(const char* who, const aae_cooc* cooc, int32_t n_items, const aae
     return AAE_OK;
 }
 
-int cooc_launch(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, float* scores_dev, int64_t ld, hipStream_t s) {
+template <class SC>
+int cooc_launch(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, SC* scores_dev, int64_t ld, hipStream_t s) {
     const int ntiles = (n_items + kCoocTile - 1) / kCoocTile;
     const CoocView C{cooc->indptr_dev, cooc->indices_dev, cooc->values_dev, cooc->n_rows};
-    hipLaunchKernelGGL(cooc_scores_kernel, dim3((unsigned)(batch->n_rows * ntiles)), dim3(kCoocNT), 0, s, C, (int)n_items, ntiles,
+    hipLaunchKernelGGL(pick_cooc_scores<SC>(), dim3((unsigned)(batch->n_rows * ntiles)), dim3(kCoocNT), 0, s, C, (int)n_items, ntiles,
                        rank_view(batch), scores_dev, (long long)ld);
     LAUNCHCHK("cooc_scores");
+    return AAE_OK;
+}
+
+template <class SC>
+int cooc_scores(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, SC* scores_dev, int64_t ld, void* stream) {
+    TRY(cooc_check(who, cooc, n_items, batch, scores_dev, ld));
+    if (batch->n_rows == 0) return AAE_OK;
+    return cooc_launch(cooc, n_items, batch, scores_dev, ld, S(stream));
+}
+
+template <class SC>
+int cooc_topk(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
+              SC* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    const std::string w(who);
+    TRY(cooc_check(who, cooc, n_items, batch, scratch_dev, scratch_ld));
+    if (k < 1 || k > kLongKMax || k > n_items) return fail(AAE_EINVAL, w + ": k must be in [1, min(1024, n_items)]");
+    if (!idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, w + ": idx_out_dev / val_out_dev is NULL");
+    if (batch->n_rows == 0) return AAE_OK;
+    hipStream_t s = S(stream);
+    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
+    hipLaunchKernelGGL(pick_rank_long_dense<SC>(), dim3(batch->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
+                       rank_view(batch), (int)exclude_known, (int)k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
+    LAUNCHCHK("rank_long_dense (cooc)");
+    return AAE_OK;
+}
+
+template <class SC>
+int cooc_ranks(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
+               SC* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream) {
+    const std::string w(who);
+    TRY(cooc_check(who, cooc, n_items, batch, scratch_dev, scratch_ld));
+    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, w + ": truth pointers are NULL");
+    if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, w + ": truth names another number of rows than batch");
+    if (!ranks_out_dev) return fail(AAE_EINVAL, w + ": ranks_out_dev is NULL");
+    if (batch->n_rows == 0) return AAE_OK;
+    hipStream_t s = S(stream);
+    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
+    hipLaunchKernelGGL(pick_rank_full_dense<SC>(), dim3(batch->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
+                       rank_view(batch), rank_view(truth), 0, (int)exclude_known, reinterpret_cast<int*>(ranks_out_dev));
+    LAUNCHCHK("rank_full_dense (cooc)");
     return AAE_OK;
 }
 
@@ -38,38 +80,28 @@ int cooc_launch(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, f
 extern "C" {
 
 int aae_cooc_scores(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, float* scores_dev, int64_t ld, void* stream) {
-    TRY(cooc_check("aae_cooc_scores", cooc, n_items, batch, scores_dev, ld));
-    if (batch->n_rows == 0) return AAE_OK;
-    return cooc_launch(cooc, n_items, batch, scores_dev, ld, S(stream));
+    return cooc_scores("aae_cooc_scores", cooc, n_items, batch, scores_dev, ld, stream);
+}
+int aae_cooc_scores_i32(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t* scores_dev, int64_t ld, void* stream) {
+    return cooc_scores("aae_cooc_scores_i32", cooc, n_items, batch, scores_dev, ld, stream);
 }
 
 int aae_cooc_topk(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
                   float* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    TRY(cooc_check("aae_cooc_topk", cooc, n_items, batch, scratch_dev, scratch_ld));
-    if (k < 1 || k > kLongKMax || k > n_items) return fail(AAE_EINVAL, "aae_cooc_topk: k must be in [1, min(1024, n_items)]");
-    if (!idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "aae_cooc_topk: idx_out_dev / val_out_dev is NULL");
-    if (batch->n_rows == 0) return AAE_OK;
-    hipStream_t s = S(stream);
-    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(rank_long_dense_kernel, dim3(batch->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
-                       rank_view(batch), (int)exclude_known, (int)k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    LAUNCHCHK("rank_long_dense (cooc)");
-    return AAE_OK;
+    return cooc_topk("aae_cooc_topk", cooc, n_items, batch, k, exclude_known, scratch_dev, scratch_ld, idx_out_dev, val_out_dev, stream);
+}
+int aae_cooc_topk_i32(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
+                      int32_t* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    return cooc_topk("aae_cooc_topk_i32", cooc, n_items, batch, k, exclude_known, scratch_dev, scratch_ld, idx_out_dev, val_out_dev, stream);
 }
 
 int aae_cooc_ranks(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
                    float* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream) {
-    TRY(cooc_check("aae_cooc_ranks", cooc, n_items, batch, scratch_dev, scratch_ld));
-    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, "aae_cooc_ranks: truth pointers are NULL");
-    if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, "aae_cooc_ranks: truth names another number of rows than batch");
-    if (!ranks_out_dev) return fail(AAE_EINVAL, "aae_cooc_ranks: ranks_out_dev is NULL");
-    if (batch->n_rows == 0) return AAE_OK;
-    hipStream_t s = S(stream);
-    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(rank_full_dense_kernel, dim3(batch->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
-                       rank_view(batch), rank_view(truth), 0, (int)exclude_known, reinterpret_cast<int*>(ranks_out_dev));
-    LAUNCHCHK("rank_full_dense (cooc)");
-    return AAE_OK;
+    return cooc_ranks("aae_cooc_ranks", cooc, n_items, batch, truth, exclude_known, scratch_dev, scratch_ld, ranks_out_dev, stream);
+}
+int aae_cooc_ranks_i32(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
+                       int32_t* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream) {
+    return cooc_ranks("aae_cooc_ranks_i32", cooc, n_items, batch, truth, exclude_known, scratch_dev, scratch_ld, ranks_out_dev, stream);
 }
 
 }  // extern "C"

@@ -101,7 +101,7 @@ int aae_lowrank_topk(const aae_lowrank* lowrank, int32_t n_items, const aae_batc
     if (features->n_rows == 0) return AAE_OK;
     hipStream_t s = S(stream);
     TRY(lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(rank_long_dense_kernel, dim3(items->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
+    hipLaunchKernelGGL(pick_rank_long_dense<float>(), dim3(items->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
                        rank_view(items), (int)exclude_known, (int)k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
     LAUNCHCHK("rank_long_dense (lowrank)");
     return AAE_OK;
@@ -118,7 +118,7 @@ int aae_lowrank_ranks(const aae_lowrank* lowrank, int32_t n_items, const aae_bat
     if (features->n_rows == 0) return AAE_OK;
     hipStream_t s = S(stream);
     TRY(lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(rank_full_dense_kernel, dim3(items->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
+    hipLaunchKernelGGL(pick_rank_full_dense<float>(), dim3(items->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
                        rank_view(items), rank_view(truth), 0, (int)exclude_known, reinterpret_cast<int*>(ranks_out_dev));
     LAUNCHCHK("rank_full_dense (lowrank)");
     return AAE_OK;

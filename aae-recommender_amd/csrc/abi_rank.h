@@ -181,7 +181,7 @@ int rank_full_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, con
 int rank_full_dense(aae_model* m, const BatchView& bv, const BatchView& tv, int row0, int exclude_known, int32_t* ranks_out,
                     hipStream_t s) {
     ProfScope ps(m, AAE_K_RANK, s);
-    hipLaunchKernelGGL(rank_full_dense_kernel, dim3(m->rows), dim3(kFullNT), 0, s, m->G.p, m->ldn, m->N, bv, tv, row0, exclude_known,
+    hipLaunchKernelGGL(pick_rank_full_dense<float>(), dim3(m->rows), dim3(kFullNT), 0, s, m->G.p, m->ldn, m->N, bv, tv, row0, exclude_known,
                        reinterpret_cast<int*>(ranks_out));
     LAUNCHCHK("rank_full_dense");
     return AAE_OK;
@@ -293,7 +293,7 @@ int rank_full_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae
 // k > 32, the dense form: [rows][ldn] scores in the scratch -> [rows][k]
 int rank_long_dense(aae_model* m, int k, int exclude_known, int32_t* idx_out, float* val_out, hipStream_t s) {
     ProfScope ps(m, AAE_K_RANK, s);
-    hipLaunchKernelGGL(rank_long_dense_kernel, dim3(m->rows), dim3(kLongNT), 0, s, m->G.p, m->ldn, m->N, m->bv, exclude_known, k,
+    hipLaunchKernelGGL(pick_rank_long_dense<float>(), dim3(m->rows), dim3(kLongNT), 0, s, m->G.p, m->ldn, m->N, m->bv, exclude_known, k,
                        reinterpret_cast<int*>(idx_out), val_out);
     LAUNCHCHK("rank_long_dense");
     return AAE_OK;

@@ -1,18 +1,20 @@
 // Item co-occurrence scores (the reference's Countbased baseline, baselines.py:22-43: predict = X @ C with C = X^T X of the
 // training set): for call row r with entries (i, x_i) and the co-occurrence matrix C in CSR form
 //
-//   scores[r][j] = sum_i x_i * C[i][j]            fp32 [rows][ld] in HBM, every column j < n_items written
+//   scores[r][j] = sum_i x_i * C[i][j]            fp32 or int32 [rows][ld] in HBM, every column j < n_items written
 //
-// - a sparse row times a sparse matrix with INTEGER values.  The sum is formed in int32 and converted once, so it is exact and
-// does not depend on the order the terms arrive in: the same bits from run to run and however the caller chunks its rows.
-// (The caller keeps every sum below 2^24 - aaerec/cooc.py device_route_ok - so the fp32 it reads is that integer.)
+// - a sparse row times a sparse matrix with INTEGER values.  The sum is formed in int32, so it is exact and does not depend on
+// the order the terms arrive in: the same bits from run to run and however the caller chunks its rows.  Two stored types
+// (OUT; kernel_pick.h names both): float - the sum converted once (the caller keeps every sum below 2^24, aaerec/cooc.py
+// device_route's "f32", so the fp32 it reads is that integer) - and int32_t - the sum as it is (the caller keeps every sum
+// inside int32, device_route's "i32"), for the integer form of the dense rank kernels (rank_long.h DenseScore).
 //
 //   cooc_scores_kernel       one workgroup per (row, tile of kCoocTile items).  The workgroup zeroes an int32 tile in LDS; its
 //                            16 waves take the row's entries in turn; for entry (i, x_i) the wave finds, by a lower-bound search
 //                            in the ascending columns of C's row i, the first column inside the tile, and its lanes stride over
 //                            the segment from there while the column stays below the tile's end, each adding x_i * C[i][j] to
-//                            tile[j] with an integer LDS atomic.  Behind a barrier the tile is converted and stored with plain
-//                            coalesced stores (float4 where the matrix is 16-byte aligned).
+//                            tile[j] with an integer LDS atomic.  Behind a barrier the tile is stored with plain coalesced
+//                            stores - converted (float4) or as it is (int4) where the matrix is 16-byte aligned.
 //
 // kCoocTile = 16384 items = 64 KB of the CU's 160 KB of LDS: two workgroups fit a CU by LDS, and two workgroups of 16 waves
 // are the CU's 32 wave slots as well, so one workgroup's atomics run beside the other's zeroing and stores.  A wider tile
@@ -23,6 +25,8 @@
 // entries is a row of zeros.  Columns of C outside the tile's span - or, against the contract, descending - are never added.
 // No float atomics, no inline assembly.
 #pragma once
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace aae {
@@ -32,8 +36,10 @@ constexpr int kCoocNT = 1024;
 
 struct CoocView { const int64_t* indptr; const int32_t* indices; const int32_t* values; int n_rows; };
 
+template <class OUT>
 __global__ __launch_bounds__(kCoocNT) void cooc_scores_kernel(CoocView C, int n_items, int ntiles, BatchView bv,
-                                                              float* __restrict__ scores, long long ld) {
+                                                              OUT* __restrict__ scores, long long ld) {
+    static_assert(std::is_same_v<OUT, float> || std::is_same_v<OUT, int32_t>, "the score matrix is fp32 or int32");
     __shared__ __attribute__((aligned(16))) int tile[kCoocTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row = blockIdx.x / ntiles, t = blockIdx.x - row * ntiles;
@@ -59,16 +65,17 @@ __global__ __launch_bounds__(kCoocNT) void cooc_scores_kernel(CoocView C, int n_
         }
     }
     __syncthreads();
-    float* out = scores + (size_t)row * (size_t)ld + col0;      // (col0 is a multiple of 4: a float4 of the row is one of the matrix)
+    OUT* out = scores + (size_t)row * (size_t)ld + col0;        // (col0 is a multiple of 4: a float4 / int4 of the row is one of the matrix)
     if ((ld & 3) == 0 && (reinterpret_cast<uintptr_t>(scores) & 15) == 0) {
         const int w4 = width >> 2;
         for (int j = tid; j < w4; j += kCoocNT) {
             const int4 v = reinterpret_cast<const int4*>(tile)[j];
-            reinterpret_cast<float4*>(out)[j] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+            if constexpr (std::is_same_v<OUT, float>) reinterpret_cast<float4*>(out)[j] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+            else reinterpret_cast<int4*>(out)[j] = v;
         }
-        for (int j = 4 * w4 + tid; j < width; j += kCoocNT) out[j] = (float)tile[j];
+        for (int j = 4 * w4 + tid; j < width; j += kCoocNT) out[j] = (OUT)tile[j];
     } else {
-        for (int j = tid; j < width; j += kCoocNT) out[j] = (float)tile[j];
+        for (int j = tid; j < width; j += kCoocNT) out[j] = (OUT)tile[j];
     }
 }
 

@@ -108,6 +108,23 @@ template <class F> void each_rank_x3v2(F&& f) {
     for (int nb : kPickNb) for (int win = 0; win < 2; ++win) for (int K : kPickK) f(pick_rank_x3v2(nb, K, win), nb);
 }
 
+// ---- rank_long.h / rank_full.h, the dense forms, and cooc.h: one member per score type (DenseScore) - float, what every
+// dense ranking call launches, and int32_t, the exact route of the co-occurrence baseline (abi_cooc.h aae_cooc_*_i32).  The
+// type is the caller's matrix, so it is a template argument here and no run-time value.  Static LDS: no limit to raise
+template <class SC> constexpr bool kDenseScoreType = std::is_same_v<SC, float> || std::is_same_v<SC, int32_t>;
+template <class SC> using RankLongDenseKernel = void (*)(SC*, int, int, BatchView, int, int, int*, float*);
+template <class SC> using RankFullDenseKernel = void (*)(SC*, int, int, BatchView, BatchView, int, int, int*);
+template <class SC> using CoocScoresKernel = void (*)(CoocView, int, int, BatchView, SC*, long long);
+template <class SC> inline RankLongDenseKernel<SC> pick_rank_long_dense() {
+    static_assert(kDenseScoreType<SC>, "scores are fp32 or int32"); return rank_long_dense_kernel<SC>;
+}
+template <class SC> inline RankFullDenseKernel<SC> pick_rank_full_dense() {
+    static_assert(kDenseScoreType<SC>, "scores are fp32 or int32"); return rank_full_dense_kernel<SC>;
+}
+template <class SC> inline CoocScoresKernel<SC> pick_cooc_scores() {
+    static_assert(kDenseScoreType<SC>, "scores are fp32 or int32"); return cooc_scores_kernel<SC>;
+}
+
 // ---- chain.h (NM: the r6 activation classes, device_common.h act_fwd); chain4.h: the timeline in fp32 alone, the column
 // form (a program without k-slices) in bf16 alone, the VAE's reparametrisation op in plain fp32 alone; chain16x3.h: the
 // timeline in fp32 alone

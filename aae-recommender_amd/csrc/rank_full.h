@@ -26,7 +26,8 @@
 //   dense form (every other handle; rows beyond the fused call's limit)
 //     rank_full_dense_kernel             one workgroup per row of the [rows][N] score matrix in the scratch: known items masked
 //                                        to -inf in place (as rank_long_dense_kernel), then 8 held-out items at a time counted
-//                                        over the row - by score, then the smaller id.
+//                                        over the row - by score, then the smaller id.  Templated on the score type as
+//                                        rank_long_dense_kernel (rank_long.h DenseScore): float, or the int32 co-occurrence scores.
 // No float atomics, no inline assembly: integer counters in LDS / HBM and plain stores.
 #pragma once
 #include "rank_long.h"
@@ -81,20 +82,22 @@ __global__ __launch_bounds__(256) void rank_full_finish_kernel(BatchView tv, int
 // ---- dense form -------------------------------------------------------------------------------------------------
 // One workgroup per row of the score matrix (sigmoids): row `blockIdx.x` of the matrix is row `row0 + blockIdx.x` of the call
 // (`kv`: its input rows, `tv`: its truth rows).
-__global__ __launch_bounds__(kFullNT) void rank_full_dense_kernel(float* __restrict__ scores, int ld, int n_items, BatchView kv,
+template <class SC>
+__global__ __launch_bounds__(kFullNT) void rank_full_dense_kernel(SC* __restrict__ scores, int ld, int n_items, BatchView kv,
                                                                   BatchView tv, int row0, int exclude_known,
                                                                   int* __restrict__ ranks_out) {
     __shared__ long long red[kFullNT / 64];
     __shared__ int t_id[kFullSlots], t_cnt[kFullSlots];
-    __shared__ float t_sc[kFullSlots];
+    __shared__ SC t_sc[kFullSlots];
+    using D = DenseScore<SC>;
     const int tid = threadIdx.x, row = row0 + blockIdx.x;
-    float* sc = scores + (size_t)blockIdx.x * ld;
+    SC* sc = scores + (size_t)blockIdx.x * ld;
     if (exclude_known) {
         const int dc = kv.doc(row);
         const int64_t lo = kv.indptr[dc], hi = kv.indptr[dc + 1];
         for (int64_t e = lo + tid; e < hi; e += kFullNT) {
             const int i = kv.indices[e];
-            if (i >= 0 && i < n_items) sc[i] = -INFINITY;
+            if (i >= 0 && i < n_items) sc[i] = D::lowest();
         }
     }
     const int dc = tv.doc(row);
@@ -105,14 +108,14 @@ __global__ __launch_bounds__(kFullNT) void rank_full_dense_kernel(float* __restr
         if (tid < kFullSlots) {
             int t = e0 + tid < hi ? tv.indices[e0 + tid] : -1;
             if (t < 0 || t >= n_items) t = -1;
-            t_id[tid] = t; t_sc[tid] = t >= 0 ? sc[t] : INFINITY; t_cnt[tid] = 0;
+            t_id[tid] = t; t_sc[tid] = t >= 0 ? sc[t] : D::highest(); t_cnt[tid] = 0;      // (nothing comes before an unused slot: its id is -1)
         }
         __syncthreads();
-        int id[kFullSlots], cnt[kFullSlots]; float ts[kFullSlots];
+        int id[kFullSlots], cnt[kFullSlots]; SC ts[kFullSlots];
 #pragma unroll
         for (int s = 0; s < kFullSlots; ++s) { id[s] = t_id[s]; ts[s] = t_sc[s]; cnt[s] = 0; }
         for (int i = tid; i < n_items; i += kFullNT) {
-            const float v = sc[i];
+            const SC v = sc[i];
 #pragma unroll
             for (int s = 0; s < kFullSlots; ++s) cnt[s] += (v > ts[s] || (v == ts[s] && i < id[s])) ? 1 : 0;
         }

@@ -19,9 +19,14 @@
 //     rank_long_dense_kernel             one workgroup per row of the [rows][N] score matrix: known items masked as
 //                                        topk_rows_kernel (kernels.h) masks them, radix select (4 x 8 bits of the key) of the k-th
 //                                        best value T, every item above T + the smallest ids among the items equal to T, the
-//                                        same LDS sort.
+//                                        same LDS sort.  Templated on the score type (DenseScore): float, what every caller
+//                                        but one launches, and int32_t - the co-occurrence scores ranked as the integers they
+//                                        are (abi_cooc.h aae_cooc_topk_i32): the keys are the scores, so the order is exact up to
+//                                        2^31 where fp32 keys tie from 2^24 on.
 // A row with fewer than k rankable items: its items, then id -1 / score 0 - what topk_rows_kernel and rank_merge_kernel emit.
 #pragma once
+#include <limits.h>
+
 #include "rank_x3.h"
 
 namespace aae {
@@ -38,6 +43,29 @@ __device__ __forceinline__ unsigned ord_key(float v) {
 __device__ __forceinline__ float ord_val(unsigned k) {
     return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
+// The score type of the dense rank kernels (rank_long_dense_kernel, rank_full.h rank_full_dense_kernel): the value a known item
+// is masked to (below every real score), its counterpart above every score, the order-preserving key and its inverse, the
+// conversion to float (round to nearest) the scaled value is formed from.  int32_t: lowest() is key 0, and the caller keeps
+// every real score strictly above it.
+template <class SC> struct DenseScore;
+template <> struct DenseScore<float> {
+    static __device__ __forceinline__ float lowest() { return -INFINITY; }
+    static __device__ __forceinline__ float highest() { return INFINITY; }
+    static __device__ __forceinline__ unsigned key(float v) { return ord_key(v); }
+    static __device__ __forceinline__ float unkey(unsigned k) { return ord_val(k); }
+    static __device__ __forceinline__ float to_float(float v) { return v; }
+    static __device__ __forceinline__ float lesser(float a, float b) { return fminf(a, b); }
+    static __device__ __forceinline__ float greater(float a, float b) { return fmaxf(a, b); }
+};
+template <> struct DenseScore<int32_t> {
+    static __device__ __forceinline__ int32_t lowest() { return INT_MIN; }
+    static __device__ __forceinline__ int32_t highest() { return INT_MAX; }
+    static __device__ __forceinline__ unsigned key(int32_t v) { return (unsigned)v ^ 0x80000000u; }
+    static __device__ __forceinline__ int32_t unkey(unsigned k) { return (int32_t)(k ^ 0x80000000u); }
+    static __device__ __forceinline__ float to_float(int32_t v) { return __int2float_rn(v); }
+    static __device__ __forceinline__ int32_t lesser(int32_t a, int32_t b) { return min(a, b); }
+    static __device__ __forceinline__ int32_t greater(int32_t a, int32_t b) { return max(a, b); }
+};
 __device__ __forceinline__ unsigned long long long_entry(unsigned key, int item) {
     return ((unsigned long long)key << 32) | (unsigned)~item;        // (descending: larger key, then smaller item; 0 = no item)
 }
@@ -155,55 +183,60 @@ __global__ __launch_bounds__(kLongNT) void rank_long_sort_kernel(const unsigned 
 }
 
 // ---- dense form -------------------------------------------------------------------------------------------------
-// One workgroup per row of the score matrix (sigmoids).  As topk_rows_kernel: known items are masked to -inf in place, their
-// scores still enter the row minimum / maximum.  Ties of the k-th value go to the smaller item ids.
-__global__ __launch_bounds__(kLongNT) void rank_long_dense_kernel(float* __restrict__ scores, int ld, int n_items, BatchView bv,
+// One workgroup per row of the score matrix (sigmoids; SC = int32_t: whole-number scores).  As topk_rows_kernel: known items
+// are masked to -inf (DenseScore<SC>::lowest()) in place, their scores still enter the row minimum / maximum - kept in SC, so
+// the integer form's are exact.  Ties of the k-th value go to the smaller item ids.
+// The scaled value is (float(v) - float(min)) * inv, span = float(max) - float(min), inv = span > 0 ? 1 / span : 1.
+template <class SC>
+__global__ __launch_bounds__(kLongNT) void rank_long_dense_kernel(SC* __restrict__ scores, int ld, int n_items, BatchView bv,
                                                                   int exclude_known, int k_out, int* __restrict__ idx_out,
                                                                   float* __restrict__ val_out) {
+    using D = DenseScore<SC>;
     __shared__ unsigned long long ent[kLongKMax];
     __shared__ int hist[258];
-    __shared__ float s_min[kLongNT / 64], s_max[kLongNT / 64];
+    __shared__ SC s_min[kLongNT / 64], s_max[kLongNT / 64];
     __shared__ int s_w[kLongNT / 64];
     __shared__ int s_n;
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sc = scores + (size_t)row * ld;
-    float vmin = INFINITY, vmax = -INFINITY;
+    SC* sc = scores + (size_t)row * ld;
+    SC vmin = D::highest(), vmax = D::lowest();
     if (exclude_known) {
         const int dc = bv.doc(row);
         const int64_t lo = bv.indptr[dc], hi = bv.indptr[dc + 1];
         for (int64_t e = lo + tid; e < hi; e += kLongNT) {
             const int i = bv.indices[e];
-            const float v = sc[i];
-            vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
-            sc[i] = -INFINITY;
+            const SC v = sc[i];
+            vmin = D::lesser(vmin, v); vmax = D::greater(vmax, v);
+            sc[i] = D::lowest();
         }
     }
     if (tid == 0) s_n = 0;
     for (int i = tid; i < kLongKMax; i += kLongNT) ent[i] = 0ull;
     __syncthreads();
     for (int i = tid; i < n_items; i += kLongNT) {
-        const float v = sc[i];
-        if (v != -INFINITY) { vmin = fminf(vmin, v); vmax = fmaxf(vmax, v); }
+        const SC v = sc[i];
+        if (v != D::lowest()) { vmin = D::lesser(vmin, v); vmax = D::greater(vmax, v); }
     }
-    for (int o = 32; o > 0; o >>= 1) { vmin = fminf(vmin, __shfl_xor(vmin, o, 64)); vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64)); }
+    for (int o = 32; o > 0; o >>= 1) { vmin = D::lesser(vmin, __shfl_xor(vmin, o, 64)); vmax = D::greater(vmax, __shfl_xor(vmax, o, 64)); }
     if (lane == 0) { s_min[wave] = vmin; s_max[wave] = vmax; }
     int ties;
-    const unsigned T = block_select_kth([&](int i) { return ord_key(sc[i]); }, n_items, k_out, hist, &ties);
-    for (int w = 0; w < kLongNT / 64; ++w) { vmin = fminf(vmin, s_min[w]); vmax = fmaxf(vmax, s_max[w]); }
-    const float span = vmax - vmin;
+    const unsigned T = block_select_kth([&](int i) { return D::key(sc[i]); }, n_items, k_out, hist, &ties);
+    for (int w = 0; w < kLongNT / 64; ++w) { vmin = D::lesser(vmin, s_min[w]); vmax = D::greater(vmax, s_max[w]); }
+    const float fmin_ = D::to_float(vmin);
+    const float span = D::to_float(vmax) - fmin_;
     const float inv = span > 0.f ? 1.f / span : 1.f;
     const int above = k_out - ties;                 // items strictly better than T: all of them belong to the list
     for (int i = tid; i < n_items; i += kLongNT) {
-        const unsigned key = ord_key(sc[i]);
+        const unsigned key = D::key(sc[i]);
         if (key > T) { const int pos = atomicAdd(&s_n, 1); if (pos < kLongKMax) ent[pos] = long_entry(key, i); }
     }
-    // the `ties` smallest ids among the items equal to T (T = a masked item's -inf: the row has fewer than k rankable
-    // items, the rest of the list stays empty)
-    if (T != ord_key(-INFINITY)) {
+    // the `ties` smallest ids among the items equal to T (T = a masked item's -inf - key 0 in the integer form: the row has
+    // fewer than k rankable items, the rest of the list stays empty)
+    if (T != D::key(D::lowest())) {
         int base = 0;
         for (int i0 = 0; i0 < n_items && base < ties; i0 += kLongNT) {
             const int i = i0 + tid;
-            const bool hit = i < n_items && ord_key(sc[i]) == T;
+            const bool hit = i < n_items && D::key(sc[i]) == T;
             const unsigned long long bal = __ballot(hit);
             if (lane == 0) s_w[wave] = __popcll(bal);
             __syncthreads();
@@ -222,7 +255,7 @@ __global__ __launch_bounds__(kLongNT) void rank_long_dense_kernel(float* __restr
         const unsigned long long e = ent[r];
         const int item = (int)~(unsigned)e;
         idx_out[(size_t)row * k_out + r] = item;
-        val_out[(size_t)row * k_out + r] = item >= 0 ? (ord_val((unsigned)(e >> 32)) - vmin) * inv : 0.f;
+        val_out[(size_t)row * k_out + r] = item >= 0 ? (D::to_float(D::unkey((unsigned)(e >> 32))) - fmin_) * inv : 0.f;
     }
 }
 

@@ -478,7 +478,15 @@ int aae_vae_rank_full_max_rows(aae_handle h, int32_t* rows_out);
  *                  entry of the truth rows, CSR order; a truth entry that is a known item ranks behind every rankable item, an
  *                  id outside [0, n_items) ranks 0.  truth->max_row_nnz is not read.
  * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, n_items <= 0, k outside its range,
- * scratch_ld < n_items (or beyond 2^31 - 1), negative row counts, truth->n_rows != batch->n_rows.  No rows: nothing is launched. */
+ * scratch_ld < n_items (or beyond 2^31 - 1), negative row counts, truth->n_rows != batch->n_rows.  No rows: nothing is launched.
+ * aae_cooc_scores_i32 / aae_cooc_topk_i32 / aae_cooc_ranks_i32   the same three calls with an int32 score matrix / scratch: the
+ *                  int32 sum is stored as it is and ranked AS AN INTEGER, so ids and ranks are exact wherever the sums fit
+ *                  int32 - fp32 scores tie from 2^24 on.  Same arguments, same checks, same ordering, padding and truth rules.
+ *                  The row minimum and maximum are integers; a scaled score is (float(v) - float(min)) * inv with
+ *                  span = float(max) - float(min), inv = span > 0 ? 1 / span : 1, every conversion rounded to nearest.  A known
+ *                  item is masked to INT32_MIN (the scratch is left so).  CONTRACT: the caller guarantees that for every row
+ *                  sum_i |x_i| * max_j |C[i][j]| < 2^31 (aaerec/cooc.py device_route): then no partial sum wraps and no score
+ *                  is INT32_MIN.  The calls do not check it; beyond it sums wrap and a score of INT32_MIN counts as masked. */
 typedef struct aae_cooc {
     const int64_t* indptr_dev;
     const int32_t* indices_dev;
@@ -490,6 +498,11 @@ int aae_cooc_topk(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch,
                   float* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream);
 int aae_cooc_ranks(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
                    float* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
+int aae_cooc_scores_i32(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t* scores_dev, int64_t ld, void* stream);
+int aae_cooc_topk_i32(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
+                      int32_t* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_cooc_ranks_i32(const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
+                       int32_t* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream);
 /* items per LDS tile of the score kernel (csrc/cooc.h kCoocTile): tests place their shapes across its multiples */
 #define AAE_COOC_TILE 16384
 /* The exact sparse product behind the co-occurrence matrix (csrc/spgemm.h): C = A . B, A [A->n_rows x p], B [p x n] with

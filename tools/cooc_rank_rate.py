@@ -4,9 +4,12 @@
 commit (Countbased.predict -> toarray -> remove_non_missing -> argtopk, what Evaluation does with a recommender that has no
 predict_topk) on a synthetic corpus: documents of 2-12 items from a skewed (1 / rank) popularity over --items, --docs of them
 to train on, --rows to rank.  Prints both wall times (median of --repeats, one warm-up each), their ratio, and the same for the
-full ranking (predict_ranks against argsort-free host ranks of one held-out item a row).
+full ranking (predict_ranks against argsort-free host ranks of one held-out item a row).  --scale S multiplies the training
+values by the whole number S (C by S^2), which moves the same corpus from the fp32 device route past 2^24 onto the int32 one;
+the route taken (Countbased.route) is printed.
 
     python tools/cooc_rank_rate.py --items 100000 --docs 50000 --rows 500 --k 10
+    python tools/cooc_rank_rate.py --items 100000 --docs 50000 --rows 500 --k 10 --scale 256
 """
 import argparse
 import os
@@ -26,6 +29,7 @@ ap.add_argument("--docs", type=int, default=50000)
 ap.add_argument("--rows", type=int, default=500)
 ap.add_argument("--k", type=int, default=10)
 ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--scale", type=int, default=1, help="whole-number factor on the training values: C grows by its square")
 a = ap.parse_args()
 med = lambda t: sorted(t)[len(t) // 2]                                                                  # noqa: E731
 
@@ -61,13 +65,15 @@ def wall(fn, reps):
 
 
 X, T = corpus(a.docs, a.items, 1), corpus(a.rows, a.items, 2)
+X.data *= a.scale
 rec = Countbased()
 t0 = time.perf_counter()
 rec.train(Set(X))
 C = rec.cooccurences
 print(f"train (scipy X^T X + one upload): {time.perf_counter() - t0:.2f} s; C: {C.nnz} entries, max {int(C.max())}, "
-      f"longest row {int(np.diff(C.indptr).max())}; device route: {rec.on_device(T, a.k)}", flush=True)
-assert rec.on_device(T, a.k), "the corpus left the exactness guard: nothing to compare"
+      f"longest row {int(np.diff(C.indptr).max())}; scale {a.scale}; route of the top-{a.k} call: {rec.route(Set(T), a.k)}, "
+      f"of the ranks call: {rec.route(Set(T))}", flush=True)
+assert rec.route(Set(T), a.k) and rec.route(Set(T)), "the corpus left both device routes: nothing to compare"
 
 
 def host_topk():
