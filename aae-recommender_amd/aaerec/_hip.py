@@ -282,6 +282,14 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _arg(a):
+    """An argument of an entry point: a device tensor (None: absent) by its address, a struct by reference, anything else as
+    it is.  The caller's argument tuple keeps every tensor alive until the call is enqueued."""
+    if a is None or torch.is_tensor(a):
+        return _ptr(a)
+    return C.byref(a) if isinstance(a, C.Structure) else a
+
+
 _UPLOAD_STREAMS = {}
 
 
@@ -531,7 +539,9 @@ class DeviceCooc:
         return c
 
 
-def _cooc_batch(csr, row_start, n_rows, rows=None):
+def _csr_batch(csr, row_start, n_rows, rows=None):
+    """The aae_batch of rows [row_start, row_start + n_rows) of a DeviceCSR (or of the rows named by `rows`) for the handle-free
+    calls: no per-model bounds, no content id."""
     b = AaeBatch()
     b.indptr_dev, b.indices_dev, b.values_dev = csr.indptr.data_ptr(), csr.indices.data_ptr(), csr.values.data_ptr()
     b.rows_dev = rows.data_ptr() if rows is not None else None
@@ -541,51 +551,70 @@ def _cooc_batch(csr, row_start, n_rows, rows=None):
     return b
 
 
-def _cooc_scratch(cooc, n_rows, scratch, dtype=torch.float32):
-    """[n_rows, ld] of `dtype` (float32; int32 for the _i32 calls) on cooc's device: the caller's (at least n_rows rows, unit
-    column stride) or a new one."""
-    N = int(cooc.shape[1])
+def _scratch(device, n_rows, width, scratch, dtype, what, aligned):
+    """[n_rows, ld] of `dtype` on `device`, ld = width rounded up to 4: the caller's (at least n_rows x width, unit column
+    stride; aligned: on a 16-byte aligned base with a row stride that is a multiple of 4, what the float4 loads of the
+    truncated-SVD kernels need) or a new one."""
     if scratch is None:
-        return torch.empty(n_rows, (N + 3) & ~3, dtype=dtype, device=cooc.device)
-    if not scratch.is_cuda or scratch.dtype != dtype or scratch.dim() != 2 or scratch.stride(1) != 1 \
-            or scratch.shape[0] < n_rows or scratch.shape[1] < N:
-        raise TypeError("aaerec: scratch must be a {} GPU matrix of at least [n_rows, n_items] with unit column stride".format(
-            "float32" if dtype == torch.float32 else "int32"))
+        return torch.empty(n_rows, (width + 3) & ~3, dtype=dtype, device=device)
+    if not scratch.is_cuda or scratch.dtype != dtype or scratch.dim() != 2 or scratch.stride(1) != 1 or scratch.shape[0] < n_rows \
+            or scratch.shape[1] < width or (aligned and (scratch.stride(0) % 4 or scratch.data_ptr() % 16)):
+        raise TypeError("aaerec: {} must be a {}{} GPU matrix of at least [n_rows, {}] with unit column stride{}".format(
+            what, "16-byte aligned " if aligned else "", "float32" if dtype == torch.float32 else "int32", width,
+            " and a row stride that is a multiple of 4" if aligned else ""))
     return scratch
 
 
+def _stream_of(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# The two skeletons of every ranking call, a model handle's and the handle-free baselines' alike.  ctx: a context that makes
+# `device` current; lead, mid: the entry point's other arguments as _arg takes them.
+def _list_call(entry, device, ctx, n_rows, k, exclude_known, lead, mid=()):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors - of
+    entry(*lead, k, exclude_known, *mid, idx_out, val_out, stream)."""
+    idx = torch.empty(n_rows, k, dtype=torch.int32, device=device)
+    val = torch.empty(n_rows, k, dtype=torch.float32, device=device)
+    with ctx:
+        _check(entry(*map(_arg, lead), int(k), int(bool(exclude_known)), *map(_arg, mid), _ptr(idx), _ptr(val),
+                     _stream_of(device)))
+    return idx, val
+
+
+def _ranks_call(entry, device, ctx, n_truth, exclude_known, lead, mid=()):
+    """int32 device tensor [n_truth] of entry(*lead, exclude_known, *mid, ranks_out, stream), lead ending in the truth batch;
+    nothing is called where there is no truth entry."""
+    ranks = torch.empty(int(n_truth), dtype=torch.int32, device=device)
+    if n_truth:
+        with ctx:
+            _check(entry(*map(_arg, lead), int(bool(exclude_known)), *map(_arg, mid), _ptr(ranks), _stream_of(device)))
+    return ranks
+
+
 def _cooc_scores(entry, dtype, cooc, csr, row_start, n_rows, rows, out):
-    out = _cooc_scratch(cooc, n_rows, out, dtype)
-    c, b = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows)
+    out = _scratch(cooc.device, n_rows, int(cooc.shape[1]), out, dtype, "scratch", False)
+    c, b = cooc.struct(), _csr_batch(csr, row_start, n_rows, rows)
     with torch.cuda.device(cooc.device):
         _check(getattr(load_library(), entry)(C.byref(c), int(cooc.shape[1]), C.byref(b), _ptr(out), out.stride(0),
-                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
+                                              _stream_of(cooc.device)))
     return out[:n_rows, :cooc.shape[1]]
 
 
 def _cooc_topk(entry, dtype, cooc, csr, row_start, n_rows, k, rows, exclude_known, scratch):
-    scratch = _cooc_scratch(cooc, n_rows, scratch, dtype)
-    idx = torch.empty(n_rows, k, dtype=torch.int32, device=cooc.device)
-    val = torch.empty(n_rows, k, dtype=torch.float32, device=cooc.device)
-    c, b = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows)
-    with torch.cuda.device(cooc.device):
-        _check(getattr(load_library(), entry)(C.byref(c), int(cooc.shape[1]), C.byref(b), int(k), int(bool(exclude_known)),
-                                              _ptr(scratch), scratch.stride(0), _ptr(idx), _ptr(val),
-                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
-    return idx, val
+    n_items = int(cooc.shape[1])
+    scratch = _scratch(cooc.device, n_rows, n_items, scratch, dtype, "scratch", False)
+    lead = (cooc.struct(), n_items, _csr_batch(csr, row_start, n_rows, rows))
+    return _list_call(getattr(load_library(), entry), cooc.device, torch.cuda.device(cooc.device), n_rows, k, exclude_known,
+                      lead, (scratch, scratch.stride(0)))
 
 
 def _cooc_ranks(entry, dtype, cooc, csr, row_start, n_rows, truth_csr, n_truth, rows, exclude_known, scratch):
-    scratch = _cooc_scratch(cooc, n_rows, scratch, dtype)
-    ranks = torch.empty(int(n_truth), dtype=torch.int32, device=cooc.device)
-    if not n_truth:
-        return ranks
-    c, b, t = cooc.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(truth_csr, row_start, n_rows, rows)
-    with torch.cuda.device(cooc.device):
-        _check(getattr(load_library(), entry)(C.byref(c), int(cooc.shape[1]), C.byref(b), C.byref(t), int(bool(exclude_known)),
-                                              _ptr(scratch), scratch.stride(0), _ptr(ranks),
-                                              C.c_void_p(torch.cuda.current_stream(cooc.device).cuda_stream)))
-    return ranks
+    n_items = int(cooc.shape[1])
+    scratch = _scratch(cooc.device, n_rows, n_items, scratch, dtype, "scratch", False)
+    lead = (cooc.struct(), n_items, _csr_batch(csr, row_start, n_rows, rows), _csr_batch(truth_csr, row_start, n_rows, rows))
+    return _ranks_call(getattr(load_library(), entry), cooc.device, torch.cuda.device(cooc.device), n_truth, exclude_known,
+                       lead, (scratch, scratch.stride(0)))
 
 
 def cooc_scores(cooc, csr, row_start, n_rows, rows=None, out=None):
@@ -724,7 +753,7 @@ def spmm_f32(csr, dense, width=None, out=None):
         out = torch.empty(n_rows, (max(width, 1) + 3) & ~3, dtype=torch.float32, device=dev)
     elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_rows:
         raise TypeError("aaerec: out must be a float32 GPU matrix of at least [rows of csr, width] with unit column stride")
-    b = _cooc_batch(csr, 0, n_rows)
+    b = _csr_batch(csr, 0, n_rows)
     with torch.cuda.device(dev):
         _check(load_library().aae_spmm_f32(C.byref(b), _ptr(dense), dense.stride(0), n_cols, width, _ptr(out), out.stride(0),
                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
@@ -754,26 +783,19 @@ class DeviceLowRank:
         return s
 
 
-def _lowrank_scratch(lr, n_rows, width, scratch, what):
-    """[n_rows, ld] float32 on lr's device, ld a multiple of 4 floats: the caller's (at least n_rows x width) or a new one."""
-    if scratch is None:
-        return torch.empty(n_rows, (width + 3) & ~3, dtype=torch.float32, device=lr.device)
-    if not scratch.is_cuda or scratch.dtype != torch.float32 or scratch.dim() != 2 or scratch.stride(1) != 1 \
-            or scratch.shape[0] < n_rows or scratch.shape[1] < width or scratch.stride(0) % 4 or scratch.data_ptr() % 16:
-        raise TypeError("aaerec: %s must be a 16-byte aligned float32 GPU matrix of at least [n_rows, %d] with unit column stride "
-                        "and a row stride that is a multiple of 4" % (what, width))
-    return scratch
+def _lowrank_buffers(lr, n_rows, n_items, scratch, hidden, what="scratch"):
+    return _scratch(lr.device, n_rows, int(n_items), scratch, torch.float32, what, True), \
+        _scratch(lr.device, n_rows, lr.shape[1], hidden, torch.float32, "hidden", True)
 
 
 def lowrank_scores(lr, n_items, csr, row_start, n_rows, rows=None, out=None, hidden=None):
     """float32 device tensor [n_rows, n_items]: (X[rows] Vt) Vt[:n_items]^T for rows [row_start, row_start + n_rows) of the
     DeviceCSR `csr` of feature rows (or the rows named by the int32 device tensor `rows`) (aae_lowrank_scores)."""
-    out = _lowrank_scratch(lr, n_rows, int(n_items), out, "out")
-    hidden = _lowrank_scratch(lr, n_rows, lr.shape[1], hidden, "hidden")
-    v, b = lr.struct(), _cooc_batch(csr, row_start, n_rows, rows)
+    out, hidden = _lowrank_buffers(lr, n_rows, n_items, out, hidden, "out")
+    v, b = lr.struct(), _csr_batch(csr, row_start, n_rows, rows)
     with torch.cuda.device(lr.device):
         _check(load_library().aae_lowrank_scores(C.byref(v), int(n_items), C.byref(b), _ptr(hidden), hidden.stride(0), _ptr(out),
-                                                 out.stride(0), C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream)))
+                                                 out.stride(0), _stream_of(lr.device)))
     return out[:n_rows, :n_items]
 
 
@@ -781,16 +803,10 @@ def lowrank_topk(lr, n_items, csr, items_csr, row_start, n_rows, k, rows=None, e
     """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: predict -> remove_non_missing -> argtopk of
     the truncated-SVD scores of the feature rows `csr`; `items_csr` names the known items of the same rows (ids below
     n_items).  The better score first, the smaller id at equal scores (aae_lowrank_topk)."""
-    scratch = _lowrank_scratch(lr, n_rows, int(n_items), scratch, "scratch")
-    hidden = _lowrank_scratch(lr, n_rows, lr.shape[1], hidden, "hidden")
-    idx = torch.empty(n_rows, k, dtype=torch.int32, device=lr.device)
-    val = torch.empty(n_rows, k, dtype=torch.float32, device=lr.device)
-    v, b, i = lr.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(items_csr, row_start, n_rows, rows)
-    with torch.cuda.device(lr.device):
-        _check(load_library().aae_lowrank_topk(C.byref(v), int(n_items), C.byref(b), C.byref(i), int(k), int(bool(exclude_known)),
-                                               _ptr(hidden), hidden.stride(0), _ptr(scratch), scratch.stride(0), _ptr(idx), _ptr(val),
-                                               C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream)))
-    return idx, val
+    scratch, hidden = _lowrank_buffers(lr, n_rows, n_items, scratch, hidden)
+    lead = (lr.struct(), int(n_items), _csr_batch(csr, row_start, n_rows, rows), _csr_batch(items_csr, row_start, n_rows, rows))
+    return _list_call(load_library().aae_lowrank_topk, lr.device, torch.cuda.device(lr.device), n_rows, k, exclude_known,
+                      lead, (hidden, hidden.stride(0), scratch, scratch.stride(0)))
 
 
 def lowrank_ranks(lr, n_items, csr, items_csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, scratch=None,
@@ -798,18 +814,11 @@ def lowrank_ranks(lr, n_items, csr, items_csr, row_start, n_rows, truth_csr, n_t
     """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with
     the addressing of the input rows; n_truth = their stored entries), CSR order, in lowrank_topk's ordering
     (aae_lowrank_ranks)."""
-    scratch = _lowrank_scratch(lr, n_rows, int(n_items), scratch, "scratch")
-    hidden = _lowrank_scratch(lr, n_rows, lr.shape[1], hidden, "hidden")
-    ranks = torch.empty(int(n_truth), dtype=torch.int32, device=lr.device)
-    if not n_truth:
-        return ranks
-    v, b, i = lr.struct(), _cooc_batch(csr, row_start, n_rows, rows), _cooc_batch(items_csr, row_start, n_rows, rows)
-    t = _cooc_batch(truth_csr, row_start, n_rows, rows)
-    with torch.cuda.device(lr.device):
-        _check(load_library().aae_lowrank_ranks(C.byref(v), int(n_items), C.byref(b), C.byref(i), C.byref(t), int(bool(exclude_known)),
-                                                _ptr(hidden), hidden.stride(0), _ptr(scratch), scratch.stride(0), _ptr(ranks),
-                                                C.c_void_p(torch.cuda.current_stream(lr.device).cuda_stream)))
-    return ranks
+    scratch, hidden = _lowrank_buffers(lr, n_rows, n_items, scratch, hidden)
+    lead = (lr.struct(), int(n_items), _csr_batch(csr, row_start, n_rows, rows), _csr_batch(items_csr, row_start, n_rows, rows),
+            _csr_batch(truth_csr, row_start, n_rows, rows))
+    return _ranks_call(load_library().aae_lowrank_ranks, lr.device, torch.cuda.device(lr.device), n_truth, exclude_known,
+                       lead, (hidden, hidden.stride(0), scratch, scratch.stride(0)))
 
 
 # state_dict key <-> (net, layer)
@@ -1460,10 +1469,13 @@ class HipAAE:
     def rank_max_rows(self, k=10):
         """Rows one predict_topk / decode_topk call may rank (aae_rank_max_rows): far more than max_batch where the fused
         predict -> rank kernels apply, max_batch otherwise."""
-        key = int(k)
+        return self._max_rows(int(k), self.lib.aae_rank_max_rows, int(k))
+
+    def _max_rows(self, key, entry, *args):
+        """A row limit of the handle (one of the *_max_rows entry points), asked once."""
         if key not in self._rank_rows:
             out = C.c_int32()
-            _check(self.lib.aae_rank_max_rows(self.handle, key, C.byref(out)))
+            _check(entry(self.handle, *args, C.byref(out)))
             self._rank_rows[key] = int(out.value)
         return self._rank_rows[key]
 
@@ -1481,36 +1493,46 @@ class HipAAE:
         the fused path's row limit order such items by their LOGIT (saturated sigmoids included), the dense fallback by the
         smaller item id: the k scores are the same either way, the items named may differ exactly where scores tie
         (tests/test_rank_gpu.py::test_saturated_scores_tie_and_both_rank_paths_return_a_valid_top_k)."""
-        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)     # (beyond max_batch: the fused rank path, which has no per-batch lists)
-        idx = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
-        val = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
-        if cond is not None:
-            cond = upload(cond, self.device, torch.float32).contiguous()
-        with self._on_device():
-            _check(self.lib.aae_predict_topk(self.handle, C.byref(b), _ptr(cond), int(k), int(bool(exclude_known)),
-                                             _ptr(idx), _ptr(val), self._stream()))
-        return idx, val
+        return self._topk(self.lib.aae_predict_topk, csr, row_start, n_rows, k, exclude_known, (self._cond_rows(cond),))
+
+    def _cond_rows(self, cond):
+        return None if cond is None else upload(cond, self.device, torch.float32).contiguous()
+
+    def _lead(self, batch, lo, hi, per_row, zc):
+        """The arguments of a ranking entry point from the handle to the batch for rows [lo, hi) of a call: the predict form
+        (handle, batch, the rows of cond / eps) or, with zc, the decode form (handle, the rows of zc, its stride, batch)."""
+        if zc is not None:
+            return (self.handle, zc[lo:hi], zc.shape[1], batch)
+        return (self.handle, batch, *(None if t is None else t[lo:hi] for t in per_row))
+
+    def _topk(self, entry, csr, row_start, n_rows, k, exclude_known, per_row=(), zc=None):
+        """A list call of the handle (per_row, zc: _lead)."""
+        # (beyond max_batch: the fused rank path, which has no per-batch lists)
+        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
+        return _list_call(entry, self.device, self._on_device(), n_rows, k, exclude_known, self._lead(b, 0, n_rows, per_row, zc))
+
+    def _ranks(self, entry, cap, csr, row_start, n_rows, truth_csr, exclude_known, per_row=(), zc=None):
+        """A full-ranking call of the handle over any number of rows, `cap` (the entry's row limit) at a time, every chunk with
+        its rows of per_row / zc (_lead).  A chunk without truth entries builds no batch and calls nothing."""
+        out = []
+        for s0 in range(row_start, row_start + n_rows, cap):
+            n, lo = min(cap, row_start + n_rows - s0), s0 - row_start
+            nnz, tb = self._truth_span(truth_csr, s0, n)
+            lead = ()
+            if nnz:
+                lead = self._lead(self._batch(csr, s0, n, bounded=n <= self.max_batch), lo, lo + n, per_row, zc) + (tb,)
+            out.append(_ranks_call(entry, self.device, self._on_device(), nnz, exclude_known, lead))
+        return torch.cat(out) if len(out) != 1 else out[0]
 
     def decode_topk(self, zc, csr, row_start, k, exclude_known=True):
         """Top-k of decode(zc) for the input rows csr[row_start : row_start + len(zc)] (aae_decode_topk)."""
         zc = zc.detach().to(self.device, torch.float32).contiguous()
-        n_rows = zc.shape[0]
-        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
-        idx = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
-        val = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
-        with self._on_device():
-            _check(self.lib.aae_decode_topk(self.handle, _ptr(zc), zc.shape[1], C.byref(b), int(k), int(bool(exclude_known)),
-                                            _ptr(idx), _ptr(val), self._stream()))
-        return idx, val
+        return self._topk(self.lib.aae_decode_topk, csr, row_start, zc.shape[0], k, exclude_known, zc=zc)
 
     # ---- full ranking: the rank of every held-out item (csrc/rank_full.h) ------------------------
     def rank_full_max_rows(self):
         """Rows one aae_predict_ranks / aae_decode_ranks call may take (aae_rank_full_max_rows)."""
-        if "full" not in self._rank_rows:
-            out = C.c_int32()
-            _check(self.lib.aae_rank_full_max_rows(self.handle, C.byref(out)))
-            self._rank_rows["full"] = int(out.value)
-        return self._rank_rows["full"]
+        return self._max_rows("full", self.lib.aae_rank_full_max_rows)
 
     def _truth_span(self, truth_csr, row_start, n_rows):
         """(entries of truth rows [row_start, row_start + n_rows), the batch naming them); indptr is read on the host once."""
@@ -1528,57 +1550,23 @@ class HipAAE:
         with exclude_known; better score first, equal logits to the smaller id; a truth item that is itself a known item
         ranks behind every rankable one: n_rankable + 1 + #{known ids < it}).  Any number of rows: chunked by
         rank_full_max_rows().  Row i of truth_csr belongs to row i of csr."""
-        if cond is not None:
-            cond = upload(cond, self.device, torch.float32).contiguous()
-        out, chunk = [], self.rank_full_max_rows()
-        for s0 in range(row_start, row_start + n_rows, chunk):
-            n = min(chunk, row_start + n_rows - s0)
-            nnz, tb = self._truth_span(truth_csr, s0, n)
-            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
-            if nnz:
-                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
-                c = None if cond is None else cond[s0 - row_start:s0 - row_start + n]
-                with self._on_device():
-                    _check(self.lib.aae_predict_ranks(self.handle, C.byref(b), _ptr(c), C.byref(tb), int(bool(exclude_known)),
-                                                      _ptr(ranks), self._stream()))
-            out.append(ranks)
-        return torch.cat(out) if len(out) != 1 else out[0]
+        return self._ranks(self.lib.aae_predict_ranks, self.rank_full_max_rows(), csr, row_start, n_rows, truth_csr, exclude_known,
+                           (self._cond_rows(cond),))
 
     def decode_ranks(self, zc, csr, row_start, truth_csr, exclude_known=True):
         """The same for decode(zc): the input rows csr[row_start : row_start + len(zc)] (aae_decode_ranks)."""
         zc = zc.detach().to(self.device, torch.float32).contiguous()
-        n_rows = zc.shape[0]
-        out, chunk = [], self.rank_full_max_rows()
-        for s0 in range(row_start, row_start + n_rows, chunk):
-            n = min(chunk, row_start + n_rows - s0)
-            nnz, tb = self._truth_span(truth_csr, s0, n)
-            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
-            if nnz:
-                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
-                z = zc[s0 - row_start:s0 - row_start + n]
-                with self._on_device():
-                    _check(self.lib.aae_decode_ranks(self.handle, _ptr(z), z.shape[1], C.byref(b), C.byref(tb),
-                                                     int(bool(exclude_known)), _ptr(ranks), self._stream()))
-            out.append(ranks)
-        return torch.cat(out) if len(out) != 1 else out[0]
+        return self._ranks(self.lib.aae_decode_ranks, self.rank_full_max_rows(), csr, row_start, zc.shape[0], truth_csr,
+                           exclude_known, zc=zc)
 
     # ---- the VAE's predict -> rank (aae_vae_predict_topk / ...; csrc/abi_rank.h, the VAE's form) ----------
     def vae_rank_max_rows(self, k=10):
         """Rows one vae_predict_topk / vae_decode_topk call may rank (aae_vae_rank_max_rows)."""
-        key = ("vae", int(k))
-        if key not in self._rank_rows:
-            out = C.c_int32()
-            _check(self.lib.aae_vae_rank_max_rows(self.handle, int(k), C.byref(out)))
-            self._rank_rows[key] = int(out.value)
-        return self._rank_rows[key]
+        return self._max_rows(("vae", int(k)), self.lib.aae_vae_rank_max_rows, int(k))
 
     def vae_rank_full_max_rows(self):
         """Rows one aae_vae_predict_ranks / aae_vae_decode_ranks call may take (aae_vae_rank_full_max_rows)."""
-        if "vae_full" not in self._rank_rows:
-            out = C.c_int32()
-            _check(self.lib.aae_vae_rank_full_max_rows(self.handle, C.byref(out)))
-            self._rank_rows["vae_full"] = int(out.value)
-        return self._rank_rows["vae_full"]
+        return self._max_rows("vae_full", self.lib.aae_vae_rank_full_max_rows)
 
     def _eps_rows(self, eps, n_rows):
         if eps is None:
@@ -1591,67 +1579,25 @@ class HipAAE:
     def vae_predict_topk(self, csr, row_start, n_rows, k, cond=None, eps=None, exclude_known=True):
         """predict_topk of a VAE handle: the scores of vae_predict for the same rows and eps ([n_rows, n_code]; None: the
         device generator), ranked as predict_topk ranks.  n_rows <= vae_rank_max_rows(k)."""
-        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
-        idx = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
-        val = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
-        if cond is not None:
-            cond = upload(cond, self.device, torch.float32).contiguous()
-        eps = self._eps_rows(eps, n_rows)
-        with self._on_device():
-            _check(self.lib.aae_vae_predict_topk(self.handle, C.byref(b), _ptr(cond), _ptr(eps), int(k), int(bool(exclude_known)),
-                                                 _ptr(idx), _ptr(val), self._stream()))
-        return idx, val
+        return self._topk(self.lib.aae_vae_predict_topk, csr, row_start, n_rows, k, exclude_known,
+                          (self._cond_rows(cond), self._eps_rows(eps, n_rows)))
 
     def vae_decode_topk(self, zc, csr, row_start, k, exclude_known=True):
         """Top-k of the VAE's decode(zc) for the input rows csr[row_start : row_start + len(zc)] (aae_vae_decode_topk)."""
         zc = zc.detach().to(self.device, torch.float32).contiguous()
-        n_rows = zc.shape[0]
-        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
-        idx = torch.empty(n_rows, k, dtype=torch.int32, device=self.device)
-        val = torch.empty(n_rows, k, dtype=torch.float32, device=self.device)
-        with self._on_device():
-            _check(self.lib.aae_vae_decode_topk(self.handle, _ptr(zc), zc.shape[1], C.byref(b), int(k), int(bool(exclude_known)),
-                                                _ptr(idx), _ptr(val), self._stream()))
-        return idx, val
+        return self._topk(self.lib.aae_vae_decode_topk, csr, row_start, zc.shape[0], k, exclude_known, zc=zc)
 
     def vae_predict_ranks(self, csr, row_start, n_rows, truth_csr, cond=None, eps=None, exclude_known=True):
         """predict_ranks of a VAE handle (aae_vae_predict_ranks).  Any number of rows: chunked by vae_rank_full_max_rows(),
         every chunk with its rows of cond and eps."""
-        if cond is not None:
-            cond = upload(cond, self.device, torch.float32).contiguous()
-        eps = self._eps_rows(eps, n_rows)
-        out, chunk = [], self.vae_rank_full_max_rows()
-        for s0 in range(row_start, row_start + n_rows, chunk):
-            n = min(chunk, row_start + n_rows - s0)
-            nnz, tb = self._truth_span(truth_csr, s0, n)
-            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
-            if nnz:
-                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
-                c = None if cond is None else cond[s0 - row_start:s0 - row_start + n]
-                e = None if eps is None else eps[s0 - row_start:s0 - row_start + n]
-                with self._on_device():
-                    _check(self.lib.aae_vae_predict_ranks(self.handle, C.byref(b), _ptr(c), _ptr(e), C.byref(tb),
-                                                          int(bool(exclude_known)), _ptr(ranks), self._stream()))
-            out.append(ranks)
-        return torch.cat(out) if len(out) != 1 else out[0]
+        return self._ranks(self.lib.aae_vae_predict_ranks, self.vae_rank_full_max_rows(), csr, row_start, n_rows, truth_csr,
+                           exclude_known, (self._cond_rows(cond), self._eps_rows(eps, n_rows)))
 
     def vae_decode_ranks(self, zc, csr, row_start, truth_csr, exclude_known=True):
         """The same for the VAE's decode(zc) (aae_vae_decode_ranks)."""
         zc = zc.detach().to(self.device, torch.float32).contiguous()
-        n_rows = zc.shape[0]
-        out, chunk = [], self.vae_rank_full_max_rows()
-        for s0 in range(row_start, row_start + n_rows, chunk):
-            n = min(chunk, row_start + n_rows - s0)
-            nnz, tb = self._truth_span(truth_csr, s0, n)
-            ranks = torch.empty(nnz, dtype=torch.int32, device=self.device)
-            if nnz:
-                b = self._batch(csr, s0, n, bounded=n <= self.max_batch)
-                z = zc[s0 - row_start:s0 - row_start + n]
-                with self._on_device():
-                    _check(self.lib.aae_vae_decode_ranks(self.handle, _ptr(z), z.shape[1], C.byref(b), C.byref(tb),
-                                                         int(bool(exclude_known)), _ptr(ranks), self._stream()))
-            out.append(ranks)
-        return torch.cat(out) if len(out) != 1 else out[0]
+        return self._ranks(self.lib.aae_vae_decode_ranks, self.vae_rank_full_max_rows(), csr, row_start, zc.shape[0], truth_csr,
+                           exclude_known, zc=zc)
 
     def encode(self, csr, row_start, n_rows):
         b = self._batch(csr, row_start, n_rows)

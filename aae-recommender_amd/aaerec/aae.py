@@ -27,7 +27,7 @@ import scipy.sparse as sp
 import sklearn  # noqa: F401  (sklearn.utils.shuffle semantics are reproduced with np.random below)
 import torch
 
-from . import _hip
+from . import _hip, ranking
 from .base import Recommender
 from .condition import _check_conditions
 
@@ -625,49 +625,49 @@ class AutoEncoder(AdversarialAutoEncoder):
         return [mask(p1), mask(p2), mask(p1), mask(p2)] + [None] * 8, None
 
 
-def _predict_topk(self, X, k=10, condition_data=None, exclude_known=True):
-    """Top-k recommendations without materialising the [n, N] score matrix on the host: the
-    reference's predict -> remove_non_missing -> argtopk pipeline (aae.py:840-870,
-    evaluation.py:183-199, 20-58) with only [n, k] ids and scaled scores crossing PCIe.
-    Conditions as in predict(): constant concatenation and the device-native CategoricalCondition ride in the fused
-    call, any other plugin imposes itself on the code between aae_encode and aae_decode_topk."""
+def _rank_chunks(self, Xs, condition_data, chunk, fused, decode):
+    """The rows of Xs, `chunk` at a time, through fused(csr, start, n, cond) - constant concatenation and the device-native
+    CategoricalCondition ride in the call, as in predict() - or, behind any other plugin, decode(csr, start, zc): the plugin
+    imposes itself on the code between aae_encode and the decode form of the call."""
     self.eval()
     use_condition = _check_conditions(self.conditions, condition_data)
     if self.conditions:
         self.conditions.eval()
-    fused = (not use_condition) or self._is_constant_concat()
-    native = use_condition and not fused and self._is_device_native()
-    Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+    concat = (not use_condition) or self._is_constant_concat()
+    native = use_condition and not concat and self._is_device_native()
     csr = _hip.DeviceCSR(Xs, self.hip.device)
     self._dp_settle()
     if self._slice is not None:
         self._dp.gather_output_layer()
-    ids, vals = [], []
-    # rows per call: what one fused predict -> rank launch takes (aae_rank_max_rows: hundreds to thousands of rows, the
-    # parameter stream of dec.lin3 is read once per call), the training batch size otherwise
-    chunk = max(self.batch_size, min(self.hip.rank_max_rows(k), 2048))
-    for start in range(0, Xs.shape[0], chunk):
-        n = min(chunk, Xs.shape[0] - start)
+    out = []
+    for start, n in ranking.row_chunks(Xs.shape[0], chunk):
         cond = None
         c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
-        if use_condition and fused:
+        if use_condition and concat:
             cond = torch.cat([_hip.upload(c.encode(x), self.hip.device) for c, x in zip(self.conditions.values(), c_batch)], 1)
         elif native:
             cond = self._native_cond_block(c_batch, n)
-        if fused or native:
-            i, v = self.hip.predict_topk(csr, start, n, k, cond=cond, exclude_known=exclude_known)
+        if concat or native:
+            out.append(fused(csr, start, n, cond))
         else:
             with torch.no_grad():
                 # (aae_encode takes the handle's per-batch buffers: batch_size rows at a time; the ranking is one call)
                 z = torch.cat([self.hip.encode(csr, s0, min(self.batch_size, start + n - s0))
                                for s0 in range(start, start + n, self.batch_size)])
-                i, v = self.hip.decode_topk(self.conditions.encode_impose(z, c_batch), csr, start, k, exclude_known=exclude_known)
-        ids.append(i)
-        vals.append(v)
-    return torch.cat(ids).cpu().numpy(), torch.cat(vals).cpu().numpy()
+                out.append(decode(csr, start, self.conditions.encode_impose(z, c_batch)))
+    return out
 
 
-AdversarialAutoEncoder.predict_topk = _predict_topk
+def _predict_topk(self, X, k=10, condition_data=None, exclude_known=True):
+    """Top-k recommendations without materialising the [n, N] score matrix on the host: the
+    reference's predict -> remove_non_missing -> argtopk pipeline (aae.py:840-870,
+    evaluation.py:183-199, 20-58) with only [n, k] ids and scaled scores crossing PCIe.
+    Conditions as in predict(): see _rank_chunks."""
+    Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+    return ranking.lists(self._rank_chunks(
+        Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.rank_max_rows(k)),
+        lambda csr, start, n, cond: self.hip.predict_topk(csr, start, n, k, cond=cond, exclude_known=exclude_known),
+        lambda csr, start, zc: self.hip.decode_topk(zc, csr, start, k, exclude_known=exclude_known)), k)
 
 
 def _predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
@@ -676,45 +676,17 @@ def _predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
     the int32 1-based ranks of those items among the row's items - predict_topk's ordering (the items of X's row are not
     rankable with exclude_known).  Everything evaluation.METRICS needs follows from them (evaluation.evaluate_ranks); only
     nnz(Y) integers cross PCIe.  Conditions as in predict_topk()."""
-    self.eval()
-    use_condition = _check_conditions(self.conditions, condition_data)
-    if self.conditions:
-        self.conditions.eval()
-    fused = (not use_condition) or self._is_constant_concat()
-    native = use_condition and not fused and self._is_device_native()
     Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
-    Ys = sp.csr_matrix(Y, copy=True) if not sp.issparse(Y) else Y.tocsr(copy=True)
-    if Ys.shape != Xs.shape:
-        raise ValueError("the ground truth has shape {}, the inputs {}".format(Ys.shape, Xs.shape))
-    Ys.sum_duplicates()
-    Ys.sort_indices()
-    csr = _hip.DeviceCSR(Xs, self.hip.device)
+    Ys = ranking.canonical_truth(Y, Xs.shape)
     truth = _hip.DeviceCSR(Ys, self.hip.device)
-    self._dp_settle()
-    if self._slice is not None:
-        self._dp.gather_output_layer()
-    ranks = []
-    chunk = max(self.batch_size, min(self.hip.rank_full_max_rows(), 2048))
-    for start in range(0, Xs.shape[0], chunk):
-        n = min(chunk, Xs.shape[0] - start)
-        cond = None
-        c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
-        if use_condition and fused:
-            cond = torch.cat([_hip.upload(c.encode(x), self.hip.device) for c, x in zip(self.conditions.values(), c_batch)], 1)
-        elif native:
-            cond = self._native_cond_block(c_batch, n)
-        if fused or native:
-            ranks.append(self.hip.predict_ranks(csr, start, n, truth, cond=cond, exclude_known=exclude_known))
-        else:
-            with torch.no_grad():
-                z = torch.cat([self.hip.encode(csr, s0, min(self.batch_size, start + n - s0))
-                               for s0 in range(start, start + n, self.batch_size)])
-                ranks.append(self.hip.decode_ranks(self.conditions.encode_impose(z, c_batch), csr, start, truth,
-                                                   exclude_known=exclude_known))
-    data = torch.cat(ranks).cpu().numpy().astype(np.int32, copy=False) if ranks else np.zeros(0, dtype=np.int32)
-    return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+    return ranking.ranks_csr(self._rank_chunks(
+        Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.rank_full_max_rows()),
+        lambda csr, start, n, cond: self.hip.predict_ranks(csr, start, n, truth, cond=cond, exclude_known=exclude_known),
+        lambda csr, start, zc: self.hip.decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys)
 
 
+AdversarialAutoEncoder._rank_chunks = _rank_chunks
+AdversarialAutoEncoder.predict_topk = _predict_topk
 AdversarialAutoEncoder.predict_ranks = _predict_ranks
 
 
@@ -894,33 +866,26 @@ class DecodingRecommender(Recommender):
         self.conditions.eval()
         out = []
         with torch.no_grad():
-            for start in range(0, X.shape[0], chunk):
-                c_batch = [_take(c, slice(start, min(start + chunk, X.shape[0]))) for c in condition_data]
+            for start, n in ranking.row_chunks(X.shape[0], chunk):
+                c_batch = [_take(c, slice(start, start + n)) for c in condition_data]
                 out.append(call(self._inputs(c_batch), csr, start))
         return out
 
     def predict_topk(self, test_set, k=10):
         """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag: predict -> remove_non_missing ->
         argtopk on the device (aae_decode_topk), only [n, k] crosses PCIe."""
-        chunk = max(self.batch_size, min(self.hip.rank_max_rows(k), 2048))
+        chunk = ranking.chunk_rows(self.batch_size, self.hip.rank_max_rows(k))
         parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_topk(zc, csr, start, k))
-        if not parts:
-            return np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32)
-        return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
+        return ranking.lists(parts, k)
 
     def predict_ranks(self, test_set, y_true):
         """CSR with y_true's (canonical) pattern: the rank of every held-out item in the full ranking of its test bag
         (aae_decode_ranks)."""
-        Ys = sp.csr_matrix(y_true, copy=True) if not sp.issparse(y_true) else y_true.tocsr(copy=True)
-        if Ys.shape != (test_set.size(0), self.hip.N):
-            raise ValueError("the ground truth has shape {}, the test set {}".format(Ys.shape, (test_set.size(0), self.hip.N)))
-        Ys.sum_duplicates()
-        Ys.sort_indices()
+        Ys = ranking.canonical_truth(y_true, (test_set.size(0), self.hip.N), "the test set")
         truth = _hip.DeviceCSR(Ys, self.hip.device)
-        chunk = max(self.batch_size, min(self.hip.rank_full_max_rows(), 2048))
-        ranks = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_ranks(zc, csr, start, truth))
-        data = torch.cat(ranks).cpu().numpy().astype(np.int32, copy=False) if ranks else np.zeros(0, dtype=np.int32)
-        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+        chunk = ranking.chunk_rows(self.batch_size, self.hip.rank_full_max_rows())
+        parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_ranks(zc, csr, start, truth))
+        return ranking.ranks_csr(parts, Ys)
 
 
 def _validate_targets(X):

@@ -33,7 +33,7 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import _hip
+from . import _hip, ranking
 from .base import Recommender
 
 EXACT_FP32 = 1 << 24          # every whole number up to here is an fp32
@@ -150,10 +150,11 @@ def _power_ok(C):
     return int(torch.zeros(C.shape[0], dtype=torch.int64, device=C.device).index_add_(0, rows, sq).max()) < INT32_LIMIT
 
 
-def _order_row(s, known):
-    """Item ids of one row, best first: score descending, the smaller id at equal scores, known items left out."""
-    ids = np.lexsort((np.arange(s.size), -s))
-    return ids[~np.isin(ids, known)] if len(known) else ids
+def _scaled(s, best):
+    """The scaled scores of the items `best` of a row as the device routes form them: fp32 arithmetic throughout."""
+    lo, span = np.float32(s.min()), np.float32(s.max()) - np.float32(s.min())
+    inv = np.float32(1) / span if span > 0 else np.float32(1)
+    return (s[best].astype(np.float32) - lo) * inv
 
 
 _SCRATCH = {"f32": torch.float32, "i32": torch.int32}      # the score type of each device route
@@ -162,7 +163,7 @@ BUILDS = ("auto", "host", "device")
 AUTO_BUILDS_ON_DEVICE = True
 
 
-class Countbased(Recommender):
+class Countbased(ranking.ScratchRanker, Recommender):
     """Item Co-Occurrence.  order: 1 = C = X^T X; n = C <- C^T C repeated n - 1 times.  scratch_bytes: the [rows, items]
     scratch (fp32 or int32) of one device call - the rows of a predict_topk / predict_ranks call are chunked to it.  device: where C
     lives and the ranking runs; None keeps everything on the host.  build: where train() forms C - "host" (scipy), "device"
@@ -272,16 +273,12 @@ class Countbased(Recommender):
         device (device_route), None on the host."""
         return self._route_of(self._inputs(test_set), k)
 
-    def _chunk_rows(self, n_items):
-        return max(1, self.scratch_bytes // (4 * ((n_items + 3) & ~3)))
-
     def _host_rows(self, X):
-        """(row number, its scores float64 [items], its known item ids) over the rows of X, a bounded block at a time."""
-        step = max(1, (64 << 20) // (8 * max(1, X.shape[1])))
-        for r0 in range(0, X.shape[0], step):
-            S = np.asarray((X[r0:r0 + step] @ self.cooccurences).toarray(), dtype=np.float64)
-            for j in range(S.shape[0]):
-                yield r0 + j, S[j], X.indices[X.indptr[r0 + j]:X.indptr[r0 + j + 1]]
+        return ranking.host_rows(X, lambda r0, r1: (X[r0:r1] @ self.cooccurences).toarray())
+
+    def _scratch(self, route, n_items):
+        """The one buffer of a device call on `route`, for _device_chunks."""
+        return lambda rows: {"scratch": torch.empty(rows, (n_items + 3) & ~3, dtype=_SCRATCH[route], device=self._dev.device)}
 
     def predict_topk(self, test_set, k=10):
         """(item ids int32 [n, k], scaled scores float32 [n, k]) of the k best new items per test bag: predict ->
@@ -291,22 +288,12 @@ class Countbased(Recommender):
         if k < 1:
             raise ValueError("k must be positive")
         route = self._route_of(X, k) if n else None
-        if route:
-            topk, dtype = getattr(_hip, "cooc_topk" if route == "f32" else "cooc_topk_i32"), _SCRATCH[route]
-            csr = _hip.DeviceCSR(X, self._dev.device)
-            chunk = self._chunk_rows(n_items)
-            scratch = torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=dtype, device=self._dev.device)
-            parts = [topk(self._dev, csr, s0, min(chunk, n - s0), k, scratch=scratch) for s0 in range(0, n, chunk)]
-            return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
-        ids = np.full((n, k), -1, dtype=np.int32)
-        val = np.zeros((n, k), dtype=np.float32)
-        for r, s, known in self._host_rows(X):
-            best = _order_row(s, known)[:k]
-            lo, span = np.float32(s.min()), np.float32(s.max()) - np.float32(s.min())
-            inv = np.float32(1) / span if span > 0 else np.float32(1)
-            ids[r, :best.size] = best
-            val[r, :best.size] = (s[best].astype(np.float32) - lo) * inv
-        return ids, val
+        if not route:
+            return ranking.host_topk(self._host_rows(X), n, k, _scaled)
+        topk, csr = getattr(_hip, "cooc_topk" if route == "f32" else "cooc_topk_i32"), _hip.DeviceCSR(X, self._dev.device)
+        parts = self._device_chunks(n, n_items, self._scratch(route, n_items),
+                                    lambda s0, rows, **b: topk(self._dev, csr, s0, rows, k, **b))
+        return ranking.lists(parts, k)
 
     def predict_ranks(self, test_set, y_true):
         """CSR of int32 with y_true's (canonical) pattern: the 1-based rank of every held-out item in the full ranking of its
@@ -314,33 +301,12 @@ class Countbased(Recommender):
         the known items by id."""
         X = self._inputs(test_set)
         n, n_items = X.shape
-        Ys = sp.csr_matrix(y_true, copy=True) if not sp.issparse(y_true) else y_true.tocsr(copy=True)
-        if Ys.shape != X.shape:
-            raise ValueError("the ground truth has shape {}, the test set {}".format(Ys.shape, X.shape))
-        Ys.sum_duplicates()
-        Ys.sort_indices()
+        Ys = ranking.canonical_truth(y_true, X.shape, "the test set")
         route = self._route_of(X) if n else None
-        if route:
-            ranks, dtype = getattr(_hip, "cooc_ranks" if route == "f32" else "cooc_ranks_i32"), _SCRATCH[route]
-            csr, truth = _hip.DeviceCSR(X, self._dev.device), _hip.DeviceCSR(Ys, self._dev.device)
-            chunk = self._chunk_rows(n_items)
-            scratch = torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=dtype, device=self._dev.device)
-            parts = []
-            for s0 in range(0, n, chunk):
-                rows = min(chunk, n - s0)
-                nnz = int(Ys.indptr[s0 + rows] - Ys.indptr[s0])
-                parts.append(ranks(self._dev, csr, s0, rows, truth, nnz, scratch=scratch))
-            data = torch.cat(parts).cpu().numpy().astype(np.int32, copy=False)
-        else:
-            data = np.zeros(Ys.nnz, dtype=np.int32)
-            for r, s, known in self._host_rows(X):
-                lo, hi = Ys.indptr[r], Ys.indptr[r + 1]
-                if lo == hi:
-                    continue
-                s = s.copy()
-                s[known] = -np.inf
-                ids = np.arange(n_items)
-                for e in range(lo, hi):
-                    t = Ys.indices[e]
-                    data[e] = 1 + np.count_nonzero((s > s[t]) | ((s == s[t]) & (ids < t)))
-        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+        if not route:
+            return ranking.host_ranks(self._host_rows(X), Ys)
+        ranks = getattr(_hip, "cooc_ranks" if route == "f32" else "cooc_ranks_i32")
+        csr, truth = _hip.DeviceCSR(X, self._dev.device), _hip.DeviceCSR(Ys, self._dev.device)
+        return ranking.ranks_csr(self._device_chunks(
+            n, n_items, self._scratch(route, n_items),
+            lambda s0, rows, **b: ranks(self._dev, csr, s0, rows, truth, int(Ys.indptr[s0 + rows] - Ys.indptr[s0]), **b)), Ys)

@@ -32,9 +32,8 @@ from sklearn.utils import check_random_state
 from sklearn.utils.extmath import svd_flip
 from sklearn.utils.sparsefuncs import mean_variance_axis
 
-from . import _hip
+from . import _hip, ranking
 from .base import Recommender
-from .cooc import _order_row
 from .ub import AutoEncoderMixin
 
 
@@ -45,7 +44,13 @@ def _canonical(M):
     return M
 
 
-class SVDRecommender(Recommender, AutoEncoderMixin):
+def _scaled(s, best):
+    """The scaled scores of the items `best` of a row: float64, rounded to fp32 once (where they are stored)."""
+    span = s.max() - s.min()
+    return (s[best] - s.min()) / (span if span > 0 else 1.0)
+
+
+class SVDRecommender(ranking.ScratchRanker, Recommender, AutoEncoderMixin):
     """SVD baseline, capable of dealing with text.  dims, use_title, tfidf_params and the further keyword arguments
     (TruncatedSVD's) are the reference's.  scratch_bytes: the [rows, items] fp32 scratch of one device call - the rows of a
     predict_topk / predict_ranks call are chunked to it.  device: where Vt lives and the ranking runs; None keeps everything
@@ -259,22 +264,16 @@ class SVDRecommender(Recommender, AutoEncoderMixin):
             raise ValueError("the test set has {} feature columns, the model {}".format(F.shape[1], self.svd.components_.shape[1]))
         return F, _canonical(F[:, :self.n_classes])
 
-    def _chunk_rows(self, n_items):
-        return max(1, self.scratch_bytes // (4 * ((n_items + 3) & ~3)))
-
     def _host_rows(self, F, X):
-        """(row number, its scores float64 [items], its known item ids) over the rows, a bounded block at a time."""
-        step = max(1, (64 << 20) // (8 * max(1, F.shape[1])))
-        for r0 in range(0, F.shape[0], step):
-            S = np.asarray(self.reconstruct(F[r0:r0 + step]), dtype=np.float64)[:, :self.n_classes]
-            for j in range(S.shape[0]):
-                yield r0 + j, S[j], X.indices[X.indptr[r0 + j]:X.indptr[r0 + j + 1]]
+        def scores(r0, r1):
+            return np.asarray(self.reconstruct(F[r0:r1]), dtype=np.float64)[:, :self.n_classes]
+        return ranking.host_rows(X, scores, F.shape[1])
 
-    def _scratch(self, n, n_items):
-        chunk = self._chunk_rows(n_items)
+    def _scratch(self, n_items):
+        """The two buffers of a device call, for _device_chunks."""
         dev, dims = self._dev.device, self._dev.shape[1]
-        return chunk, torch.empty(min(chunk, n), (n_items + 3) & ~3, dtype=torch.float32, device=dev), \
-            torch.empty(min(chunk, n), (dims + 3) & ~3, dtype=torch.float32, device=dev)
+        return lambda rows: {"scratch": torch.empty(rows, (n_items + 3) & ~3, dtype=torch.float32, device=dev),
+                             "hidden": torch.empty(rows, (dims + 3) & ~3, dtype=torch.float32, device=dev)}
 
     def predict_topk(self, test_set, k=10):
         """(item ids int32 [n, k], scaled scores float32 [n, k]) of the k best new items per test bag: predict ->
@@ -283,21 +282,13 @@ class SVDRecommender(Recommender, AutoEncoderMixin):
         n, n_items = X.shape
         if k < 1:
             raise ValueError("k must be positive")
-        if self.on_device(k) and n:
-            lr = self._dev
-            feat, items = _hip.DeviceCSR(F, lr.device), _hip.DeviceCSR(X, lr.device)
-            chunk, scratch, hidden = self._scratch(n, n_items)
-            parts = [_hip.lowrank_topk(lr, n_items, feat, items, s0, min(chunk, n - s0), k, scratch=scratch, hidden=hidden)
-                     for s0 in range(0, n, chunk)]
-            return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
-        ids = np.full((n, k), -1, dtype=np.int32)
-        val = np.zeros((n, k), dtype=np.float32)
-        for r, s, known in self._host_rows(F, X):
-            best = _order_row(s, known)[:k]
-            span = s.max() - s.min()
-            ids[r, :best.size] = best
-            val[r, :best.size] = (s[best] - s.min()) / (span if span > 0 else 1.0)        # (float64, rounded to fp32 once)
-        return ids, val
+        if not (self.on_device(k) and n):
+            return ranking.host_topk(self._host_rows(F, X), n, k, _scaled)
+        lr = self._dev
+        feat, items = _hip.DeviceCSR(F, lr.device), _hip.DeviceCSR(X, lr.device)
+        parts = self._device_chunks(n, n_items, self._scratch(n_items),
+                                    lambda s0, rows, **b: _hip.lowrank_topk(lr, n_items, feat, items, s0, rows, k, **b))
+        return ranking.lists(parts, k)
 
     def predict_ranks(self, test_set, y_true):
         """CSR of int32 with y_true's (canonical) pattern: the 1-based rank of every held-out item in the full ranking of its
@@ -305,31 +296,12 @@ class SVDRecommender(Recommender, AutoEncoderMixin):
         the known items by id."""
         F, X = self._inputs(test_set)
         n, n_items = X.shape
-        Ys = sp.csr_matrix(y_true, copy=True) if not sp.issparse(y_true) else y_true.tocsr(copy=True)
-        if Ys.shape != X.shape:
-            raise ValueError("the ground truth has shape {}, the test set {}".format(Ys.shape, X.shape))
-        Ys.sum_duplicates()
-        Ys.sort_indices()
-        if self.on_device() and n:
-            lr = self._dev
-            feat, items, truth = (_hip.DeviceCSR(M, lr.device) for M in (F, X, Ys))
-            chunk, scratch, hidden = self._scratch(n, n_items)
-            parts = []
-            for s0 in range(0, n, chunk):
-                rows = min(chunk, n - s0)
-                nnz = int(Ys.indptr[s0 + rows] - Ys.indptr[s0])
-                parts.append(_hip.lowrank_ranks(lr, n_items, feat, items, s0, rows, truth, nnz, scratch=scratch, hidden=hidden))
-            data = torch.cat(parts).cpu().numpy().astype(np.int32, copy=False)
-        else:
-            data = np.zeros(Ys.nnz, dtype=np.int32)
-            ids = np.arange(n_items)
-            for r, s, known in self._host_rows(F, X):
-                lo, hi = Ys.indptr[r], Ys.indptr[r + 1]
-                if lo == hi:
-                    continue
-                s = s.copy()
-                s[known] = -np.inf
-                for e in range(lo, hi):
-                    t = Ys.indices[e]
-                    data[e] = 1 + np.count_nonzero((s > s[t]) | ((s == s[t]) & (ids < t)))
-        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+        Ys = ranking.canonical_truth(y_true, X.shape, "the test set")
+        if not (self.on_device() and n):
+            return ranking.host_ranks(self._host_rows(F, X), Ys)
+        lr = self._dev
+        feat, items, truth = (_hip.DeviceCSR(M, lr.device) for M in (F, X, Ys))
+        return ranking.ranks_csr(self._device_chunks(
+            n, n_items, self._scratch(n_items),
+            lambda s0, rows, **b: _hip.lowrank_ranks(lr, n_items, feat, items, s0, rows, truth,
+                                                     int(Ys.indptr[s0 + rows] - Ys.indptr[s0]), **b)), Ys)

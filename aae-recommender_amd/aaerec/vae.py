@@ -18,7 +18,7 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import _hip
+from . import _hip, ranking
 from .aae import TORCH_OPTIMIZERS, AdversarialAutoEncoder, _take, _validate_targets
 from .base import Recommender
 from .condition import _check_conditions
@@ -222,8 +222,7 @@ class VAE:
             eps_all = torch.cat(draws).to(self.device) if draws else None
         out = []
         with torch.no_grad():
-            for start in range(0, n_rows, chunk):
-                n = min(chunk, n_rows - start)
+            for start, n in ranking.row_chunks(n_rows, chunk):
                 eps = None if eps_all is None else eps_all[start:start + n]
                 c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
                 if use_condition and not self._cond_native:
@@ -239,34 +238,23 @@ class VAE:
         """(item ids [n, k], scaled scores [n, k]) of predict -> remove_non_missing -> argtopk (vae.py:229-266,
         evaluation.py:183-199, 20-58) without the [n, N] score matrix: see AdversarialAutoEncoder.predict_topk."""
         Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
-        chunk = max(self.batch_size, min(self.hip.vae_rank_max_rows(k), 2048))
-        parts = self._rank_chunks(
-            Xs, condition_data, chunk,
+        return ranking.lists(self._rank_chunks(
+            Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.vae_rank_max_rows(k)),
             lambda csr, start, n, cond, eps: self.hip.vae_predict_topk(csr, start, n, k, cond=cond, eps=eps,
                                                                        exclude_known=exclude_known),
-            lambda csr, start, zc: self.hip.vae_decode_topk(zc, csr, start, k, exclude_known=exclude_known))
-        if not parts:
-            return np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32)
-        return torch.cat([p[0] for p in parts]).cpu().numpy(), torch.cat([p[1] for p in parts]).cpu().numpy()
+            lambda csr, start, zc: self.hip.vae_decode_topk(zc, csr, start, k, exclude_known=exclude_known)), k)
 
     def predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
         """A scipy CSR with Y's (canonical) pattern whose data are the int32 1-based ranks of the held-out items in the full
         ranking of their rows: see AdversarialAutoEncoder.predict_ranks."""
         Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
-        Ys = sp.csr_matrix(Y, copy=True) if not sp.issparse(Y) else Y.tocsr(copy=True)
-        if Ys.shape != Xs.shape:
-            raise ValueError("the ground truth has shape {}, the inputs {}".format(Ys.shape, Xs.shape))
-        Ys.sum_duplicates()
-        Ys.sort_indices()
+        Ys = ranking.canonical_truth(Y, Xs.shape)
         truth = _hip.DeviceCSR(Ys, self.device)
-        chunk = max(self.batch_size, min(self.hip.vae_rank_full_max_rows(), 2048))
-        ranks = self._rank_chunks(
-            Xs, condition_data, chunk,
+        return ranking.ranks_csr(self._rank_chunks(
+            Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.vae_rank_full_max_rows()),
             lambda csr, start, n, cond, eps: self.hip.vae_predict_ranks(csr, start, n, truth, cond=cond, eps=eps,
                                                                         exclude_known=exclude_known),
-            lambda csr, start, zc: self.hip.vae_decode_ranks(zc, csr, start, truth, exclude_known=exclude_known))
-        data = torch.cat(ranks).cpu().numpy().astype(np.int32, copy=False) if ranks else np.zeros(0, dtype=np.int32)
-        return sp.csr_matrix((data, Ys.indices.copy(), Ys.indptr.copy()), shape=Ys.shape)
+            lambda csr, start, zc: self.hip.vae_decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys)
 
 
 class VAERecommender(Recommender):

@@ -1,5 +1,5 @@
 // Entry points of the item co-occurrence baseline (cooc.h): scores alone, or scores into the caller's scratch followed by the
-// dense ranking kernels of rank_long.h / rank_full.h.  Each call exists for both score types of those kernels (SC: float, and
+// dense ranking calls of abi_rank.h (dense_topk / dense_ranks).  Each call exists for both score types of those kernels (SC: float, and
 // int32_t behind the _i32 names - the same checks, the same launches, the integer members of the three kernels).  Handle-free:
 // every buffer is the caller's, every launch goes to the caller's stream, nothing synchronises.
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
@@ -45,34 +45,23 @@ int cooc_scores(const char* who, const aae_cooc* cooc, int32_t n_items, const aa
 template <class SC>
 int cooc_topk(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, int32_t k, int32_t exclude_known,
               SC* scratch_dev, int64_t scratch_ld, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    const std::string w(who);
     TRY(cooc_check(who, cooc, n_items, batch, scratch_dev, scratch_ld));
-    if (k < 1 || k > kLongKMax || k > n_items) return fail(AAE_EINVAL, w + ": k must be in [1, min(1024, n_items)]");
-    if (!idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, w + ": idx_out_dev / val_out_dev is NULL");
+    TRY(rank_check_k(who, k, n_items));
+    TRY(rank_check_lists(who, idx_out_dev, val_out_dev));
     if (batch->n_rows == 0) return AAE_OK;
-    hipStream_t s = S(stream);
-    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(pick_rank_long_dense<SC>(), dim3(batch->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
-                       rank_view(batch), (int)exclude_known, (int)k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    LAUNCHCHK("rank_long_dense (cooc)");
-    return AAE_OK;
+    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, S(stream)));
+    return dense_topk(scratch_dev, scratch_ld, n_items, rank_view(batch), batch->n_rows, k, exclude_known, idx_out_dev, val_out_dev, S(stream));
 }
 
 template <class SC>
 int cooc_ranks(const char* who, const aae_cooc* cooc, int32_t n_items, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
                SC* scratch_dev, int64_t scratch_ld, int32_t* ranks_out_dev, void* stream) {
-    const std::string w(who);
     TRY(cooc_check(who, cooc, n_items, batch, scratch_dev, scratch_ld));
-    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, w + ": truth pointers are NULL");
-    if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, w + ": truth names another number of rows than batch");
-    if (!ranks_out_dev) return fail(AAE_EINVAL, w + ": ranks_out_dev is NULL");
+    TRY(rank_check_truth(who, batch->n_rows, truth));
+    if (!ranks_out_dev) return fail(AAE_EINVAL, std::string(who) + ": ranks_out_dev is NULL");
     if (batch->n_rows == 0) return AAE_OK;
-    hipStream_t s = S(stream);
-    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(pick_rank_full_dense<SC>(), dim3(batch->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
-                       rank_view(batch), rank_view(truth), 0, (int)exclude_known, reinterpret_cast<int*>(ranks_out_dev));
-    LAUNCHCHK("rank_full_dense (cooc)");
-    return AAE_OK;
+    TRY(cooc_launch(cooc, n_items, batch, scratch_dev, scratch_ld, S(stream)));
+    return dense_ranks(scratch_dev, scratch_ld, n_items, rank_view(batch), rank_view(truth), batch->n_rows, exclude_known, ranks_out_dev, S(stream));
 }
 
 }  // namespace

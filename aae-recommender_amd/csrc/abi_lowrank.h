@@ -1,5 +1,5 @@
 // Entry points of the truncated-SVD baseline (lowrank.h): scores alone, or scores into the caller's scratch followed by the
-// dense ranking kernels of rank_long.h / rank_full.h as they stand.  Handle-free like the cooc calls: every buffer is the
+// dense ranking calls of abi_rank.h (dense_topk / dense_ranks) as they stand.  Handle-free like the cooc calls: every buffer is the
 // caller's, every launch goes to the caller's stream, nothing synchronises.
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
 #pragma once
@@ -94,34 +94,27 @@ int aae_spmm_f32(const aae_batch* rows, const float* dense_dev, int64_t ld, int3
 int aae_lowrank_topk(const aae_lowrank* lowrank, int32_t n_items, const aae_batch* features, const aae_batch* items, int32_t k,
                      int32_t exclude_known, float* hidden_dev, int64_t hidden_ld, float* scratch_dev, int64_t scratch_ld,
                      int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    TRY(lowrank_check("aae_lowrank_topk", lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld));
-    TRY(lowrank_check_items("aae_lowrank_topk", features, items));
-    if (k < 1 || k > kLongKMax || k > n_items) return fail(AAE_EINVAL, "aae_lowrank_topk: k must be in [1, min(1024, n_items)]");
-    if (!idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "aae_lowrank_topk: idx_out_dev / val_out_dev is NULL");
+    const char* who = "aae_lowrank_topk";
+    TRY(lowrank_check(who, lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld));
+    TRY(lowrank_check_items(who, features, items));
+    TRY(rank_check_k(who, k, n_items));
+    TRY(rank_check_lists(who, idx_out_dev, val_out_dev));
     if (features->n_rows == 0) return AAE_OK;
-    hipStream_t s = S(stream);
-    TRY(lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(pick_rank_long_dense<float>(), dim3(items->n_rows), dim3(kLongNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
-                       rank_view(items), (int)exclude_known, (int)k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    LAUNCHCHK("rank_long_dense (lowrank)");
-    return AAE_OK;
+    TRY(lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld, S(stream)));
+    return dense_topk(scratch_dev, scratch_ld, n_items, rank_view(items), items->n_rows, k, exclude_known, idx_out_dev, val_out_dev, S(stream));
 }
 
 int aae_lowrank_ranks(const aae_lowrank* lowrank, int32_t n_items, const aae_batch* features, const aae_batch* items,
                       const aae_batch* truth, int32_t exclude_known, float* hidden_dev, int64_t hidden_ld, float* scratch_dev,
                       int64_t scratch_ld, int32_t* ranks_out_dev, void* stream) {
-    TRY(lowrank_check("aae_lowrank_ranks", lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld));
-    TRY(lowrank_check_items("aae_lowrank_ranks", features, items));
-    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, "aae_lowrank_ranks: truth pointers are NULL");
-    if (truth->n_rows != features->n_rows) return fail(AAE_EINVAL, "aae_lowrank_ranks: truth names another number of rows than the feature batch");
-    if (!ranks_out_dev) return fail(AAE_EINVAL, "aae_lowrank_ranks: ranks_out_dev is NULL");
+    const char* who = "aae_lowrank_ranks";
+    TRY(lowrank_check(who, lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld));
+    TRY(lowrank_check_items(who, features, items));
+    TRY(rank_check_truth(who, features->n_rows, truth));
+    if (!ranks_out_dev) return fail(AAE_EINVAL, std::string(who) + ": ranks_out_dev is NULL");
     if (features->n_rows == 0) return AAE_OK;
-    hipStream_t s = S(stream);
-    TRY(lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld, s));
-    hipLaunchKernelGGL(pick_rank_full_dense<float>(), dim3(items->n_rows), dim3(kFullNT), 0, s, scratch_dev, (int)scratch_ld, (int)n_items,
-                       rank_view(items), rank_view(truth), 0, (int)exclude_known, reinterpret_cast<int*>(ranks_out_dev));
-    LAUNCHCHK("rank_full_dense (lowrank)");
-    return AAE_OK;
+    TRY(lowrank_launch(lowrank, n_items, features, hidden_dev, hidden_ld, scratch_dev, scratch_ld, S(stream)));
+    return dense_ranks(scratch_dev, scratch_ld, n_items, rank_view(items), rank_view(truth), items->n_rows, exclude_known, ranks_out_dev, S(stream));
 }
 
 }  // extern "C"

@@ -65,10 +65,6 @@ int aae_predict(aae_handle m, const aae_batch* batch, const float* cond_dev, flo
 // items per row (ids and min-max-scaled scores) leave the GPU
 }  // extern "C"
 namespace {
-int check_topk_k(const aae_model* m, int k) {
-    if (k < 1 || k > kLongKMax || k > m->N) return fail(AAE_EINVAL, "k must be in [1, min(1024, n_items)]");
-    return AAE_OK;
-}
 // the [rows][N] scores in the scratch -> [rows][k]: register lists up to k = 32 (kernels.h), the long-list kernel beyond
 int topk_from_scores(aae_model* m, int k, int exclude_known, int32_t* idx_out_dev, float* val_out_dev, hipStream_t s) {
     if (rank_long(k)) return rank_long_dense(m, k, exclude_known, idx_out_dev, val_out_dev, s);
@@ -84,36 +80,68 @@ int topk_from_scores(aae_model* m, int k, int exclude_known, int32_t* idx_out_de
     LAUNCHCHK("topk_rows");
     return AAE_OK;
 }
+// the dense form's scores: rows of `batch` (<= max_batch) into the [max_batch][n_items] scratch
+int aae_scores_to_scratch(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* zc_dev, int64_t zc_ld, void* stream) {
+    if (!zc_dev) return aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream);
+    TRY(set_batch(m, batch));
+    return aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream);
+}
+// The four ranking calls of an AAE / AE handle.  zc_dev != NULL: the decode form - a caller-built decoder input (code |
+// imposed conditions of any plugin kind), the second half of predict (aae.py:855-866); `batch` names the input rows whose
+// items are excluded and cond_dev is not read.
+int aae_topk(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* zc_dev, int64_t zc_ld, int k, int exclude_known,
+             int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    hipStream_t s = S(stream);
+    if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {   // fused: no [rows][N] matrix (abi_rank.h)
+        m->phase = 0;
+        if (zc_dev) TRY(rank_decode(m, zc_dev, zc_ld, batch, k, exclude_known, idx_out_dev, val_out_dev, s));
+        else TRY(rank_predict(m, batch, cond_dev, k, exclude_known, idx_out_dev, val_out_dev, s));
+        if (!rank_long(k)) return AAE_OK;
+        std::vector<std::pair<int, int>> spans;        // rows whose collect list overflowed: through the score matrix
+        TRY(rank_long_overflow(m, batch, k, s, spans));
+        for (const auto& sp : spans) {
+            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
+            const size_t r0 = (size_t)sp.first;
+            TRY(aae_scores_to_scratch(m, &sub, cond_dev ? cond_dev + r0 * m->cfg.cond_inc : nullptr, zc_dev ? zc_dev + r0 * zc_ld : nullptr,
+                                      zc_ld, stream));
+            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + r0 * k, val_out_dev + r0 * k, s));
+        }
+        return AAE_OK;
+    }
+    TRY(aae_scores_to_scratch(m, batch, cond_dev, zc_dev, zc_ld, stream));
+    TRY(topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s));
+    m->phase = 0;
+    return AAE_OK;
+}
+// ... the rank of every held-out item in the full ranking of its row (rank_full.h)
+int aae_ranks(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* zc_dev, int64_t zc_ld, const aae_batch* truth,
+              int exclude_known, int32_t* ranks_out_dev, void* stream) {
+    hipStream_t s = S(stream);
+    if (batch->n_rows >= 1 && batch->n_rows <= rank_full_rows_cap(m)) {     // fused: no [rows][N] matrix (abi_rank.h)
+        m->phase = 0;
+        if (zc_dev) return rank_full_decode(m, zc_dev, zc_ld, batch, truth, exclude_known, ranks_out_dev, s);
+        return rank_full_predict(m, batch, cond_dev, truth, exclude_known, ranks_out_dev, s);
+    }
+    TRY(aae_scores_to_scratch(m, batch, cond_dev, zc_dev, zc_ld, stream));
+    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), exclude_known, ranks_out_dev, s));
+    m->phase = 0;
+    return AAE_OK;
+}
 }  // namespace
 extern "C" {
 
 int aae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev, int32_t k, int32_t exclude_known,
                      int32_t* idx_out_dev, float* val_out_dev, void* stream) {
     if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(check_topk_k(m, k));
+    TRY(rank_check_k("aae_predict_topk", k, m->N));
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     TRY(rank_check_batch(batch));
-    hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {   // fused: no [rows][N] matrix (abi_rank.h)
-        m->phase = 0;
-        TRY(rank_predict(m, batch, cond_dev, k, exclude_known, idx_out_dev, val_out_dev, s));
-        if (!rank_long(k)) return AAE_OK;
-        std::vector<std::pair<int, int>> spans;        // rows whose collect list overflowed: through the score matrix
-        TRY(rank_long_overflow(m, batch, k, s, spans));
-        for (const auto& sp : spans) {
-            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
-            TRY(aae_predict(m, &sub, cond_dev ? cond_dev + (size_t)sp.first * m->cfg.cond_inc : nullptr, m->G.p, m->ldn, stream));
-            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + (size_t)sp.first * k, val_out_dev + (size_t)sp.first * k, s));
-        }
-        return AAE_OK;
-    }
-    TRY(aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream));      // scores into the [rows][N] scratch
-    return topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s);
+    return aae_topk(m, batch, cond_dev, nullptr, 0, k, exclude_known, idx_out_dev, val_out_dev, stream);
 }
 
 int aae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
     if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
-    TRY(check_topk_k(m, k));
+    TRY(rank_check_k("aae_rank_max_rows", k, m->N));
     *rows_out = std::max(m->R, rank_rows_cap(m, k));
     return AAE_OK;
 }
@@ -124,37 +152,15 @@ int aae_rank_long_stats(aae_handle m, int64_t out[5]) {
     return AAE_OK;
 }
 
-// the same for a caller-built decoder input (code | imposed conditions of any plugin kind): the second half of predict
-// (aae.py:855-866) + remove_non_missing / argtopk; `batch` names the input rows whose items are excluded
 int aae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k,
                     int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
     if (!m || !zc_dev || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(check_topk_k(m, k));
+    TRY(rank_check_k("aae_decode_topk", k, m->N));
     if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
     TRY(rank_check_batch(batch));
-    hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {
-        m->phase = 0;
-        TRY(rank_decode(m, zc_dev, zc_ld, batch, k, exclude_known, idx_out_dev, val_out_dev, s));
-        if (!rank_long(k)) return AAE_OK;
-        std::vector<std::pair<int, int>> spans;
-        TRY(rank_long_overflow(m, batch, k, s, spans));
-        for (const auto& sp : spans) {
-            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
-            TRY(set_batch(m, &sub));
-            TRY(aae_decode(m, zc_dev + (size_t)sp.first * zc_ld, zc_ld, m->rows, m->G.p, m->ldn, stream));
-            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + (size_t)sp.first * k, val_out_dev + (size_t)sp.first * k, s));
-        }
-        return AAE_OK;
-    }
-    TRY(set_batch(m, batch));
-    TRY(aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream));   // scores into the [rows][N] scratch
-    TRY(topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s));
-    m->phase = 0;
-    return AAE_OK;
+    return aae_topk(m, batch, nullptr, zc_dev, zc_ld, k, exclude_known, idx_out_dev, val_out_dev, stream);
 }
 
-// ---- the rank of every held-out item in the full ranking of its row (rank_full.h) ------------------------------------
 int aae_rank_full_max_rows(aae_handle m, int32_t* rows_out) {
     if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
     *rows_out = std::max(m->R, rank_full_rows_cap(m));
@@ -166,14 +172,9 @@ int aae_predict_ranks(aae_handle m, const aae_batch* batch, const float* cond_de
     if (!m || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     TRY(rank_check_batch(batch));
-    TRY(rank_check_truth(batch, truth));
-    hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_full_rows_cap(m)) {     // fused: no [rows][N] matrix (abi_rank.h)
-        m->phase = 0;
-        return rank_full_predict(m, batch, cond_dev, truth, exclude_known, ranks_out_dev, s);
-    }
-    TRY(aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream));           // scores into the [rows][N] scratch
-    return rank_full_dense(m, rank_view(batch), rank_view(truth), 0, exclude_known, ranks_out_dev, s);
+    TRY(rank_check_truth("aae_predict_ranks", batch->n_rows, truth));
+    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_predict_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
+    return aae_ranks(m, batch, cond_dev, nullptr, 0, truth, exclude_known, ranks_out_dev, stream);
 }
 
 int aae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
@@ -181,17 +182,9 @@ int aae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae
     if (!m || !zc_dev || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
     if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
     TRY(rank_check_batch(batch));
-    TRY(rank_check_truth(batch, truth));
-    hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_full_rows_cap(m)) {
-        m->phase = 0;
-        return rank_full_decode(m, zc_dev, zc_ld, batch, truth, exclude_known, ranks_out_dev, s);
-    }
-    TRY(set_batch(m, batch));
-    TRY(aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream));     // scores into the [rows][N] scratch
-    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), 0, exclude_known, ranks_out_dev, s));
-    m->phase = 0;
-    return AAE_OK;
+    TRY(rank_check_truth("aae_decode_ranks", batch->n_rows, truth));
+    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_decode_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
+    return aae_ranks(m, batch, nullptr, zc_dev, zc_ld, truth, exclude_known, ranks_out_dev, stream);
 }
 
 }  // extern "C"
@@ -256,7 +249,7 @@ int vae_ranks(aae_model* m, const aae_batch* batch, const float* cond_dev, const
         return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out_dev, s);
     }
     TRY(vae_scores_to_scratch(m, batch, cond_dev, eps_dev, zc_dev, zc_ld, stream));
-    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), 0, exclude_known, ranks_out_dev, s));
+    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), exclude_known, ranks_out_dev, s));
     m->phase = 0;
     return AAE_OK;
 }
@@ -267,7 +260,7 @@ int aae_vae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond
                          int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
     if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
     TRY(vae_rank_check(m, cond_dev, eps_dev, false));
-    TRY(check_topk_k(m, k));
+    TRY(rank_check_k("aae_vae_predict_topk", k, m->N));
     TRY(rank_check_batch(batch));
     return vae_topk(m, batch, cond_dev, eps_dev, nullptr, 0, k, exclude_known, idx_out_dev, val_out_dev, stream);
 }
@@ -276,7 +269,7 @@ int aae_vae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const 
                         int32_t* idx_out_dev, float* val_out_dev, void* stream) {
     if (!m || !zc_dev || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
     TRY(vae_rank_check(m, nullptr, nullptr, true));
-    TRY(check_topk_k(m, k));
+    TRY(rank_check_k("aae_vae_decode_topk", k, m->N));
     if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
     TRY(rank_check_batch(batch));
     return vae_topk(m, batch, nullptr, nullptr, zc_dev, zc_ld, k, exclude_known, idx_out_dev, val_out_dev, stream);
@@ -287,7 +280,8 @@ int aae_vae_predict_ranks(aae_handle m, const aae_batch* batch, const float* con
     if (!m || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
     TRY(vae_rank_check(m, cond_dev, eps_dev, false));
     TRY(rank_check_batch(batch));
-    TRY(rank_check_truth(batch, truth));
+    TRY(rank_check_truth("aae_vae_predict_ranks", batch->n_rows, truth));
+    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_vae_predict_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
     return vae_ranks(m, batch, cond_dev, eps_dev, nullptr, 0, truth, exclude_known, ranks_out_dev, stream);
 }
 
@@ -297,14 +291,15 @@ int aae_vae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const
     TRY(vae_rank_check(m, nullptr, nullptr, true));
     if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
     TRY(rank_check_batch(batch));
-    TRY(rank_check_truth(batch, truth));
+    TRY(rank_check_truth("aae_vae_decode_ranks", batch->n_rows, truth));
+    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_vae_decode_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
     return vae_ranks(m, batch, nullptr, nullptr, zc_dev, zc_ld, truth, exclude_known, ranks_out_dev, stream);
 }
 
 int aae_vae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
     if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
     TRY(vae_rank_check(m, nullptr, nullptr, true));
-    TRY(check_topk_k(m, k));
+    TRY(rank_check_k("aae_vae_rank_max_rows", k, m->N));
     *rows_out = std::max(m->R, vae_rank_rows_cap(m, k));
     return AAE_OK;
 }

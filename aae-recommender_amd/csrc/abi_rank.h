@@ -177,14 +177,31 @@ int rank_full_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, con
     return AAE_OK;
 }
 
-// the dense form: rows [row0, row0 + m->rows) of the call, their scores in the [max_batch][n_items] scratch
-int rank_full_dense(aae_model* m, const BatchView& bv, const BatchView& tv, int row0, int exclude_known, int32_t* ranks_out,
-                    hipStream_t s) {
-    ProfScope ps(m, AAE_K_RANK, s);
-    hipLaunchKernelGGL(pick_rank_full_dense<float>(), dim3(m->rows), dim3(kFullNT), 0, s, m->G.p, m->ldn, m->N, bv, tv, row0, exclude_known,
-                       reinterpret_cast<int*>(ranks_out));
+// ---- the dense form, written once: a [rows][ld] score matrix of fp32 or int32 -> lists / ranks -----------------------------
+// The only launches of rank_long_dense_kernel / rank_full_dense_kernel: behind the model's calls (below) and the handle-free
+// baselines (abi_cooc.h, abi_lowrank.h).  known: the rows' known items (masked in place when exclude_known); truth: the rows'
+// held-out items.  The scores are overwritten where a known item is masked.
+template <class SC>
+int dense_topk(SC* scores, int64_t ld, int n_items, const BatchView& known, int rows, int k, int exclude_known, int32_t* idx_out,
+               float* val_out, hipStream_t s) {
+    hipLaunchKernelGGL(pick_rank_long_dense<SC>(), dim3(rows), dim3(kLongNT), 0, s, scores, (int)ld, n_items, known, exclude_known, k,
+                       reinterpret_cast<int*>(idx_out), val_out);
+    LAUNCHCHK("rank_long_dense");
+    return AAE_OK;
+}
+template <class SC>
+int dense_ranks(SC* scores, int64_t ld, int n_items, const BatchView& known, const BatchView& truth, int rows, int exclude_known,
+                int32_t* ranks_out, hipStream_t s) {
+    hipLaunchKernelGGL(pick_rank_full_dense<SC>(), dim3(rows), dim3(kFullNT), 0, s, scores, (int)ld, n_items, known, truth, 0,
+                       exclude_known, reinterpret_cast<int*>(ranks_out));
     LAUNCHCHK("rank_full_dense");
     return AAE_OK;
+}
+
+// the model's dense form: the m->rows rows of the call, their scores in the [max_batch][n_items] scratch
+int rank_full_dense(aae_model* m, const BatchView& bv, const BatchView& tv, int exclude_known, int32_t* ranks_out, hipStream_t s) {
+    ProfScope ps(m, AAE_K_RANK, s);
+    return dense_ranks(m->G.p, m->ldn, m->N, bv, tv, m->rows, exclude_known, ranks_out, s);
 }
 
 // the decoder's hidden layers of a chain program whose slot `src` holds [z | condition head] (and slot 5 the rest of a wide
@@ -293,10 +310,7 @@ int rank_full_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae
 // k > 32, the dense form: [rows][ldn] scores in the scratch -> [rows][k]
 int rank_long_dense(aae_model* m, int k, int exclude_known, int32_t* idx_out, float* val_out, hipStream_t s) {
     ProfScope ps(m, AAE_K_RANK, s);
-    hipLaunchKernelGGL(pick_rank_long_dense<float>(), dim3(m->rows), dim3(kLongNT), 0, s, m->G.p, m->ldn, m->N, m->bv, exclude_known, k,
-                       reinterpret_cast<int*>(idx_out), val_out);
-    LAUNCHCHK("rank_long_dense");
-    return AAE_OK;
+    return dense_topk(m->G.p, m->ldn, m->N, m->bv, m->rows, k, exclude_known, idx_out, val_out, s);
 }
 
 // After a fused k > 32 call: the rows' entry counts (synchronises `s`), the handle's statistics, and the spans of at most
@@ -330,16 +344,24 @@ aae_batch rank_sub_batch(const aae_model* m, const aae_batch* b, int off, int n)
     return c;
 }
 
+// ---- argument checks of every ranking entry point, the handle-free ones included: `who` (the entry point) opens the message ----
 int rank_check_batch(const aae_batch* b) {
     if (!b || !b->indptr_dev || !b->indices_dev || !b->values_dev) return fail(AAE_EINVAL, "batch pointers are NULL");
     return AAE_OK;
 }
-
-// the ground truth of a full-ranking call: the rows of `batch`, one for one (its values are not read)
-int rank_check_truth(const aae_batch* batch, const aae_batch* truth) {
-    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, "truth pointers are NULL");
-    if (truth->n_rows != batch->n_rows) return fail(AAE_EINVAL, "truth names another number of rows than batch");
-    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "truth needs max_row_nnz: the entries of its longest row (an upper bound)");
+int rank_check_k(const char* who, int k, int n_items) {
+    if (k < 1 || k > kLongKMax || k > n_items) return fail(AAE_EINVAL, std::string(who) + ": k must be in [1, min(1024, n_items)]");
+    return AAE_OK;
+}
+int rank_check_lists(const char* who, const int32_t* idx_out_dev, const float* val_out_dev) {
+    if (!idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, std::string(who) + ": idx_out_dev / val_out_dev is NULL");
+    return AAE_OK;
+}
+// the ground truth of a full-ranking call: the `n_rows` rows of the call, one for one (its values are not read)
+int rank_check_truth(const char* who, int n_rows, const aae_batch* truth) {
+    const std::string w(who);
+    if (!truth || !truth->indptr_dev || !truth->indices_dev) return fail(AAE_EINVAL, w + ": truth pointers are NULL");
+    if (truth->n_rows != n_rows) return fail(AAE_EINVAL, w + ": truth names another number of rows than the call's input rows");
     return AAE_OK;
 }
 

@@ -413,9 +413,9 @@ def test_i32_calls_refuse_bad_arguments_with_einval(small):
     from aaerec import _hip
     lib = _hip.load_library()
     n = 4
-    c, b = small["C"].struct(), _hip._cooc_batch(small["csr"], 0, n)
+    c, b = small["C"].struct(), _hip._csr_batch(small["csr"], 0, n)
     tcsr = _hip.DeviceCSR(small["Y"], DEV)
-    t = _hip._cooc_batch(tcsr, 0, n)
+    t = _hip._csr_batch(tcsr, 0, n)
     scratch = torch.zeros(n, N_SMALL, dtype=torch.int32, device=DEV)
     idx = torch.full((n, 10), -5, dtype=torch.int32, device=DEV)
     val = torch.zeros(n, 10, dtype=torch.float32, device=DEV)

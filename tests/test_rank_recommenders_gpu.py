@@ -141,3 +141,29 @@ def test_evaluation_ranks_the_recommender_on_the_device(kind):
         setattr(rec2, method, lambda *a, **kw: took.append(1) or real2(*a, **kw))
         ev_dense([rec2])
         assert not took
+
+
+class _NoRows:
+    """A test set without rows over n_items items (what AAERecommender reads of one: tocsr())."""
+
+    def __init__(self, n_items):
+        self._X = sp.csr_matrix((0, n_items), dtype=np.float32)
+
+    def tocsr(self):
+        return self._X
+
+
+@pytest.mark.parametrize("adversarial", [True, False])
+def test_a_test_set_without_rows_gives_empty_lists_and_ranks(adversarial):
+    """predict_topk of a test set without rows returns [0, k] arrays, as the other four recommenders do (it used to raise:
+    torch.cat of no parts), and predict_ranks the empty CSR."""
+    from aaerec.aae import AAERecommender
+    train_set = _bags().build_vocab(apply=True)
+    rec = AAERecommender(adversarial=adversarial, n_hidden=40, n_code=16, n_epochs=1, batch_size=50, verbose=False, seed=11)
+    rec.train(train_set)
+    n_items = train_set.size(1)
+    ids, val = rec.predict_topk(_NoRows(n_items), k=10)
+    assert ids.shape == (0, 10) and ids.dtype == np.int32
+    assert val.shape == (0, 10) and val.dtype == np.float32
+    ranks = rec.predict_ranks(_NoRows(n_items), sp.csr_matrix((0, n_items)))
+    assert sp.issparse(ranks) and ranks.shape == (0, n_items) and ranks.nnz == 0 and ranks.dtype == np.int32
