@@ -197,6 +197,11 @@ _PROTOS = {
     "aae_csr_transpose_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "aae_csr_transpose_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "aae_mi_i32_marginals": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "aae_mi_i32_rows": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "aae_mi_i32_finish": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_spmm_f32": (C.c_int, [C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_lowrank_scores": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
@@ -736,6 +741,33 @@ def cooc_transpose(cooc):
     """The transpose of a DeviceCooc as a DeviceCooc: csr_transpose for the int32 operands of spgemm_i32."""
     indptr, indices, values, _ = _transpose_arrays(cooc.indptr, cooc.indices, cooc.values, cooc.shape, cooc.device)
     return DeviceCooc.from_device(indptr, indices, values, (cooc.shape[1], cooc.shape[0]), cooc.device)
+
+
+# ---- mutual information of an unstored contingency table (aae_mi_i32_*; csrc/mutinfo.h) -----------------------------
+def mutual_info_i32(A, B):
+    """(mi, T, row_s1, row_pi) of the contingency table C = A . B, which is never stored: mi a float (base e, scikit-learn's
+    mutual_info_score(contingency=C)), T = sum C an int, row_s1 [rows of A] float64 and row_pi [rows of A] int64 device tensors
+    (S1_i = sum_j c_ij (ln c_ij - ln pj_j), pi_i = sum_j c_ij).  A = X^T, B = Y: DeviceCooc (int32 CSR in HBM, canonical,
+    strictly positive values, every c_ij below 2^31 and T below 2^53 - the caller's guarantee, aaerec.utils.device_mi_ok).
+    The same bits every run.  One host read: the 16 bytes of (mi, T).  Operands without an entry launch nothing."""
+    a, b, stream = _spgemm_operands(A, B)
+    m, p, n, dev = int(A.shape[0]), int(B.shape[0]), int(B.shape[1]), A.device
+    row_s1 = torch.zeros(m, dtype=torch.float64, device=dev)
+    row_pi = torch.zeros(m, dtype=torch.int64, device=dev)
+    if m == 0 or p == 0 or n == 0 or A.nnz == 0 or B.nnz == 0:
+        return 0.0, 0, row_s1, row_pi
+    lib = load_library()
+    u = torch.empty(m, dtype=torch.int64, device=dev)
+    ints = torch.empty(p + n, dtype=torch.int64, device=dev)                    # a [p], pj [n]
+    lnpj = torch.empty(n, dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.int64, device=dev)                         # the bits of (double mi, int64 T)
+    with torch.cuda.device(dev):
+        _check(lib.aae_spgemm_i32_bound(C.byref(a), C.byref(b), p, _ptr(u), stream))
+        _check(lib.aae_mi_i32_marginals(C.byref(a), C.byref(b), p, n, _ptr(ints), _ptr(ints[p:]), _ptr(lnpj), stream))
+        _check(lib.aae_mi_i32_rows(C.byref(a), C.byref(b), n, _ptr(u), _ptr(lnpj), _ptr(row_s1), _ptr(row_pi), stream))
+        _check(lib.aae_mi_i32_finish(m, _ptr(row_s1), _ptr(row_pi), _ptr(out), stream))
+        host = out.cpu().numpy()
+    return float(host[:1].view(np.float64)[0]), int(host[1]), row_s1, row_pi
 
 
 def spmm_f32(csr, dense, width=None, out=None):

@@ -37,6 +37,7 @@
 #include "cooc.h"
 #include "spgemm.h"
 #include "sptrans.h"
+#include "mutinfo.h"
 #include "lowrank.h"
 #include "chain.h"
 #include "chain4.h"
@@ -474,6 +475,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_cooc.h"
 #include "abi_spgemm.h"
 #include "abi_sptrans.h"
+#include "abi_mutinfo.h"
 #include "abi_lowrank.h"
 #include "abi_data_parallel.h"
 

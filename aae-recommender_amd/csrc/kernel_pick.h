@@ -165,6 +165,15 @@ inline SptransKernel pick_sptrans_count() { return sptrans_count_kernel; }
 inline SptransKernel pick_sptrans_scatter() { return sptrans_scatter_kernel; }
 inline SptransKernel pick_sptrans_sort() { return sptrans_sort_kernel; }
 
+// ---- mutinfo.h: the three marginal kernels, the row kernel of each spgemm path, the finish.  Static LDS: no limit to raise
+using MiRowKernel = void (*)(MiRowArgs);
+inline auto pick_mi_colsum() { return mi_colsum_kernel; }
+inline auto pick_mi_pj() { return mi_pj_kernel; }
+inline auto pick_mi_lnpj() { return mi_lnpj_kernel; }
+inline MiRowKernel pick_mi_hash() { return mi_hash_kernel; }
+inline MiRowKernel pick_mi_tile() { return mi_tile_kernel; }
+inline auto pick_mi_finish() { return mi_finish_kernel; }
+
 // ---- lowrank.h: the CSR x row-major-dense product - the projection of the ranking calls and aae_spmm_f32 alike
 using SpmmKernel = void (*)(LowRankView, BatchView, float*, long long);
 inline SpmmKernel pick_lowrank_project() { return lowrank_project_kernel; }

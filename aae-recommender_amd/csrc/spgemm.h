@@ -75,49 +75,50 @@ __global__ __launch_bounds__(256) void spgemm_bound_kernel(CoocView A, CoocView 
     if (lane == 0) u[row] = sum;
 }
 
-template <bool FILL>
-__global__ __launch_bounds__(kSpgemmHashNT) void spgemm_hash_kernel(SpgemmArgs g) {
-    __shared__ int keys[kSpgemmHashCap];
-    __shared__ int vals[kSpgemmHashCap];
-    __shared__ int inserted;
-    const int tid = threadIdx.x, row = blockIdx.x;
-    const int64_t u = g.u[row];
-    if (u > kSpgemmHashProducts) return;                                    // the tile kernel's row
+// The accumulation phases of the two paths as device functions: the product kernels below and the row kernels of mutinfo.h
+// (which reduce a row where these store it) run the same code.
+//
+// Hash path: cap = the slots row `row` uses (0: the row is the tile kernel's).  Initialises them, inserts every product of the
+// row; returns this thread's count of fresh inserts.  No barrier behind the inserts: the caller's.
+__device__ __forceinline__ int spgemm_hash_cap(int64_t u) {
+    if (u > kSpgemmHashProducts) return 0;
     int cap = 64;
     while (cap < 2 * u) cap <<= 1;
-    const int mask = cap - 1;
+    return cap;
+}
+template <bool FILL>
+__device__ __forceinline__ int spgemm_hash_accumulate(const CoocView& A, const CoocView& B, int p, int n, int row, int cap,
+                                                      int* keys, int* vals) {
+    const int tid = threadIdx.x, mask = cap - 1;
     for (int j = tid; j < cap; j += kSpgemmHashNT) { keys[j] = -1; if (FILL) vals[j] = 0; }
-    if (tid == 0) inserted = 0;
     __syncthreads();
     const int grp = tid / kSpgemmGroup, gl = tid % kSpgemmGroup;
     int fresh = 0;
-    for (int64_t e = g.A.indptr[row] + grp, ehi = g.A.indptr[row + 1]; e < ehi; e += kSpgemmHashNT / kSpgemmGroup) {
-        const int d = g.A.indices[e];
-        if (d < 0 || d >= g.p) continue;
-        const int a = g.A.values[e];
-        for (int64_t q = g.B.indptr[d] + gl, qhi = g.B.indptr[d + 1]; q < qhi; q += kSpgemmGroup) {
-            const int c = g.B.indices[q];
-            if (c < 0 || c >= g.n) continue;
+    for (int64_t e = A.indptr[row] + grp, ehi = A.indptr[row + 1]; e < ehi; e += kSpgemmHashNT / kSpgemmGroup) {
+        const int d = A.indices[e];
+        if (d < 0 || d >= p) continue;
+        const int a = A.values[e];
+        for (int64_t q = B.indptr[d] + gl, qhi = B.indptr[d + 1]; q < qhi; q += kSpgemmGroup) {
+            const int c = B.indices[q];
+            if (c < 0 || c >= n) continue;
             int h = c & mask;
             for (int probe = 0; probe < cap; ++probe) {                     // (load <= 1/2: an empty slot comes long before cap)
                 const int prev = atomicCAS(&keys[h], -1, c);
                 if (prev == -1 || prev == c) {
                     fresh += prev == -1;
-                    if (FILL) atomicAdd(&vals[h], a * g.B.values[q]);
+                    if (FILL) atomicAdd(&vals[h], a * B.values[q]);
                     break;
                 }
                 h = (h + 1) & mask;
             }
         }
     }
-    if (!FILL) {
-        if (fresh) atomicAdd(&inserted, fresh);
-        __syncthreads();
-        if (tid == 0) g.row_nnz[row] = inserted;
-        return;
-    }
-    __syncthreads();
-    // bitonic over the cap slots in use, keys as unsigned: the occupied slots come first, ascending; empty ones (~0u) last
+    return fresh;
+}
+// bitonic over the cap slots in use, keys as unsigned: the occupied slots come first, ascending; empty ones (~0u) last.  The
+// caller's barrier stands between the last insert and this; a barrier closes every stage, the last one included
+__device__ __forceinline__ void spgemm_hash_sort(int cap, int* keys, int* vals) {
+    const int tid = threadIdx.x;
     for (int k = 2; k <= cap; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = tid; t < (cap >> 1); t += kSpgemmHashNT) {
@@ -131,6 +132,26 @@ __global__ __launch_bounds__(kSpgemmHashNT) void spgemm_hash_kernel(SpgemmArgs g
             __syncthreads();
         }
     }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(kSpgemmHashNT) void spgemm_hash_kernel(SpgemmArgs g) {
+    __shared__ int keys[kSpgemmHashCap];
+    __shared__ int vals[kSpgemmHashCap];
+    __shared__ int inserted;
+    const int tid = threadIdx.x, row = blockIdx.x;
+    const int cap = spgemm_hash_cap(g.u[row]);
+    if (cap == 0) return;                                                   // the tile kernel's row
+    if (tid == 0) inserted = 0;
+    const int fresh = spgemm_hash_accumulate<FILL>(g.A, g.B, g.p, g.n, row, cap, keys, vals);
+    if (!FILL) {
+        if (fresh) atomicAdd(&inserted, fresh);
+        __syncthreads();
+        if (tid == 0) g.row_nnz[row] = inserted;
+        return;
+    }
+    __syncthreads();
+    spgemm_hash_sort(cap, keys, vals);
     const int64_t lo = g.indptr[row];
     const int64_t cnt = min(g.indptr[row + 1] - lo, (int64_t)cap);
     for (int j = tid; j < cnt; j += kSpgemmHashNT) {
@@ -138,6 +159,44 @@ __global__ __launch_bounds__(kSpgemmHashNT) void spgemm_hash_kernel(SpgemmArgs g
         g.indices[lo + j] = keys[j];
         g.values[lo + j] = vals[j];
     }
+}
+
+// Tile path: the cells [col0, col1) of one row into `tile` (kCoocTile ints: zeroed here, then every product of the row whose
+// column is inside the span added - Count only marks the cell), the row's A entries [alo, ahi) staged kSpgemmStage at a time
+// through s_lo / s_hi / s_val.  Ends behind a barrier: the tile is complete for every thread.
+template <bool FILL>
+__device__ __forceinline__ void spgemm_tile_accumulate(const CoocView& A, const CoocView& B, int p, int64_t alo, int64_t ahi,
+                                                       int col0, int col1, int* tile, int64_t* s_lo, int64_t* s_hi, int* s_val) {
+    const int tid = threadIdx.x, grp = tid / kSpgemmGroup, gl = tid % kSpgemmGroup;
+    for (int j = tid; j < kCoocTile; j += kSpgemmTileNT) tile[j] = 0;
+    for (int64_t e0 = alo; e0 < ahi; e0 += kSpgemmStage) {
+        const int piece = (int)min((int64_t)kSpgemmStage, ahi - e0);
+        __syncthreads();                                                    // the tile is zero / the last piece has been read
+        if (tid < piece) {
+            const int d = A.indices[e0 + tid];
+            const bool ok = d >= 0 && d < p;
+            s_val[tid] = A.values[e0 + tid];
+            s_lo[tid] = ok ? B.indptr[d] : 0;
+            s_hi[tid] = ok ? B.indptr[d + 1] : 0;
+        }
+        __syncthreads();
+        for (int s = grp; s < piece; s += kSpgemmTileNT / kSpgemmGroup) {
+            const int64_t bhi = s_hi[s];
+            int64_t a = s_lo[s], b = bhi;                                   // the first entry of B's row with column >= col0
+            while (a < b) {
+                const int64_t mid = a + ((b - a) >> 1);
+                if (B.indices[mid] < col0) a = mid + 1; else b = mid;
+            }
+            const int x = s_val[s];
+            for (int64_t q = a + gl; q < bhi; q += kSpgemmGroup) {
+                const int c = B.indices[q];
+                if (c >= col1) break;
+                if (c < col0) continue;
+                if (FILL) atomicAdd(&tile[c - col0], x * B.values[q]); else tile[c - col0] = 1;
+            }
+        }
+    }
+    __syncthreads();
 }
 
 template <bool FILL>
@@ -149,41 +208,12 @@ __global__ __launch_bounds__(kSpgemmTileNT) void spgemm_tile_kernel(SpgemmArgs g
     constexpr int kWaves = kSpgemmTileNT / 64, kSeg = kCoocTile / kWaves;       // cells of the tile one wave compacts
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
     if (g.u[row] <= kSpgemmHashProducts) return;                            // the hash kernel's row
-    const int grp = tid / kSpgemmGroup, gl = tid % kSpgemmGroup;
     const int64_t alo = g.A.indptr[row], ahi = g.A.indptr[row + 1];
     const int64_t out0 = FILL ? g.indptr[row] : 0, out1 = FILL ? g.indptr[row + 1] : 0;
     int64_t running = 0;                                                    // entries of the row emitted by the tiles so far
     for (int col0 = 0; col0 < g.n; col0 += kCoocTile) {
         const int col1 = min(col0 + kCoocTile, g.n), width = col1 - col0;
-        for (int j = tid; j < kCoocTile; j += kSpgemmTileNT) tile[j] = 0;
-        for (int64_t e0 = alo; e0 < ahi; e0 += kSpgemmStage) {
-            const int piece = (int)min((int64_t)kSpgemmStage, ahi - e0);
-            __syncthreads();                                                // the tile is zero / the last piece has been read
-            if (tid < piece) {
-                const int d = g.A.indices[e0 + tid];
-                const bool ok = d >= 0 && d < g.p;
-                s_val[tid] = g.A.values[e0 + tid];
-                s_lo[tid] = ok ? g.B.indptr[d] : 0;
-                s_hi[tid] = ok ? g.B.indptr[d + 1] : 0;
-            }
-            __syncthreads();
-            for (int s = grp; s < piece; s += kSpgemmTileNT / kSpgemmGroup) {
-                const int64_t bhi = s_hi[s];
-                int64_t a = s_lo[s], b = bhi;                               // the first entry of B's row with column >= col0
-                while (a < b) {
-                    const int64_t mid = a + ((b - a) >> 1);
-                    if (g.B.indices[mid] < col0) a = mid + 1; else b = mid;
-                }
-                const int x = s_val[s];
-                for (int64_t q = a + gl; q < bhi; q += kSpgemmGroup) {
-                    const int c = g.B.indices[q];
-                    if (c >= col1) break;
-                    if (c < col0) continue;
-                    if (FILL) atomicAdd(&tile[c - col0], x * g.B.values[q]); else tile[c - col0] = 1;
-                }
-            }
-        }
-        __syncthreads();
+        spgemm_tile_accumulate<FILL>(g.A, g.B, g.p, alo, ahi, col0, col1, tile, s_lo, s_hi, s_val);
         int mine = 0;                                                       // non-zero cells of this wave's segment
         for (int j = wave * kSeg + lane; j < (wave + 1) * kSeg; j += 64)
             mine += __popcll(__ballot(j < width && tile[j] != 0));

@@ -547,6 +547,29 @@ int aae_csr_transpose_count(const int64_t* indptr_dev, const int32_t* indices_de
 int aae_csr_transpose_fill(const int64_t* indptr_dev, const int32_t* indices_dev, const void* values_dev, int32_t n_rows,
                            int32_t n_cols, const int64_t* t_indptr_dev, int32_t* t_indices_dev, void* t_values_dev,
                            int64_t* cursor_dev, void* scratch_dev, int64_t scratch_pairs, int64_t nnz, void* stream);
+/* Mutual information of a contingency table that is never stored (reference utils.py:10-71, compute_mutual_info; csrc/mutinfo.h):
+ * C = A . B with the operands of the spgemm calls - A = X^T [A->n_rows x p], B = Y [p x n], p = B->n_rows, strictly positive int32
+ * values - and scikit-learn's mutual_info_score(contingency=C) in the per-row form
+ *   MI = (1/T) sum_i [ S1_i + pi_i (ln T - ln pi_i) ],  S1_i = sum_j c_ij (ln c_ij - ln pj_j),  pi_i = sum_j c_ij,  T = sum_i pi_i
+ * with pj_j = sum_d B_dj a_d, a_d = sum_i A_id.  c_ij is int32; a, pi, pj and T are int64; every logarithm and sum is fp64.
+ * Handle-free like the spgemm calls; the caller runs aae_spgemm_i32_bound and then the three in this order on one stream:
+ * aae_mi_i32_marginals  a_dev [p] and pj_dev [n] int64 (zeroed by the call, then integer atomics: the same bits every run),
+ *                       lnpj_dev [n] fp64 = log((double)pj_j), 0 where pj_j = 0 (the row pass never reads such an entry).
+ * aae_mi_i32_rows       row_s1_dev [A->n_rows] fp64 = S1_i and row_pi_dev [A->n_rows] int64 = pi_i: row i of C is accumulated in
+ *                       LDS exactly as aae_spgemm_i32_fill accumulates it (u_dev deals the rows to the same two paths) and
+ *                       reduced there in a fixed order - the same bits every run.  An empty row writes 0 and 0.
+ * aae_mi_i32_finish     out_dev, 16 bytes, 8-byte aligned: double mi = max(sum / T, 0) at byte 0, int64 T at byte 8; the row
+ *                       terms are summed by one workgroup in a fixed order.  T = 0 (m = 0 included) gives mi = 0, not NaN.
+ * CONTRACT (aaerec/utils.py device_mi_ok; not checked by the calls): canonical operands, every c_ij < 2^31, T < 2^53 - then
+ * every marginal is an exact double.  A column id of A outside [0, p) or of B outside [0, n) is skipped; A->n_rows = 0 launches
+ * no row kernel.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, a negative size, p > B->n_rows, an
+ * out_dev that is not 8-byte aligned. */
+int aae_mi_i32_marginals(const aae_cooc* A, const aae_cooc* B, int32_t p, int32_t n, int64_t* a_dev, int64_t* pj_dev,
+                         double* lnpj_dev, void* stream);
+int aae_mi_i32_rows(const aae_cooc* A, const aae_cooc* B, int32_t n, const int64_t* u_dev, const double* lnpj_dev,
+                    double* row_s1_dev, int64_t* row_pi_dev, void* stream);
+int aae_mi_i32_finish(int32_t m, const double* row_s1_dev, const int64_t* row_pi_dev, void* out_dev, void* stream);
 /* The truncated-SVD baseline (reference svd.py:15-57, SVDRecommender: predict = (X V^T) V[:, :n_items], V = TruncatedSVD's
  * components_ [dims][n_features], n_features = items (+ the tf-idf vocabulary of the titles); csrc/lowrank.h).  Handle-free like
  * the cooc calls.  `lowrank` is ONE fp32 table for both products: vt_dev [n_features][ld], row f = column f of V, ld a multiple

@@ -1211,6 +1211,41 @@ def gen_svd():
         print(name, "train", Xtr.shape, "test", Xte.shape, "features", rec.svd.components_.shape[1], "bytes", os.path.getsize(path))
 
 
+def gen_mi():
+    """The reference's compute_mutual_info (utils.py:10-71) on a tiny synthetic Bags: 48 bags over 30 items drawn from 6 item
+    pools, one title per bag from the pool's words, one CountCondition on the titles.  All three input forms - labels only,
+    the condition imposed on the labels, the condition alone - normalised and not.  mutual_info.npz holds the bags as index
+    lists, the titles and the six results: data only."""
+    import_reference()
+    import aaerec.datasets as ref_ds
+    import aaerec.utils as ref_utils
+    import aaerec.condition as ref_cond
+    rng = np.random.RandomState(23)
+    n_bags, n_items, n_pools = 48, 30, 6
+    pools = [rng.choice(n_items, size=8, replace=False) for _ in range(n_pools)]
+    words = [["p%dw%d" % (p, j) for j in range(4)] for p in range(n_pools)]
+    raw, titles = [], []
+    for _ in range(n_bags):
+        p = rng.randint(n_pools)
+        raw.append(["i%d" % t for t in rng.choice(pools[p], size=rng.randint(2, 7), replace=False)])
+        titles.append(" ".join(rng.choice(words[p], size=rng.randint(1, 4), replace=False).tolist() +
+                               rng.choice(["study", "data", "model"], size=rng.randint(0, 3), replace=False).tolist()))
+    owners = ["d%d" % i for i in range(n_bags)]
+    bags = ref_ds.Bags(raw, owners, {"title": dict(zip(owners, titles))}).build_vocab(apply=True)
+    forms = (("labels", False, True), ("imposed", True, True), ("conditions", True, False))
+    out = dict(bag_indptr=np.concatenate([[0], np.cumsum([len(b) for b in bags.data])]).astype(np.int64),
+               bag_tokens=np.asarray([t for b in bags.data for t in b], dtype=np.int32), n_items=np.asarray(len(bags.vocab)),
+               titles=np.asarray(titles), forms=np.asarray([f[0] for f in forms]))
+    for name, with_cond, include_labels in forms:
+        for normalize in (False, True):
+            conditions = ref_cond.ConditionList([("title", ref_cond.CountCondition())]) if with_cond else None
+            mi = ref_utils.compute_mutual_info(bags, conditions=conditions, include_labels=include_labels, normalize=normalize)
+            out["mi.%s.%s" % (name, "normalized" if normalize else "raw")] = np.asarray(float(mi), dtype=np.float64)
+    path = os.path.join(OUT, "mutual_info.npz")
+    np.savez_compressed(path, **out)
+    print("mutual_info:", {k: float(v) for k, v in out.items() if k.startswith("mi.")}, "bytes", os.path.getsize(path))
+
+
 ACT_NAMES = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink",
              "Identity", "GELU", "SiLU", "Mish", "Hardswish", "ELU", "LeakyReLU", "Sigmoid"]
 
@@ -1292,6 +1327,8 @@ def main():
         gen_embedded_vectorizer()
     if want("svd"):
         gen_svd()
+    if want("mi"):
+        gen_mi()
     if want("metrics"):
         gen_metric_known_answers()
     if want("e2e"):
