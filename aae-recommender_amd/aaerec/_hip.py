@@ -101,6 +101,10 @@ class AaeCooc(C.Structure):
     _fields_ = [("indptr_dev", C.c_void_p), ("indices_dev", C.c_void_p), ("values_dev", C.c_void_p), ("n_rows", C.c_int32)]
 
 
+class AaePopular(C.Structure):
+    _fields_ = [("counts_dev", C.c_void_p), ("order_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("n_items", C.c_int32)]
+
+
 class AaeLowRank(C.Structure):
     _fields_ = [("vt_dev", C.c_void_p), ("ld", C.c_int64), ("n_features", C.c_int32), ("dims", C.c_int32)]
 
@@ -202,6 +206,9 @@ _PROTOS = {
     "aae_mi_i32_rows": (C.c_int, [C.POINTER(AaeCooc), C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "aae_mi_i32_finish": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_pop_counts": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_pop_topk": (C.c_int, [C.POINTER(AaePopular), C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_pop_ranks": (C.c_int, [C.POINTER(AaePopular), C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p, C.c_void_p]),
     "aae_spmm_f32": (C.c_int, [C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_lowrank_scores": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
@@ -768,6 +775,59 @@ def mutual_info_i32(A, B):
         _check(lib.aae_mi_i32_finish(m, _ptr(row_s1), _ptr(row_pi), _ptr(out), stream))
         host = out.cpu().numpy()
     return float(host[:1].view(np.float64)[0]), int(host[1]), row_s1, row_pi
+
+
+# ---- the most-popular baseline (aae_pop_*; csrc/popular.h) ----------------------------------------------------------
+def pop_counts(X):
+    """int32 device tensor [items]: the column sums of the DeviceCooc `X` (a training matrix as int32 CSR in HBM), integer adds
+    only (aae_pop_counts).  The caller keeps every column's absolute sum below 2^31 (aaerec.popular.device_count_ok)."""
+    n_items = int(X.shape[1])
+    counts = torch.empty(n_items, dtype=torch.int32, device=X.device)
+    x = X.struct()
+    with torch.cuda.device(X.device):
+        _check(load_library().aae_pop_counts(C.byref(x), n_items, _ptr(counts), _stream_of(X.device)))
+    return counts
+
+
+class DevicePopular:
+    """The item counts resident in HBM with the one order every row is ranked from: int32 `counts` [items], `order` - the
+    ids by (count descending, id ascending) - and `pos`, its inverse.  counts: an int32 device tensor (pop_counts) or a host
+    array of whole numbers below 2^31, uploaded once.  The order is a stable descending torch.sort on the device and `pos` a
+    scatter: plumbing, done once per train()."""
+
+    def __init__(self, counts, device):
+        self.device = torch.device(device)
+        if not torch.is_tensor(counts):
+            counts = upload(np.ascontiguousarray(np.rint(np.asarray(counts).ravel()).astype(np.int32)), self.device)
+        if not counts.is_cuda or counts.dtype != torch.int32 or counts.dim() != 1 or not counts.is_contiguous() or counts.numel() < 1:
+            raise TypeError("aaerec: counts must be a contiguous int32 GPU vector of at least one item")
+        self.counts = counts
+        self.n_items = int(counts.numel())
+        order = torch.sort(counts, descending=True, stable=True).indices
+        self.order = order.to(torch.int32)
+        self.pos = torch.empty(self.n_items, dtype=torch.int32, device=counts.device)
+        self.pos[order] = torch.arange(self.n_items, dtype=torch.int32, device=counts.device)
+
+    def struct(self):
+        p = AaePopular()
+        p.counts_dev, p.order_dev, p.pos_dev = self.counts.data_ptr(), self.order.data_ptr(), self.pos.data_ptr()
+        p.n_items = self.n_items
+        return p
+
+
+def pop_topk(pop, csr, row_start, n_rows, k, rows=None, exclude_known=True):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: the first k items of the DevicePopular's
+    order that a row of the DeviceCSR `csr` does not hold, for rows [row_start, row_start + n_rows) (or the rows named by the
+    int32 device tensor `rows`); every k in [1, items] (aae_pop_topk)."""
+    lead = (pop.struct(), _csr_batch(csr, row_start, n_rows, rows))
+    return _list_call(load_library().aae_pop_topk, pop.device, torch.cuda.device(pop.device), n_rows, k, exclude_known, lead)
+
+
+def pop_ranks(pop, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True):
+    """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with
+    the addressing of the input rows; n_truth = their stored entries), CSR order, in pop_topk's ordering (aae_pop_ranks)."""
+    lead = (pop.struct(), _csr_batch(csr, row_start, n_rows, rows), _csr_batch(truth_csr, row_start, n_rows, rows))
+    return _ranks_call(load_library().aae_pop_ranks, pop.device, torch.cuda.device(pop.device), n_truth, exclude_known, lead)
 
 
 def spmm_f32(csr, dense, width=None, out=None):

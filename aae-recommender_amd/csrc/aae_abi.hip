@@ -38,6 +38,7 @@
 #include "spgemm.h"
 #include "sptrans.h"
 #include "mutinfo.h"
+#include "popular.h"
 #include "lowrank.h"
 #include "chain.h"
 #include "chain4.h"
@@ -476,6 +477,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_spgemm.h"
 #include "abi_sptrans.h"
 #include "abi_mutinfo.h"
+#include "abi_popular.h"
 #include "abi_lowrank.h"
 #include "abi_data_parallel.h"
 

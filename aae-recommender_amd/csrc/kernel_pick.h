@@ -174,6 +174,11 @@ inline MiRowKernel pick_mi_hash() { return mi_hash_kernel; }
 inline MiRowKernel pick_mi_tile() { return mi_tile_kernel; }
 inline auto pick_mi_finish() { return mi_finish_kernel; }
 
+// ---- popular.h: the item counts, and lists / ranks from the one shared item order.  No LDS
+inline auto pick_pop_counts() { return pop_counts_kernel; }
+inline auto pick_pop_topk() { return pop_topk_kernel; }
+inline auto pick_pop_ranks() { return pop_ranks_kernel; }
+
 // ---- lowrank.h: the CSR x row-major-dense product - the projection of the ranking calls and aae_spmm_f32 alike
 using SpmmKernel = void (*)(LowRankView, BatchView, float*, long long);
 inline SpmmKernel pick_lowrank_project() { return lowrank_project_kernel; }

@@ -570,6 +570,41 @@ int aae_mi_i32_marginals(const aae_cooc* A, const aae_cooc* B, int32_t p, int32_
 int aae_mi_i32_rows(const aae_cooc* A, const aae_cooc* B, int32_t n, const int64_t* u_dev, const double* lnpj_dev,
                     double* row_s1_dev, int64_t* row_pi_dev, void* stream);
 int aae_mi_i32_finish(int32_t m, const double* row_s1_dev, const int64_t* row_pi_dev, void* out_dev, void* stream);
+/* The most-popular baseline (reference baselines.py:46-58, MostPopular: predict = the item counts of the training set, the same
+ * vector for every row; csrc/popular.h).  Handle-free like the cooc calls: every buffer is the caller's, the launches go to
+ * `stream`, nothing synchronises.  Every row ranks the same scores, so the items are ordered ONCE by the caller and a row only
+ * leaves its known items out: no [rows][n_items] scratch, no limit on a row's known items, every k in [1, n_items].
+ * aae_pop_counts  counts_dev [n_items] int32 (overwritten: zeroed by the call, then integer atomics - the same bits every run):
+ *                 counts[j] = sum over the rows d of X of x_dj, X the training matrix in the `aae_cooc` layout (int32 values).
+ *                 A column id outside [0, n_items) is skipped.  CONTRACT (not checked): max_j sum_d |x_dj| < 2^31.
+ * `aae_popular`   counts_dev as above; order_dev [n_items] int32, the item ids by (count descending, id ascending); pos_dev
+ *                 [n_items] int32, its inverse (pos[order[i]] = i).  The caller builds the last two from the first.
+ * aae_pop_topk    idx_out_dev / val_out_dev [batch->n_rows][k]: a row's list is the first k items of `order` that are not among
+ *                 its known items (exclude_known; otherwise the first k of `order`) - the better score first and the smaller id
+ *                 at equal scores, as in every ranking call - id -1 / score 0 behind its last rankable item.  A scaled score is
+ *                 the min-max scaling over ALL items, known ones included, with the fp32 formula of aae_cooc_topk_i32:
+ *                 (float(v) - float(min)) * inv, span = float(max) - float(min), inv = span > 0 ? 1 / span : 1, where
+ *                 min = counts[order[n_items - 1]] and max = counts[order[0]].
+ * aae_pop_ranks   one int32 per stored entry of the truth rows, CSR order: 1 + the number of items ordered before it,
+ *                 1 + pos[t] - #{known j : pos[j] < pos[t]}.  A truth entry that is a known item ranks behind every rankable
+ *                 item, among the known items by id: 1 + (n_items - m) + #{known j < t} for a row of m known items.  A truth id
+ *                 outside [0, n_items) ranks 0 and pos_dev is not read for it.  truth->max_row_nnz is not read.
+ * CONTRACT for both ranking calls, as in every dense ranking call: the ids of a batch row lie in [0, n_items) and ascend without
+ * duplicates.  The values of `batch` and `truth` are not read (values_dev may be NULL); row_start / rows_dev address rows as in
+ * every aae_batch.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, n_items <= 0, k outside [1, n_items],
+ * negative row counts, truth->n_rows != batch->n_rows.  No rows: nothing is launched. */
+typedef struct aae_popular {
+    const int32_t* counts_dev;
+    const int32_t* order_dev;
+    const int32_t* pos_dev;
+    int32_t n_items;
+} aae_popular;
+int aae_pop_counts(const aae_cooc* X, int32_t n_items, int32_t* counts_dev, void* stream);
+int aae_pop_topk(const aae_popular* pop, const aae_batch* batch, int32_t k, int32_t exclude_known, int32_t* idx_out_dev,
+                 float* val_out_dev, void* stream);
+int aae_pop_ranks(const aae_popular* pop, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
+                  int32_t* ranks_out_dev, void* stream);
 /* The truncated-SVD baseline (reference svd.py:15-57, SVDRecommender: predict = (X V^T) V[:, :n_items], V = TruncatedSVD's
  * components_ [dims][n_features], n_features = items (+ the tf-idf vocabulary of the titles); csrc/lowrank.h).  Handle-free like
  * the cooc calls.  `lowrank` is ONE fp32 table for both products: vt_dev [n_features][ld], row f = column f of V, ld a multiple

@@ -1246,6 +1246,41 @@ def gen_mi():
     print("mutual_info:", {k: float(v) for k, v in out.items() if k.startswith("mi.")}, "bytes", os.path.getsize(path))
 
 
+def gen_popular():
+    """The reference's MostPopular (baselines.py:46-58) behind the reference's own BagsWithVocab: train on 200 bags over 120
+    items (skewed popularity, a few repeated items, the last four items in no bag), predict for 9 test bags (one empty).
+    most_popular.npz holds arrays only: the two sets as CSR, the counts and the prediction with their dtypes, str(model)."""
+    import_reference()
+    import aaerec.baselines as ref_bl
+    import aaerec.datasets as ref_ds
+    rng = np.random.RandomState(31)
+    n_train, n_test, n_items = 200, 9, 120
+    vocab = {"i%d" % i: i for i in range(n_items)}
+    p = 1.0 / (np.arange(n_items - 4) + 3.0)
+    p /= p.sum()
+
+    def bag(lo, hi):
+        b = rng.choice(n_items - 4, size=rng.randint(lo, hi), replace=False, p=p).tolist()
+        return b + b[:1] if rng.rand() < 0.1 else b                      # (now and then an item twice)
+
+    train = ref_ds.BagsWithVocab([bag(2, 9) for _ in range(n_train)], vocab, owners=["d%d" % i for i in range(n_train)])
+    test = ref_ds.BagsWithVocab([bag(1, 7) for _ in range(n_test - 1)] + [[]], vocab, owners=["t%d" % i for i in range(n_test)])
+    rec = ref_bl.MostPopular()
+    rec.train(train)
+    pred = rec.predict(test)
+    Xtr, Xte = train.tocsr(), test.tocsr()
+    assert isinstance(rec.most_popular, np.matrix) and pred.shape == (n_test, n_items)
+    out = dict(n_items=np.asarray(n_items),
+               train_indptr=Xtr.indptr.astype(np.int64), train_indices=Xtr.indices.astype(np.int32), train_data=np.asarray(Xtr.data),
+               test_indptr=Xte.indptr.astype(np.int64), test_indices=Xte.indices.astype(np.int32), test_data=np.asarray(Xte.data),
+               most_popular=np.asarray(rec.most_popular), pred=np.asarray(pred), pred_is_matrix=np.asarray(int(isinstance(pred, np.matrix))),
+               model_str=np.asarray(str(rec)))
+    path = os.path.join(OUT, "most_popular.npz")
+    np.savez_compressed(path, **out)
+    print("most_popular: train", Xtr.shape, Xtr.dtype, "counts", out["most_popular"].dtype, "max", int(out["most_popular"].max()),
+          "pred", pred.shape, type(pred).__name__, "bytes", os.path.getsize(path))
+
+
 ACT_NAMES = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink",
              "Identity", "GELU", "SiLU", "Mish", "Hardswish", "ELU", "LeakyReLU", "Sigmoid"]
 
@@ -1329,6 +1364,8 @@ def main():
         gen_svd()
     if want("mi"):
         gen_mi()
+    if want("popular"):
+        gen_popular()
     if want("metrics"):
         gen_metric_known_answers()
     if want("e2e"):
