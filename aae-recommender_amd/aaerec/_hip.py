@@ -918,6 +918,7 @@ _NETS = {"enc": 0, "dec": 1, "disc": 2}
 _PARAM_ID = {("enc", 1): T_ENC_W1T, ("enc", 2): T_ENC_W2, ("enc", 3): T_ENC_W3,
              ("dec", 1): T_DEC_V1, ("dec", 2): T_DEC_V2, ("dec", 3): T_DEC_V3,
              ("disc", 1): T_DISC_D1, ("disc", 2): T_DISC_D2, ("disc", 3): T_DISC_D3}
+_OPTIM_ID = {"enc": O_ENC, "dec": O_DEC, "gen": O_GEN, "disc": O_DISC}
 
 
 class HipAAE:
@@ -1138,6 +1139,73 @@ class HipAAE:
         _check(self.lib.aae_store_adam(self.handle, oid, 2, None, None, None, None, C.byref(step)))
         out["step"] = step.value
         return out
+
+    def load_adam_state(self, which, state):
+        """The inverse of adam_state (aae_load_adam): state = {'lin1.weight': (m, v), 'lin1.bias': (m, v), ..., 'step': n}
+        for optimiser `which` in 'enc','dec','gen','disc'; layers that are absent stay as they are, and so does the step
+        count without a 'step' entry.  enc_optim and gen_optim share one count (include/aaerec_hip.h: aae_load_adam)."""
+        oid = _OPTIM_ID[which]
+        for layer in (1, 2, 3):
+            wk, bk = f"lin{layer}.weight", f"lin{layer}.bias"
+            if wk not in state and bk not in state:
+                continue
+            (mw, vw), (mb, vb) = state.get(wk, (None, None)), state.get(bk, (None, None))
+            self.load_adam(oid, layer, mw, vw, mb, vb)
+        if state.get("step") is not None:
+            self.load_adam(oid, 2, step=int(state["step"]))
+
+    # ---- the checkpoint entry points of the C ABI as they are: host arrays in the reference's layout ----
+    def linear_shape(self, net, layer):
+        """(out, in) of net 0 enc / 1 dec / 2 disc, layer 1..3 - the shape of the [out, in] weight aae_store_linear writes."""
+        info = AaeTensor()
+        _check(self.lib.aae_tensor_info(self.handle, _PARAM_ID[(("enc", "dec", "disc")[net], layer)], C.byref(info)))
+        return (int(info.cols), int(info.rows)) if (net, layer) == (0, 1) else (int(info.rows), int(info.cols) - 1)
+
+    @staticmethod
+    def _host_in(a, shape, what):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError(f"{what}: shape {a.shape}, expected {shape}")
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def store_linear(self, net, layer, weight=True, bias=True):
+        """aae_store_linear: (weight [out, in] or None, bias [out] or None) as numpy arrays."""
+        out, inn = self.linear_shape(net, layer)
+        w = np.empty((out, inn), dtype=np.float32) if weight else None
+        b = np.empty((out,), dtype=np.float32) if bias else None
+        with self._on_device():
+            _check(self.lib.aae_store_linear(self.handle, net, layer, None if w is None else w.ctypes.data_as(C.c_void_p),
+                                             None if b is None else b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def load_linear(self, net, layer, weight=None, bias=None):
+        """aae_load_linear: weight [out, in] and / or bias [out] (None = left as it is)."""
+        out, inn = self.linear_shape(net, layer)
+        w, wp = self._host_in(weight, (out, inn), "weight")
+        b, bp = self._host_in(bias, (out,), "bias")
+        with self._on_device():
+            _check(self.lib.aae_load_linear(self.handle, net, layer, wp, bp))
+
+    def store_adam(self, which, layer, weight=True, bias=True, step=True):
+        """aae_store_adam of optimiser id `which` (O_ENC ..): (m_w, v_w, m_b, v_b, step), None for what was not asked for."""
+        out, inn = self.linear_shape({O_ENC: 0, O_GEN: 0, O_DEC: 1, O_DISC: 2}[which], layer)
+        mw, vw = (np.empty((out, inn), dtype=np.float32) for _ in range(2)) if weight else (None, None)
+        mb, vb = (np.empty((out,), dtype=np.float32) for _ in range(2)) if bias else (None, None)
+        st = C.c_int64(-1)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)           # noqa: E731
+        with self._on_device():
+            _check(self.lib.aae_store_adam(self.handle, which, layer, p(mw), p(vw), p(mb), p(vb), C.byref(st) if step else None))
+        return mw, vw, mb, vb, (st.value if step else None)
+
+    def load_adam(self, which, layer, m_w=None, v_w=None, m_b=None, v_b=None, step=-1):
+        """aae_load_adam: any of the four moment arrays (None = left as it is); step < 0 leaves the count alone."""
+        out, inn = self.linear_shape({O_ENC: 0, O_GEN: 0, O_DEC: 1, O_DISC: 2}[which], layer)
+        keep = [self._host_in(a, s, n) for a, s, n in ((m_w, (out, inn), "m_w"), (v_w, (out, inn), "v_w"),
+                                                      (m_b, (out,), "m_b"), (v_b, (out,), "v_b"))]
+        with self._on_device():
+            _check(self.lib.aae_load_adam(self.handle, which, layer, keep[0][1], keep[1][1], keep[2][1], keep[3][1], int(step)))
 
     # ---- batches / randomness ----------------------------------------------------------
     def _batch(self, csr, row_start, n_rows, rows=None, bounded=True):

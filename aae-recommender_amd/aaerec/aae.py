@@ -89,6 +89,11 @@ class _OptimView:
         self._owner._dp_settle()
         return self._owner.hip.adam_state(self._name)
 
+    def load_state_dict(self, sd):
+        """What state_dict() returned, back into the optimiser (moments and step count)."""
+        self._owner._dp_settle()
+        self._owner.hip.load_adam_state(self._name, sd)
+
 
 class AdversarialAutoEncoder:
     """ Adversarial Autoencoder """

@@ -476,7 +476,7 @@ int side_done(aae_model* m, hipEvent_t ev) {
 int join_host(aae_model* m) {
     if (!m->opt_pending && !m->pf_pending) return AAE_OK;
     HIPCHK(hipStreamSynchronize(m->side));
-    m->opt_pending = m->pf_pending = false;
+    m->opt_pending = m->pf_pending = m->late_ok = false;      // (as join_deferred: no launch is pending that late_ok could describe)
     return AAE_OK;
 }
 

@@ -91,6 +91,7 @@ int aae_load_adam(aae_handle h, int which, int layer, const float* m_w, const fl
     if (!h) return fail(AAE_EINVAL, "handle is NULL");
     int pid, set;
     if (adam_sel(which, layer, &pid, &set)) return fail(AAE_EINVAL, "bad optimiser/layer");
+    if (step > 0x7fffffffll) return fail(AAE_EINVAL, "step count beyond 2^31 - 1");      // (tsync[] holds it as int)
     TRY(join_host(h));
     TRY(lazy_flush(h, nullptr));
     HIPCHK(hipDeviceSynchronize());
@@ -99,17 +100,26 @@ int aae_load_adam(aae_handle h, int which, int layer, const float* m_w, const fl
     TRY(put_linear(h, pid, h->M[set][pid], mb, m_w, m_b));
     TRY(put_linear(h, pid, h->V[set][pid], vb, v_w, v_b));
     if (step >= 0) {
-        OptScalars hs;
-        HIPCHK(hipMemcpy(&hs, h->sc + which, sizeof(hs), hipMemcpyDeviceToHost));
-        hs.t = step;
-        HIPCHK(hipMemcpy(h->sc + which, &hs, sizeof(hs), hipMemcpyHostToDevice));
+        // enc_optim and gen_optim step together: ONE count for both (advance_step_body files nss_gen under enc_optim's count
+        // and nss_reg under gen_optim's in the same ring the catch-up reads by the step counter), so loading either sets both,
+        // the step counter (device generator, deferred first-layer updates) and the host's own count of opened steps
+        const bool shared = which == O_ENC || which == O_GEN;
+        OptScalars hs[4];
+        HIPCHK(hipMemcpy(hs, h->sc, sizeof(hs), hipMemcpyDeviceToHost));
+        hs[which].t = step;
+        if (shared) hs[O_ENC].t = hs[O_GEN].t = step;
+        HIPCHK(hipMemcpy(h->sc, hs, sizeof(hs), hipMemcpyHostToDevice));
         h->spec_tab_ok = false;
-        if (which == O_ENC || which == O_GEN) {
-            // enc_optim and gen_optim step together; the rng/lazy step counter follows them
+        if (shared) {
             long long t = step;
             HIPCHK(hipMemcpy(h->step_ctr, &t, sizeof(t), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(fill_int_kernel, dim3(256), dim3(256), 0, 0, h->tsync, (size_t)h->N, (int)step);
             HIPCHK(hipDeviceSynchronize());
+            // what the host derived from the old count: the step-opening gather and the early catch-up take the step number
+            // from hstep; a list built ahead was caught up through the old count's steps; a rank call's flush was filed under it
+            h->hstep = step;
+            h->pf_built = false; h->pf_step = -1;
+            h->flushed_hstep = -1;
         }
     }
     return AAE_OK;

@@ -206,12 +206,26 @@ int aae_params_changed(aae_handle h);
 int aae_set_lr(aae_handle h, double gen_lr, double reg_lr);
 
 /* nn.Linear state in the reference's state_dict layout (weight [out,in] row-major, bias
- * [out]), host pointers.  Synchronous. net: 0 enc 1 dec 2 disc; layer: 1..3. */
+ * [out]), host pointers.  Synchronous. net: 0 enc 1 dec 2 disc; layer: 1..3.
+ * Either pointer may be NULL: that half is neither read nor written.  A bad net / layer / optimiser id or a NULL handle is
+ * AAE_EINVAL and changes nothing.  All four calls may be made at any point between two steps, on a handle that has run: they
+ * wait for the handle's side stream (deferred dec_optim launch, a batch's catch-up built ahead), replay the deferred
+ * first-layer updates (aae_sync) and invalidate what the library derives from the tensors they write.  A VAE handle's
+ * enc.lin3 is [fc21; fc22]: 2 * n_code rows.  Every handle kind carries all nine layers and all four optimisers' tensors
+ * (the plain autoencoder's discriminator, the VAE's lin2 layers: stored and loaded, never used). */
 int aae_load_linear(aae_handle h, int net, int layer, const float* weight_host,
                     const float* bias_host);
 int aae_store_linear(aae_handle h, int net, int layer, float* weight_host, float* bias_host);
 /* optimiser state_dict (exp_avg / exp_avg_sq in [out,in] + [out] layout, step count).
- * which: 0 enc_optim 1 dec_optim 2 gen_optim 3 disc_optim. */
+ * which: 0 enc_optim 1 dec_optim 2 gen_optim 3 disc_optim.  Any of the four moment pointers may be NULL (left alone);
+ * load: step < 0 leaves the count alone, step > 2^31 - 1 is AAE_EINVAL; store: step may be NULL.
+ * The step count: every optimiser advances once per training step.  enc_optim and gen_optim update the same tensors and
+ * SHARE ONE COUNT - the deferred first-layer updates replay both from one table indexed by it, and it keys the device random
+ * generator -, so a count loaded for either is the count of both, of the handle's step counter and of every item's "updated
+ * through" step: after loading 5 for enc_optim and then 7 for gen_optim both hold 7.  dec_optim and disc_optim keep counts of
+ * their own.  The next step is step count + 1 in every respect (bias corrections, dropout draws, catch-up).
+ * cfg.optimizer = AAE_OPT_SGD: the handle carries the same moment tensors and never reads or writes them: store returns what
+ * was last loaded (zeros on a new handle), load is a plain round trip, the counts count steps as under Adam. */
 int aae_load_adam(aae_handle h, int which, int layer, const float* m_w, const float* v_w,
                   const float* m_b, const float* v_b, int64_t step);
 int aae_store_adam(aae_handle h, int which, int layer, float* m_w, float* v_w, float* m_b,

@@ -1406,3 +1406,44 @@ def test_fit_on_two_ranks_through_the_ipc_all_reduce_equals_single_process():
         assert (d > tol).sum() <= max(8, 0.01 * d.size) and d.max() < 0.02, f"{k}: {(d > tol).sum()} off, max {d.max():.2e}"
     np.testing.assert_allclose(got["pred"], one.predict(X[:33]), atol=10 * tol)
     assert abs(got["loss"] - one.last_losses[0]) < 1e-5
+
+
+def test_model_rebuilt_from_state_dicts_continues_like_the_original():
+    """The reference's checkpoint: the nets' state_dict() and the four optimisers' state_dict() / load_state_dict().
+    Model A is fitted for some steps; model B - same arguments and seed, and one step of its own behind it, so that it is a
+    handle that has run - takes A's enc / dec / disc and the state of A's four optimisers (moments and step counts:
+    HipAAE.load_adam_state on aae_load_adam); both continue on the same batches with the device generator and predict the
+    same bits (README: the same seeds on the same batch order give bit-identical weights; the logged losses are sums whose
+    last bit is not promised at this batch size and are not compared)."""
+    from aaerec.aae import AdversarialAutoEncoder
+    N, B = 700, 37
+    X = sp.random(9 * B, N, density=0.02, random_state=5, format="csr", dtype=np.float32)
+    X.data[:] = 1.0
+
+    def new():
+        torch.manual_seed(11)
+        return AdversarialAutoEncoder(n_hidden=40, n_code=12, batch_size=B, verbose=False, rng_mode="device", seed=5)
+    a, b = new(), new()
+    for s in range(4):
+        a.partial_fit(X[s * B:(s + 1) * B])
+    b.partial_fit(X[8 * B:9 * B])
+    for net in ("enc", "dec", "disc"):
+        getattr(b, net).load_state_dict(getattr(a, net).state_dict())
+    for opt in ("enc_optim", "dec_optim", "gen_optim", "disc_optim"):
+        sd = getattr(a, opt).state_dict()
+        assert sd["step"] == 4
+        getattr(b, opt).load_state_dict(sd)
+        back = getattr(b, opt).state_dict()
+        assert back["step"] == 4
+        for k, mv in sd.items():
+            if k != "step":
+                np.testing.assert_array_equal(back[k][0], mv[0], err_msg=f"{opt} exp_avg {k}")
+                np.testing.assert_array_equal(back[k][1], mv[1], err_msg=f"{opt} exp_avg_sq {k}")
+    for s in range(4, 8):
+        a.partial_fit(X[s * B:(s + 1) * B])
+        b.partial_fit(X[s * B:(s + 1) * B])
+    np.testing.assert_array_equal(b.predict(X[:50]), a.predict(X[:50]))
+    sa, sb = a.hip.state_dict(), b.hip.state_dict()
+    for k, v in sa.items():
+        np.testing.assert_array_equal(sb[k], v, err_msg=k)
+    assert b.gen_optim.state_dict()["step"] == 8
