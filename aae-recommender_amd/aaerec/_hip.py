@@ -35,6 +35,11 @@ SPGEMM_HASH_PRODUCTS = 4096   # most products of a row the sparse product keeps 
 SPGEMM_STAGE = 512        # entries of a row of A its tile kernel stages in LDS at a time (AAE_SPGEMM_STAGE)
 SPTRANS_LDS = 4096        # longest row of a transpose sorted in LDS in one go (AAE_SPTRANS_LDS; csrc/sptrans.h): longer ones merge through a scratch
 LOWRANK_DIMS_MAX = 4096   # widest hidden vector of the truncated-SVD projection kernel (AAE_LOWRANK_DIMS_MAX; csrc/lowrank.h)
+METRIC_MAX = 32           # most metric specs of one aae_metric_rows call (AAE_METRIC_MAX; csrc/rank_metrics.h)
+METRIC_ROW_MAX = 4096     # longest row of held-out ranks the metric kernel sorts in LDS (AAE_METRIC_ROW_MAX)
+RANK_ABSENT = 2 ** 31 - 1  # the stored rank of a held-out item a list does not hold (AAE_RANK_ABSENT)
+METRIC_NDCG_K_MAX = 1 << 20    # longest discount table the wrapper builds and uploads: an ndcg@k beyond it is the host's
+METRIC_KINDS = {"mrr": 0, "map": 1, "p": 2, "ndcg": 3, "r-prec": 4, "clicks": 5}        # aae_metric_kind
 GRAD_FUSED, GRAD_EXPORT = 0, 1
 
 
@@ -103,6 +108,14 @@ class AaeCooc(C.Structure):
 
 class AaePopular(C.Structure):
     _fields_ = [("counts_dev", C.c_void_p), ("order_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("n_items", C.c_int32)]
+
+
+class AaeMetricSpec(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("k", C.c_int32)]
+
+
+class AaeRankRows(C.Structure):
+    _fields_ = [("indptr_dev", C.c_void_p), ("ranks_dev", C.c_void_p), ("n_rows", C.c_int32)]
 
 
 class AaeLowRank(C.Structure):
@@ -209,6 +222,10 @@ _PROTOS = {
     "aae_pop_counts": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p]),
     "aae_pop_topk": (C.c_int, [C.POINTER(AaePopular), C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_pop_ranks": (C.c_int, [C.POINTER(AaePopular), C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_metric_rows": (C.c_int, [C.POINTER(AaeRankRows), C.POINTER(AaeMetricSpec), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_int64, C.c_void_p]),
+    "aae_metric_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_ranks_from_lists": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
     "aae_spmm_f32": (C.c_int, [C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_lowrank_scores": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
@@ -828,6 +845,78 @@ def pop_ranks(pop, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclud
     the addressing of the input rows; n_truth = their stored entries), CSR order, in pop_topk's ordering (aae_pop_ranks)."""
     lead = (pop.struct(), _csr_batch(csr, row_start, n_rows, rows), _csr_batch(truth_csr, row_start, n_rows, rows))
     return _ranks_call(load_library().aae_pop_ranks, pop.device, torch.cuda.device(pop.device), n_truth, exclude_known, lead)
+
+
+# ---- ranking metrics from held-out ranks (aae_metric_*, aae_ranks_from_lists; csrc/rank_metrics.h) ------------------------------
+def discount_table(K):
+    """float64 [K]: d[i] = 1 / log2(1 + i) at index i - 1, with the reference's own expression (eval/mpd/mpd_metrics.py:80)."""
+    return 1.0 / np.log2(1 + np.arange(1, int(K) + 1))
+
+
+class DeviceDiscounts:
+    """The ndcg discount table resident in HBM, one per device: built on the host by discount_table and uploaded when a call needs
+    more entries than the table kept so far holds, which it then replaces - d[i] sits at index i - 1 whatever the length, so the
+    longest table asked for serves every smaller K with the same doubles."""
+    _tables = {}
+
+    @classmethod
+    def get(cls, K, device):
+        K, dev = int(K), torch.device(device)
+        if not 1 <= K <= METRIC_NDCG_K_MAX:
+            raise ValueError("a discount table holds 1 to {} entries, not {}".format(METRIC_NDCG_K_MAX, K))
+        key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in cls._tables or cls._tables[key].numel() < K:
+            cls._tables[key] = upload(discount_table(K), dev)
+        return cls._tables[key]
+
+
+def rank_metrics(indptr, ranks, specs, per_row=False):
+    """The metrics `specs` - [(kind, k)], kind a METRIC_KINDS value, k = 0 unbounded - of the rows of held-out ranks on the
+    device: indptr int64 [n + 1], ranks int32 in CSR order (as the *_ranks calls and ranks_from_lists write them), both device
+    tensors.  float64 host array [len(specs), 2] of (mean, population std) - the only bytes that leave the device - or, with
+    per_row, [len(specs), n].  The caller keeps every row within METRIC_ROW_MAX entries, every rank >= 1 and every ndcg k
+    within METRIC_NDCG_K_MAX (aaerec.evaluation does): a row beyond that comes back NaN."""
+    dev = indptr.device
+    if not (indptr.is_cuda and ranks.is_cuda and indptr.dtype == torch.int64 and ranks.dtype == torch.int32
+            and indptr.is_contiguous() and ranks.is_contiguous() and indptr.numel() >= 1):
+        raise TypeError("aaerec: indptr / ranks must be contiguous int64 / int32 GPU vectors")
+    specs = [(int(kind), int(k)) for kind, k in specs]
+    n, lib = int(indptr.numel()) - 1, load_library()
+    if ranks.numel() == 0:
+        ranks = torch.zeros(1, dtype=torch.int32, device=dev)        # (a valid pointer: nothing reads it)
+    kd = max([k for kind, k in specs if kind == METRIC_KINDS["ndcg"]], default=0)
+    disc = DeviceDiscounts.get(kd, dev) if kd else None
+    rows = AaeRankRows()
+    rows.indptr_dev, rows.ranks_dev, rows.n_rows = indptr.data_ptr(), ranks.data_ptr(), n
+    vals = torch.empty(len(specs), max(n, 1), dtype=torch.float64, device=dev)
+    out = torch.empty(len(specs), 2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = _stream_of(dev)
+        for q0 in range(0, len(specs), METRIC_MAX):
+            part = specs[q0:q0 + METRIC_MAX]
+            arr = (AaeMetricSpec * len(part))(*[AaeMetricSpec(kind, k) for kind, k in part])
+            _check(lib.aae_metric_rows(C.byref(rows), arr, len(part), _ptr(disc), 0 if disc is None else int(disc.numel()), _ptr(vals[q0:]),
+                                       vals.stride(0), stream))
+            if not per_row:
+                _check(lib.aae_metric_finish(_ptr(vals[q0:]), vals.stride(0), n, len(part), _ptr(out[q0:]), stream))
+    return vals[:, :n].cpu().numpy() if per_row else out.cpu().numpy()
+
+
+def ranks_from_lists(ids, truth_csr, row_start, n_rows, n_truth, k=None, rows=None):
+    """int32 device tensor [n_truth]: for every stored entry of the truth rows (DeviceCSR `truth_csr`, canonical; rows
+    [row_start, row_start + n_rows) or those named by `rows`; n_truth their stored entries), CSR order, its position + 1 among
+    the first k ids of its row of `ids` (int32 device tensor [n_rows, >= k], best first, -1 padding) or RANK_ABSENT."""
+    if not ids.is_cuda or ids.dtype != torch.int32 or ids.dim() != 2 or ids.stride(1) != 1 or ids.shape[0] < n_rows:
+        raise TypeError("aaerec: ids must be an int32 GPU matrix [n_rows, k] with unit column stride")
+    k = int(ids.shape[1] if k is None else k)
+    if not 1 <= k <= ids.shape[1]:
+        raise ValueError("k must be in [1, {}]".format(ids.shape[1]))
+    out = torch.empty(int(n_truth), dtype=torch.int32, device=ids.device)
+    if n_truth and n_rows:
+        b = _csr_batch(truth_csr, row_start, n_rows, rows)
+        with torch.cuda.device(ids.device):
+            _check(load_library().aae_ranks_from_lists(_ptr(ids), int(ids.stride(0)), k, C.byref(b), _ptr(out), _stream_of(ids.device)))
+    return out
 
 
 def spmm_f32(csr, dense, width=None, out=None):

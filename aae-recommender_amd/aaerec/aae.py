@@ -663,31 +663,33 @@ def _rank_chunks(self, Xs, condition_data, chunk, fused, decode):
     return out
 
 
-def _predict_topk(self, X, k=10, condition_data=None, exclude_known=True):
+def _predict_topk(self, X, k=10, condition_data=None, exclude_known=True, y_true=None, metrics=None):
     """Top-k recommendations without materialising the [n, N] score matrix on the host: the
     reference's predict -> remove_non_missing -> argtopk pipeline (aae.py:840-870,
     evaluation.py:183-199, 20-58) with only [n, k] ids and scaled scores crossing PCIe.
-    Conditions as in predict(): see _rank_chunks."""
+    Conditions as in predict(): see _rank_chunks.  metrics: a list of bounded metric names - [(mean, std)] per name against
+    y_true comes back instead, computed where the lists are (ranking.rank_metrics)."""
     Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
-    return ranking.lists(self._rank_chunks(
+    return ranking.finish_lists(self._rank_chunks(
         Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.rank_max_rows(k)),
         lambda csr, start, n, cond: self.hip.predict_topk(csr, start, n, k, cond=cond, exclude_known=exclude_known),
-        lambda csr, start, zc: self.hip.decode_topk(zc, csr, start, k, exclude_known=exclude_known)), k)
+        lambda csr, start, zc: self.hip.decode_topk(zc, csr, start, k, exclude_known=exclude_known)), k, metrics, y_true, Xs.shape)
 
 
-def _predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
+def _predict_ranks(self, X, Y, condition_data=None, exclude_known=True, metrics=None):
     """The rank of every held-out item in the full ranking of its row, without the [n, N] score matrix leaving the device
     or being sorted anywhere: a scipy CSR with Y's pattern (canonical: duplicates summed, indices sorted) whose data are
     the int32 1-based ranks of those items among the row's items - predict_topk's ordering (the items of X's row are not
     rankable with exclude_known).  Everything evaluation.METRICS needs follows from them (evaluation.evaluate_ranks); only
-    nnz(Y) integers cross PCIe.  Conditions as in predict_topk()."""
+    nnz(Y) integers cross PCIe.  Conditions as in predict_topk().  metrics: a list of metric names - [(mean, std)] per name
+    comes back instead, computed where the ranks are (ranking.rank_metrics)."""
     Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
     Ys = ranking.canonical_truth(Y, Xs.shape)
     truth = _hip.DeviceCSR(Ys, self.hip.device)
-    return ranking.ranks_csr(self._rank_chunks(
+    return ranking.finish_ranks(self._rank_chunks(
         Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.rank_full_max_rows()),
         lambda csr, start, n, cond: self.hip.predict_ranks(csr, start, n, truth, cond=cond, exclude_known=exclude_known),
-        lambda csr, start, zc: self.hip.decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys)
+        lambda csr, start, zc: self.hip.decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys, metrics)
 
 
 AdversarialAutoEncoder._rank_chunks = _rank_chunks
@@ -876,21 +878,22 @@ class DecodingRecommender(Recommender):
                 out.append(call(self._inputs(c_batch), csr, start))
         return out
 
-    def predict_topk(self, test_set, k=10):
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
         """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag: predict -> remove_non_missing ->
-        argtopk on the device (aae_decode_topk), only [n, k] crosses PCIe."""
+        argtopk on the device (aae_decode_topk), only [n, k] crosses PCIe.  metrics: [(mean, std)] per name against y_true
+        instead (ranking.rank_metrics)."""
         chunk = ranking.chunk_rows(self.batch_size, self.hip.rank_max_rows(k))
         parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_topk(zc, csr, start, k))
-        return ranking.lists(parts, k)
+        return ranking.finish_lists(parts, k, metrics, y_true, (test_set.size(0), self.hip.N))
 
-    def predict_ranks(self, test_set, y_true):
+    def predict_ranks(self, test_set, y_true, metrics=None):
         """CSR with y_true's (canonical) pattern: the rank of every held-out item in the full ranking of its test bag
-        (aae_decode_ranks)."""
+        (aae_decode_ranks).  metrics: [(mean, std)] per name instead (ranking.rank_metrics)."""
         Ys = ranking.canonical_truth(y_true, (test_set.size(0), self.hip.N), "the test set")
         truth = _hip.DeviceCSR(Ys, self.hip.device)
         chunk = ranking.chunk_rows(self.batch_size, self.hip.rank_full_max_rows())
         parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_ranks(zc, csr, start, truth))
-        return ranking.ranks_csr(parts, Ys)
+        return ranking.finish_ranks(parts, Ys, metrics)
 
 
 def _validate_targets(X):
@@ -947,18 +950,20 @@ class AAERecommender(Recommender):
             condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
         return self.model.predict(X, condition_data=condition_data)
 
-    def predict_topk(self, test_set, k=10):
-        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag."""
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
+        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag; with metrics, [(mean, std)] per name
+        against y_true."""
         X = test_set.tocsr()
         condition_data = None
         if self.conditions:
             condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
-        return self.model.predict_topk(X, k=k, condition_data=condition_data)
+        return self.model.predict_topk(X, k=k, condition_data=condition_data, y_true=y_true, metrics=metrics)
 
-    def predict_ranks(self, test_set, y_true):
-        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag."""
+    def predict_ranks(self, test_set, y_true, metrics=None):
+        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag; with metrics,
+        [(mean, std)] per name."""
         X = test_set.tocsr()
         condition_data = None
         if self.conditions:
             condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
-        return self.model.predict_ranks(X, y_true, condition_data=condition_data)
+        return self.model.predict_ranks(X, y_true, condition_data=condition_data, metrics=metrics)

@@ -280,33 +280,34 @@ class Countbased(ranking.ScratchRanker, Recommender):
         """The one buffer of a device call on `route`, for _device_chunks."""
         return lambda rows: {"scratch": torch.empty(rows, (n_items + 3) & ~3, dtype=_SCRATCH[route], device=self._dev.device)}
 
-    def predict_topk(self, test_set, k=10):
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
         """(item ids int32 [n, k], scaled scores float32 [n, k]) of the k best new items per test bag: predict ->
-        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item."""
+        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item.  metrics: a list of bounded metric
+        names - [(mean, std)] per name against y_true comes back instead (ranking.rank_metrics on the device route)."""
         X = self._inputs(test_set)
         n, n_items = X.shape
         if k < 1:
             raise ValueError("k must be positive")
         route = self._route_of(X, k) if n else None
         if not route:
-            return ranking.host_topk(self._host_rows(X), n, k, _scaled)
+            return ranking.host_finish_lists(ranking.host_topk(self._host_rows(X), n, k, _scaled), metrics, y_true, X.shape)
         topk, csr = getattr(_hip, "cooc_topk" if route == "f32" else "cooc_topk_i32"), _hip.DeviceCSR(X, self._dev.device)
         parts = self._device_chunks(n, n_items, self._scratch(route, n_items),
                                     lambda s0, rows, **b: topk(self._dev, csr, s0, rows, k, **b))
-        return ranking.lists(parts, k)
+        return ranking.finish_lists(parts, k, metrics, y_true, X.shape)
 
-    def predict_ranks(self, test_set, y_true):
+    def predict_ranks(self, test_set, y_true, metrics=None):
         """CSR of int32 with y_true's (canonical) pattern: the 1-based rank of every held-out item in the full ranking of its
         test bag, in predict_topk's ordering.  A held-out item that is a known item ranks behind every rankable one, among
-        the known items by id."""
+        the known items by id.  metrics: a list of metric names - [(mean, std)] per name comes back instead."""
         X = self._inputs(test_set)
         n, n_items = X.shape
         Ys = ranking.canonical_truth(y_true, X.shape, "the test set")
         route = self._route_of(X) if n else None
         if not route:
-            return ranking.host_ranks(self._host_rows(X), Ys)
+            return ranking.host_finish_ranks(ranking.host_ranks(self._host_rows(X), Ys), metrics)
         ranks = getattr(_hip, "cooc_ranks" if route == "f32" else "cooc_ranks_i32")
         csr, truth = _hip.DeviceCSR(X, self._dev.device), _hip.DeviceCSR(Ys, self._dev.device)
-        return ranking.ranks_csr(self._device_chunks(
+        return ranking.finish_ranks(self._device_chunks(
             n, n_items, self._scratch(route, n_items),
-            lambda s0, rows, **b: ranks(self._dev, csr, s0, rows, truth, int(Ys.indptr[s0 + rows] - Ys.indptr[s0]), **b)), Ys)
+            lambda s0, rows, **b: ranks(self._dev, csr, s0, rows, truth, int(Ys.indptr[s0 + rows] - Ys.indptr[s0]), **b)), Ys, metrics)

@@ -183,10 +183,13 @@ class DAERecommender(Recommender):
             return None
         return self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
 
-    def predict_topk(self, test_set, k=10):
-        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag (AdversarialAutoEncoder.predict_topk)."""
-        return self.dae.predict_topk(test_set.tocsr(), k=k, condition_data=self._conditions_of(test_set))
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
+        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag (AdversarialAutoEncoder.predict_topk);
+        with metrics, [(mean, std)] per name against y_true."""
+        return self.dae.predict_topk(test_set.tocsr(), k=k, condition_data=self._conditions_of(test_set), y_true=y_true,
+                                     metrics=metrics)
 
-    def predict_ranks(self, test_set, y_true):
-        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag."""
-        return self.dae.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set))
+    def predict_ranks(self, test_set, y_true, metrics=None):
+        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag; with metrics,
+        [(mean, std)] per name."""
+        return self.dae.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set), metrics=metrics)

@@ -124,68 +124,209 @@ def evaluate(ground_truth, predictions, metrics, batch_size=None):
     return [(np.mean(v), np.std(v)) for v in map(np.asarray, per_metric)]
 
 
-def evaluate_topk(ground_truth, topk_idx, metrics):
-    """The bounded ranking metrics ('mrr@k', 'map@k', 'p@k', 'P@1') from top-k item ids alone:
+# ---- metric names -----------------------------------------------------------------------------------------------------------
+# A metric a rank-based route can answer is (kind, k): kind one of METRIC_KINDS, k a positive integer or None (unbounded: 'mrr',
+# 'map').  The three kinds of the RecSys-2018 challenge (reference eval/mpd/mpd_metrics.py:43-144, as eval/evaluate_dev.py uses
+# them) are functions of a row's sorted held-out ranks r_1 < ... < r_m and the list cap k alone:
+#   r-prec@k = #{r_j <= min(m, k)} / m
+#   ndcg@k   = sum_{r_j <= k} d[r_j] / sum_{i = 1 .. min(k, m)} d[i],  d[i] = 1 / log2(1 + i)
+#   clicks@k = floor((r_1 - 1) / 10) if r_1 <= k, else k / 10 + 1
+METRIC_KINDS = ("mrr", "map", "p", "ndcg", "r-prec", "clicks")
+RANK_ABSENT = 2 ** 31 - 1       # the stored rank of a held-out item that a top-k list does not hold: never <= k, counts towards m
+
+
+def metric_spec(name):
+    """(kind, k) of a metric name: 'mrr', 'map' (k None), 'mrr@k', 'map@k', 'p@k' / 'P@k', 'ndcg@k', 'r-prec@k', 'clicks@k' with
+    any integer k >= 1.  ValueError for anything else."""
+    if not isinstance(name, str):
+        raise ValueError("a metric name is a string, not {!r}".format(name))
+    kind, at, tail = name.partition("@")
+    kind = "p" if kind == "P" else kind
+    if kind not in METRIC_KINDS:
+        raise ValueError("unknown metric {!r}".format(name))
+    if not at:
+        if kind not in ("mrr", "map"):
+            raise ValueError("metric {!r} needs a cap: {}@k".format(name, kind))
+        return kind, None
+    if not (tail.isascii() and tail.isdigit()) or int(tail) < 1:
+        raise ValueError("the cap of metric {!r} must be an integer >= 1".format(name))
+    return kind, int(tail)
+
+
+def metric_name(kind, k=None):
+    """The name metric_spec reads (kind, k) from ('p@k' in lower case)."""
+    if kind not in METRIC_KINDS or (k is None and kind not in ("mrr", "map")) or (k is not None and int(k) < 1):
+        raise ValueError("no metric ({!r}, {!r})".format(kind, k))
+    return kind if k is None else "{}@{}".format(kind, int(k))
+
+
+CHALLENGE_METRICS = {metric_name(kind, k): (kind, k) for kind in ("r-prec", "ndcg", "clicks") for k in (5, 10, 20, 500)}
+
+
+def _is_metric_name(name):
+    try:
+        metric_spec(name)
+    except ValueError:
+        return False
+    return True
+
+
+def _specs(metrics):
+    """[(kind, k)] of a list of names: a name of METRICS by its object (as ever), any other through metric_spec."""
+    out = []
+    for name in metrics:
+        if isinstance(name, str) and name in METRICS:
+            metric = METRICS[name]
+            out.append(("mrr" if isinstance(metric, MRR) else "map" if isinstance(metric, MAP) else "p", metric.k))
+        else:
+            out.append(metric_spec(name))
+    return out
+
+
+def device_metrics_ok(row_lengths, specs, device="cuda:0"):
+    """True when csrc/rank_metrics.h answers `specs` for rows of these lengths: a device is named and present, no row is longer
+    than AAE_METRIC_ROW_MAX, every cap fits int32 and no ndcg cap exceeds the longest discount table (2^20)."""
+    from . import _hip
+    import torch
+    if device is None or not torch.cuda.is_available():
+        return False
+    lengths = np.asarray(row_lengths)
+    if lengths.size >= 2 ** 31 - 1 or (lengths.size and int(lengths.max()) > _hip.METRIC_ROW_MAX):
+        return False
+    return all(k is None or (k < RANK_ABSENT and (kind != "ndcg" or k <= _hip.METRIC_NDCG_K_MAX)) for kind, k in specs)
+
+
+def _device_specs(specs):
+    from . import _hip
+    return [(_hip.METRIC_KINDS[kind], 0 if k is None else k) for kind, k in specs]
+
+
+def _pairs(stats):
+    return [(m, s) for m, s in np.asarray(stats, dtype=np.float64)]
+
+
+def _host_ranks_from_lists(gt, topk_idx):
+    """The int32 CSR with gt's (canonical) pattern: position + 1 of every truth entry in its row of topk_idx - the smaller one for
+    an id listed twice - or RANK_ABSENT (what aae_ranks_from_lists computes)."""
+    n, K = topk_idx.shape
+    data = np.full(gt.nnz, RANK_ABSENT, dtype=np.int32)
+    for r in range(n):
+        lo, hi = gt.indptr[r], gt.indptr[r + 1]
+        if lo == hi:
+            continue
+        ids = topk_idx[r]
+        pos = np.flatnonzero(ids >= 0)
+        first_ids, first_at = np.unique(ids[pos], return_index=True)           # (the first place of every id, ids ascending)
+        at = np.searchsorted(first_ids, gt.indices[lo:hi])
+        hit = (at < first_ids.size) & (first_ids[np.minimum(at, max(first_ids.size - 1, 0))] == gt.indices[lo:hi]) \
+            if first_ids.size else np.zeros(hi - lo, dtype=bool)
+        data[lo:hi][hit] = pos[first_at[at[hit]]] + 1
+    return sp.csr_matrix((data, gt.indices.copy(), gt.indptr.copy()), shape=gt.shape)
+
+
+def evaluate_topk(ground_truth, topk_idx, metrics, device=None, per_row=False):
+    """The bounded ranking metrics ('mrr@k', 'map@k', 'p@k', 'P@1', 'ndcg@k', 'r-prec@k', 'clicks@k') from top-k item ids alone:
     a metric at k only ever looks at the relevance of the k best predictions (RankingMetric above),
     so [(mean, std)] equals evaluate() on the full score matrix.  topk_idx: [n, K] ids, best first,
-    K >= the largest k asked for; -1 entries count as irrelevant."""
+    K >= the largest k asked for; -1 entries count as irrelevant.
+    device: the lists and the truth go up, aae_ranks_from_lists turns them into ranks (RANK_ABSENT for a truth entry outside its
+    list) and csrc/rank_metrics.h answers; per_row: the [metrics, n] values instead of [(mean, std)]."""
     gt = sp.csr_matrix(ground_truth)
     topk_idx = np.asarray(topk_idx)
     n, K = topk_idx.shape
     assert gt.shape[0] == n
-    rel = np.zeros((n, K), dtype=np.int64)
-    for r in range(n):
-        truth = set(gt.indices[gt.indptr[r]:gt.indptr[r + 1]].tolist())
-        rel[r] = [1 if int(i) in truth else 0 for i in topk_idx[r]]
-    out = []
-    for name in metrics:
-        metric = METRICS[name]
-        k = metric.k
+    specs = _specs(metrics)
+    for name, (kind, k) in zip(metrics, specs):
         if k is None or k > K:
             raise ValueError("metric {} needs the full ranking / more than the {} ids given".format(name, K))
-        rs = rel[:, :k]
-        if isinstance(metric, MRR):
-            out.append(rm.mean_reciprocal_rank(rs))
-        elif isinstance(metric, MAP):
-            out.append(rm.mean_average_precision(rs))
-        else:
-            ps = (rs > 0).mean(axis=1)
-            out.append((ps.mean(), ps.std()))
-    return out
+    if device is None and not per_row and all(name in METRICS for name in metrics):
+        rel = np.zeros((n, K), dtype=np.int64)
+        for r in range(n):
+            truth = set(gt.indices[gt.indptr[r]:gt.indptr[r + 1]].tolist())
+            rel[r] = [1 if int(i) in truth else 0 for i in topk_idx[r]]
+        out = []
+        for name in metrics:
+            metric = METRICS[name]
+            rs = rel[:, :metric.k]
+            if isinstance(metric, MRR):
+                out.append(rm.mean_reciprocal_rank(rs))
+            elif isinstance(metric, MAP):
+                out.append(rm.mean_average_precision(rs))
+            else:
+                ps = (rs > 0).mean(axis=1)
+                out.append((ps.mean(), ps.std()))
+        return out
+    gt = gt.copy()
+    gt.sum_duplicates()
+    gt.sort_indices()
+    if n and K and device_metrics_ok(np.diff(gt.indptr), specs, device):
+        from . import _hip
+        truth = _hip.DeviceCSR(gt, device)
+        ids = _hip.upload(np.ascontiguousarray(topk_idx, dtype=np.int32), device)
+        ranks = _hip.ranks_from_lists(ids, truth, 0, n, int(gt.nnz))
+        got = _hip.rank_metrics(truth.indptr, ranks, _device_specs(specs), per_row=per_row)
+        return got if per_row else _pairs(got)
+    return evaluate_ranks(_host_ranks_from_lists(gt, topk_idx), metrics, per_row=per_row)
 
 
-def evaluate_ranks(ranks_csr, metrics):
+def evaluate_ranks(ranks_csr, metrics, device=None, per_row=False):
     """Every metric of METRICS, bounded or not, from the ranks of the held-out items alone: ranks_csr [n, items] holds, for
     every stored entry, the 1-based rank of that held-out item in the full ranking of its row (predict_ranks).  With a row's
     sorted ranks r_1 < r_2 < ... < r_m:  RR = 1 / r_1,  AP = mean_j (j / r_j);  'mrr@k' / 'map@k' the same over the r_j <= k
     (0 if there are none),  'p@k' = #{r_j <= k} / k;  a row without held-out items scores 0 everywhere, as
-    rank_metrics_with_std has it.  [(mean, std)] in float64 with the population std, as evaluate() - no per-row loop."""
+    rank_metrics_with_std has it.  [(mean, std)] in float64 with the population std, as evaluate() - no per-row loop.
+    Any name metric_spec reads is answered, the challenge's 'ndcg@k', 'r-prec@k', 'clicks@k' (see METRIC_KINDS above) among them;
+    a row without held-out items has clicks@k = k / 10 + 1.  Equal ranks order by their place in the row (the lexsort is stable).
+    A stored RANK_ABSENT counts towards m and is never <= k.  A rank below 1 raises ValueError.
+    device: the ranks go up and csrc/rank_metrics.h answers (the host does where device_metrics_ok says no: the same definitions);
+    per_row: the float64 [metrics, n] values instead of [(mean, std)]."""
     R = sp.csr_matrix(ranks_csr)
     n = R.shape[0]
-    rows = np.repeat(np.arange(n), np.diff(R.indptr))
+    specs = _specs(metrics)
+    if R.nnz and np.asarray(R.data[:R.indptr[-1]]).min() < 1:
+        raise ValueError("a rank below 1: ranks are 1-based")
+    if n and device_metrics_ok(np.diff(R.indptr), specs, device):
+        from . import _hip
+        indptr = _hip.upload(np.asarray(R.indptr, dtype=np.int64), device)
+        ranks = _hip.upload(np.ascontiguousarray(R.data[:R.indptr[-1]], dtype=np.int32), device)
+        got = _hip.rank_metrics(indptr, ranks, _device_specs(specs), per_row=per_row)
+        return got if per_row else _pairs(got)
+    lengths = np.diff(R.indptr)
+    rows = np.repeat(np.arange(n), lengths)
     order = np.lexsort((R.data, rows))                       # (row after row, a row's ranks ascending)
     r = np.asarray(R.data)[order].astype(np.float64)
     j = (np.arange(r.size) - np.asarray(R.indptr, dtype=np.int64)[rows] + 1).astype(np.float64)
-    has = np.diff(R.indptr) > 0
+    has = lengths > 0
     first = np.zeros(n, dtype=np.float64)                    # r_1 of the rows that have one
     first[has] = r[np.asarray(R.indptr[:-1])[has]]
+    m = lengths.astype(np.float64)
     out = []
-    for name in metrics:
-        metric = METRICS[name]
-        k = metric.k
-        inside = np.ones(r.size, dtype=bool) if k is None else r <= k
-        if isinstance(metric, MRR):
-            ok = has & (first <= k) if k is not None else has
-            per_row = np.where(ok, 1.0 / np.where(ok, first, 1.0), 0.0)
-        elif isinstance(metric, MAP):
+    for kind, k in specs:
+        inside = r != RANK_ABSENT if k is None else r <= k
+        if kind == "mrr":
+            ok = has & (first <= k) if k is not None else has & (first != RANK_ABSENT)
+            per = np.where(ok, 1.0 / np.where(ok, first, 1.0), 0.0)
+        elif kind == "map":
             # (the r_j <= k of a sorted row are its first ones: their j are their places among the hits)
             hits = np.bincount(rows[inside], minlength=n).astype(np.float64)
             total = np.bincount(rows[inside], weights=(j / r)[inside], minlength=n)
-            per_row = np.where(hits > 0, total / np.where(hits > 0, hits, 1.0), 0.0)
+            per = np.where(hits > 0, total / np.where(hits > 0, hits, 1.0), 0.0)
+        elif kind == "p":
+            per = np.bincount(rows[inside], minlength=n).astype(np.float64) / k
+        elif kind == "r-prec":
+            within = r <= np.minimum(m, float(k))[rows]
+            per = np.where(has, np.bincount(rows[within], minlength=n).astype(np.float64) / np.where(has, m, 1.0), 0.0)
+        elif kind == "clicks":
+            ok = has & (first <= k)
+            per = np.where(ok, np.floor((np.where(ok, first, 1.0) - 1.0) / 10.0), k / 10.0 + 1.0)
         else:
-            per_row = np.bincount(rows[inside], minlength=n).astype(np.float64) / k
-        out.append((per_row.mean(), per_row.std()))
-    return out
+            # ndcg: the discounts of the hits one by one, a table only as far as min(k, m) of the longest row - whatever k is
+            top = max(min(k, int(lengths.max()) if n else 0), 1)
+            ideal = np.concatenate(([0.0], np.cumsum(1.0 / np.log2(1 + np.arange(1, top + 1)))))[np.minimum(lengths, k)]
+            gain = np.bincount(rows[inside], weights=1.0 / np.log2(1 + r[inside].astype(np.int64)), minlength=n)
+            per = np.where(gain > 0, gain / np.where(ideal > 0, ideal, 1.0), 0.0)
+        out.append(per)
+    return np.asarray(out, dtype=np.float64).reshape(len(specs), n) if per_row else [(v.mean(), v.std()) for v in out]
 
 
 def reevaluate(gold_file, predictions_file, metrics):
@@ -204,8 +345,15 @@ def maybe_close(fh):
 class Evaluation:
     """Year split -> vocabulary -> pruning -> drop `drop` items per test bag -> train/predict/score."""
 
-    def __init__(self, dataset, year, metrics=METRICS, logfile=sys.stdout, logdir=None, topk=True):
+    def __init__(self, dataset, year, metrics=METRICS, logfile=sys.stdout, logdir=None, topk=True, metrics_on="host"):
         self.dataset, self.year, self.metrics = dataset, year, metrics
+        if metrics_on not in ("host", "device"):
+            raise ValueError('metrics_on must be "host" or "device", not {!r}'.format(metrics_on))
+        # metrics_on="device": on the two ranking branches of __call__ the recommender is asked for the metrics themselves
+        # (predict_topk / predict_ranks(..., metrics=names)): lists or ranks stay on the device, csrc/rank_metrics.h turns them
+        # into [(mean, std)] and only those doubles come back.  "host" (the default) brings ids or ranks back and scores them
+        # with evaluate_topk / evaluate_ranks, as ever.
+        self.metrics_on = metrics_on
         self.logfile, self.logdir = logfile, logdir
         # topk: a recommender that can rank on the device (predict_topk: the fused predict -> remove_non_missing -> top-k
         # pass, only [n, k] ids cross PCIe) is asked for its k best items instead of the dense [n, items] score matrix
@@ -250,9 +398,16 @@ class Evaluation:
         from ._hip import RANK_K_MAX
         ks = []
         for m in self.metrics:
-            if not isinstance(m, str) or m not in BOUNDED_METRICS:
+            if isinstance(m, str) and m in BOUNDED_METRICS:
+                ks.append(BOUNDED_METRICS[m].k)
+                continue
+            try:                                    # (a bounded name beyond METRICS: 'ndcg@10', 'r-prec@500', 'mrr@50' ...)
+                k = metric_spec(m)[1]
+            except ValueError:
                 return None
-            ks.append(BOUNDED_METRICS[m].k)
+            if k is None:
+                return None
+            ks.append(k)
         return max(ks) if ks and max(ks) <= RANK_K_MAX else None
 
     def __call__(self, recommenders, batch_size=None):
@@ -276,18 +431,26 @@ class Evaluation:
             t1 = timer()
             kmax = self._bounded_k()
             if self.topk and kmax is not None and not self.logdir and hasattr(rec, "predict_topk"):
-                top_ids, _ = rec.predict_topk(test_set, k=kmax)
+                if self.metrics_on == "device":
+                    results = rec.predict_topk(test_set, k=kmax, y_true=self.y_test, metrics=list(self.metrics))
+                else:
+                    top_ids, _ = rec.predict_topk(test_set, k=kmax)
                 print("Prediction took {} seconds.".format(timedelta(seconds=timer() - t1)), file=fh)
                 t1 = timer()
-                results = evaluate_topk(self.y_test, top_ids, list(self.metrics))
+                if self.metrics_on != "device":
+                    results = evaluate_topk(self.y_test, top_ids, list(self.metrics))
             elif (self.topk and kmax is None and not self.logdir and hasattr(rec, "predict_ranks")
-                  and all(isinstance(m, str) and m in METRICS for m in self.metrics)):
+                  and all(isinstance(m, str) and (m in METRICS or _is_metric_name(m)) for m in self.metrics)):
                 # an unbounded metric among them (mrr, map: what the reference's drivers ask for): the device ranks every
                 # held-out item in the full ranking of its row, nnz(y_test) integers cross PCIe (csrc/rank_full.h)
-                ranks = rec.predict_ranks(test_set, self.y_test)
+                if self.metrics_on == "device":
+                    results = rec.predict_ranks(test_set, self.y_test, metrics=list(self.metrics))
+                else:
+                    ranks = rec.predict_ranks(test_set, self.y_test)
                 print("Prediction took {} seconds.".format(timedelta(seconds=timer() - t1)), file=fh)
                 t1 = timer()
-                results = evaluate_ranks(ranks, list(self.metrics))
+                if self.metrics_on != "device":
+                    results = evaluate_ranks(ranks, list(self.metrics))
             else:
                 y_pred = rec.predict(test_set)
                 y_pred = y_pred.toarray() if sp.issparse(y_pred) else np.asarray(y_pred)

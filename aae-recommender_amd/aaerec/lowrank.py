@@ -275,33 +275,34 @@ class SVDRecommender(ranking.ScratchRanker, Recommender, AutoEncoderMixin):
         return lambda rows: {"scratch": torch.empty(rows, (n_items + 3) & ~3, dtype=torch.float32, device=dev),
                              "hidden": torch.empty(rows, (dims + 3) & ~3, dtype=torch.float32, device=dev)}
 
-    def predict_topk(self, test_set, k=10):
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
         """(item ids int32 [n, k], scaled scores float32 [n, k]) of the k best new items per test bag: predict ->
-        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item."""
+        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item.  metrics: a list of bounded metric
+        names - [(mean, std)] per name against y_true comes back instead (ranking.rank_metrics on the device route)."""
         F, X = self._inputs(test_set)
         n, n_items = X.shape
         if k < 1:
             raise ValueError("k must be positive")
         if not (self.on_device(k) and n):
-            return ranking.host_topk(self._host_rows(F, X), n, k, _scaled)
+            return ranking.host_finish_lists(ranking.host_topk(self._host_rows(F, X), n, k, _scaled), metrics, y_true, X.shape)
         lr = self._dev
         feat, items = _hip.DeviceCSR(F, lr.device), _hip.DeviceCSR(X, lr.device)
         parts = self._device_chunks(n, n_items, self._scratch(n_items),
                                     lambda s0, rows, **b: _hip.lowrank_topk(lr, n_items, feat, items, s0, rows, k, **b))
-        return ranking.lists(parts, k)
+        return ranking.finish_lists(parts, k, metrics, y_true, X.shape)
 
-    def predict_ranks(self, test_set, y_true):
+    def predict_ranks(self, test_set, y_true, metrics=None):
         """CSR of int32 with y_true's (canonical) pattern: the 1-based rank of every held-out item in the full ranking of its
         test bag, in predict_topk's ordering.  A held-out item that is a known item ranks behind every rankable one, among
-        the known items by id."""
+        the known items by id.  metrics: a list of metric names - [(mean, std)] per name comes back instead."""
         F, X = self._inputs(test_set)
         n, n_items = X.shape
         Ys = ranking.canonical_truth(y_true, X.shape, "the test set")
         if not (self.on_device() and n):
-            return ranking.host_ranks(self._host_rows(F, X), Ys)
+            return ranking.host_finish_ranks(ranking.host_ranks(self._host_rows(F, X), Ys), metrics)
         lr = self._dev
         feat, items, truth = (_hip.DeviceCSR(M, lr.device) for M in (F, X, Ys))
-        return ranking.ranks_csr(self._device_chunks(
+        return ranking.finish_ranks(self._device_chunks(
             n, n_items, self._scratch(n_items),
             lambda s0, rows, **b: _hip.lowrank_ranks(lr, n_items, feat, items, s0, rows, truth,
-                                                     int(Ys.indptr[s0 + rows] - Ys.indptr[s0]), **b)), Ys)
+                                                     int(Ys.indptr[s0 + rows] - Ys.indptr[s0]), **b)), Ys, metrics)

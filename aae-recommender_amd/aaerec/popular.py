@@ -148,25 +148,26 @@ class MostPopular(Recommender):
         counts = np.asarray(self.most_popular, dtype=np.float64).ravel()
         return ranking.host_rows(X, lambda r0, r1: np.broadcast_to(counts, (min(r1, X.shape[0]) - r0, counts.size)))
 
-    def predict_topk(self, test_set, k=10):
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
         """(item ids int32 [n, k], scaled scores float32 [n, k]) of the k most popular new items per test bag: predict ->
-        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item."""
+        remove_non_missing -> argtopk; id -1 / score 0 behind a row's last rankable item.  metrics: a list of bounded metric
+        names - [(mean, std)] per name against y_true comes back instead (ranking.rank_metrics on the device route)."""
         X = self._inputs(test_set)
         n = X.shape[0]
         if k < 1:
             raise ValueError("k must be positive")
         if not self._route_of(n, k):
-            return ranking.host_topk(self._host_rows(X), n, k, _scaled)
-        return ranking.lists([_hip.pop_topk(self._dev, _hip.DeviceCSR(X, self._dev.device), 0, n, k)], k)
+            return ranking.host_finish_lists(ranking.host_topk(self._host_rows(X), n, k, _scaled), metrics, y_true, X.shape)
+        return ranking.finish_lists([_hip.pop_topk(self._dev, _hip.DeviceCSR(X, self._dev.device), 0, n, k)], k, metrics, y_true, X.shape)
 
-    def predict_ranks(self, test_set, y_true):
+    def predict_ranks(self, test_set, y_true, metrics=None):
         """CSR of int32 with y_true's (canonical) pattern: the 1-based rank of every held-out item in the full ranking of its
         test bag, in predict_topk's ordering.  A held-out item that is a known item ranks behind every rankable one, among
-        the known items by id."""
+        the known items by id.  metrics: a list of metric names - [(mean, std)] per name comes back instead."""
         X = self._inputs(test_set)
         n = X.shape[0]
         Ys = ranking.canonical_truth(y_true, X.shape, "the test set")
         if not self._route_of(n):
-            return ranking.host_ranks(self._host_rows(X), Ys)
+            return ranking.host_finish_ranks(ranking.host_ranks(self._host_rows(X), Ys), metrics)
         csr, truth = _hip.DeviceCSR(X, self._dev.device), _hip.DeviceCSR(Ys, self._dev.device)
-        return ranking.ranks_csr([_hip.pop_ranks(self._dev, csr, 0, n, truth, int(Ys.nnz))], Ys)
+        return ranking.finish_ranks([_hip.pop_ranks(self._dev, csr, 0, n, truth, int(Ys.nnz))], Ys, metrics)

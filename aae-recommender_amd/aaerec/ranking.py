@@ -4,7 +4,8 @@ The ordering is one rule everywhere: the better score first, THE SMALLER ID AT E
 held-out item is 1 + the number of items ordered before it, a known item behind every rankable one.  The device kernels
 (csrc/rank_long.h, rank_full.h) implement it; `host_topk` / `host_ranks` are its reference, which the baselines answer with
 where the device route is closed.  The rest is the plumbing around either: the canonical ground truth, the rows of a call a chunk
-at a time, and the two tails that turn the parts of a chunked call into what `Evaluation` reads.
+at a time, and the tails that turn the parts of a chunked call into what `Evaluation` reads: `lists` / `ranks_csr` bring them to
+the host, `rank_metrics` leaves them where they are and brings back the metrics alone (csrc/rank_metrics.h).
 """
 import numpy as np
 import scipy.sparse as sp
@@ -48,6 +49,72 @@ def _ranks_csr(data, Ys):
 def ranks_csr(parts, Ys):
     """The int32 CSR of ranks with the pattern of the canonical truth Ys from the device parts of a chunked call (CSR order)."""
     return _ranks_csr(torch.cat(parts).cpu().numpy().astype(np.int32, copy=False) if parts else np.zeros(0, dtype=np.int32), Ys)
+
+
+def rank_metrics(parts, Ys, metrics, k=None):
+    """[(mean, std)] per metric name from the device parts of a chunked call and the canonical truth Ys, without a CSR of ranks
+    on the host: the parts are concatenated where they are and csrc/rank_metrics.h answers; 16 bytes per metric come back.
+    k None: parts are the int32 rank parts of a predict_ranks call (CSR order of Ys).  k given: parts are the (ids, scores) parts
+    of a predict_topk call with lists of k ids; aae_ranks_from_lists turns them into ranks, and an unbounded name or one beyond
+    k raises the ValueError of evaluation.evaluate_topk.  Where the device route is closed (evaluation.device_metrics_ok: a row
+    of more than AAE_METRIC_ROW_MAX held-out items, an ndcg cap beyond 2^20) the host answers under the same definitions.
+    A rank below 1 raises ValueError on both routes."""
+    from . import _hip, evaluation as ev
+    specs = ev._specs(metrics)
+    if k is not None:
+        for name, (_, cap) in zip(metrics, specs):
+            if cap is None or cap > k:
+                raise ValueError("metric {} needs the full ranking / more than the {} ids given".format(name, k))
+    device = (parts[0] if k is None else parts[0][0]).device if parts else None
+    if not parts or not Ys.shape[0] or not ev.device_metrics_ok(np.diff(Ys.indptr), specs, device):
+        if k is None:
+            return ev.evaluate_ranks(ranks_csr(parts, Ys), metrics)
+        return ev.evaluate_topk(Ys, lists(parts, k)[0], metrics)
+    if k is None:
+        ranks = torch.cat(parts).to(torch.int32).contiguous()
+        if ranks.numel() and int(ranks.min()) < 1:
+            raise ValueError("a rank below 1: ranks are 1-based")
+        indptr = _hip.upload(np.asarray(Ys.indptr, dtype=np.int64), device)
+    else:
+        truth = _hip.DeviceCSR(Ys, device)
+        ids = torch.cat([p[0] for p in parts]).contiguous()
+        ranks, indptr = _hip.ranks_from_lists(ids, truth, 0, Ys.shape[0], int(Ys.nnz), k=k), truth.indptr
+    return ev._pairs(_hip.rank_metrics(indptr, ranks, ev._device_specs(specs)))
+
+
+# What predict_ranks / predict_topk return, by route and by whether metrics were asked for (metrics=None: ranks / lists as ever)
+def finish_ranks(parts, Ys, metrics=None):
+    """The device route of a predict_ranks call: the CSR of ranks, or [(mean, std)] of `metrics`."""
+    return ranks_csr(parts, Ys) if metrics is None else rank_metrics(parts, Ys, metrics)
+
+
+def finish_lists(parts, k, metrics=None, y_true=None, shape=None):
+    """The device route of a predict_topk call: (ids, scores), or [(mean, std)] of `metrics` against y_true [shape]."""
+    if metrics is None:
+        return lists(parts, k)
+    return rank_metrics(parts, list_truth(y_true, shape), metrics, k=k)
+
+
+def list_truth(y_true, shape):
+    if y_true is None:
+        raise ValueError("predict_topk(..., metrics=names) needs the ground truth: y_true=")
+    return canonical_truth(y_true, shape, "the test set")
+
+
+def host_finish_ranks(R, metrics=None):
+    """The host route of a predict_ranks call (host_ranks) likewise."""
+    if metrics is None:
+        return R
+    from .evaluation import evaluate_ranks
+    return evaluate_ranks(R, metrics)
+
+
+def host_finish_lists(pair, metrics=None, y_true=None, shape=None):
+    """The host route of a predict_topk call (host_topk) likewise."""
+    if metrics is None:
+        return pair
+    from .evaluation import evaluate_topk
+    return evaluate_topk(list_truth(y_true, shape), pair[0], metrics)
 
 
 # ---- the host reference ranker -------------------------------------------------------------------------------------------

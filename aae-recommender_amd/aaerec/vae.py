@@ -234,27 +234,29 @@ class VAE:
                     out.append(fused(csr, start, n, self._cond(c_batch) if use_condition else None, eps))
         return out
 
-    def predict_topk(self, X, k=10, condition_data=None, exclude_known=True):
+    def predict_topk(self, X, k=10, condition_data=None, exclude_known=True, y_true=None, metrics=None):
         """(item ids [n, k], scaled scores [n, k]) of predict -> remove_non_missing -> argtopk (vae.py:229-266,
-        evaluation.py:183-199, 20-58) without the [n, N] score matrix: see AdversarialAutoEncoder.predict_topk."""
+        evaluation.py:183-199, 20-58) without the [n, N] score matrix: see AdversarialAutoEncoder.predict_topk.
+        metrics: [(mean, std)] per bounded metric name against y_true instead (ranking.rank_metrics)."""
         Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
-        return ranking.lists(self._rank_chunks(
+        return ranking.finish_lists(self._rank_chunks(
             Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.vae_rank_max_rows(k)),
             lambda csr, start, n, cond, eps: self.hip.vae_predict_topk(csr, start, n, k, cond=cond, eps=eps,
                                                                        exclude_known=exclude_known),
-            lambda csr, start, zc: self.hip.vae_decode_topk(zc, csr, start, k, exclude_known=exclude_known)), k)
+            lambda csr, start, zc: self.hip.vae_decode_topk(zc, csr, start, k, exclude_known=exclude_known)), k, metrics, y_true,
+            Xs.shape)
 
-    def predict_ranks(self, X, Y, condition_data=None, exclude_known=True):
+    def predict_ranks(self, X, Y, condition_data=None, exclude_known=True, metrics=None):
         """A scipy CSR with Y's (canonical) pattern whose data are the int32 1-based ranks of the held-out items in the full
-        ranking of their rows: see AdversarialAutoEncoder.predict_ranks."""
+        ranking of their rows: see AdversarialAutoEncoder.predict_ranks.  metrics: [(mean, std)] per metric name instead."""
         Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
         Ys = ranking.canonical_truth(Y, Xs.shape)
         truth = _hip.DeviceCSR(Ys, self.device)
-        return ranking.ranks_csr(self._rank_chunks(
+        return ranking.finish_ranks(self._rank_chunks(
             Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.vae_rank_full_max_rows()),
             lambda csr, start, n, cond, eps: self.hip.vae_predict_ranks(csr, start, n, truth, cond=cond, eps=eps,
                                                                         exclude_known=exclude_known),
-            lambda csr, start, zc: self.hip.vae_decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys)
+            lambda csr, start, zc: self.hip.vae_decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys, metrics)
 
 
 class VAERecommender(Recommender):
@@ -304,10 +306,13 @@ class VAERecommender(Recommender):
             return None
         return self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
 
-    def predict_topk(self, test_set, k=10):
-        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag."""
-        return self.model.predict_topk(test_set.tocsr(), k=k, condition_data=self._conditions_of(test_set))
+    def predict_topk(self, test_set, k=10, y_true=None, metrics=None):
+        """(item ids [n, k], scaled scores [n, k]) of the k best new items per test bag; with metrics, [(mean, std)] per name
+        against y_true."""
+        return self.model.predict_topk(test_set.tocsr(), k=k, condition_data=self._conditions_of(test_set), y_true=y_true,
+                                       metrics=metrics)
 
-    def predict_ranks(self, test_set, y_true):
-        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag."""
-        return self.model.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set))
+    def predict_ranks(self, test_set, y_true, metrics=None):
+        """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag; with metrics,
+        [(mean, std)] per name."""
+        return self.model.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set), metrics=metrics)

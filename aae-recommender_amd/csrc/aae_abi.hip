@@ -39,6 +39,7 @@
 #include "sptrans.h"
 #include "mutinfo.h"
 #include "popular.h"
+#include "rank_metrics.h"
 #include "lowrank.h"
 #include "chain.h"
 #include "chain4.h"
@@ -478,6 +479,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_sptrans.h"
 #include "abi_mutinfo.h"
 #include "abi_popular.h"
+#include "abi_metrics.h"
 #include "abi_lowrank.h"
 #include "abi_data_parallel.h"
 

@@ -179,6 +179,11 @@ inline auto pick_pop_counts() { return pop_counts_kernel; }
 inline auto pick_pop_topk() { return pop_topk_kernel; }
 inline auto pick_pop_ranks() { return pop_ranks_kernel; }
 
+// ---- rank_metrics.h: per-row metric values from ranks, their (mean, std), ranks from lists.  Static LDS: no limit to raise
+inline auto pick_metric_rows() { return metric_rows_kernel; }
+inline auto pick_metric_finish() { return metric_finish_kernel; }
+inline auto pick_ranks_from_lists() { return ranks_from_lists_kernel; }
+
 // ---- lowrank.h: the CSR x row-major-dense product - the projection of the ranking calls and aae_spmm_f32 alike
 using SpmmKernel = void (*)(LowRankView, BatchView, float*, long long);
 inline SpmmKernel pick_lowrank_project() { return lowrank_project_kernel; }

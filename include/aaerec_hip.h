@@ -619,6 +619,55 @@ int aae_pop_topk(const aae_popular* pop, const aae_batch* batch, int32_t k, int3
                  float* val_out_dev, void* stream);
 int aae_pop_ranks(const aae_popular* pop, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
                   int32_t* ranks_out_dev, void* stream);
+/* Ranking metrics from held-out ranks (csrc/rank_metrics.h).  Handle-free like the calls above: every buffer is the caller's, the
+ * launches go to `stream`, nothing synchronises.  With a row's stored ranks in ascending order r_1 <= ... <= r_m - entries order by
+ * (rank, position in the row) - and h = #{r_j <= k}:
+ *   AAE_METRIC_MRR    1 / r_1 if r_1 <= k, else 0                          (replaces reference evaluation.py:94-115 with
+ *   AAE_METRIC_MAP    (sum_{j <= h} j / r_j) / h, 0 if h = 0                rank_metrics_with_std.py mean_reciprocal_rank,
+ *   AAE_METRIC_P      h / k                                                 average_precision; evaluation.py:118-164)
+ *   AAE_METRIC_NDCG   (sum_{j <= h} d[r_j]) / (sum_{i = 1 .. min(k, m)} d[i])   (replaces eval/mpd/mpd_metrics.py:53-119)
+ *   AAE_METRIC_RPREC  #{r_j <= min(m, k)} / m                               (replaces eval/mpd/mpd_metrics.py:43-51)
+ *   AAE_METRIC_CLICKS floor((r_1 - 1) / 10) if r_1 <= k, else k / 10 + 1    (replaces eval/mpd/mpd_metrics.py:133-144)
+ * k = 0 means unbounded and is defined for MRR and MAP only.  A row without entries scores 0, CLICKS k / 10 + 1.  A stored rank
+ * AAE_RANK_ABSENT is "not retrieved": it counts towards m and satisfies no r <= k, unbounded kinds included.  A row of more than
+ * AAE_METRIC_ROW_MAX entries, or with a rank below 1, is NaN in every metric; its neighbours are not touched.
+ * aae_metric_rows    (replaces evaluation.py:94-164, rank_metrics_with_std.py and eval/mpd/mpd_metrics.py:43-144 per row)
+ *                    rows: int64 indptr_dev [n_rows + 1] and int32 ranks_dev in CSR order, as the aae_*_ranks calls write them
+ *                    (item-id order within a row, not ascending).  specs: a HOST array of n_metrics in [1, AAE_METRIC_MAX].
+ *                    discounts_dev [n_discounts] fp64: d[i] at index i - 1, the caller's table (the reference's is
+ *                    1 / log2(1 + i)); read by NDCG specs only, may be NULL without one.  per_row_dev [n_metrics][ld] fp64,
+ *                    ld >= n_rows.  Sums run one term after the other in ascending j: the same bits every run.
+ * aae_metric_finish  (replaces the (mean, std) of evaluation.py:160-163 and rank_metrics_with_std.py: np.mean, np.std)
+ *                    out_dev [n_metrics][2] fp64: the mean and the population standard deviation of the n_rows values of each
+ *                    metric - two passes (the mean, then the mean of the squared deviations, then sqrt), one workgroup per metric,
+ *                    a fixed reduction shape, no float atomics.  n_rows = 0 gives NaN.
+ * aae_ranks_from_lists  (replaces the relevance lookup of evaluation.py:80-91 on lists; eval/mpd/mpd_metrics.py:43-144 take lists)
+ *                    ids_dev [truth->n_rows][ld] int32, a row's list its first k ids, best first, -1 padding as the *_topk calls
+ *                    write it.  truth: the canonical truth rows (ids ascending without duplicates; values not read).
+ *                    ranks_out_dev: one int32 per stored truth entry, CSR order of the call's rows: position + 1 of the entry in
+ *                    its row's list - the smaller one for an id listed twice - or AAE_RANK_ABSENT.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, a negative size, n_metrics out of range,
+ * an unknown kind, k < 0, k = 0 on a kind without an unbounded form, an NDCG spec with k above n_discounts, ld too small, a
+ * negative truth->row_start without rows_dev. */
+#define AAE_METRIC_MAX 32
+#define AAE_METRIC_ROW_MAX 4096
+#define AAE_RANK_ABSENT 2147483647
+typedef enum aae_metric_kind {
+    AAE_METRIC_MRR = 0, AAE_METRIC_MAP = 1, AAE_METRIC_P = 2, AAE_METRIC_NDCG = 3, AAE_METRIC_RPREC = 4, AAE_METRIC_CLICKS = 5
+} aae_metric_kind;
+typedef struct aae_metric_spec {
+    int32_t kind;             /* aae_metric_kind */
+    int32_t k;                /* the cap; 0 = unbounded (MRR, MAP) */
+} aae_metric_spec;
+typedef struct aae_rank_rows {
+    const int64_t* indptr_dev;
+    const int32_t* ranks_dev;
+    int32_t n_rows;
+} aae_rank_rows;
+int aae_metric_rows(const aae_rank_rows* rows, const aae_metric_spec* specs, int32_t n_metrics, const double* discounts_dev,
+                    int32_t n_discounts, double* per_row_dev, int64_t ld, void* stream);
+int aae_metric_finish(const double* per_row_dev, int64_t ld, int32_t n_rows, int32_t n_metrics, double* out_dev, void* stream);
+int aae_ranks_from_lists(const int32_t* ids_dev, int64_t ld, int32_t k, const aae_batch* truth, int32_t* ranks_out_dev, void* stream);
 /* The truncated-SVD baseline (reference svd.py:15-57, SVDRecommender: predict = (X V^T) V[:, :n_items], V = TruncatedSVD's
  * components_ [dims][n_features], n_features = items (+ the tf-idf vocabulary of the titles); csrc/lowrank.h).  Handle-free like
  * the cooc calls.  `lowrank` is ONE fp32 table for both products: vt_dev [n_features][ld], row f = column f of V, ld a multiple

@@ -1281,6 +1281,50 @@ def gen_popular():
           "pred", pred.shape, type(pred).__name__, "bytes", os.path.getsize(path))
 
 
+def gen_challenge():
+    """The three metrics of the RecSys-2018 challenge (eval/mpd/mpd_metrics.py:43-144, as eval/evaluate_dev.py uses them) and the
+    reference's METRICS, per row, on fixed-seed rankings: 700 items, every row a permutation of them (the ranking, best first)
+    and 1 to 200 targets, no row empty.  challenge_metrics.npz holds arrays only: the rankings, the targets as CSR, and per k of
+    CHALLENGE_KS the per-row r_precision / ndcg / playlist_extender_clicks of the ranking cut at k, and per name of METRICS the
+    per-row values of METRICS[name](y_true, y_pred, average=False) on scores that order the items as the ranking does."""
+    import_reference()
+    import aaerec.evaluation as ref_ev
+    import aaerec.rank_metrics_with_std as ref_rm    # noqa: F401  (what ref_ev.METRICS computes with)
+    import eval.mpd.mpd_metrics as ref_mpd
+    rng = np.random.RandomState(2018)
+    n_items, ks = 700, (1, 10, 64, 65, 500)
+    lengths = [1, 2, 3, 63, 64, 65, 200, 1, 2, 5, 10, 11, 20, 21, 100, 199] + rng.randint(1, 201, size=24).tolist()
+    n = len(lengths)
+    perms = np.stack([rng.permutation(n_items) for _ in range(n)]).astype(np.int32)
+    indptr = np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+    targets = []
+    for r, m in enumerate(lengths):
+        # the first rows keep their targets near the head of the ranking, so that small k see hits; the rest anywhere
+        pool = perms[r][:max(m, 40)] if r % 3 == 0 else perms[r]
+        targets.append(np.sort(rng.choice(pool, size=m, replace=False)))
+    indices = np.concatenate(targets).astype(np.int32)
+    out = dict(n_items=np.asarray(n_items), ks=np.asarray(ks, dtype=np.int64), rankings=perms, indptr=indptr, indices=indices)
+    rprec, ndcg, clicks = (np.zeros((len(ks), n)) for _ in range(3))
+    for i, k in enumerate(ks):
+        for r in range(n):
+            t, pred = targets[r].tolist(), perms[r].tolist()
+            rprec[i, r] = ref_mpd.r_precision(t, pred, k)
+            ndcg[i, r] = ref_mpd.ndcg(t, pred, k)
+            clicks[i, r] = ref_mpd.playlist_extender_clicks(t, pred, k)
+    out.update({"r-prec": rprec, "ndcg": ndcg, "clicks": clicks})
+    y_true = np.zeros((n, n_items))
+    y_pred = np.zeros((n, n_items))
+    for r in range(n):
+        y_true[r, targets[r]] = 1.0
+        y_pred[r, perms[r]] = np.arange(n_items, 0, -1, dtype=np.float64)
+    names = sorted(ref_ev.METRICS)
+    out["metric_names"] = np.asarray(names)
+    out["metric_values"] = np.stack([np.asarray(ref_ev.METRICS[name](y_true, y_pred, average=False), dtype=np.float64) for name in names])
+    path = os.path.join(OUT, "challenge_metrics.npz")
+    np.savez_compressed(path, **out)
+    print("challenge_metrics:", n, "rows, lengths", min(lengths), "-", max(lengths), "names", names, "bytes", os.path.getsize(path))
+
+
 ACT_NAMES = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink",
              "Identity", "GELU", "SiLU", "Mish", "Hardswish", "ELU", "LeakyReLU", "Sigmoid"]
 
@@ -1368,6 +1412,8 @@ def main():
         gen_popular()
     if want("metrics"):
         gen_metric_known_answers()
+    if want("challenge"):
+        gen_challenge()
     if want("e2e"):
         gen_e2e_c1(ref_aae)
     if want("e2e_big"):
