@@ -233,8 +233,8 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         m->x3_ok = ok;
         each_dec_crit_x3(false, limit(m->x3_ok, maxlds));
         each_dec_opt_blocks_x3(limit(m->x3_ok, maxlds));
-        // (dec_opt_x3_kernel: the deferred launch of the fp32 step too.  Its 58 112 bytes fit the default limit today, and
-        //  raising the limit of a kernel that already fits is harmless - a wider kXGS then does not fail at the launch)
+        // (dec_opt_x3_kernel: the deferred launch of the fp32 step too.  Its three-term instantiations take 123 648 bytes - the
+        //  58 112 of the tile and 64 KB for the third term of dh2's fragments - and need the raised limit)
         each_dec_opt_x3(false, limit(m->x3_ok, maxlds));
         (void)hipGetLastError();
         if (m->bf16) {
@@ -263,10 +263,17 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
             // at 100).  tools/debug/sweep_split_wgs*.sh, r3: C3 (3125 tiles, 200) 128 -> 0.2652-0.2733 ms/step, 144 ->
             // 0.2651-0.2655, 160 -> 0.2683, 176 -> 0.282; C2 (1469 tiles, 100) 64 -> 0.1806, 80 -> 0.1710, 96 -> 0.1721,
             // 128 -> 0.177, 160 -> 0.185.
+            // Since the launch requests a tile's streams a tile ahead and deals the requests over the matrix phase
+            // (dec_crit_x3.h) a tile costs 2.2 us + 9.6 ns per hidden unit on 112-120 workgroups (tools/dec_opt_width_table.py:
+            // 4.11 us at 200, 3.15 at 100, one-term 3.1 at 100; 3.34 / 2.83 / 2.60 on 32 workgroups) - 0.69 of the above, and
+            // the targets went down with it (57 / 127 us for 82 / 165), so that a shape nobody swept again keeps its width.
             const int ntiles = (m->N + 31) / 32;
-            const double t_tile = (3.3 + 0.0131 * m->h) * (m->bf16_one ? 0.87 : 1.0);     // (one-term products: 4.0 us at 100)
-            int w = (int)(ntiles * t_tile / (m->bf16_one ? 165.0 : 82.0) / 8.0 + 0.5) * 8;      // (C3's shape in bf16: 0.2230 / 0.2264 / 0.2317 / 0.2374 ms on 96 / 112 / 128 / 144)
-            w = std::max(w, std::min(ntiles, m->bf16_one ? 48 : 64));
+            const double t_tile = (2.2 + 0.0096 * m->h) * (m->bf16_one ? 0.98 : 1.0);
+            int w = (int)(ntiles * t_tile / (m->bf16_one ? 127.0 : 57.0) / 8.0 + 0.5) * 8;      // (C3's shape in bf16: 0.2230 / 0.2264 / 0.2317 / 0.2374 ms on 96 / 112 / 128 / 144)
+            // (C2 in bf16, formula: 32, with the tile-ahead launch, tools/split_width_sweep.py, two passes: 0.1532-0.1534 | 0.1542-
+            //  0.1549 | 0.1553-0.1556 | 0.1554-0.1556 | 0.1556-0.1560 | 0.1563-0.1565 | 0.157 | 0.157 | 0.158 ms/step on 40 | 48 | 56 |
+            //  64 | 72 | 80 | 88 | 96 | 104-128: the floor of the one-term launch 48 -> 40)
+            w = std::max(w, std::min(ntiles, m->bf16_one ? 40 : 64));
             // r4, late join (abi_model.h: the launch may run on into the next step's forward pass, so it need not end with the
             // step): half the chip at most - C3 0.2493 (early join, 144) -> 0.2430 ms/step on 128; 0.2515 / 0.2483 / 0.2497 /
             // 0.2492 on 112 / 120 / 136 / 144 (sharp: 124 -> 0.2459, 132 -> 0.2503); the early join on 128: 0.2608.  C2 (formula:
@@ -274,7 +281,12 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
             // r5: the deferred launch no longer requests the 416 float4 slots beyond a tile's span (it read 1.25x the layer): 139.7 ->
             // 130.9 us on 128 workgroups, and the optimum moved down with it - same box, C3: 0.2469 / 0.2359 / 0.2368 / 0.2386 / 0.2378 /
             // 0.2412 ms/step on 104 / 112 / 120 / 124 / 128 / 136 (tools/debug/sweep_split_wgs.sh): 15/32 of the chip
-            const int cap = m->late_enabled ? m->n_cu * 15 / 32 : m->n_cu * 9 / 16;
+            // The tile-ahead launch (110.9 us instead of 126.7 on 120 workgroups, the launch alone): the optimum moved down again -
+            // same box, C3, two passes: 0.2652 / 0.2523 / 0.2423 / 0.2339 / 0.2259 / 0.2255 / 0.2266 / 0.2284 / 0.2331 and 0.2646 /
+            // 0.2520 / 0.2423 / 0.2341 / 0.2255 / 0.2262 / 0.2270 / 0.2281 / 0.2330 ms/step on 72 / 80 / 88 / 96 / 104 / 112 / 120 /
+            // 128 / 136 (the launch before it: 0.2434 / 0.2327 / 0.2294 / 0.2313 and 0.2438 / 0.2326 / 0.2289 / 0.2314 on 104 / 112 /
+            // 120 / 128).  104 and 112 tie and 96 is over the edge: 112, 7/16 of the chip
+            const int cap = m->late_enabled ? m->n_cu * 7 / 16 : m->n_cu * 9 / 16;
             m->split_wgs = std::max(1, std::min(w, cap));
         }
     }

@@ -176,7 +176,8 @@ int launch_output_deferred(aae_model* m, const DecLaunch& L, bool late, bool* la
             // (the 3-term bf16 emulation of dV3 = G^T dh2, dec_crit_x3.h)
             // (one-term instantiation: 78 VGPRs - six of its waves fit a SIMD, so the step's own launches would be dealt onto
             //  its CUs and run beside its streams; its LDS claim is raised until no other workgroup of the step fits there)
-            const uint32_t lds_nat = (uint32_t)dec_opt_x3_lds_bytes();
+            // (the three-term instantiations keep dh2's third term in a 64 KB block of LDS behind the tile: ~124 KB)
+            const uint32_t lds_nat = (uint32_t)dec_opt_x3_lds_bytes(!m->bf16_one);
             const uint32_t lds3 = m->bf16_one ? std::max(lds_nat, 150u * 1024u) : lds_nat;
             // (late join: dec_opt_x3_kernel reads the copies the critical launch set aside)
             if (late) { b.dh2 = m->dh2s.p; b.sc = m->sc_snap; *late_launched = true; }

@@ -514,12 +514,22 @@ namespace aae {
 //   G   (the tile's stored dL/dlogits, fp32 [B][32]) -> three bf16 images gB[t][b][n]; the A operand G^T[n][k = b] is their
 //        transpose: ds_read_b64_tr_b16;
 //   dV3 tile -> os [32][kSO] (fp32) -> the optimiser exactly as in dec_fused.h (S5), V3a / m / v streamed non-temporally,
-//        V3a kept in registers between its load and its update (no LDS copy).
+//        V3a kept in registers between its load and its update (no LDS copy);
+//   the NEXT tile's G, V3a, m and v are requested while this tile multiplies, one request per k-step, into a second
+//        register set; the three-term instantiations pay for it with the third term of dh2's fragments, which lives in a
+//        64 KB block of LDS (one ds_read_b128 per k-step) instead of 16 registers.
 // Waves 0..9 own a column block for both item halves, waves 10..15 one (column block, item half) each of blocks 10..12.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kXGS = 20;       // row stride (dwords) of a G image row: 32 bf16 + pad
 
-inline size_t dec_opt_x3_lds_bytes() { return sizeof(float) * ((size_t)3 * 128 * kXGS + (size_t)kTI * kSO + 64); }
+constexpr int kXDL = 16 * 4 * 64;   // 16-byte slots of the third-term block: [16 waves][4 k-steps][64 lanes]
+
+// three_term: the instantiations that keep dh2's third bf16 term in LDS (ONE == false; the block starts 16-byte aligned)
+inline size_t dec_opt_x3_lds_bytes(bool three_term) {
+    const size_t base = sizeof(float) * ((size_t)3 * 128 * kXGS + (size_t)kTI * kSO + 64);
+    static_assert((3 * 128 * kXGS + kTI * kSO + 64) % 4 == 0, "the third-term block is read 16 bytes at a time");
+    return base + (three_term ? (size_t)kXDL * 16 : 0);
+}
 
 template <int NB, bool ONE = false, bool WIN = false>      // ONE: bf16 mode (first terms only, one matrix instruction per product - see dec_crit_x3_kernel)
 __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
@@ -530,6 +540,7 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     unsigned* gB = reinterpret_cast<unsigned*>(lds);            // [3][128][kXGS]  G tile, rows = batch rows (>= B: zero)
     float* os = reinterpret_cast<float*>(gB + 3 * 128 * kXGS);  // [32][kSO]       dV3a tile
+    u32x4_t* dB2 = reinterpret_cast<u32x4_t*>(os + kTI * kSO + 64);      // [16][KR][64] third term of dh2's fragments (!ONE)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fk = lane >> 4;
@@ -556,7 +567,12 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
     const bool live = cb < NB;
     cb = min(cb, NB - 1);
     // dh2 -> split B fragments: lane (fr, fk) holds column 16 cb + fr, k = batch rows 32 kc + 8 fk + {0..7}
-    bf16x8 dB[KR][3];
+    // The third term of the three-term form is "spilled by design", as the critical launch's dAl / dAx are: each lane writes
+    // its own 16 bytes per k-step here, once, and reads them back in GEMM2 (lane-contiguous 16-byte slots: one conflict-free
+    // ds_read_b128 per k-step, no barrier: writer = reader) - the 16 registers hold the next tile's Adam moments instead.
+    constexpr int NR = ONE ? 1 : 2;             // terms resident in registers
+    bf16x8 dB[KR][NR];
+    u32x4_t* const dB2w = dB2 + (wave * KR) * 64 + lane;
     {
         const int c = min(16 * cb + fr, a.ldh - 1);
 #pragma unroll
@@ -573,7 +589,8 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const u32x4_t v = {p[t][0], p[t][1], p[t][2], p[t][3]};
-                dB[kc][t] = __builtin_bit_cast(bf16x8, v);
+                if (t < NR) dB[kc][t] = __builtin_bit_cast(bf16x8, v);
+                else dB2w[kc * 64] = v;
             }
         }
     }
@@ -587,12 +604,14 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
     const int g_f4 = B * (kTI / 4);             // float4 per stored tile (<= 1024: B <= 128)
     const unsigned gbytes = (unsigned)min((size_t)0x7FFFFFF0u, (size_t)ntiles * g_f4 * 16);
     const __amdgpu_buffer_rsrc_t rGt = __builtin_amdgcn_make_buffer_rsrc(a.Gt, 0, gbytes, 0x00020000);
-    auto ld4 = [&](const __amdgpu_buffer_rsrc_t& r, int tile, int j) {      // (beyond the tensor or the tile's span: zeros, no access; aux 2 = non-temporal)
-        const unsigned vo = tid + kNT * j < tile_f4 ? lane_off + (unsigned)(kNT * 16 * j) : 0x80000000u;
+    // (beyond the tensor or the tile's span, and every slot of a tile past the last one - `there` false: an offset beyond
+    //  the descriptor, zeros, no access; the scalar offset stays that of a real tile.  aux 2 = non-temporal)
+    auto ld4 = [&](const __amdgpu_buffer_rsrc_t& r, int tile, bool there, int j) {
+        const unsigned vo = there && tid + kNT * j < tile_f4 ? lane_off + (unsigned)(kNT * 16 * j) : 0x80000000u;
         return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, vo, win.so(tile), 2));
     };
-    auto ldg = [&](int tile) {
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rGt, tid < g_f4 ? lane_off : 0x80000000u, (unsigned)tile * (unsigned)g_f4 * 16u, 2));
+    auto ldg = [&](int tile, bool there) {
+        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rGt, there && tid < g_f4 ? lane_off : 0x80000000u, (unsigned)tile * (unsigned)g_f4 * 16u, 2));
     };
     int s_rc[NV];
 #pragma unroll
@@ -600,13 +619,31 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
         const int fc = min(tid + kNT * j, tile_f4 - 1), row = fc / f4_per_row;
         s_rc[j] = row * 64 + (fc - row * f4_per_row);
     }
-    float4 p_cur[NV], p_nxt[NV], mreg[NV], sreg[NV], g_nxt;
+    // The pipeline: a tile's four streams (G, V3a, m, v: 1 + 2 + 2 + 2 requests of 16 bytes per lane) are requested a whole
+    // tile ahead, during GEMM2 of the tile before (the first tile's in the prologue), into a second register set that
+    // becomes the current one at the next S0.  In the steady-state loop no wait in front of GEMM2 is for a request of the
+    // same iteration (the one wait there, vmcnt(6), is for the set requested a tile earlier and leaves the six stores of the
+    // tile before in flight), and S5's waits (vmcnt(12) / (8) / (10)) leave the next tile's seven requests in flight; the
+    // copies into the current set sit behind S5's stores.  Plain buffer loads, counted by the compiler.
+    float4 p_cur[NV], p_nxt[NV], m_cur[NV], m_nxt[NV], s_cur[NV], s_nxt[NV], g_nxt;
+    // adam_update (device_common.h) with its multiply-adds fused BY NAME, the way the compiler fused them in this kernel as
+    // long as the update sat in straight-line code: which ones it fuses depends on the control flow around them, and every
+    // bit of a training run is pinned to that choice
+    auto upd = [&](float& p, float& m, float& v, float g) {
+        if (sc.is_sgd) { p = __builtin_fmaf(sc.neg_step_size, g, p); return; }
+        m = __builtin_fmaf(0.1f, g - m, m);
+        v = __builtin_fmaf(0.001f * g, g, v * 0.999f);
+        const float denom = __builtin_fmaf(__builtin_amdgcn_sqrtf(v), sc.inv_bc2_sqrt, 1e-8f);
+        p = __builtin_fmaf(sc.neg_step_size * m, __builtin_amdgcn_rcpf(denom), p);
+    };
     int tile = blockIdx.x;
     const int stride = gridDim.x;
     if (tile < ntiles) {
+        g_nxt = ldg(tile, true);
 #pragma unroll
-        for (int j = 0; j < NV; ++j) p_nxt[j] = ld4(rP, tile, j);
-        g_nxt = ldg(tile);
+        for (int j = 0; j < NV; ++j) p_nxt[j] = ld4(rP, tile, true, j);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) { m_nxt[j] = ld4(rM, tile, true, j); s_nxt[j] = ld4(rV, tile, true, j); }
     }
     __syncthreads();
 
@@ -627,23 +664,38 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
             for (int t = 0; t < NT; ++t) *reinterpret_cast<uint2*>(d + t * (128 * kXGS)) = make_uint2(q0[t], q1[t]);
         }
 #pragma unroll
-        for (int j = 0; j < NV; ++j) p_cur[j] = p_nxt[j];
-        g_nxt = ldg(min(tile + stride, ntiles - 1));
-#pragma unroll
-        for (int j = 0; j < NV; ++j) p_nxt[j] = ld4(rP, min(tile + stride, ntiles - 1), j);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) { mreg[j] = ld4(rM, tile, j); sreg[j] = ld4(rV, tile, j); }
+        for (int j = 0; j < NV; ++j) { p_cur[j] = p_nxt[j]; m_cur[j] = m_nxt[j]; s_cur[j] = s_nxt[j]; }
         lds_barrier();
 
+        // the next tile's seven requests, one at a time (i = 0: G; then V3a, m, v of slot 0 and of slot 1: the order S0 and
+        // S5 need them in).  The last tile of this workgroup requests nothing.
+        const bool there = tile + stride < ntiles;
+        const int tn = min(tile + stride, ntiles - 1);
+        auto req = [&](auto I) {
+            constexpr int i = decltype(I)::value, j = (i - 1) / 3, w = (i - 1) % 3;
+            if constexpr (i == 0) g_nxt = ldg(tn, there);
+            else if constexpr (w == 0) p_nxt[j] = ld4(rP, tn, there, j);
+            else if constexpr (w == 1) m_nxt[j] = ld4(rM, tn, there, j);
+            else s_nxt[j] = ld4(rV, tn, there, j);
+        };
+
         // ---- GEMM2: dV3a[n][c] = sum_b G[b][n] dh2[b][c].  A = G^T: the transpose of 2 x (4 rows b x 16 columns n) of a
-        // G image per fragment (ds_read_b64_tr_b16: lane 4 q + p of a 16-lane group names row q, columns 4 p .. 4 p + 3)
-        if (live) {
-            const int tq = (lz >> 2) & 3, tp = lz & 3, g = lz >> 4;
-            for (int nb2 = nb_lo; nb2 < nb_hi; ++nb2) {
-                f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
-                const unsigned* base = gB + (8 * g + tq) * kXGS + 8 * nb2 + 2 * tp;      // (16 nb2 + 4 p) bf16 = 8 nb2 + 2 p dwords
-#pragma unroll
-                for (int kc = 0; kc < KR; ++kc) {
+        // G image per fragment (ds_read_b64_tr_b16: lane 4 q + p of a 16-lane group names row q, columns 4 p .. 4 p + 3).
+        // The requests are dealt over the phase's k-steps, each at ONE place in the code whatever the wave multiplies: a
+        // request of 1 KB per wave holds the CU's vector-memory path for ~16 clocks, 16 waves x 13 of them per tile for
+        // as long as the tile's matrix instructions take.  Issued in one burst in front of a barrier, behind the six stores of
+        // the tile before, they kept every wave at that barrier while the matrix pipe stood idle.
+        const int tq = (lz >> 2) & 3, tp = lz & 3, gq = lz >> 4;
+        auto gemm2 = [&](auto IT) {             // the wave's IT-th item half (waves 10..15 have one) and requests 4 IT .. 4 IT + 3
+            constexpr int it = decltype(IT)::value;
+            const bool act = live && nb_lo + it < nb_hi;        // (wave-uniform)
+            const int nb2 = nb_lo + it;
+            f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
+            const unsigned* base = gB + (8 * gq + tq) * kXGS + 8 * nb2 + 2 * tp;      // (16 nb2 + 4 p) bf16 = 8 nb2 + 2 p dwords
+            auto kstep = [&](auto KC) {
+                constexpr int kc = decltype(KC)::value;
+                if constexpr (4 * it + kc < 7) req(std::integral_constant<int, (4 * it + kc < 7 ? 4 * it + kc : 0)>());
+                if (act) {
                     bf16x8 ga[3];
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
@@ -654,13 +706,23 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
                         const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                         ga[t] = __builtin_bit_cast(bf16x8, v);
                     }
-                    c = mfma_xt<ONE>(ga, dB[kc], c);
+                    bf16x8 db[3];
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) db[t] = t < NR ? dB[kc][t < NR ? t : 0] : __builtin_bit_cast(bf16x8, dB2w[kc * 64 + oz]);
+                    c = mfma_xt<ONE>(ga, db, c);
                 }
-                // C map: row = item 16 nb2 + 4 fk + r, column = 16 cb + fr
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            kstep(std::integral_constant<int, 0>()); kstep(std::integral_constant<int, 1>());
+            kstep(std::integral_constant<int, 2>()); kstep(std::integral_constant<int, 3>());
+            // C map: row = item 16 nb2 + 4 fk + r, column = 16 cb + fr
+            if (act) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) os[(16 * nb2 + 4 * fk + r) * kSO + 16 * cb + fr] = c[r];
             }
-        }
+        };
+        gemm2(std::integral_constant<int, 0>());
+        gemm2(std::integral_constant<int, 1>());
         lds_barrier();                          // os complete
 
         // ---- S5: optimiser on the tile (or gradient export), as dec_fused.h: every store issued on every path, a lane
@@ -671,9 +733,9 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
             const float4 g = *reinterpret_cast<const float4*>(os + (s_rc[j] >> 6) * kSO + (s_rc[j] & 63) * 4);
             const unsigned so = win.so(tile);
             const unsigned vo = valid ? lane_off + (unsigned)(kNT * 16 * j) : 0x80000000u;
-            float4 p = p_cur[j], mm = mreg[j], vv = sreg[j];
-            adam_update(p.x, mm.x, vv.x, g.x, sc); adam_update(p.y, mm.y, vv.y, g.y, sc);
-            adam_update(p.z, mm.z, vv.z, g.z, sc); adam_update(p.w, mm.w, vv.w, g.w, sc);
+            float4 p = p_cur[j], mm = m_cur[j], vv = s_cur[j];
+            upd(p.x, mm.x, vv.x, g.x); upd(p.y, mm.y, vv.y, g.y);
+            upd(p.z, mm.z, vv.z, g.z); upd(p.w, mm.w, vv.w, g.w);
             const float4 out = do_adam ? p : g;
             const unsigned vo2 = (do_adam && !sc.is_sgd) ? vo : 0x80000000u;
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fu32x4, out), do_adam ? rP : rG, vo, so, 2);
