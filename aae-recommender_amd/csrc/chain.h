@@ -504,16 +504,9 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                 if (lrow < nrows && col < n) {
                     if (grow >= op.row_split) v = op.W[(size_t)grow * op.ldw + col];
                     else if (op.aux_ptr) v = op.aux_ptr[(size_t)grow * op.aux_ld + col] * op.scale;
-                    else if (op.aux == 0) {          // gauss: Box-Muller on two words of the counter generator
-                        const uint32_t u1 = hash_cell(k, (uint32_t)(grow + op.grow0), (uint32_t)(2 * col));
-                        const uint32_t u2 = hash_cell(k, (uint32_t)(grow + op.grow0), (uint32_t)(2 * col + 1));
-                        const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
-                        const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
-                        v = sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2) * op.scale;
-                    } else if (op.aux == 1) {        // categorical: one-hot of a uniform class per row
-                        const uint32_t u = hash_cell(k, (uint32_t)(grow + op.grow0), 0xFFFFFFFFu);
-                        v = ((int)(u % (uint32_t)n) == col) ? op.scale : 0.f;
-                    }                                // bernoulli: the reference's randint(0, 1) is always 0 (aae.py:86-88)
+                    else if (op.aux == 0) v = draw_gauss(k, (uint32_t)(grow + op.grow0), col) * op.scale;
+                    else if (op.aux == 1) v = draw_class(k, (uint32_t)(grow + op.grow0), n) == col ? op.scale : 0.f;   // categorical: one-hot of a uniform class per row
+                    // bernoulli: the reference's randint(0, 1) is always 0 (aae.py:86-88)
                 }
                 dst[lrow * kCL + col] = v;
             }
@@ -524,13 +517,9 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                 if (lrow < nrows && col < n) {
                     float eps;
                     if (op.W) eps = op.W[(size_t)(r0 + lrow) * op.ldw + col];
-                    else {      // Box-Muller on two words of the counter generator (stream id = op.aux)
+                    else {      // the counter generator, stream id = op.aux, the row of the call (every program of this kernel starts at the call's row 0)
                         const uint64_t k = key ^ ((uint64_t)(uint32_t)op.aux * 0xA0761D6478BD642Full);
-                        const uint32_t u1 = hash_cell(k, (uint32_t)(r0 + lrow), (uint32_t)(2 * col));
-                        const uint32_t u2 = hash_cell(k, (uint32_t)(r0 + lrow), (uint32_t)(2 * col + 1));
-                        const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
-                        const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
-                        eps = sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2);
+                        eps = draw_gauss(k, (uint32_t)(r0 + lrow), col);
                     }
                     op.aux_ptr[(size_t)(r0 + lrow) * op.aux_ld + col] = eps;
                     const float mu = src[lrow * kCL + col], lv = src[lrow * kCL + n + col];

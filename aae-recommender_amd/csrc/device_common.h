@@ -185,15 +185,6 @@ struct DropSpec {
     int goff_a, goff_b;
 };
 
-__device__ __forceinline__ uint32_t hash_u32(uint64_t key, uint64_t ctr) {
-    uint64_t x = key ^ (ctr * 0x9E3779B97F4A7C15ull);
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31; x *= 0xD6E8FEB86659FD93ull;
-    x ^= x >> 32;
-    return (uint32_t)x;
-}
-
 __device__ __forceinline__ uint64_t rng_key(uint64_t seed, uint64_t step, uint32_t stream) {
     return seed ^ (step * 0xD1B54A32D192ED03ull) ^ ((uint64_t)stream << 56);
 }
@@ -208,6 +199,22 @@ __device__ __forceinline__ uint32_t hash_cell(uint64_t key, uint32_t row, uint32
     x ^= x >> 15; x *= 0x846CA68Bu;
     x ^= x >> 16;
     return x;
+}
+
+// The two draws behind every sample of a step, from the words of one stream (k = rng_key(seed, step, 0) ^ stream id *
+// 0xA0761D6478BD642F: stream 100 the prior, 12 the VAE's eps), for prior_kernel (kernels.h) and chain.h's COP_PRIOR / COP_REPARAM
+// ops.  chain4.h and chain16x3.h keep their own copies; tests/test_device_rng_gpu.py holds every copy to the same restatement.
+// Standard normal for cell (row, col): Box-Muller on the top 24 bits of the words of columns 2 col and 2 col + 1.
+__device__ __forceinline__ float draw_gauss(uint64_t k, uint32_t row, int col) {
+    const uint32_t u1 = hash_cell(k, row, (uint32_t)(2 * col));
+    const uint32_t u2 = hash_cell(k, row, (uint32_t)(2 * col + 1));
+    const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
+    const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2);
+}
+// Uniform class in [0, n) for a row: the word of column 0xFFFFFFFF.
+__device__ __forceinline__ int draw_class(uint64_t k, uint32_t row, int n) {
+    return (int)(hash_cell(k, row, 0xFFFFFFFFu) % (uint32_t)n);
 }
 
 // returns keep in {0,1}
