@@ -1149,6 +1149,11 @@ class HipAAE:
         """Make the current stream wait for the last step's deferred dec_optim launch (aae_join; no-op when none)."""
         _check(self.lib.aae_join(self.handle, self._stream()))
 
+    def set_lr(self, gen_lr, reg_lr):
+        """The learning rates from the next step on (aae_set_lr): gen_lr for enc_optim / dec_optim, reg_lr for gen_optim / disc_optim."""
+        with self._on_device():
+            _check(self.lib.aae_set_lr(self.handle, float(gen_lr), float(reg_lr)))
+
     def set_split(self, workgroups):
         """0: the fused output layer as one launch on the caller's stream; n > 0: split form, n workgroups for the
         deferred dec_optim launch (aae_set_split)."""
