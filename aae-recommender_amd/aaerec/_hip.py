@@ -253,6 +253,8 @@ _PROTOS = {
     "aae_ipc_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(AaeCollectives)]),
     "aae_ipc_destroy": (C.c_int, [C.POINTER(AaeCollectives), C.c_void_p]),
     "aae_set_input_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "aae_set_input_noise_gen": (C.c_int, [C.c_void_p, C.c_float]),
+    "aae_dae_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "aae_prefetch_batch": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch)]),
     "aae_set_split": (C.c_int, [C.c_void_p, C.c_int32]),
 }
@@ -1359,6 +1361,31 @@ class HipAAE:
         assert noise.shape[1] == self.N
         self._noise_keep = noise
         _check(self.lib.aae_set_input_noise(self.handle, _ptr(noise), noise.shape[1]))
+
+    def set_input_noise_gen(self, scale):
+        """The NEXT training step's encoder reads the dense batch + `scale` x N(0, 1) drawn from the device generator (stream
+        14 of that step, keyed by the global batch row and the item: aae_set_input_noise_gen) - no noise block in memory, and
+        `seed` determines the draws.  Replaces a pending set_input_noise, and is replaced by a later one."""
+        self._noise_keep = None
+        _check(self.lib.aae_set_input_noise_gen(self.handle, float(scale)))
+
+    def dae_thin(self, csr, p, out=None):
+        """`csr` with every entry zeroed with probability `p` by the device generator (aae_dae_thin: stream 13 of the NEXT
+        training step of this handle, keyed by the row's index in `csr` and the item id): a DeviceCSR that shares csr's
+        structure and carries new values - `out` (a float32 device tensor of csr.values' shape; csr.values itself is allowed)
+        or a fresh tensor - and a content id of its own."""
+        if out is None:
+            out = torch.empty_like(csr.values)
+        elif out.shape != csr.values.shape or out.dtype != torch.float32 or out.device != csr.values.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 device tensor of csr.values' shape")
+        with self._on_device():
+            _check(self.lib.aae_dae_thin(self.handle, _ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.values), int(csr.shape[0]),
+                                         float(p), _ptr(out), self._stream()))
+        thinned = DeviceCSR.__new__(DeviceCSR)
+        thinned.touch()                                          # (new values: a content id of its own, aae_batch.generation)
+        thinned.shape, thinned.nnz_per_row_max = csr.shape, csr.nnz_per_row_max
+        thinned.indptr, thinned.indices, thinned.values = csr.indptr, csr.indices, out
+        return thinned
 
     def step(self, csr, row_start, n_rows, rows=None, cond=None, masks=None, z_real=None):
         """One partial_fit without generic conditions (cond: device tensor [n_rows, cond_inc])."""

@@ -9,6 +9,12 @@ noise to every one of the N input columns and returns a NEW tensor: the encoder'
 [B,N]x[N,h] product with a dense weight gradient and an eager Adam over every row of enc.lin1 for those steps
 (`aae_set_input_noise` before the step: `dense_input_kernel` + the split-K GEMM of csrc/gemm_f32.h), the BCE target
 stays the clean batch.
+
+``corrupt_draws`` says where the corruption's draws come from in the device modes.  ``"torch"`` (the default) is torch's global
+generator on the device: `seed` does not determine them.  ``"step"`` draws them from the counter generator that draws the dropout
+masks (stream 13 thins, stream 14 is the Gauss noise), so that `seed` determines the run and a restored
+checkpoint continues it: `aae_dae_thin` thins the matrix handed over - the resident corpus once per epoch, a `partial_fit`
+batch per call - keyed by the first step that reads it, and `aae_set_input_noise_gen` lets the step draw its own noise.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -21,12 +27,18 @@ from .condition import _check_conditions
 
 TINY = 1e-12
 NOISE_TYPES = ("gauss", "zeros")
+CORRUPT_DRAWS = ("torch", "step")
 
 
 class DenoisingAutoEncoder(AutoEncoder):
     def __init__(self, n_hidden=100, n_code=50, lr=0.001, batch_size=100, n_epochs=500, optimizer='adam',
                  normalize_inputs=True, activation='ReLU', dropout=(.2, .2), noise_factor=0.2, corrupt='zeros',
-                 conditions=None, verbose=True, device=None, rng_mode="device", seed=None):
+                 conditions=None, verbose=True, device=None, rng_mode="device", seed=None, corrupt_draws="torch"):
+        if corrupt_draws not in CORRUPT_DRAWS:
+            raise ValueError("corrupt_draws must be one of {}, not {!r}".format(CORRUPT_DRAWS, corrupt_draws))
+        if corrupt_draws == "step" and rng_mode == "reference":
+            raise ValueError("corrupt_draws='step' draws from the device generator: not with rng_mode='reference'")
+        self.corrupt_draws = corrupt_draws
         super().__init__(n_hidden=n_hidden, n_code=n_code, lr=lr, batch_size=batch_size, n_epochs=n_epochs,
                          optimizer=optimizer, normalize_inputs=normalize_inputs, activation=activation,
                          dropout=dropout, conditions=conditions, verbose=verbose, device=device,
@@ -64,6 +76,10 @@ class DenoisingAutoEncoder(AutoEncoder):
         # randomness is the per-batch zeros_noise of the reference (dae.py:48-52, 191) in distribution
         if self.corrupt == "gauss" or self.rng_mode == "reference":
             return csr                                           # drawn per batch, in the reference's order
+        if self.corrupt_draws == "step":
+            # the corpus thinned whole, keyed by (corpus row, item, the epoch's first step); fresh values every epoch - the
+            # previous epoch's last deferred launch may still be reading the previous ones
+            return self.hip.dae_thin(csr, self.noise_factor)
         return self._thinned(csr, torch.rand_like(csr.values) >= self.noise_factor)
 
     def _reference_keep(self, X_batch):
@@ -76,7 +92,10 @@ class DenoisingAutoEncoder(AutoEncoder):
         if self.corrupt == "gauss":
             # the encoder of THIS step reads the dense batch + noise (corruption is drawn before the dropout masks);
             # the BCE target stays the clean batch (gauss_noise returns a new tensor, dae.py:40-45)
-            self.hip.set_input_noise(self._gauss_noise(n_rows))
+            if self.corrupt_draws == "step":
+                self.hip.set_input_noise_gen(self.noise_factor)
+            else:
+                self.hip.set_input_noise(self._gauss_noise(n_rows))
             return super()._run_step(csr, row_start, n_rows, rows, c_batch)
         if self.rng_mode == "reference" and getattr(self, "_in_fit", False):
             # the reference's draw order within a step: corruption mask first, then the dropout masks
@@ -106,20 +125,27 @@ class DenoisingAutoEncoder(AutoEncoder):
         csr = _hip.DeviceCSR(Xs, self.hip.device)
         if self.corrupt == "gauss":
             self.train()
-            self.hip.set_input_noise(torch.as_tensor(noise, dtype=torch.float32) if noise is not None
-                                     else self._gauss_noise(Xs.shape[0]))
+            if noise is None and self.corrupt_draws == "step":
+                self.hip.set_input_noise_gen(self.noise_factor)
+            else:
+                self.hip.set_input_noise(torch.as_tensor(noise, dtype=torch.float32) if noise is not None
+                                         else self._gauss_noise(Xs.shape[0]))
             AutoEncoder._run_step(self, csr, 0, Xs.shape[0], None, condition_data if use_condition else None)
             if self.verbose:
                 self.last_losses = self.hip.losses()
                 log_losses(self.last_losses[0], 0, 0)
             return self
-        if keep is not None:
-            kp = torch.as_tensor(np.asarray(keep), device=self.hip.device) != 0
-        elif self.rng_mode == "reference":
-            kp = self._reference_keep(Xs).to(self.hip.device)
+        if keep is None and self.corrupt_draws == "step":
+            # the batch thinned whole, keyed by (row of the batch, item, the step about to open)
+            csr = self.hip.dae_thin(csr, self.noise_factor)
         else:
-            kp = torch.rand_like(csr.values) >= self.noise_factor
-        csr = self._thinned(csr, kp)
+            if keep is not None:
+                kp = torch.as_tensor(np.asarray(keep), device=self.hip.device) != 0
+            elif self.rng_mode == "reference":
+                kp = self._reference_keep(Xs).to(self.hip.device)
+            else:
+                kp = torch.rand_like(csr.values) >= self.noise_factor
+            csr = self._thinned(csr, kp)
         self.train()
         AutoEncoder._run_step(self, csr, 0, Xs.shape[0], None, condition_data if use_condition else None)
         if self.verbose:

@@ -46,6 +46,7 @@
 #include "chain16x3.h"
 #include "cond_embed.h"
 #include "w1_update.h"
+#include "dae_corrupt.h"
 
 using namespace aae;
 
@@ -114,7 +115,7 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     m->blocked_any = m->opt.blocked_any;
     m->split_any = m->opt.split_any;
     m->x3_gemm = !m->bf16;
-    m->noise_next = nullptr; m->noise_ld = 0; m->dense_step = false;
+    m->noise_next = nullptr; m->noise_ld = 0; m->dense_step = false; m->noise_gen_next = false; m->noise_gen_scale = 0.f;
     m->ae_only = cfg->model_kind == 1 || m->vae;
     m->lazy = true;    // deferred Adam on W1T in both gradient modes (export mode exchanges packed rows)
     // the dynamic-LDS limit of a kernel family (kernel_pick.h each_*): a failure clears the capability flag it belongs to.
@@ -376,6 +377,7 @@ int aae_set_input_noise(aae_handle h, const float* noise_dev, int64_t noise_ld) 
     if (!h->Xn.p) return fail(AAE_ESTATE, "aae_set_input_noise: the model was not created with cfg.dense_noise = 1");
     if (noise_dev && noise_ld < h->N) return fail(AAE_EINVAL, "noise_ld < n_items");
     h->noise_next = noise_dev; h->noise_ld = noise_ld;
+    h->noise_gen_next = false;                 // (a pending aae_set_input_noise_gen is replaced: the later call wins)
     return AAE_OK;
 }
 
@@ -482,6 +484,7 @@ int aae_sync(aae_handle h, void* stream) {
 
 #include "abi_condition.h"
 #include "abi_state_dict.h"
+#include "abi_dae.h"
 #include "abi_step_open.h"
 #include "abi_output_layer.h"
 #include "abi_step_phases.h"

@@ -156,6 +156,8 @@ struct aae_model {
     bool bf16_x3 = false;    // bf16 mode with the output layer on the dec_crit_x3.h kernels (operands rounded to bf16: DecFusedArgs::one_term)
     float* Gt;               // [ntiles][rows][32] dL/dlogits of the running step (aliases the [R][N] scratch G)
     Ten Xn; const float* noise_next; int64_t noise_ld; bool dense_step;   // cfg.dense_noise: dense noisy encoder input (DenoisingAutoEncoder corrupt='gauss')
+    bool noise_gen_next; float noise_gen_scale;   // aae_set_input_noise_gen: the next step draws its noise (stream 14) instead of reading noise_next
+    float* noise_l1;                              // ... [R][kDaeChunksMax] chunk sums of |noise| of the running step's rows (dae_corrupt.h)
     bool bucket_wide_ok = false;   // tile_bucket_wide_kernel may take its LDS
     bool split_any = false;        // AAE_SPLIT_ANY at creation: the split form of the output layer at any size (tests: small fixtures through the critical / deferred kernels)
     float* dp_scratch = nullptr; size_t dp_scratch_floats = 0;   // aae_dp_step: the ranks' gathered packets (hipMalloc, owned by the handle)
@@ -340,6 +342,7 @@ size_t layout(aae_model* m, char* base, bool dry) {
     m->da2 = a.mat(R, h + 1, m->ldh);
     m->Xn = Ten();
     if (c.dense_noise == 1) m->Xn = a.mat(R, N, m->ldn);
+    m->noise_l1 = c.dense_noise == 1 ? a.take((size_t)R * kDaeChunksMax, nullptr) : nullptr;
     m->Gacc = Ten();
     if (c.blocked_output && c.grad_mode == AAE_GRAD_FUSED && R > 16 * kMB) m->Gacc = a.mat(N, h + 1, m->ldh, 2 * kTI);
     m->dh2f = Ten();

@@ -30,11 +30,13 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
     // With the batch's list built ahead nothing sits between the step-opening bookkeeping and the first gather: it rides
     // in that launch (one launch floor, ~4.5 us, less per step)
     constexpr bool fold_ok = true;
-    const bool fold_advance = fold_ok && ahead && m->use_chain && !m->ext_first && m->noise_next == nullptr;
+    // (noise_gen: aae_set_input_noise_gen is pending - the step's noise is drawn, abi_dae.h; a dense step either way)
+    const bool noise_gen = m->noise_gen_next; const float noise_gen_scale = m->noise_gen_scale; m->noise_gen_next = false;
+    const bool fold_advance = fold_ok && ahead && m->use_chain && !m->ext_first && m->noise_next == nullptr && !noise_gen;
     if (!fold_advance)
     hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
                        ahead ? (int*)nullptr : m->stamp, ahead ? (int*)nullptr : m->ucount, m->losses);
-    m->dense_step = m->noise_next != nullptr;
+    m->dense_step = m->noise_next != nullptr || noise_gen;
     const float* noise = m->noise_next; m->noise_next = nullptr;
     if (m->dense_step) {
         if (!m->use_chain) return fail(AAE_ESTATE, "the dense noisy input needs the layer-chain kernels");
@@ -47,9 +49,12 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
         }
         hipLaunchKernelGGL(uniq_items_kernel, dim3(m->rows, std::max(1, std::min(16, m->chunks / 16 + 1))), dim3(256), 0, s, m->bv,
                            m->mark, m->stamp, m->ulist, m->ucount);       // (the list later phases of the step expect)
+        if (noise_gen) TRY(launch_dense_noise_gen(m, noise_gen_scale, s));
+        else {
         hipLaunchKernelGGL(dense_input_kernel, dim3(m->rows), dim3(1024), 0, s, m->bv, noise, m->noise_ld, m->N,
                            (int)m->cfg.normalize_inputs, m->Xn.p, m->ldn);
         LAUNCHCHK("dense_input");
+        }
         const int B = m->rows, h = m->h, N = m->N;
         int tiles = ((B + 63) / 64) * ((h + 63) / 64);
         int splits = std::max(1, std::min(m->max_slabs, 2048 / tiles));

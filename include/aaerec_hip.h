@@ -855,6 +855,23 @@ int aae_profile_read(aae_handle h, int kernel_id, double* total_ms, int64_t* lau
  * optimiser on every row of ENC_W1T.  The BCE target stays the clean batch.  Needs cfg.dense_noise = 1 (room for the
  * dense input; plain autoencoder, fp32, fused optimiser); noise_dev must stay valid until the step has run. */
 int aae_set_input_noise(aae_handle h, const float* noise_dev, int64_t noise_ld);
+/* The same corruption drawn from the device generator (cfg.rng_mode == AAE_RNG_DEVICE, else AAE_ESTATE), so that cfg.seed
+ * determines it and no [rows][n_items] noise block exists in memory: the NEXT step-opening call's encoder reads the dense
+ * batch plus scale x N(0, 1), cell (r, j) = scale * gauss(word stream 14 of the opened step, r, j) with the product in
+ * fp32, r the row of the GLOBAL batch as dropout places it (aae_set_rng_rows), j the item.  Same contract as
+ * aae_set_input_noise: needs cfg.dense_noise = 1, holds for one step, cleared when the step opens.  A pointer set by
+ * aae_set_input_noise and a pending request of this call replace each other: the later call wins. */
+int aae_set_input_noise_gen(aae_handle h, float scale);
+/* DenoisingAutoEncoder(corrupt='zeros'), reference dae.py:48-52 (`batch[rand(batch.size()) < noise_factor] = 0`), on the
+ * entries of a CSR matrix [n_rows, *] in device memory, from the device generator (cfg.rng_mode == AAE_RNG_DEVICE, else
+ * AAE_ESTATE):  out_values[e] = keep ? values[e] : 0  for every entry e of rows [0, n_rows), entry (r, j) kept iff
+ * word(cfg.seed, step, stream 13, r, j) >= min(2^32 - 1, p * 2^32) - the dropout rule, p in [0, 1] the DROP probability
+ * (p == 0 keeps everything).  r is the row's index in the matrix handed over, j the item id, step is *step counter* + 1
+ * read on the device in stream order: the value of the first training step that can read the thinned matrix.  int64
+ * indptr (indptr[0] need not be 0: entries are addressed by indptr's values), int32 indices, float32 values;
+ * out_values_dev == values_dev is allowed.  One launch of a fixed grid whatever n_rows is. */
+int aae_dae_thin(aae_handle h, const int64_t* indptr_dev, const int32_t* indices_dev, const float* values_dev, int64_t n_rows,
+                 float p, float* out_values_dev, void* stream);
 int aae_join(aae_handle h, void* stream);
 /* ... the deferred optimiser launch alone: enough before reading or writing the AAE_T_ACT_* tensors (a prefetch started
  * with aae_prefetch_batch touches enc.lin1 and its bookkeeping only and keeps running). */
