@@ -24,6 +24,9 @@ from .base import Recommender
 from .condition import _check_conditions
 
 STATUS_FORMAT = "[ R: {:.4f}]"
+# widest decoder input [z | conditions | 1] of a VAE handle: fc3 in up to five k-parts of 208 columns (csrc/abi_model.h
+# kVaeDecInMax, include/aaerec_hip.h) - the reference drivers' CONDITIONS need 383 and, eval/mpd/mpd.py, 983
+DEC_IN_MAX = 1040
 
 
 def log_losses(loss):
@@ -51,6 +54,10 @@ class VAE:
         self.training = True
         self.last_loss = None
         code_inc = int(conditions.size_increment()) if conditions else 0
+        if n_code + code_inc + 1 > DEC_IN_MAX:
+            raise ValueError("the VAE's decoder input [z | conditions | 1] is n_code + conditions.size_increment() + 1 = "
+                             "{} + {} + 1 columns: the kernels take at most {} (five parts of 208)".format(
+                                 n_code, code_inc, DEC_IN_MAX))
         dev_probe = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # conditions the kernels produce / train themselves ride in aae_vae_step; any other plugin gets the step cut at
         # the condition boundary and runs with torch autograd in between (aae_vae_encode / _decode_backward / ...)

@@ -132,8 +132,9 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         const int nb = (m->h + 1 + 15) / 16;
         m->fused_nb = nb <= 4 ? 4 : nb <= 7 ? 7 : nb <= 13 ? 13 : 0;
         m->fused_ok = m->fused_nb != 0 && fused_width_ok(m->h, m->ldh);       // (the arena's slab area is sized by the same test)
-        // (a decoder input [z | condition | 1] of up to 2 x 208 columns: two k-parts on the 4-row kernel; the VAE's programs keep 208)
-        m->use_chain = (m->h + 1 <= 208) && (m->c + 1 <= 208) && (m->cp + 1 <= (cfg->model_kind == 3 ? 208 : 2 * 208)) &&
+        // (a decoder input [z | condition | 1] of up to 2 x 208 columns: two k-parts on the 4-row kernel; a VAE handle's: up to
+        //  kVaeInParts parts on the 16-row kernel, abi_chains.h)
+        m->use_chain = (m->h + 1 <= 208) && (m->c + 1 <= 208) && (m->cp + 1 <= (m->vae ? kVaeDecInMax : 2 * 208)) &&
                        !m->opt.no_chain;      // (the code itself has to fit a slot: only the condition block may exceed it)
         const size_t chain_lds = kCSlots * kCR * kCL * sizeof(float);
         if (m->use_chain) each_chain(false, limit(m->use_chain, chain_lds));
@@ -142,7 +143,7 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         if (m->use_chain && m->act_nm) each_chain(true, limit(m->use_chain, chain_lds));
         m->use_chain4 = m->use_chain && !m->act_nm && !m->opt.chain16;
         if (m->use_chain4) each_chain4(limit(m->use_chain4, chain_lds));
-        if (m->use_chain && m->cp + 1 > 208 && !m->use_chain4) m->use_chain = false;
+        if (m->use_chain && m->cp + 1 > 208 && !m->use_chain4 && !m->vae) m->use_chain = false;      // (the AAE's two k-parts: chain4.h alone)
         m->x16_rows = m->opt.x16_rows;
         m->dw_ksplit_rows = 256;                       // (the handle is zero-filled after construction: no default member values)
         if (m->opt.dw_ksplit_rows >= 0) m->dw_ksplit_rows = m->opt.dw_ksplit_rows;

@@ -124,6 +124,58 @@ ChainOp& add_dec_in_dx(ChainBuilder& cb, aae_model* m, int src, int dstA, int ds
     return a;
 }
 
+// ---- the VAE's fc3 over a decoder input wider than a slot: n k-parts of kCWide input columns (the idiom above from 2 to n) ----
+// Part p takes input columns [208 p, 208 (p + 1)), the last one what is left with the constant 1 behind it.  Part 0 sits in a
+// slot of the program (z and the condition's first columns); every later part is loaded into ONE staging slot and added to
+// the layer's destination slot (acc_in), part after part, the last op carrying the epilogue.  A part's weights are the
+// matrix from its first input column on: host pointer arithmetic.  Up to kVaeInParts parts every VAE program is one launch.
+inline int dec_in_parts(const aae_model* m) { return (m->cp + 1 + kCWide - 1) / kCWide; }
+// g: input column j >= g_col0 of row r at g[r * ldg + j - g_col0] (the condition block, or the staged decoder input);
+// keep_zc: the parts go to m->zc as they pass (fc3's weight-gradient launch reads the whole row there); w4: the rank
+// workspace's F4 copy of fc3 (the 4-row kernel's VAE member) or NULL (chain.h's kernel walks the matrix itself)
+ChainOp& add_vae_dec_in_fwd(ChainBuilder& cb, aae_model* m, const float* g, int ldg, int g_col0, bool keep_zc, int slot0, int stage,
+                            int dst, const float* w4) {
+    const int h = m->h, cp = m->cp, n = dec_in_parts(m);
+    auto part = [&](int src, int c0, int K, bool last) -> ChainOp& {
+        ChainOp o = cop_linear(COP_LINEAR, src, dst, m->P[P_V1], K, h, last ? CEPI_DROPACT : CEPI_NONE);
+        o.W += c0; o.acc_in = c0 > 0;
+        if (w4) { o.W4 = w4 + (size_t)(c0 / 4) * h * 4; o.ns4 = h; }      // (F4: chunk stride = outputs x 4 floats)
+        return cb.add(o);
+    };
+    if (n == 1) return part(slot0, 0, cp + 1, true);
+    part(slot0, 0, kCWide, false);
+    for (int p = 1; p < n; ++p) {
+        const int c0 = p * kCWide, nd = std::min(kCWide, cp - c0);       // nd: the part's data columns (0: the constant 1 alone)
+        const bool last = p == n - 1;
+        if (nd > 0) {
+            ChainOp& l = cb.add(cop_load(g + (c0 - g_col0), ldg, stage, nd));
+            if (last) l.one_col = nd;
+            if (keep_zc) cop_out(l, m->zc.p + c0, m->ldc);
+        } else {
+            ChainOp& z = cb.add(cop(COP_DROPACT, stage, stage, 0)); z.one_col = 0;      // (width 0: clears the slot, reads nothing)
+        }
+        ChainOp& o = part(stage, c0, nd + (last ? 1 : 0), last);
+        if (last) return o;
+    }
+    return cb.P.ops[cb.P.nops - 1];      // (not reached: n >= 2)
+}
+// dX of fc3 -> gzc (+ dzc_out, [rows][cp]): the condition's parts through the staging slot first (cond_cols: somebody reads
+// them), then columns [0, 208) - dL/dz among them - into dst0; returns that op
+ChainOp& add_vae_dec_in_dx(ChainBuilder& cb, aae_model* m, int src, int dst0, int stage, bool cond_cols, float* dzc_out) {
+    const int h = m->h, cp = m->cp;
+    auto part = [&](int dst, int c0, int N) -> ChainOp& {
+        ChainOp o = cop_linear(COP_LINEAR_DX, src, dst, m->P[P_V1], h, N, CEPI_NONE);
+        o.W += c0; o.Wkn += c0;
+        if (cond_cols) cop_out(o, m->gzc.p + c0, m->ldc);
+        if (dzc_out) { o.out2 = dzc_out + c0; o.ldo2 = cp; }
+        return cb.add(o);
+    };
+    if (cond_cols)
+        for (int p = dec_in_parts(m) - 1; p >= 1; --p)
+            if (cp - p * kCWide > 0) part(stage, p * kCWide, std::min(kCWide, cp - p * kCWide));
+    return part(dst0, 0, std::min(cp, kCWide));
+}
+
 // chain16x3.h keeps 7 slots: the program's slot numbers (up to 10, one per value for readability) are renamed by live range.
 // A value = one full write of a slot and the reads up to the next full write; it holds a physical slot from its write to its
 // last read.  false: more than 7 values live at once (the caller stays on the 4-row kernel).
@@ -262,8 +314,8 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
         if (cb.P.ops[i].kind == COP_ADV || (cb.P.ops[i].kind == COP_REPARAM && !cb.vae4) || cb.P.ops[i].kind == COP_REPARAM_BWD) four = false;
     if (cb.vae4 && !four) return fail(AAE_ESTATE, "a VAE rank program needs the 4-row chain kernel");
     for (int i = 0; i < cb.P.nops; ++i)
-        if ((cb.P.ops[i].row_lo > 0 || cb.P.ops[i].acc_in || cb.P.ops[i].y_glb) && !four)
-            return fail(AAE_ESTATE, "a program prefix for the upper rows / a layer in two k-parts needs the 4-row chain kernel");
+        if ((cb.P.ops[i].row_lo > 0 || cb.P.ops[i].y_glb) && !four)      // (acc_in: every chain kernel carries it)
+            return fail(AAE_ESTATE, "a program prefix for the upper rows / an epilogue's y from global memory needs the 4-row chain kernel");
     // wide batches: 16 rows per workgroup on the bf16 matrix cores (chain16x3.h)
     if (four && m->x16_ok && cb.P.rows >= (cb.x16_rows > 0 ? cb.x16_rows : m->x16_rows) && !cb.P.bk.enabled && x16_program_ok(cb.P)) {
         ChainProgram X = cb.P;
@@ -811,13 +863,19 @@ int chain_vae_forward(aae_model* m, const float* cond_dev, const float* eps_dev,
     cop_out(ml, m->mulv.p, (int)m->mulv.ld);
     ChainOp& rp = cb.add(cop(COP_REPARAM, 1, 2, c));
     rp.W = eps_dev; rp.ldw = c; rp.aux = 12; rp.aux_ptr = m->veps.p; rp.aux_ld = (int)m->veps.ld;
-    if (m->cfg.cond_inc > 0) {
-        ChainOp& cl = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, m->cfg.cond_inc)); cl.dst_col0 = c; cl.one_col = cp;
+    if (wide_dec_in(m)) {
+        // the condition's first columns behind z (208 columns in all) -> zc; the later parts pass through slot 4
+        ChainOp& ca = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, kCWide - c)); ca.dst_col0 = c;
+        ChainOp& st = cb.add(cop(COP_STORE, 2, 2, kCWide)); cop_out(st, m->zc.p, m->ldc);
     } else {
-        rp.one_col = cp;
+        if (m->cfg.cond_inc > 0) {
+            ChainOp& cl = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, m->cfg.cond_inc)); cl.dst_col0 = c; cl.one_col = cp;
+        } else {
+            rp.one_col = cp;
+        }
+        ChainOp& st = cb.add(cop(COP_STORE, 2, 2, cp)); cop_out(st, m->zc.p, m->ldc);
     }
-    ChainOp& st = cb.add(cop(COP_STORE, 2, 2, cp)); cop_out(st, m->zc.p, m->ldc);
-    ChainOp& v1 = cb.add(cop_fwd(m, P_V1, 2, 3, cp + 1, h, CEPI_DROPACT, s));
+    ChainOp& v1 = add_vae_dec_in_fwd(cb, m, cond_dev, m->cfg.cond_inc, c, true, 2, 4, 3, nullptr);
     v1.one_col = h; cop_out(v1, m->dh2.p, m->ldh);        // no dropout in the VAE: DropSpec stays disabled
     return launch_chain(m, cb, s);
 }
@@ -839,8 +897,9 @@ int chain_vae_encode(aae_model* m, const float* eps_dev, float* z_out, int rows,
 int chain_vae_dec_hidden(aae_model* m, int rows, hipStream_t s) {
     const int h = m->h, cp = m->cp;
     ChainBuilder cb(m, rows);
-    ChainOp& l = cb.add(cop_load(m->zc.p, m->ldc, 2, cp)); l.one_col = cp;
-    ChainOp& v1 = cb.add(cop_fwd(m, P_V1, 2, 3, cp + 1, h, CEPI_DROPACT, s));
+    ChainOp& l = cb.add(cop_load(m->zc.p, m->ldc, 2, std::min(cp, kCWide)));
+    if (!wide_dec_in(m)) l.one_col = cp;
+    ChainOp& v1 = add_vae_dec_in_fwd(cb, m, m->zc.p, m->ldc, 0, false, 2, 4, 3, nullptr);
     v1.one_col = h; cop_out(v1, m->dh2.p, m->ldh);
     return launch_chain(m, cb, s);
 }
@@ -855,9 +914,7 @@ int chain_vae_backward_dec(aae_model* m, const float* part_slabs, size_t slab_st
     } else {
         cb.add(cop_load(m->gb0.p, m->ldh, 2, h));
     }
-    ChainOp& dzc = cb.add(cop_linear(COP_LINEAR_DX, 2, 3, m->P[P_V1], h, cp, CEPI_NONE));
-    cop_out(dzc, m->gzc.p, m->ldc);
-    if (dzc_out) { dzc.out2 = dzc_out; dzc.ldo2 = cp; }
+    add_vae_dec_in_dx(cb, m, 2, 3, 8, true, dzc_out);     // (every column: the caller's plugins take their gradient from dzc_out)
     return launch_chain(m, cb, s);
 }
 int chain_vae_backward_enc(aae_model* m, const float* dz_dev, int ld_dz, hipStream_t s) {
@@ -886,8 +943,8 @@ int chain_vae_backward(aae_model* m, const float* part_slabs, size_t slab_stride
     } else {
         cb.add(cop_load(m->gb0.p, m->ldh, 2, h));         // unfused decoder path: gb0 already holds dL/d(pre-activation)
     }
-    ChainOp& dzc = cb.add(cop_linear(COP_LINEAR_DX, 2, 3, m->P[P_V1], h, cp, CEPI_NONE));
-    if (cp > c) cop_out(dzc, m->gzc.p, m->ldc);          // dL/d(decoder input): its condition columns train a device-native CategoricalCondition
+    // dL/d(decoder input): its condition columns (AAE_T_ACT_DZC) train a device-native CategoricalCondition
+    add_vae_dec_in_dx(cb, m, 2, 3, 8, cp > c, nullptr);
     cb.add(cop_load(m->mulv.p, (int)m->mulv.ld, 4, 2 * c));
     ChainOp& rb = cb.add(cop(COP_REPARAM_BWD, 3, 5, 2 * c)); rb.yslot = 4; rb.scale = m->grad_scale;
     rb.aux_ptr = m->veps.p; rb.aux_ld = (int)m->veps.ld; cop_out(rb, m->gmulv.p, (int)m->gmulv.ld);

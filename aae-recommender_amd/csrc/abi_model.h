@@ -224,6 +224,10 @@ inline bool fused_width_ok(int h, int ldh) {
     return (h + 1 + 15) / 16 <= 13 && ldh <= 256 && (ldh % 4) == 0 && ldh <= kSD - 2;
 }
 
+// a VAE handle's decoder input [z | condition | 1]: fc3 runs in up to kVaeInParts k-parts of kCWide columns (abi_chains.h) -
+// every program of the step, predict and the rank calls is still one launch of at most kCMaxOps ops (the forward: 6 + 2 (n - 1))
+constexpr int kVaeInParts = 5, kVaeDecInMax = kVaeInParts * kCWide;      // 1040: mpd.py's 50 + 932 + 1 = 983 columns
+static_assert(kVaeDecInMax == 1040, "validate()'s message, include/aaerec_hip.h, README.md and aaerec/vae.py name this bound");
 int validate(const aae_config* c) {
     if (!c) return fail(AAE_EINVAL, "cfg is NULL");
     if (c->abi_version != AAE_ABI_VERSION) return fail(AAE_EINVAL, "abi_version mismatch");
@@ -248,8 +252,8 @@ int validate(const aae_config* c) {
     if (c->dtype == 1 && c->model_kind == 3) return fail(AAE_EINVAL, "bf16 arithmetic is not available in VAE mode");
     if (c->model_kind < 0 || c->model_kind > 3 || c->model_kind == 2)
         return fail(AAE_EINVAL, "model_kind must be 0 (AAE), 1 (plain autoencoder) or 3 (VAE)");
-    if (c->model_kind == 3 && (c->n_hidden + 1 > 208 || c->n_code + c->cond_inc + 1 > 208 || 2 * c->n_code > 208))
-        return fail(AAE_EINVAL, "VAE mode needs n_hidden <= 207, n_code + cond_inc <= 207, 2 * n_code <= 208");
+    if (c->model_kind == 3 && (c->n_hidden + 1 > 208 || c->n_code + c->cond_inc + 1 > kVaeDecInMax || 2 * c->n_code > 208))
+        return fail(AAE_EINVAL, "VAE mode needs n_hidden <= 207, n_code + cond_inc + 1 <= 1040 (the decoder input in up to five parts of 208 columns), 2 * n_code <= 208");
     if (c->dp_world < 0 || c->dp_world > 64) return fail(AAE_EINVAL, "dp_world (data-parallel world size) out of range");
     if (c->unfused_decoder != 0 && c->unfused_decoder != 1) return fail(AAE_EINVAL, "unfused_decoder must be 0 or 1");
     return AAE_OK;

@@ -414,9 +414,10 @@ ChainOp vae_cop_fwd(const aae_model* m, int pid, const float* w4, int src, int d
     return o;
 }
 
-// the decoder half: slot 2 holds [z | condition | 1] -> dh2 = act(fc3 zc) (no dropout in the VAE: the DropSpec stays disabled)
-void vae_rank_dec_hidden(aae_model* m, ChainBuilder& cb, const VaeRankCopies& c, float* dh2) {
-    ChainOp& v1 = cb.add(vae_cop_fwd(m, P_V1, c.v1, 2, 3, m->cp + 1, m->h, CEPI_DROPACT));
+// the decoder half: slot 2 holds [z | condition | 1], or the first 208 columns of a wider input whose later k-parts come from
+// g (add_vae_dec_in_fwd) through slot 4 -> dh2 = act(fc3 zc) (no dropout in the VAE: the DropSpec stays disabled)
+void vae_rank_dec_hidden(aae_model* m, ChainBuilder& cb, const VaeRankCopies& c, const float* g, int ldg, int g_col0, float* dh2) {
+    ChainOp& v1 = add_vae_dec_in_fwd(cb, m, g, ldg, g_col0, false, 2, 4, 3, c.v1);
     v1.one_col = m->h; cop_out(v1, dh2, m->ldh);
 }
 
@@ -433,12 +434,14 @@ int vae_rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* c
     cb.add(vae_cop_fwd(m, P_W3, c.w3, 0, 1, h + 1, 2 * nc, CEPI_NONE));
     ChainOp& rp = cb.add(cop(COP_REPARAM, 1, 2, nc));
     rp.W = eps_dev; rp.ldw = nc; rp.aux = 12; rp.grow0 = grow0;        // (stream id 12: chain_vae_forward's draws)
-    if (m->cfg.cond_inc > 0) {
+    if (wide_dec_in(m)) {
+        ChainOp& ca = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, kCWide - nc)); ca.dst_col0 = nc;
+    } else if (m->cfg.cond_inc > 0) {
         ChainOp& cl = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, m->cfg.cond_inc)); cl.dst_col0 = nc; cl.one_col = cp;
     } else {
         rp.one_col = cp;
     }
-    vae_rank_dec_hidden(m, cb, c, dh2);
+    vae_rank_dec_hidden(m, cb, c, cond_dev, m->cfg.cond_inc, nc, dh2);
     return launch_chain(m, cb, s);
 }
 
@@ -448,8 +451,9 @@ int vae_rank_decode_hidden(aae_model* m, const float* zc_dev, int64_t zc_ld, int
     TRY(vae_rank_derive(m, c, s));
     ChainBuilder cb(m, rows);
     cb.vae4 = true;
-    ChainOp& l = cb.add(cop_load(zc_dev, (int)zc_ld, 2, m->cp)); l.one_col = m->cp;
-    vae_rank_dec_hidden(m, cb, c, dh2);
+    ChainOp& l = cb.add(cop_load(zc_dev, (int)zc_ld, 2, std::min(m->cp, kCWide)));
+    if (!wide_dec_in(m)) l.one_col = m->cp;
+    vae_rank_dec_hidden(m, cb, c, zc_dev, (int)zc_ld, 0, dh2);
     return launch_chain(m, cb, s);
 }
 

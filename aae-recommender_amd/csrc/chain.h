@@ -21,7 +21,7 @@ namespace aae {
 constexpr int kCR = 16;        // rows per workgroup
 constexpr int kCL = 212;       // slot row stride (floats): widths up to 208, 16-byte aligned rows
 constexpr int kCSlots = 10;
-constexpr int kCWide = 208;    // columns of a slot row a layer may read (16-byte aligned rows of kCL floats); a wider decoder input runs in two k-parts
+constexpr int kCWide = 208;    // columns of a slot row a layer may read (16-byte aligned rows of kCL floats); a wider decoder input runs in k-parts of this many columns
 constexpr int kCT = 1024;      // threads per workgroup
 constexpr int kCW = kCT / 64;  // waves: 16 (one 16-column block of a layer per wave) or 8 (two blocks per wave)
 constexpr int kCQ = (13 + kCW - 1) / kCW;   // blocks per wave (N <= 208 -> 13 blocks)
@@ -77,8 +77,8 @@ struct ChainOp {
     int fake_slot;                      // COP_PRIOR, chain4.h: >= 0: rows >= row_split come from this slot instead of from W
     const float* y_glb; int y_ld;       // chain4.h, a linear op with the ACTBWD epilogue: y read from global memory [rows][y_ld] (requested
                                         // before the op's products) instead of from a slot that an op of its own loaded
-    int acc_in;                         // COP_LINEAR, chain4.h: 1 = the products are added to what dst holds before the epilogue (the
-                                        // second k-part of a layer whose input is wider than a slot: the decoder's [z | condition | 1])
+    int acc_in;                         // COP_LINEAR: 1 = the products are added to what dst holds before the epilogue (a later k-part
+                                        // of a layer whose input is wider than a slot: the decoder's [z | condition | 1])
 };
 
 struct ChainProgram {
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
             const int b0 = min(wave, nblk - 1), b1 = min(wave + kCW, nblk - 1);
             const bool two = kCQ > 1 && nblk > kCW;
             const EpiCtx ec = chain_epi_ctx(op.epi, op, P, key, slots);
-            const int epiN = chain_pin(op.N);
+            const int epiN = chain_pin(op.N), acc_in = chain_pin(op.acc_in);
             if (!(P.dbg & 1) && wave < nblk) {          // waves without a block (narrow layers) only meet the barriers
                 // Load volume follows the layer: short-K layers (K <= 64) take the 4-chunk /
                 // chunk variant and layers of <= 128 columns skip the second block - the weight stream of a
@@ -404,7 +404,8 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                     for (int r = 0; r < 4; ++r) {
                         const int lrow = fk * 4 + r;
                         float v = 0.f;
-                        if (col < epiN && lrow < nrows) v = chain_epi<NM>(ec, r0 + lrow, lrow, col, acc[q][r]);
+                        // (acc_in, uniform: the layer's earlier k-parts wait in dst - this thread's own cell)
+                        if (col < epiN && lrow < nrows) v = chain_epi<NM>(ec, r0 + lrow, lrow, col, acc_in ? acc[q][r] + dst[lrow * kCL + col] : acc[q][r]);
                         dst[lrow * kCL + col] = v;
                     }
                 }

@@ -267,7 +267,10 @@ int aae_decoder_step(aae_handle h, const aae_batch* batch, const float* zin_dev,
  * cfg.model_kind = AAE_MODEL_VAE: ENC_W1T/B1 = fc1, ENC_W3 = [fc21; fc22] (2 * n_code rows: mu, then logvar), DEC_V1 = fc3,
  * DEC_V3 = fc4; ENC_W2 / DEC_V2 / the discriminator are unused; cfg.gen_lr is the single learning rate and
  * cfg.dropout must be (0, 0).  loss = mean BCE (losses[0]) + KL sum (losses[1]), vae.py:132-145.
- *   cond_dev  constant concatenated condition block [rows][cond_inc] or NULL
+ * Sizes (aae_arena_bytes / aae_create answer AAE_EINVAL beyond them): n_hidden <= 207, 2 * n_code <= 208 and
+ * n_code + cond_inc + 1 <= 1040 - the decoder input [z | condition | 1] runs through fc3 in up to five parts of 208 columns,
+ * which holds the reference drivers' conditions (50 + 332 + 1 and, mpd.py, 50 + 932 + 1 columns).
+ *   cond_dev constant concatenated condition block [rows][cond_inc] or NULL
  *   eps_dev   [rows][n_code] standard-normal draws of reparametrize() (vae.py:115-118); NULL = counter generator
  *             (required when cfg.rng_mode == AAE_RNG_INJECT).  The reference samples eps in predict as well. */
 int aae_vae_step(aae_handle h, const aae_batch* batch, const float* cond_dev, const float* eps_dev, void* stream);

@@ -12,8 +12,13 @@
    its weight copies OUTSIDE the timed launch - their cost is printed beside the pair (the same call's wall time with and
    without them is not separable from the host; they are timed as the wall time of a decode-form call on ONE row, whose
    chain program is a single 51 -> 200 layer, against the same call's chain launch).
+4. (--cond-inc a,b,..: this part alone) aae_vae_step and aae_vae_predict_topk behind a constant condition block of each
+   width, at VR_ITEMS items, VR_HIDDEN hidden units, code 50 and --batch rows per step: ms/step as the median of --repeats
+   timed runs of --steps steps behind --warmup steps, the rank call's ms per call of --batch rows beside it.  A decoder
+   input n_code + cond_inc + 1 beyond 208 columns runs fc3 in k-parts of 208 (csrc/abi_chains.h): 0 and 150 are one slot,
+   332 two parts (the reference's main.py), 932 five (mpd.py).
 VR_PARTS=1,2,3 selects the parts."""
-import os, sys, time
+import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aae-recommender_amd"))
 import numpy as np
@@ -26,7 +31,14 @@ from tools.synth import throughput_corpus
 
 N, h, c, B = int(os.environ.get("VR_ITEMS", 100000)), int(os.environ.get("VR_HIDDEN", 200)), 50, 100
 DOCS, REPS = int(os.environ.get("VR_DOCS", 10000)), int(os.environ.get("VR_REPEATS", 3))
-PARTS = [int(x) for x in os.environ.get("VR_PARTS", "1,2,3").split(",")]
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--cond-inc", default="", help="comma-separated condition widths: time aae_vae_step at each (part 4 alone)")
+_ap.add_argument("--batch", type=int, default=1000)
+_ap.add_argument("--steps", type=int, default=50)
+_ap.add_argument("--warmup", type=int, default=20)
+_ap.add_argument("--repeats", type=int, default=7)
+ARGS = _ap.parse_args()
+PARTS = [4] if ARGS.cond_inc else [int(x) for x in os.environ.get("VR_PARTS", "1,2,3").split(",")]
 med = lambda t: sorted(t)[len(t) // 2]                                                                  # noqa: E731
 
 
@@ -139,3 +151,27 @@ if 3 in PARTS:
                 t.append(ms / max(n, 1) * 1e3)
             out[name] = med(t)
             print(f"{rows:5d} rows, hidden-half program on {name}: median {med(t):.1f} us (repeats {[round(x, 1) for x in sorted(t)]})", flush=True)
+
+if 4 in PARTS:
+    Bt = ARGS.batch
+    Xt = throughput_corpus(Bt * 8, N, seed=77)
+    for inc in [int(x) for x in ARGS.cond_inc.split(",")]:
+        dev = HipAAE(N, h, c, cond_inc=inc, max_batch=Bt, rng_mode="device", seed=1, dropout=(0.0, 0.0), vae=True)
+        tcsr = DeviceCSR(Xt, dev.device)
+        cond = torch.randn(Bt, inc, device=dev.device) * 0.4 if inc else None
+        it = [0]
+
+        def one_step():
+            dev.vae_step(tcsr, (it[0] % 8) * Bt, Bt, cond=cond)
+            it[0] += 1
+        region(one_step, ARGS.warmup)
+        t_step = [region(one_step, ARGS.steps) for _ in range(ARGS.repeats)]
+        rows = min(Bt, dev.vae_rank_max_rows(10))
+        crow = None if cond is None else cond[:rows]
+        region(lambda: dev.vae_predict_topk(tcsr, 0, rows, 10, cond=crow), 3)
+        t_rank = [region(lambda: dev.vae_predict_topk(tcsr, 0, rows, 10, cond=crow), 10) for _ in range(ARGS.repeats)]
+        print(f"cond_inc {inc:4d} (decoder input {c + inc + 1:4d} columns, {(c + inc + 1 + 207) // 208} part(s)), {N} items, hidden {h}, "
+              f"batch {Bt}: aae_vae_step median {med(t_step):.4f} ms/step (min {min(t_step):.4f}, max {max(t_step):.4f}, "
+              f"{ARGS.repeats} runs of {ARGS.steps}) | aae_vae_predict_topk(k=10), {rows} rows: median {med(t_rank):.3f} ms "
+              f"(min {min(t_rank):.3f}, max {max(t_rank):.3f}); vae_rank_max_rows(10) = {dev.vae_rank_max_rows(10)}", flush=True)
+        dev.close()
