@@ -222,6 +222,11 @@ _PROTOS = {
     "aae_pop_counts": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.c_void_p, C.c_void_p]),
     "aae_pop_topk": (C.c_int, [C.POINTER(AaePopular), C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_pop_ranks": (C.c_int, [C.POINTER(AaePopular), C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32, C.c_void_p, C.c_void_p]),
+    "aae_rand_scores": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_rand_topk": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    "aae_rand_ranks": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_int32,
+                                 C.c_void_p, C.c_void_p]),
     "aae_metric_rows": (C.c_int, [C.POINTER(AaeRankRows), C.POINTER(AaeMetricSpec), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_int64, C.c_void_p]),
     "aae_metric_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -847,6 +852,45 @@ def pop_ranks(pop, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclud
     the addressing of the input rows; n_truth = their stored entries), CSR order, in pop_topk's ordering (aae_pop_ranks)."""
     lead = (pop.struct(), _csr_batch(csr, row_start, n_rows, rows), _csr_batch(truth_csr, row_start, n_rows, rows))
     return _ranks_call(load_library().aae_pop_ranks, pop.device, torch.cuda.device(pop.device), n_truth, exclude_known, lead)
+
+
+# ---- the random baseline (aae_rand_*; csrc/randrank.h) --------------------------------------------------------------------
+RAND_BITS = 24            # bits of a draw: the most a float32 score holds exactly
+RAND_TRUTH_MAX = 4096     # most held-out items of a row aae_rand_ranks sorts in LDS (csrc/randrank.h kRandTruthMax)
+
+
+def _rand_lead(seed, draw, row0, bits, n_items):
+    return (C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), int(row0), int(bits), int(n_items))
+
+
+def rand_scores(seed, draw, row0, n_rows, n_items, device, bits=RAND_BITS, out=None):
+    """float32 device matrix [n_rows, >= n_items]: the scores of rows [row0, row0 + n_rows) of draw number `draw` under `seed`,
+    s * 2^-bits with s the top `bits` bits of the generator's word for (row, item) (aae_rand_scores).  out: the caller's matrix."""
+    device = torch.device(device)
+    out = _scratch(device, n_rows, int(n_items), out, torch.float32, "out", False)
+    with torch.cuda.device(device):
+        _check(load_library().aae_rand_scores(*_rand_lead(seed, draw, row0, bits, n_items), int(n_rows), _ptr(out), int(out.stride(0)),
+                                              _stream_of(device)))
+    return out
+
+
+def rand_topk(seed, draw, row0, n_items, csr, row_start, n_rows, k, rows=None, exclude_known=True, bits=RAND_BITS):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors: per row the k items with the largest draws that
+    the row of the DeviceCSR `csr` does not hold, for rows [row_start, row_start + n_rows) (or the rows named by the int32 device
+    tensor `rows`), which are rows row0 .. of the test set for the generator; k in [1, min(RANK_K_MAX, items)] (aae_rand_topk)."""
+    device = csr.indptr.device
+    lead = _rand_lead(seed, draw, row0, bits, n_items) + (_csr_batch(csr, row_start, n_rows, rows),)
+    return _list_call(load_library().aae_rand_topk, device, torch.cuda.device(device), n_rows, k, exclude_known, lead)
+
+
+def rand_ranks(seed, draw, row0, n_items, csr, row_start, n_rows, truth_csr, n_truth, rows=None, exclude_known=True, bits=RAND_BITS):
+    """int32 device tensor [n_truth]: the 1-based rank of every stored entry of the truth rows (the rows of `truth_csr` with the
+    addressing of the input rows, at most RAND_TRUTH_MAX entries each; n_truth = their stored entries), CSR order, in rand_topk's
+    ordering (aae_rand_ranks)."""
+    device = csr.indptr.device
+    lead = _rand_lead(seed, draw, row0, bits, n_items) + (_csr_batch(csr, row_start, n_rows, rows),
+                                                          _csr_batch(truth_csr, row_start, n_rows, rows))
+    return _ranks_call(load_library().aae_rand_ranks, device, torch.cuda.device(device), n_truth, exclude_known, lead)
 
 
 # ---- ranking metrics from held-out ranks (aae_metric_*, aae_ranks_from_lists; csrc/rank_metrics.h) ------------------------------

@@ -51,9 +51,13 @@ def ranks_csr(parts, Ys):
     return _ranks_csr(torch.cat(parts).cpu().numpy().astype(np.int32, copy=False) if parts else np.zeros(0, dtype=np.int32), Ys)
 
 
-def rank_metrics(parts, Ys, metrics, k=None):
+def rank_metrics(parts, Ys, metrics, k=None, reduce_on="device"):
     """[(mean, std)] per metric name from the device parts of a chunked call and the canonical truth Ys, without a CSR of ranks
     on the host: the parts are concatenated where they are and csrc/rank_metrics.h answers; 16 bytes per metric come back.
+    reduce_on="host": the device forms the per-row values alone and [metrics, rows] doubles come back, which numpy reduces as the
+    host route reduces its own - the pairs are then the host route's to the bit wherever a row's value is (one held-out item a
+    row, the drivers' drop=1: one term, always; longer rows sum their terms in ascending j on both sides, csrc/rank_metrics.h
+    ARITHMETIC, except numpy's pairwise mean of eight or more hits), where the device's own reduction agrees to rounding.
     k None: parts are the int32 rank parts of a predict_ranks call (CSR order of Ys).  k given: parts are the (ids, scores) parts
     of a predict_topk call with lists of k ids; aae_ranks_from_lists turns them into ranks, and an unbounded name or one beyond
     k raises the ValueError of evaluation.evaluate_topk.  Where the device route is closed (evaluation.device_metrics_ok: a row
@@ -79,20 +83,22 @@ def rank_metrics(parts, Ys, metrics, k=None):
         truth = _hip.DeviceCSR(Ys, device)
         ids = torch.cat([p[0] for p in parts]).contiguous()
         ranks, indptr = _hip.ranks_from_lists(ids, truth, 0, Ys.shape[0], int(Ys.nnz), k=k), truth.indptr
+    if reduce_on == "host":
+        return [(v.mean(), v.std()) for v in _hip.rank_metrics(indptr, ranks, ev._device_specs(specs), per_row=True)]
     return ev._pairs(_hip.rank_metrics(indptr, ranks, ev._device_specs(specs)))
 
 
 # What predict_ranks / predict_topk return, by route and by whether metrics were asked for (metrics=None: ranks / lists as ever)
-def finish_ranks(parts, Ys, metrics=None):
-    """The device route of a predict_ranks call: the CSR of ranks, or [(mean, std)] of `metrics`."""
-    return ranks_csr(parts, Ys) if metrics is None else rank_metrics(parts, Ys, metrics)
+def finish_ranks(parts, Ys, metrics=None, reduce_on="device"):
+    """The device route of a predict_ranks call: the CSR of ranks, or [(mean, std)] of `metrics` (reduce_on: rank_metrics)."""
+    return ranks_csr(parts, Ys) if metrics is None else rank_metrics(parts, Ys, metrics, reduce_on=reduce_on)
 
 
-def finish_lists(parts, k, metrics=None, y_true=None, shape=None):
+def finish_lists(parts, k, metrics=None, y_true=None, shape=None, reduce_on="device"):
     """The device route of a predict_topk call: (ids, scores), or [(mean, std)] of `metrics` against y_true [shape]."""
     if metrics is None:
         return lists(parts, k)
-    return rank_metrics(parts, list_truth(y_true, shape), metrics, k=k)
+    return rank_metrics(parts, list_truth(y_true, shape), metrics, k=k, reduce_on=reduce_on)
 
 
 def list_truth(y_true, shape):

@@ -39,6 +39,7 @@
 #include "sptrans.h"
 #include "mutinfo.h"
 #include "popular.h"
+#include "randrank.h"
 #include "rank_metrics.h"
 #include "lowrank.h"
 #include "chain.h"
@@ -495,6 +496,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_sptrans.h"
 #include "abi_mutinfo.h"
 #include "abi_popular.h"
+#include "abi_random.h"
 #include "abi_metrics.h"
 #include "abi_lowrank.h"
 #include "abi_data_parallel.h"

@@ -179,6 +179,11 @@ inline auto pick_pop_counts() { return pop_counts_kernel; }
 inline auto pick_pop_topk() { return pop_topk_kernel; }
 inline auto pick_pop_ranks() { return pop_ranks_kernel; }
 
+// ---- randrank.h: the random baseline's score block, lists (static LDS) and ranks (dynamic LDS below the default limit: none to raise)
+inline auto pick_rand_scores() { return rand_scores_kernel; }
+inline auto pick_rand_topk() { return rand_topk_kernel; }
+inline auto pick_rand_ranks() { return rand_ranks_kernel; }
+
 // ---- rank_metrics.h: per-row metric values from ranks, their (mean, std), ranks from lists.  Static LDS: no limit to raise
 inline auto pick_metric_rows() { return metric_rows_kernel; }
 inline auto pick_metric_finish() { return metric_finish_kernel; }

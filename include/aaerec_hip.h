@@ -622,6 +622,38 @@ int aae_pop_topk(const aae_popular* pop, const aae_batch* batch, int32_t k, int3
                  float* val_out_dev, void* stream);
 int aae_pop_ranks(const aae_popular* pop, const aae_batch* batch, const aae_batch* truth, int32_t exclude_known,
                   int32_t* ranks_out_dev, void* stream);
+/* The random baseline (reference baselines.py:7-19, RandomBaseline: predict = rand(rows, items); csrc/randrank.h) from the
+ * library's keyed generator.  Handle-free like the pop calls: every buffer is the caller's, the launches go to `stream`, nothing
+ * synchronises, and no [rows][n_items] scratch exists on the ranking calls: a draw is regenerated wherever it is needed.
+ *   key    = rng_key(seed, draw, 0) ^ 15 * 0xA0761D6478BD642F      (stream 15 of the generator, csrc/device_common.h)
+ *   s(r,j) = hash_cell(key, r, j) >> (32 - bits)                    (an integer in [0, 2^bits))
+ *   score  = s * 2^-bits                                            (exact in fp32)
+ * for item j of row r = row0 + the row of the call: the row's index in the caller's WHOLE test set, so that a call over rows
+ * [a, b) with row0 = a computes what those rows of one call over everything compute.  `batch` addresses the known items of the
+ * call's rows as in every aae_batch (row_start / rows_dev; its values are not read, values_dev may be NULL).
+ * aae_rand_scores  out_dev [n_rows][ld] fp32, ld >= n_items: the scores.
+ * aae_rand_topk    idx_out_dev / val_out_dev [batch->n_rows][k], k in [1, min(1024, n_items)]; val_out_dev may be NULL.  A row's
+ *                  list: the k items it does not know (exclude_known; otherwise of all items) with the largest s, the larger s
+ *                  first and the smaller id at equal s, as in every ranking call - an exact two-level radix select over the
+ *                  bits-bit values, the candidate buffer bounded by k; id -1 / score 0 behind its last rankable item.  A scaled
+ *                  score is the min-max scaling over ALL items of the row, known ones included, in fp32:
+ *                  (score - min) * inv, span = max - min, inv = span > 0 ? 1 / span : 1.
+ * aae_rand_ranks   one int32 per stored entry of the truth rows, CSR order: 1 + #{i not known, i != j, s_i > s_j or (s_i == s_j
+ *                  and i < j)}.  A truth entry that is a known item ranks behind every rankable item, among the known items by id:
+ *                  1 + (n_items - m) + #{known j < t} for a row of m known items; a truth id outside [0, n_items) ranks 0 - both
+ *                  as in aae_pop_ranks.  truth->max_row_nnz bounds the entries of a truth row (0 = unknown: 4096 is assumed); a
+ *                  row that holds more entries than the bound it was given ranks 0 throughout.
+ * CONTRACT for both ranking calls, as in every dense ranking call: the ids of a batch row lie in [0, n_items) and ascend without
+ * duplicates.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, n_items <= 0, k out of range, bits outside
+ * [1, 24], a negative draw, row0 or row count, row0 + rows beyond 2^31, ld < n_items, truth->n_rows != batch->n_rows,
+ * truth->max_row_nnz > 4096.  No rows: nothing is launched. */
+int aae_rand_scores(uint64_t seed, int64_t draw, int64_t row0, int32_t bits, int32_t n_items, int32_t n_rows, float* out_dev,
+                    int64_t ld, void* stream);
+int aae_rand_topk(uint64_t seed, int64_t draw, int64_t row0, int32_t bits, int32_t n_items, const aae_batch* batch, int32_t k,
+                  int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_rand_ranks(uint64_t seed, int64_t draw, int64_t row0, int32_t bits, int32_t n_items, const aae_batch* batch,
+                   const aae_batch* truth, int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
 /* Ranking metrics from held-out ranks (csrc/rank_metrics.h).  Handle-free like the calls above: every buffer is the caller's, the
  * launches go to `stream`, nothing synchronises.  With a row's stored ranks in ascending order r_1 <= ... <= r_m - entries order by
  * (rank, position in the row) - and h = #{r_j <= k}:
