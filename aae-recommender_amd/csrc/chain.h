@@ -268,7 +268,13 @@ __device__ __forceinline__ void chain_linear_fwd(const ChainOp& op, const float*
 // 4 MFMAs; A is masked to zero for k >= K (the slot may hold stale columns there), the weight rows up to
 // 16 * ceil(K / 16) - 1 exist because the arena keeps 16 zero rows behind every weight matrix the chain reads
 // (layout(): pad_rows), so the row index needs no clamp.
-template <int MC, bool TWO>
+// BF (bf16 mode of the build): both operands rounded to the nearest bf16 value on the way into the fp32 instruction - a dX
+// product of a Linear layer is one of the mode's rounded products (oracle/aae_oracle.py _mlp_bwd), as chain4.h's and the
+// per-layer GEMM's; the products of two bf16 values are exact in fp32 and the accumulation stays fp32.
+__device__ __forceinline__ float chain_rb(float x) {       // nearest bf16 value (ties to even), as fp32
+    return __builtin_bit_cast(float, gemm_pack_bf16(x, 0.f) << 16);
+}
+template <int MC, bool TWO, bool BF>
 __device__ __forceinline__ void chain_linear_dx(const ChainOp& op, const float* src, int b0, int b1, int fr, int fk,
                                                 f32x4 (&acc)[2]) {
     const int ldw = op.ldw, N = op.N, K = op.K;
@@ -286,6 +292,13 @@ __device__ __forceinline__ void chain_linear_dx(const ChainOp& op, const float* 
             if (TWO) y1[c * 4 + e] = *reinterpret_cast<const float*>(base + o1);
         }
     }
+    if (BF) {
+#pragma unroll
+        for (int j = 0; j < MC * 4; ++j) {
+            y0[j] = chain_rb(y0[j]);
+            if (TWO) y1[j] = chain_rb(y1[j]);
+        }
+    }
 #pragma unroll
     for (int c = 0; c < MC; ++c) {
         if (c < kch) {
@@ -295,6 +308,7 @@ __device__ __forceinline__ void chain_linear_dx(const ChainOp& op, const float* 
             if (k0 + 1 >= K) xa.y = 0.f;
             if (k0 + 2 >= K) xa.z = 0.f;
             if (k0 + 3 >= K) xa.w = 0.f;
+            if (BF) { xa.x = chain_rb(xa.x); xa.y = chain_rb(xa.y); xa.z = chain_rb(xa.z); xa.w = chain_rb(xa.w); }
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.x, y0[c * 4 + 0], acc[0], 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.y, y0[c * 4 + 1], acc[0], 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.z, y0[c * 4 + 2], acc[0], 0, 0, 0);
@@ -390,8 +404,8 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                     else          { if (two) chain_linear_fwd<13, true>(op, src, b0, b1, fr, fk, acc); else chain_linear_fwd<13, false>(op, src, b0, b1, fr, fk, acc); }
                 } else {
                     const int kch = (op.K + 15) >> 4;
-                    if (kch <= 4) { if (two) chain_linear_dx<4, true>(op, src, b0, b1, fr, fk, acc); else chain_linear_dx<4, false>(op, src, b0, b1, fr, fk, acc); }
-                    else          { if (two) chain_linear_dx<13, true>(op, src, b0, b1, fr, fk, acc); else chain_linear_dx<13, false>(op, src, b0, b1, fr, fk, acc); }
+                    if (kch <= 4) { if (two) chain_linear_dx<4, true, BF>(op, src, b0, b1, fr, fk, acc); else chain_linear_dx<4, false, BF>(op, src, b0, b1, fr, fk, acc); }
+                    else          { if (two) chain_linear_dx<13, true, BF>(op, src, b0, b1, fr, fk, acc); else chain_linear_dx<13, false, BF>(op, src, b0, b1, fr, fk, acc); }
                 }
             }
             chain_barrier();      // dst may alias a slot other waves were still reading (src != dst is required)

@@ -603,8 +603,9 @@ class OracleDecoder(OracleAAE):
     aae.py:494-502) -> the 3-layer Decoder -> BCE against the item rows; one optimiser for the decoder, the
     conditions step their own.  Condition stand-ins start from an empty code block."""
 
-    def __init__(self, params, lr=1e-3, optimizer="adam", activation="ReLU", dropout=(0.2, 0.2), conditions=None):
+    def __init__(self, params, lr=1e-3, optimizer="adam", activation="ReLU", dropout=(0.2, 0.2), conditions=None, bf16=False):
         self.p = {k: np.array(v, dtype=f32) for k, v in params.items() if k.startswith("dec.")}
+        self.bf16 = bool(bf16)       # the build's bf16 mode: _mlp_fwd / _mlp_bwd round the operands of the same products as OracleAAE's
         self.N = self.p["dec.lin3.weight"].shape[0]
         self.act, self.dropout = activation, tuple(dropout)
         self.alpha_mode = activation == "SELU"

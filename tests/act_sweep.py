@@ -255,3 +255,168 @@ def ratio_tol(name, s, x, u, expected):
     """|s| L (eps(x) + eps(s f(x))) + 1e-5 |expected|: the bound of one layer's derivative, propagated through f'(u) s f'(x) with
     |f'| <= L, plus the output-layer product that feeds the upstream gradient."""
     return abs(s) * SUP_DF[name] * (eps_df(name, x) + eps_df(name, u)) + 1e-5 * np.abs(expected)
+
+
+# ---- the probes' fixed parts (tests/test_act_sweep_gpu.py; tests/test_act_sweep_cpu.py runs the bf16 reference below against the
+# oracle on the same model) --------------------------------------------------------------------------------------------------
+N_ITEMS = 2048      # the output layer: logits = h2 . u / N stay within +-1 for every class (asserted on the reference)
+
+
+@functools.lru_cache(maxsize=None)
+def out_layer(H):
+    """dec.lin3: all positive, entries in [0.5, 1.5] / N."""
+    w = (np.random.default_rng(7).uniform(0.5, 1.5, size=(N_ITEMS, H)) / N_ITEMS).astype(f32)
+    w.setflags(write=False)
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def enc_upstream(rows, H):
+    rng = np.random.default_rng(11)
+    g = (rng.uniform(0.5, 1.5, size=(rows, H)) * rng.choice([-1.0, 1.0], size=(rows, H))).astype(f32)
+    g.setflags(write=False)
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def forward_tolerance(name, rows, H, s):
+    """max(2e-6, 4 x the oracle's own error of the composite against float64 on this sweep), relative to max(1, |y|)."""
+    from oracle import aae_oracle as O
+    c = composite(name, rows, H, s)
+    y = O.act_fwd(name, (f32(s) * O.act_fwd(name, c["x"])).astype(f32))
+    keep = ~excluded(name, c["x"], c["u"])
+    own = (np.abs(y - c["h2"]) / np.maximum(1.0, np.abs(c["h2"])))[keep].max()
+    return max(2e-6, 4.0 * float(own))
+
+
+# ---- bf16 mode (dtype = 'bf16'): the same composite with bf16_round where the mode applies it ---------------------------------
+# The rounding points are OracleAAE._linear's and _mlp_bwd's (oracle/aae_oracle.py): a Linear layer's forward product and its dX
+# product take both operands rounded, the sparse first encoder layer takes none.  On the probes' model ([identity, s I] stacks,
+# zero biases; 1 and s = 1, -2 are bf16 values, so a product has one non-zero term and is exact):
+#   decoder probe   dec.lin1 = I rounds its input: h1 = f(R(X));  dec.lin2 = s I rounds h1: h2 = f(s R(h1)) = AAE_T_ACT_DH2;  the
+#                   output layer rounds h2 and G = dL/dlogits: g2 = R(G) V (V itself made of bf16 values for this test);  dX of
+#                   dec.lin2 rounds ga2 = g2 f'(u), dX of dec.lin1 rounds ga1 = s R(ga2) f'(R(X)):  dzc = R(ga1)
+#   encoder probe   the first layer is not rounded: AAE_T_ACT_A1 = X bit for bit, h1 = f(X);  enc.lin2 rounds h1: h2 = f(s R(h1));
+#                   enc.lin3 = I rounds h2: z = R(h2);  backward from dz = G: dX of enc.lin3 rounds G, dX of enc.lin2 rounds
+#                   ga2 = R(G) f'(u):  AAE_T_ACT_GA1 = s R(ga2) f'(X)
+# So the expected ratio to the upstream gradient is the plain f'(u) s f'(x) at the rounded points, and the gradient passes two
+# roundings on its way down.  bf16 keeps 8 significant bits: a rounding moves a value by up to half a unit in its last place,
+# 2^-8 relative just above a power of two (2^-9 just below the next) - so 2 x 2^-8 = 2^-7 |expected| on top of the fp32 sweep's
+# ratio_tol (derived, not measured; test_act_sweep_cpu.py holds the oracle's own run of the probes to it, and finds single
+# roundings of 0.96 x 2^-8).  Where an output is itself rounded (z = R(h2)) it is compared with R of the reference: bf16_z.
+# A device h1 that differs from the reference by fp32 units can land on the other side of a bf16 rounding boundary: a point is
+# AMBIGUOUS when its reference h1 lies within the fp32 error of h1 of the midpoint of two bf16 values, and may then match either
+# neighbour's continuation.  That error is the fp32 sweep's forward tolerance RELATIVE to |h1| - not to max(1, |h1|), the form
+# it takes where errors of both layers add up: below 1 the bf16 spacing shrinks with |h1|, and an absolute 2e-6 would call a
+# third of the grid ambiguous for every class that decays towards 0 (Sigmoid, Softplus, SiLU ..) - plus what a class computes
+# with an ABSOLUTE error: GELU's 1 + erf cancels on the left (0.5 |x| times erff's 4 units at 1), Hardsigmoid's x / 6 + 0.5 is
+# rounded at 0.5, and results below the smallest normal float32 may be flushed.
+AMBIGUITY_FLOOR = {"GELU": lambda x: 0.5 * np.abs(x) * LIB_ULPS * 2.0 ** -24, "Hardsigmoid": lambda x: 2.0 ** -24 + 0.0 * x}
+BF16_EPS = 2.0 ** -8
+
+
+def bf16_values(h):
+    """(R(h), the bf16 neighbour of R(h) on h's side, their midpoint) of float64 h, as float64"""
+    from oracle.aae_oracle import bf16_round
+    h32 = np.ascontiguousarray(h, dtype=f32)
+    r = bf16_round(h32)
+    bits = r.view(np.uint32)
+    mag = bits & np.uint32(0x7FFFFFFF)
+    up = np.abs(np.asarray(h, dtype=np.float64)) > np.abs(r.astype(np.float64))
+    step = np.where(up, np.uint32(0x10000), np.where(mag >= np.uint32(0x10000), np.uint32(0xFFFF0000), np.uint32(0)))       # (+1 / -1 bf16 unit of magnitude)
+    with np.errstate(over="ignore"):
+        other = (bits + step).view(f32)
+    r64, o64 = r.astype(np.float64), other.astype(np.float64)
+    return r64, o64, 0.5 * (r64 + o64)
+
+
+def _f_df(name, v):
+    t = torch.tensor(np.asarray(v, dtype=np.float64), requires_grad=True)
+    y = module(name)(t)
+    y.sum().backward()
+    return y.detach().numpy(), t.grad.numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def composite_bf16(name, rows, width, s, probe):
+    """The probe's element-wise composite in bf16 mode, float64 between the roundings: xin (what the first activation sees:
+    R(x) in the decoder probe, x in the encoder probe), h1 = f(xin), the ambiguity mask `amb`, and for both continuations k = 0
+    (the nearest bf16 value of h1) and 1 (its neighbour across the midpoint): u[k] = s R_k(h1), h2[k] = f(u[k]),
+    d[k] = f'(u[k]) s f'(xin).  Read-only arrays."""
+    from oracle.aae_oracle import bf16_round
+    x = sweep(name, rows, width)
+    xin = (bf16_round(x) if probe == "decoder" else x).astype(np.float64)
+    h1, d1 = _f_df(name, xin)
+    r, other, mid = bf16_values(h1)
+    tol1 = forward_tolerance(name, rows, width, s) * np.abs(h1) + 2.0 ** -126 + AMBIGUITY_FLOOR.get(name, lambda v: 0.0 * v)(xin)
+    amb = (np.abs(h1 - mid) <= tol1) & (other != r)
+    out = dict(x=x, xin=xin, h1=h1, amb=amb, u=[], h2=[], d=[])
+    for rk in (r, other):
+        u = s * rk
+        h2, d2 = _f_df(name, u)
+        out["u"].append(u), out["h2"].append(h2), out["d"].append(d2 * s * d1)
+    for v in out.values():
+        for a in (v if isinstance(v, list) else [v]):
+            a.setflags(write=False)
+    return out
+
+
+def excluded_bf16(name, c):
+    """Left out of a bf16 case: within 1e-4 of a kink, not on it, in either layer - for an ambiguous point in either continuation."""
+    return near_kink(name, c["xin"], 1e-4) | near_kink(name, c["u"][0], 1e-4) | (c["amb"] & near_kink(name, c["u"][1], 1e-4))
+
+
+@functools.lru_cache(maxsize=None)
+def out_layer_bf16(H):
+    from oracle.aae_oracle import bf16_round
+    w = bf16_round(out_layer(H))
+    w.setflags(write=False)
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def upstream_bf16(name, rows, H, s):
+    """g2 = dL/d(h2) of the decoder probe in bf16 mode: mean BCE of sigmoid(R(h2) V^T) against the one item every document holds,
+    G = dL/dlogits rounded, g2 = R(G) V - float64 between the roundings."""
+    from oracle.aae_oracle import bf16_round
+    c = composite_bf16(name, rows, H, s, "decoder")
+    V = out_layer_bf16(H).astype(np.float64)
+    h2 = bf16_round(c["h2"][0].astype(f32)).astype(np.float64)
+    p = 1.0 / (1.0 + np.exp(-(h2 @ V.T)))
+    p[:, 0] -= 1.0
+    G = bf16_round((p / (rows * N_ITEMS)).astype(f32)).astype(np.float64)
+    g2 = G @ V
+    g2.setflags(write=False)
+    return g2
+
+
+def bf16_errors(c, keep, got, want_key, tol_fn):
+    """|got - want| / tolerance per point: against continuation 0, and for an ambiguous point the better of the two."""
+    e = [np.abs(got - c[want_key][k]) / tol_fn(k) for k in (0, 1)]
+    return np.where(keep, np.where(c["amb"], np.minimum(e[0], e[1]), e[0]), 0.0)
+
+
+def bf16_forward_tol(name, rows, H, s, c, k):
+    """The fp32 sweep's forward tolerance after the last rounding the output has seen (AAE_T_ACT_DH2 = h2, not rounded itself)."""
+    return forward_tolerance(name, rows, H, s) * np.maximum(1.0, np.abs(c["h2"][k]))
+
+
+def bf16_z(name, rows, H, s, c, k):
+    """(R(h2), its tolerance) where the output is itself rounded, z = R(h2): a device h2 within the forward tolerance of the
+    reference rounds to the same bf16 value - unless the reference h2 lies that close to the midpoint of two, and then to either:
+    the forward tolerance, plus the distance of those two neighbours at such points alone."""
+    r, other, mid = bf16_values(c["h2"][k])
+    t = bf16_forward_tol(name, rows, H, s, c, k)
+    return r, t + np.where(np.abs(c["h2"][k] - mid) <= t, np.abs(other - r), 0.0)
+
+
+def weakened(name, rows, H, s, c):
+    """The ambiguous points at which matching either continuation is a weaker check than matching one: where the two differ by
+    more than the tolerances.  (GELU's tail from x = -4 down lies below 1.3e-4 with an absolute error of |x| 1.2e-7 from
+    1 + erf: more than the bf16 spacing there, so 8 % of its grid is ambiguous - between neighbours 1e-6 apart.)"""
+    return c["amb"] & ((np.abs(c["h2"][0] - c["h2"][1]) > bf16_forward_tol(name, rows, H, s, c, 0)) |
+                       (np.abs(c["d"][0] - c["d"][1]) > bf16_ratio_tol(name, s, c, 0)))
+
+
+def bf16_ratio_tol(name, s, c, k):
+    return ratio_tol(name, s, c["xin"], c["u"][k], c["d"][k]) + 2 * BF16_EPS * np.abs(c["d"][k])

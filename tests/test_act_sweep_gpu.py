@@ -34,18 +34,11 @@ from oracle import aae_oracle as O
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
-N_ITEMS = 2048      # the output layer: logits = h2 . u / N stay within +-1 for every class (asserted on the reference, below)
+from act_sweep import N_ITEMS, enc_upstream, forward_tolerance, out_layer      # noqa: E402  (shared with the CPU test of the bf16 reference)
+
 PATHS = {"default": None, "x16": ("X16_ROWS", 16), "chain16": ("CHAIN16", 1), "no_chain": ("NO_CHAIN", 1)}
 CASES = [(n, p) for n in A.R15 for p in ("default", "x16", "chain16", "no_chain")] + \
         [(n, p) for n in A.R6 for p in ("default", "no_chain")]
-
-
-@functools.lru_cache(maxsize=None)
-def out_layer(H):
-    """dec.lin3: all positive, entries in [0.5, 1.5] / N."""
-    w = (np.random.default_rng(7).uniform(0.5, 1.5, size=(N_ITEMS, H)) / N_ITEMS).astype(f32)
-    w.setflags(write=False)
-    return w
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,24 +51,6 @@ def upstream(name, rows, H, s):
     g2 = (p / (rows * N_ITEMS)) @ V
     g2.setflags(write=False)
     return g2
-
-
-@functools.lru_cache(maxsize=None)
-def enc_upstream(rows, H):
-    rng = np.random.default_rng(11)
-    g = (rng.uniform(0.5, 1.5, size=(rows, H)) * rng.choice([-1.0, 1.0], size=(rows, H))).astype(f32)
-    g.setflags(write=False)
-    return g
-
-
-@functools.lru_cache(maxsize=None)
-def forward_tolerance(name, rows, H, s):
-    """max(2e-6, 4 x the oracle's own error of the composite against float64 on this sweep), relative to max(1, |y|)."""
-    c = A.composite(name, rows, H, s)
-    y = O.act_fwd(name, (f32(s) * O.act_fwd(name, c["x"])).astype(f32))
-    keep = ~A.excluded(name, c["x"], c["u"])
-    own = (np.abs(y - c["h2"]) / np.maximum(1.0, np.abs(c["h2"])))[keep].max()
-    return max(2e-6, 4.0 * float(own))
 
 
 def params(H, s, w1):
@@ -174,6 +149,115 @@ def test_activation_sweep(name, path, rows, H):
         for s in A.SCALES:
             run_decoder_probe(m, name, path, rows, H, s, report)
             run_encoder_probe(m, name, path, rows, H, s, report)
+    finally:
+        m.close()
+    assert not report, "\n" + "\n".join(report)
+
+
+# ---- bf16 mode (dtype = 'bf16') -------------------------------------------------------------------------------------------------
+# The same sweeps, shapes and scales on a bf16 handle: bf16 mode has a kernel family of its own (the column-owner chain4 of the
+# default path, the k-slice form, chain16x3_kernel<true>, chain_kernel<true, ..>, kGemmBf16 and its per-layer epilogues).  The
+# reference is the same float64 composite with bf16_round where the mode applies it - act_sweep.composite_bf16 has the rounding
+# points, derived from OracleAAE._linear / _mlp_bwd and held to the oracle's own run of these probes by test_act_sweep_cpu.py -
+# and dec.lin3 made of bf16 values, so that the output-layer product rounds the activations alone.
+# Forward: the fp32 sweep's tolerance after the last rounding; z = R(h2) against R of the reference (act_sweep.bf16_z).
+# Derivative: the fp32 sweep's ratio_tol + 2^-7 |expected| (two bf16 roundings of the gradient, 2^-8 each).  Coarse against the
+# fp32 sweep's 1e-6 - and still far inside a lost branch bit (the sign of f' left of x*), a wrong class dispatch, or an
+# EXT = false instantiation (LeakyReLU's derivative for classes 6 - 19), which is what this test is for.
+# An ambiguous point (h1 within its fp32 error of the midpoint of two bf16 values) may match either neighbour's continuation.
+PATHS_BF16 = dict(PATHS, kslices=("CHAIN_KSLICES", 1))
+CASES_BF16 = [(n, p) for n in A.R15 for p in ("default", "kslices", "x16", "chain16", "no_chain")] + \
+             [(n, p) for n in A.R6 for p in ("default", "no_chain")]
+
+
+def make_model_bf16(name, path, rows, H):
+    """(no skip: bf16 mode refuses no shape or path of these cases, and an error of aae_create fails the test)"""
+    from aaerec import _hip
+    opt = PATHS_BF16[path]
+    if opt:
+        _hip.set_option(opt[0], opt[1])
+    try:
+        return _hip.HipAAE(N_ITEMS, H, H, cond_inc=0, max_batch=rows, activation=name, dropout=(0.0, 0.0), rng_mode="inject", dtype="bf16")
+    finally:
+        if opt:
+            _hip.set_option(opt[0], None)
+
+
+def compare_bf16(report, what, name, path, s, c, keep, got, want, tol):
+    """got against want[k] within tol[k] on the kept points - continuation 0, and for an ambiguous point the better of the two;
+    misses to the report, the worst error of the case to stdout (DESIGN.md's table)."""
+    assert np.isfinite(got).all(), (what, name, path, s, "not finite at x =", c["x"][~np.isfinite(got)][:10])
+    e = [np.abs(got - want[k]) for k in (0, 1)]
+    pick = np.where(c["amb"] & (e[1] / tol[1] < e[0] / tol[0]), 1, 0)
+    err = np.where(keep, np.where(pick == 1, e[1], e[0]), 0.0)
+    tl = np.where(pick == 1, tol[1], tol[0])
+    i = np.unravel_index(int((err / tl).argmax()), err.shape)
+    print(f"ACTSWEEP bf16 {name} {path} {got.shape[0]}x{got.shape[1]} s={s:g} {what} worst {err[i]:.3e} at x = {c['x'][i]!r} "
+          f"(tolerance there {tl[i]:.3e})")
+    bad = err > tl
+    if bad.any():
+        lines = [f"{what}: {int(bad.sum())} of {int(keep.sum())} points beyond the tolerance; class {name}, path {path}, s = {s:g}, bf16"]
+        for k in np.argsort((err / tl).ravel())[::-1][:10]:
+            j = np.unravel_index(int(k), err.shape)
+            if bad[j]:
+                lines.append(f"    x = {c['x'][j]!r}  f = {c['h1'][j]:.9g}  s R(f) = {c['u'][0][j]:.9g}  got {got[j]:.9g}  want {want[0][j]:.9g}"
+                             f"{' or %.9g' % want[1][j] if c['amb'][j] else ''}  (|d| {err[j]:.3e} > {tl[j]:.3e})")
+        report.append("\n".join(lines))
+
+
+def run_decoder_probe_bf16(m, name, path, rows, H, s, report):
+    from aaerec import _hip
+    c = A.composite_bf16(name, rows, H, s, "decoder")
+    g2 = A.upstream_bf16(name, rows, H, s)
+    assert (g2 > 0).all() and g2.min() >= 0.25 * g2.max(), ("the upstream gradient is not of one sign and magnitude", g2.min(), g2.max())
+    keep = ~A.excluded_bf16(name, c)
+    p = params(H, s, np.zeros((H, N_ITEMS), dtype=f32))
+    p["dec.lin3.weight"] = A.out_layer_bf16(H)
+    m.load_params(p)
+    csr = _hip.DeviceCSR.from_arrays(np.arange(rows + 1), np.zeros(rows, dtype=np.int32), np.ones(rows, dtype=f32), N_ITEMS, m.device)
+    m.ae_encode(csr, 0, rows)
+    dzc = m.ae_decode_backward(torch.from_numpy(c["x"].copy()))
+    m.join()
+    h2 = m.tensor(_hip.T_ACT_DH2)[:rows, :H].cpu().numpy().astype(np.float64)
+    dzc = dzc.cpu().numpy().astype(np.float64)
+    compare_bf16(report, "decoder forward", name, path, s, c, keep, h2, c["h2"], [A.bf16_forward_tol(name, rows, H, s, c, k) for k in (0, 1)])
+    compare_bf16(report, "decoder derivative", name, path, s, c, keep, dzc / g2, c["d"], [A.bf16_ratio_tol(name, s, c, k) for k in (0, 1)])
+
+
+def run_encoder_probe_bf16(m, name, path, rows, H, s, report):
+    from aaerec import _hip
+    c = A.composite_bf16(name, rows, H, s, "encoder")
+    G = enc_upstream(rows, H)
+    keep = ~A.excluded_bf16(name, c)
+    w1 = np.zeros((H, N_ITEMS), dtype=f32)
+    w1[:, :rows] = c["x"].T
+    p = params(H, s, w1)
+    p["dec.lin3.weight"] = A.out_layer_bf16(H)
+    m.load_params(p)
+    csr = _hip.DeviceCSR.from_arrays(np.arange(rows + 1), np.arange(rows, dtype=np.int32), np.ones(rows, dtype=f32), N_ITEMS, m.device)
+    z = m.ae_encode(csr, 0, rows)
+    a1 = m.tensor(_hip.T_ACT_A1)[:rows, :H].cpu().numpy()
+    m.ae_decode_backward(z)
+    m.ae_encoder_backward(torch.from_numpy(G.copy()))
+    m.join()
+    assert np.array_equal(a1.view(np.uint32), c["x"].view(np.uint32)), \
+        ("AAE_T_ACT_A1 is not the sweep bit for bit: the sparse first layer rounds nothing", name, path, c["x"][a1.view(np.uint32) != c["x"].view(np.uint32)][:10])
+    z = z.cpu().numpy().astype(np.float64)
+    ga1 = m.tensor(_hip.T_ACT_GA1)[:rows, :H].cpu().numpy().astype(np.float64)
+    zt = [A.bf16_z(name, rows, H, s, c, k) for k in (0, 1)]
+    compare_bf16(report, "encoder forward", name, path, s, c, keep, z, [zt[0][0], zt[1][0]], [zt[0][1], zt[1][1]])
+    compare_bf16(report, "encoder derivative", name, path, s, c, keep, ga1 / G, c["d"], [A.bf16_ratio_tol(name, s, c, k) for k in (0, 1)])
+
+
+@pytest.mark.parametrize("rows,H", A.SHAPES)
+@pytest.mark.parametrize("name,path", CASES_BF16)
+def test_activation_sweep_bf16(name, path, rows, H):
+    m = make_model_bf16(name, path, rows, H)
+    report = []
+    try:
+        for s in A.SCALES:
+            run_decoder_probe_bf16(m, name, path, rows, H, s, report)
+            run_encoder_probe_bf16(m, name, path, rows, H, s, report)
     finally:
         m.close()
     assert not report, "\n" + "\n".join(report)

@@ -14,38 +14,9 @@ N_SEEDS = int(os.environ.get("AAE_FUZZ_SEEDS", "28"))       # (a wider hunt: AAE
 #  single-element sensitivities described at the tolerance below)
 SEEDS = list(range(N_SEEDS))
 
-ACTS = ["ReLU", "SELU", "Tanh", "Sigmoid", "ELU", "LeakyReLU"]
-
-
-def _config(seed, tiny=False):
-    r = np.random.default_rng((3000 if tiny else 1000) + seed)
-    dims = dict(N=int(r.integers(2, 40)), h=int(r.integers(1, 9)), c=int(r.integers(1, 7)), B=int(r.integers(1, 6)),
-                inc=int(r.choice([0, 0, 1, 3]))) if tiny else \
-        dict(N=int(r.integers(17, 2500)), h=int(r.integers(3, 208)), c=int(r.integers(2, 100)),
-             B=int(r.integers(1, 105)), inc=int(r.choice([0, 0, 5, 30, 64])))
-    cfg = dict(**dims, act=str(r.choice(ACTS)),
-               prior=str(r.choice(["gauss", "gauss", "categorical", "bernoulli"])),
-               opt=str(r.choice(["adam", "adam", "sgd"])), drop=bool(r.integers(0, 2)), norm=bool(r.integers(0, 4)),
-               scale=float(r.choice([0.0, 0.0, 2.0])), cut=bool(r.integers(0, 2)))
-    cfg["inc"] = max(0, min(cfg["inc"], 206 - cfg["c"]))
-    if not tiny and r.random() < 0.2:         # batches past the fused output-layer kernel's 104 rows: the three-kernel path
-        cfg["B"] = int(r.integers(105, 260))
-        cfg["N"] = min(cfg["N"], 1200)
-    cfg["long_rows"] = bool(r.random() < 0.15)       # documents with hundreds of items (per-row chunking, >1024 entries per tile)
-    cfg["window"] = bool(r.random() < 0.3)           # the batch is a permutation window into a larger resident corpus
-    if not tiny and r.random() < 0.2:         # a condition that makes the decoder's input wider than a chain slot (two k-parts)
-        cfg["inc"] = int(r.integers(208 - cfg["c"], 415 - cfg["c"]))
-    return cfg, r
-
-
-def _close_enough(got, want, tol, dmax, tag):
-    """Element-wise |got - want| <= tol, except for what a single activation kink / an Adam-eps gradient can move (see
-    the note in test_random_configuration_matches_oracle): one hidden unit taking the other branch of its activation
-    for one document changes that unit's whole weight-gradient ROW, so up to two rows' worth of elements (at least 8,
-    at most 1 % of a large tensor) may exceed tol - none by more than dmax."""
-    d = np.abs(got - want)
-    allowed = max(8, 0.01 * d.size, 2 * (d.shape[-1] if d.ndim > 1 else 1))
-    assert (d > tol).sum() <= allowed and d.max() <= dmax, f"{tag}: {(d > tol).sum()} of {d.size} off (allowed {allowed:.0f}), max {d.max():.2e}"
+from fuzz_cases import (ACTS, ACTS_R6, WIDE, batch as _batch, check_configuration as _check_configuration,      # noqa: F401
+                        check_decoder, close_enough as _close_enough, config as _config, decoder_config, wide_config)
+# (the generator, the step loop and the comparison live in tests/fuzz_cases.py: the bf16 fuzz runs the same implementation)
 
 
 @pytest.mark.parametrize("tiny", [False, True])
@@ -58,10 +29,6 @@ def test_random_configuration_matches_oracle(seed, tiny):
 # r6: the fourteen further activation classes (csrc/device_common.h; the general program kernel chain_kernel<.., true> and the
 # per-layer epilogues carry them): the same random configurations - widths, conditions incl. the wide ones, priors, optimisers,
 # ragged batches, permutation windows, the step cut at the output layer - with the class cycling over the seeds
-ACTS_R6 = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink", "Identity",
-           "GELU", "SiLU", "Mish", "Hardswish"]
-
-
 @pytest.mark.parametrize("seed", range(int(os.environ.get("AAE_FUZZ_SEEDS", "28"))))
 def test_random_configuration_with_a_further_activation_class_matches_oracle(seed):
     cfg, r = _config(500 + seed)
@@ -77,97 +44,11 @@ def test_random_configuration_with_a_further_activation_class_matches_oracle(see
 # two k-parts, its dX as two column parts (csrc/abi_chains.h: add_dec_in_fwd / add_dec_in_dx).  C4's shape (code 50 +
 # 300-d condition), the narrowest wide input (209 columns: the second part is the bias column alone), the widest (416),
 # a part boundary inside the condition / right behind z, a batch beyond one fused launch.
-WIDE = [dict(N=300, h=40, c=50, B=37, inc=300), dict(N=120, h=200, c=10, B=100, inc=198), dict(N=500, h=64, c=100, B=64, inc=315),
-        dict(N=257, h=207, c=207, B=5, inc=33), dict(N=900, h=100, c=50, B=150, inc=300), dict(N=64, h=7, c=2, B=3, inc=206),
-        dict(N=200, h=30, c=300, B=9, inc=0), dict(N=150, h=20, c=210, B=6, inc=100)]      # (a code wider than a slot: layer by layer)
-
-
 @pytest.mark.parametrize("cut", [False, True])
 @pytest.mark.parametrize("case", range(len(WIDE)))
 def test_condition_wider_than_a_chain_slot_matches_oracle(case, cut):
-    r = np.random.default_rng(7000 + case)
-    cfg = dict(**WIDE[case], act=ACTS[case % len(ACTS)], prior=["gauss", "categorical", "gauss"][case % 3],
-               opt=["adam", "adam", "sgd"][case % 3], drop=bool(case % 2 == 0), norm=bool(case % 3), scale=0.0, cut=cut,
-               long_rows=False, window=bool(case % 2), predict=True)
+    cfg, r = wide_config(case, cut)
     _check_configuration(cfg, r, 7000 + case)
-
-
-def _check_configuration(cfg, r, seed):
-    import torch
-    from aaerec._hip import HipAAE, DeviceCSR
-    from oracle import aae_oracle as O
-    from oracle.dense_torch_port import init_params
-    N, h, c, B, inc = cfg["N"], cfg["h"], cfg["c"], cfg["B"], cfg["inc"]
-    params = init_params(N, h, c, cond_inc=inc, seed=seed)
-    p = (0.2, 0.3) if cfg["drop"] else (0.0, 0.0)
-    lr = (0.05, 0.02) if cfg["opt"] == "sgd" else (2e-3, 1e-3)
-    kw = dict(gen_lr=lr[0], reg_lr=lr[1], dropout=p, activation=cfg["act"], prior=cfg["prior"], optimizer=cfg["opt"],
-              normalize_inputs=cfg["norm"], prior_scale=cfg["scale"] or None)
-    dev = HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", **kw)
-    dev.load_params(params)
-    ora = O.OracleAAE(params, conditions=[O.ConcatConst(inc)] if inc else [], **kw)
-    for s in range(3):
-        Bs = B if s < 2 else max(1, B - int(r.integers(0, min(B, 17))))          # a shorter last batch
-        max_len = int(min(N, 600)) if cfg["long_rows"] else int(min(N + 1, 12))
-        n_docs = 3 * Bs if cfg["window"] else Bs
-        rows = [np.sort(r.choice(N, size=int(r.integers(0 if B > 2 else 1, max_len)), replace=False)) for _ in range(n_docs)]
-        if not any(len(x) for x in rows):
-            rows[0] = np.array([int(r.integers(0, N))])
-        ip = np.concatenate([[0], np.cumsum([len(x) for x in rows])]).astype(np.int64)
-        idx = np.concatenate(rows).astype(np.int32)
-        val = np.ones(len(idx), dtype=np.float32)
-        csr = DeviceCSR.from_arrays(ip, idx, val, N, dev.device)
-        sel = None
-        if cfg["window"]:                      # rows = a window of a permutation, as fit() passes it
-            pick = r.permutation(n_docs)[:Bs].astype(np.int32)
-            sel = torch.as_tensor(pick, device=dev.device)
-            rows = [rows[j] for j in pick]
-            ip = np.concatenate([[0], np.cumsum([len(x) for x in rows])]).astype(np.int64)
-            idx = np.concatenate(rows).astype(np.int32) if ip[-1] else np.zeros(0, dtype=np.int32)
-            val = np.ones(len(idx), dtype=np.float32)
-        masks = None
-        if cfg["drop"]:
-            masks = [(r.random((Bs, h)) > (p[j % 2])).astype(np.uint8) for j in range(12)]
-        if cfg["prior"] == "gauss":
-            zr = r.standard_normal((Bs, c)).astype(np.float32)
-        elif cfg["prior"] == "categorical":
-            zr = np.eye(c, dtype=np.float32)[r.integers(0, c, size=Bs)]
-        else:
-            zr = np.zeros((Bs, c), dtype=np.float32)             # the reference's randint(0, 1) bernoulli prior
-        cond = (r.standard_normal((Bs, inc)) * 0.4).astype(np.float32) if inc else None
-        cdev = torch.as_tensor(cond, device=dev.device) if inc else None
-        if cfg["cut"] and h + 1 <= 208 and c + 1 <= 208 and c + inc + 1 <= 416:     # (the cut form is the layer-chain models')
-            dev.ae_forward(csr, 0, Bs, rows=sel, cond=cdev, masks=masks, z_real=zr)
-            dev.output_layer_step()
-            dev.ae_backward()
-            dev.disc_gen()
-        else:
-            dev.step(csr, 0, Bs, rows=sel, cond=cdev, masks=masks, z_real=zr)
-        want = ora.partial_fit(ip, idx, val, zr, masks, [cond] if inc else None)
-        np.testing.assert_allclose(dev.losses(), want, rtol=5e-5, atol=2e-6, err_msg=f"{cfg} step {s}")
-    got = dev.state_dict()
-    # Parameters: 5e-5 absolute.  Two fp32 effects can move single elements further without anything being wrong, and
-    # a random search over hundreds of configurations does find them (tools/debug/fuzz_case.py prints both):
-    # a pre-activation within ~1e-7 of an activation kink (ReLU / LeakyReLU / SELU at 0) takes the other branch under a
-    # different summation order, and Adam turns a gradient of the order of its eps (1e-8) into a step of the order of
-    # the learning rate.  So: at most 1 % of a tensor's elements (8 for the small ones) may exceed the tolerance, none by
-    # more than 3 lr.
-    for k, w in ora.p.items():
-        _close_enough(got[k], w, 5e-5, 3 * max(lr), f"{cfg} {k}")
-    if cfg.get("predict"):                     # the last batch's reconstructions with the trained weights (no dropout)
-        out = dev.predict(csr, 0, Bs, cond=cdev) if sel is None else None
-        if out is not None:
-            want = ora.predict(ip, idx, val, [cond] if inc else None)
-            np.testing.assert_allclose(out.cpu().numpy(), want, atol=1e-4, err_msg=f"{cfg} predict")
-
-
-def _batch(r, N, Bs, B, max_len=12):
-    rows = [np.sort(r.choice(N, size=int(r.integers(0 if B > 2 else 1, min(N, max_len))), replace=False)) for _ in range(Bs)]
-    if not any(len(x) for x in rows):
-        rows[0] = np.array([int(r.integers(0, N))])
-    ip = np.concatenate([[0], np.cumsum([len(x) for x in rows])]).astype(np.int64)
-    idx = np.concatenate(rows).astype(np.int32)
-    return ip, idx, np.ones(len(idx), dtype=np.float32)
 
 
 class _Solo:
@@ -289,33 +170,12 @@ def _decoder_vae_case(seed, act_override=None):
     from aaerec._hip import HipAAE, DeviceCSR
     from oracle import aae_oracle as O
     from oracle.dense_torch_port import init_params
-    r = np.random.default_rng(9000 + seed)
-    N, h, B = int(r.integers(17, 1500)), int(r.integers(3, 208)), int(r.integers(1, 150))
-    act = str(r.choice(["ReLU", "Tanh", "SELU", "ELU"]))
+    r, N, h, B, act = decoder_config(seed)
     if act_override:
         act = act_override
     if seed % 2 == 0:
         # ---- decoder only: the input block is what the condition plugins produced (width n_code here) ----
-        c = int(r.integers(2, 200))
-        params = init_params(N, h, c, seed=seed)
-        p = (0.2, 0.2) if r.integers(0, 2) else (0.0, 0.0)
-        dev = HipAAE(N, h, c, max_batch=B, rng_mode="inject", gen_lr=2e-3, reg_lr=2e-3, dropout=p, activation=act)
-        dev.load_params(params)
-        ora = O.OracleDecoder(params, lr=2e-3, dropout=p, activation=act, conditions=[O.ConcatConst(c)])
-        for s in range(3):
-            ip, idx, val = _batch(r, N, B, B)
-            zin = (r.standard_normal((B, c)) * 0.5).astype(np.float32)
-            masks = [(r.random((B, h)) > 0.2).astype(np.uint8) for _ in range(2)] if p[0] else None
-            dz = dev.decoder_step(DeviceCSR.from_arrays(ip, idx, val, N, dev.device), 0, B,
-                                  torch.as_tensor(zin, device=dev.device), masks=masks)
-            want = ora.partial_fit([zin], ip, idx, val, masks)
-            np.testing.assert_allclose(dev.losses()[0], want, rtol=5e-5, atol=2e-6)
-            np.testing.assert_allclose(dz.cpu().numpy(), ora.last_dzin, rtol=5e-4, atol=1e-7)     # (entries are sums with cancellation, ~1e-4 in size)
-        got = dev.state_dict()
-        for k, w in ora.p.items():
-            _close_enough(got[k], w, 5e-5, 6e-3, f"decoder N={N} h={h} c={c} B={B} {k}")
-        zp = (r.standard_normal((B, c)) * 0.5).astype(np.float32)
-        np.testing.assert_allclose(dev.decode(torch.as_tensor(zp, device=dev.device)).cpu().numpy(), ora.predict([zp]), atol=2e-5)
+        check_decoder(r, N, h, B, act, seed)
         return
     # ---- VAE ----
     c, inc = int(r.integers(2, 100)), int(r.choice([0, 0, 9, 40]))
