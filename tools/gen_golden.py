@@ -308,6 +308,9 @@ def run_case(ref_aae, ref_cond, name, N=300, h=20, c=10, B=16, steps=3, seed=0,
         cfg["init_from"] = init_from
     if state_keys:
         cfg["state_keys"] = dict(every=list(state_keys["every"]), last=list(state_keys["last"]))
+    order = {n: [k for k, _ in net.named_parameters()] for n, net in (("enc", m.enc), ("dec", m.dec), ("disc", m.disc))}
+    if any(len(v) != 6 for v in order.values()):      # an activation with parameters (PReLU): what index i of A_*.<i>.m names
+        cfg["param_order"] = order
 
     if cond in CAT_KINDS:
         # fit the vocabulary on all raw inputs first (AAERecommender.train -> fit_transform)
@@ -950,7 +953,7 @@ def gen_vae(only=None):
     import aaerec.vae as ref_vae
     names = ("fc1", "fc21", "fc22", "fc3", "fc4")
 
-    def run(name, seed, cond):
+    def run(name, seed, cond, activation=None):
         N, h, c, B, steps, lr = 300, 20, 10, 16, 3, 2e-3
         rng = np.random.default_rng(seed)
         torch.manual_seed(5000 + seed)
@@ -980,7 +983,7 @@ def gen_vae(only=None):
         adam_every = not wide                                         # (the wide cases: moments after the last step only)
         const_block = lambda: (rng.integers(-8, 9, size=(B, wide)) / 8.0).astype(np.float32)      # noqa: E731
         m = ref_vae.VAE(N, N, n_hidden=h, n_code=c, lr=lr, batch_size=B, n_epochs=1, conditions=conditions,
-                        verbose=True, device=torch.device("cpu"))
+                        verbose=True, device=torch.device("cpu"), **(dict(activation=activation) if activation else {}))
         eps_log, loss_log = [], []
         orig_randn_like = torch.randn_like
 
@@ -1002,6 +1005,13 @@ def gen_vae(only=None):
             lin = getattr(m, n)
             out[f"init.{n}.weight"] = lin.weight.detach().numpy().copy()
             out[f"init.{n}.bias"] = lin.bias.detach().numpy().copy()
+        if activation:
+            # (vae.py:94-96 builds the optimiser before self.act exists: a weight of the activation is in no optimiser)
+            cfg["activation"] = activation
+            act_params = dict(m.act.named_parameters())
+            assert all(not any(p is q for g in m.optimizer.param_groups for q in g["params"]) for p in act_params.values())
+            for k, v in act_params.items():
+                out[f"init.act.{k}"] = v.detach().numpy().copy()
         torch.randn_like = rec_randn_like
         try:
             for s in range(steps):
@@ -1031,6 +1041,9 @@ def gen_vae(only=None):
                     out[f"step{s}.cond.t"] = np.asarray(float(st["step"]))
                 out[f"step{s}.eps"] = eps_log[-1]
                 out[f"step{s}.losses"] = np.asarray([loss_log[-1], 0.0, 0.0], dtype=np.float64)   # (BCE + KLD) / B
+                if activation:
+                    for k, v in m.act.named_parameters():
+                        out[f"step{s}.act.{k}"] = v.detach().numpy().copy()
                 params = list(m.parameters())
                 for n in names:
                     lin = getattr(m, n)
@@ -1084,7 +1097,8 @@ def gen_vae(only=None):
             run(only[0], only[1], wide_cases[only[0]][2])
             return
         run(*dict({"step_vae": ("step_vae", 51, False), "step_vae_cond": ("step_vae_cond", 52, True),
-                   "step_vae_cat": ("step_vae_cat", 53, "cat")}, **wide_cases)[only])
+                   "step_vae_cat": ("step_vae_cat", 53, "cat"), "step_vae_prelu": ("step_vae_prelu", 54, False, "PReLU")},
+                  **wide_cases)[only])
         return
     run("step_vae", 51, False)
     run("step_vae_cond", 52, True)
@@ -1374,6 +1388,9 @@ def gen_challenge():
 
 ACT_NAMES = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink",
              "Identity", "GELU", "SiLU", "Mish", "Hardswish", "ELU", "LeakyReLU", "Sigmoid"]
+# added after r6: seeds go on from ACT_NAMES', whose fixtures regenerate bit for bit.  PReLU's six weights (enc.act1 .. disc.act2)
+# are in the recorded states like every parameter, their moments under the index config.param_order gives them
+ACT_NAMES_MORE = ["Tanhshrink", "PReLU"]
 
 
 def main():
@@ -1412,6 +1429,13 @@ def main():
         for i, a in enumerate(ACT_NAMES):
             run_case(ref_aae, ref_cond, "step_act_" + a.lower(), seed=60 + i, activation=a, dropout=(0.2, 0.2),
                      capture_acts=False, states='last')
+    if want("acts") or "acts_more" in which:      # (acts_more: only the classes added since)
+        for i, a in enumerate(ACT_NAMES_MORE):
+            run_case(ref_aae, ref_cond, "step_act_" + a.lower(), seed=60 + len(ACT_NAMES) + i, activation=a, dropout=(0.2, 0.2),
+                     capture_acts=False, states='last')
+        run_case(ref_aae, ref_cond, "step_act_prelu_sgd", seed=60 + len(ACT_NAMES) + len(ACT_NAMES_MORE), activation="PReLU",
+                 optimizer="sgd", gen_lr=0.05, reg_lr=0.02, dropout=(0.2, 0.2), capture_acts=False, states='last')
+        gen_vae(only="step_vae_prelu")
     if want("headline"):
         # the headline layer widths (h=200, c=50, batch 100: 13 column blocks in the layer chains and in the fused
         # decoder output layer, 7 row blocks) on a small vocabulary, straight from the reference
