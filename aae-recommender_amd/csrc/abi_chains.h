@@ -317,7 +317,7 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
         if ((cb.P.ops[i].row_lo > 0 || cb.P.ops[i].y_glb) && !four)      // (acc_in: every chain kernel carries it)
             return fail(AAE_ESTATE, "a program prefix for the upper rows / an epilogue's y from global memory needs the 4-row chain kernel");
     // wide batches: 16 rows per workgroup on the bf16 matrix cores (chain16x3.h)
-    if (four && m->x16_ok && cb.P.rows >= (cb.x16_rows > 0 ? cb.x16_rows : m->x16_rows) && !cb.P.bk.enabled && x16_program_ok(cb.P)) {
+    if (four && m->x16_ok && cb.P.rows >= (cb.x16_rows > 0 ? cb.x16_rows : m->x16_rows) && !cb.P.bk.enabled && !cb.P.il.enabled && x16_program_ok(cb.P)) {
         ChainProgram X = cb.P;
         if (x16_remap_slots(X)) {
             // the look-ahead chains of the weight prefetch: per workgroup class, every op's next linear op
@@ -342,7 +342,11 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
     // (chain4: bf16 programs without k-slices take the column form)
     const ChainKernel kernel = four ? pick_chain4(m->bf16, ts_kernel, m->bf16 && !cb.P.kslices, cb.vae4) : pick_chain(m->bf16, m->act_nm);
     if (!kernel) return fail(AAE_ESTATE, "no chain kernel is compiled for this mode");
-    const int grid = (cb.P.rows + (four ? kR4 : kCR) - 1) / (four ? kR4 : kCR) + (cb.P.bk.enabled ? 1 : 0);
+    int grid = (cb.P.rows + (four ? kR4 : kCR) - 1) / (four ? kR4 : kCR) + (cb.P.bk.enabled ? 1 : 0);
+    // the item-list builder (piggyback_item_lists) rides on the 4-row kernel alone; builder workgroups come last in the grid,
+    // so the row workgroups are placed first.  The lists count as built from here on: stream order is the dependency
+    if (cb.P.il.enabled && !four) cb.P.il.enabled = 0;
+    if (cb.P.il.enabled) { grid += cb.P.il.nblocks; m->il_set ^= 1; m->item_lists_valid = true; }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(four ? kC4T : kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
     LAUNCHCHK("chain_kernel");
     return want_ts ? print_chain_timeline(cb.P, ts_dev, false, four, s) : AAE_OK;
@@ -350,6 +354,11 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
 
 // up to 4 weight-gradient jobs in one launch
 int launch_w1_hot(aae_model* m, hipStream_t s);
+static ItemLists item_lists_of(const aae_model* m, int set) {
+    ItemLists L;
+    L.rec = m->il_rec[set]; L.ovf = m->il_ovf[set]; L.hot_count = m->il_hot_count + set; L.cap = m->il_cap; L.hot_cap = m->il_hot_cap;
+    return L;
+}
 struct DwBuilder {
     aae_model* mh = nullptr;       // set by add_first_layer: the wave form's hot list is worked off behind the launch
     DwGroup g; int tiles;
@@ -404,6 +413,11 @@ struct DwBuilder {
                 (int64_t)m->cfg.max_nnz <= 512ll * w.nitem && ((int64_t)m->N >= 40ll * m->rows || hyb_any)) {
                 w.wave_form = 2;
                 w.nitem = (w.nitem + 3) / 4;
+                // the batch's item row lists were enqueued ahead of this launch (w1_lists.h): records instead of the tile walk
+                if (m->item_lists_valid && !w.items.gout) {
+                    w.lists_on = 1; w.lists = item_lists_of(m, m->il_set);
+                    w.nhot = std::min(m->il_hot_cap, 64);
+                }
             } else
             if (!no_wave && m->rows > 16 * kMB && m->hot_list && (int64_t)m->N >= 40ll * m->rows) {
                 w.wave_form = 1;
@@ -435,6 +449,7 @@ struct DwBuilder {
                     w.nitem = std::min(w.nitem, std::max(256, want));
                 }
             }
+            if (w.lists_on) w.nitem += w.nhot;      // (the overflow slots' workgroups come first among the item blocks)
         }
         return AAE_OK;
     }
@@ -648,6 +663,32 @@ static void piggyback_buckets(aae_model* m, ChainBuilder& cb) {
     m->buckets_valid = true;
 }
 
+// The first layer's update needs, per distinct item of the batch, its rows in ascending order with their scaled values: a function
+// of the batch alone, which both updates of a step (enc_optim's, gen_optim's) derived for themselves inside launches the whole
+// step waits for.  The ae phase's backward chain launch - 25 row workgroups for ~20 us, behind the buckets and in front of the
+// first update - carries the builder as extra workgroups on CUs that stand idle (w1_lists.h).  Only where the hybrid form of
+// the update applies (add_first_layer: wave_form 2) with the fused optimiser on a first layer of this handle's own.
+static void piggyback_item_lists(aae_model* m, ChainBuilder& cb) {
+    if (m->opt.no_item_lists || !m->il_cap || m->item_lists_valid || !m->buckets_valid || m->bk_pending) return;
+    if (m->cfg.grad_mode != AAE_GRAD_FUSED || m->dense_step || m->ext_first) return;
+    if (m->x16_ok && m->rows >= m->x16_rows) return;      // (the wide-batch chain kernel carries no builder)
+    const int bound = std::max(1, std::min(std::min(m->cfg.max_nnz, std::max(256, m->rows * 32)), m->N));
+    if (!(m->rows <= 16 * kMB && sizeof(int) * w1_items_lds_words(m->rows) <= kDwSmemBytes &&
+          sizeof(int) * w1_hybrid_lds_words(m->rows) <= kDwSmemBytes && (int64_t)m->cfg.max_nnz <= 512ll * bound &&
+          (int64_t)m->N >= 40ll * m->rows))
+        return;
+    static_assert(sizeof(int) * (kC4T / 64 * 2 * kW1HybRows + kW1BuildDeferWords + 2 * 4 + 2 * kW1OvfRows + 4) <= kCSlots * kCR * kCL * sizeof(float),
+                  "the builder's LDS fits a chain workgroup's");
+    const int set = m->il_set ^ 1;      // (launch_chain flips il_set when the builder goes out)
+    ItemListJob& j = cb.P.il;
+    j.ulist = m->ulist; j.ucount = m->ucount; j.tstart = m->tstart; j.eb = m->teb; j.en = m->ten; j.ev = m->tev;
+    j.rscale = m->rscale; j.rows = m->rows;
+    j.out = item_lists_of(m, set); j.hot_zero = m->il_hot_count + (set ^ 1);
+    // one wave per item and round: two rounds of the largest list a batch of this many rows is sized for, 64 workgroups at most
+    j.nblocks = std::max(1, std::min(64, (bound + 2 * (kC4T / 64) - 1) / (2 * (kC4T / 64))));
+    j.enabled = 1;
+}
+
 // ae forward after the gather: encoder tail (+ optionally the decoder's two hidden layers)
 int chain_ae_forward(aae_model* m, bool with_dec, const float* cond_dev, float* z_out, hipStream_t s) {
     const int B = m->rows, h = m->h, c = m->c, cp = m->cp;
@@ -703,7 +744,7 @@ int chain_dec_hidden(aae_model* m, bool train, int rows, hipStream_t s) {
 //   dec: sum of the 16 dA2 partial slabs -> act'/dropout -> V2 -> V1 -> gzc
 //   enc: dz (slot or external) -> output activation' -> W3 -> W2 -> ga1
 int chain_ae_backward(aae_model* m, bool dec_part, bool enc_part, const float* part_slabs, size_t slab_stride,
-                      const float* gz_ext, int ld_gz, float* dzc_out, int which, hipStream_t s, int nslab = 16) {
+                      const float* gz_ext, int ld_gz, float* dzc_out, int which, hipStream_t s, int nslab = 16, bool item_lists = false) {
     const int B = m->rows, h = m->h, c = m->c, cp = m->cp;
     const aae_rng_inject& I = m->inj;
     ChainBuilder cb(m, B);
@@ -743,6 +784,7 @@ int chain_ae_backward(aae_model* m, bool dec_part, bool enc_part, const float* p
         x2.d = make_drop(m, 0, true, I.masks_dev[which == O_GEN ? 8 : 0], nullptr, B, h, which == O_GEN ? 8 : 0);
         cop_out(x2, ga1_ptr(m), m->ldh);
     }
+    if (item_lists) piggyback_item_lists(m, cb);
     return launch_chain(m, cb, s);
 }
 

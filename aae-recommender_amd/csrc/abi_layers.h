@@ -59,7 +59,7 @@ int set_batch(aae_model* m, const aae_batch* b) {
     if (b->nnz_bound > m->cfg.max_nnz) return fail(AAE_EINVAL, "batch nnz_bound > max_nnz");
     m->bv.indptr = b->indptr_dev; m->bv.indices = b->indices_dev; m->bv.values = b->values_dev;
     m->bv.rows = b->rows_dev; m->bv.row_start = b->row_start; m->bv.n_rows = b->n_rows;
-    m->rows = b->n_rows; m->have_batch = true; m->buckets_valid = false; m->w1_merged = false;
+    m->rows = b->n_rows; m->have_batch = true; m->buckets_valid = false; m->item_lists_valid = false; m->w1_merged = false;
     {   // 16 entries per workgroup pass; unknown row bound -> 64 strided chunks
         int mr = b->max_row_nnz > 0 ? b->max_row_nnz : 1024;
         m->chunks = std::max(1, std::min(64, (mr + 15) / 16));

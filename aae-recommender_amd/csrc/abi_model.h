@@ -47,6 +47,7 @@ struct aae_options {
     bool blocked_any;       // BLOCKED_ANY: the row-blocked output layer at every size
     bool early_any;         // EARLY_ANY: the next batch's item list started from the step before, at every batch size
     bool no_late_join;      // NO_LATE_JOIN: a step waits for the deferred launch of the step before at its opening
+    bool no_item_lists;     // NO_ITEM_LISTS: the first layer's update collects every item's rows itself (no per-batch row lists, w1_lists.h)
     bool no_item_count;     // NO_ITEM_COUNT: first-layer item workgroups sized by the bound, not by the device's last count
     bool w1_serial;         // W1_SERIAL: data-parallel import of the peers' first-layer rows one launch per peer
     bool no_rank_fused;     // NO_RANK_FUSED: predict -> rank as two kernels over the [rows, N] score matrix
@@ -68,6 +69,7 @@ inline void read_options(aae_options& o) {
     auto num = [](const char* n, int dflt) { const char* e = option_value(n); return e ? atoi(e) : dflt; };
     o.no_chain = on("NO_CHAIN"); o.chain16 = on("CHAIN16"); o.split_any = on("SPLIT_ANY"); o.blocked_any = on("BLOCKED_ANY");
     o.early_any = on("EARLY_ANY"); o.no_late_join = on("NO_LATE_JOIN"); o.no_item_count = on("NO_ITEM_COUNT");
+    o.no_item_lists = on("NO_ITEM_LISTS");
     o.w1_serial = on("W1_SERIAL"); o.no_rank_fused = on("NO_RANK_FUSED"); o.chain_kslices = on("CHAIN_KSLICES");
     o.x16_rows = num("X16_ROWS", 1024); o.dw_ksplit_rows = num("DW_KSPLIT_ROWS", -1);
     o.rank_collect_cap = std::max(0, std::min(num("RANK_COLLECT_CAP", 0), 4096));
@@ -122,6 +124,10 @@ struct aae_model {
     bool w1_merged;          // the first layer's bias update of this phase rode in the grouped dW launch
     bool w1_items_merged;    // ... and so did its row-sparse weight gradient + optimiser (w1_update.h)
     bool buckets_valid;      // the per-tile entry buckets (tstart/teb/ten/tev) describe the running batch
+    // the running batch's item row lists (w1_lists.h): two sets, as for the buckets; built by extra workgroups of the ae phase's
+    // backward chain launch, read by both first-layer updates of the step.  il_cap = 0: this model never builds them
+    unsigned* il_rec[2]; unsigned* il_ovf[2]; int* il_hot_count; int il_cap, il_hot_cap, il_set;
+    bool item_lists_valid;   // the lists of set il_set were enqueued for the running batch (cleared by set_batch)
     // lazy Adam on W1T (kernels.h): per-row sync step, unique-row scratch, per-step scalar table
     bool lazy;
     // fused decoder output layer (dec_fused.h): tile-bucketed batch entries, eligibility
@@ -374,6 +380,18 @@ size_t layout(aae_model* m, char* base, bool dry) {
     m->hot_list = reinterpret_cast<int*>(a.take((size_t)2 * m->hot_cap, nullptr));
     m->hot_count = reinterpret_cast<int*>(a.take(4, nullptr));
     m->hot_flip = 0;
+    // batches of one fused launch: the item row lists of the first layer's update (w1_lists.h), two sets
+    m->il_cap = m->il_hot_cap = 0; m->il_set = 0; m->item_lists_valid = false;
+    m->il_rec[0] = m->il_rec[1] = m->il_ovf[0] = m->il_ovf[1] = nullptr; m->il_hot_count = nullptr;
+    if (c.grad_mode == AAE_GRAD_FUSED && !c.dense_noise && std::min<int64_t>(c.max_nnz, N) <= 262144) {
+        m->il_cap = (int)std::min<int64_t>(c.max_nnz, N);
+        m->il_hot_cap = std::min(m->il_cap, c.max_nnz / (kW1HybRows + 1) + 1);      // (an overflow item holds > kW1HybRows of the batch's entries)
+        for (int i = 0; i < 2; ++i) {
+            m->il_rec[i] = reinterpret_cast<unsigned*>(a.take((size_t)m->il_cap * kW1RecWords, nullptr));
+            m->il_ovf[i] = reinterpret_cast<unsigned*>(a.take((size_t)m->il_hot_cap * kW1OvfWords, nullptr));
+        }
+        m->il_hot_count = reinterpret_cast<int*>(a.take(4, nullptr));
+    }
     m->mark2 = m->ulist2 = m->ucount2 = m->stamp2 = nullptr;
     if (c.grad_mode == AAE_GRAD_FUSED) {      // second list set for aae_prefetch_batch (single-process training only)
         m->mark2 = reinterpret_cast<int*>(a.take(N, nullptr));

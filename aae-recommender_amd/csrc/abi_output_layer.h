@@ -379,7 +379,7 @@ int decoder_hidden_backward(aae_model* m, const float* chain_part, size_t chain_
         // decoder hidden backward (+ the encoder backward when called from aae_step) in one program,
         // then every small weight gradient + optimiser update in one grouped launch
         const bool enc_too = m->fuse_enc_bwd;
-        TRY(chain_ae_backward(m, true, enc_too, chain_part, chain_stride, nullptr, 0, dzc_out, O_ENC, s));
+        TRY(chain_ae_backward(m, true, enc_too, chain_part, chain_stride, nullptr, 0, dzc_out, O_ENC, s, 16, enc_too));
         DwBuilder dw;
         dw.add(m, m->gb0.p, m->ldh, m->dh1.p, m->ldh, B, P_V2, O_DEC);
         dw.add(m, m->gb1.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);

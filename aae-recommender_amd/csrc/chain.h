@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "buckets.h"
 #include "w1_update.h"
+#include "w1_lists.h"
 
 namespace aae {
 
@@ -97,6 +98,7 @@ struct ChainProgram {
     int kslices;                        // chain4.h: 1 = every linear op in the k-slice form (wide batches; AAE_CHAIN_KSLICES).  LAST: a field in front
                                         // of ops[] moves every op descriptor's offset in the kernel-argument segment (and with it the width of the
                                         // scalar loads that fetch it: +0.3 us per launch of every chain kernel, measured)
+    ItemListJob il;                     // chain4.h: enabled = the launch's last il.nblocks workgroups build the batch's item row lists (w1_lists.h)
 };
 
 // Workgroup barrier that orders LDS traffic only: global stores of finished activations (consumed by
@@ -657,6 +659,8 @@ struct W1Job {
     int* hot; int* hot_count; int* hot_zero;    // kW1WaveRows go to the hot list (worked off by a launch behind this one); hot_zero: the NEXT use's counter
     W1Items items;
     int* cnt_out;         // != NULL: host-visible word that receives the step's distinct-item count (the column sums' first workgroup)
+    int lists_on, nhot;   // wave_form 2 with the batch's item row lists built ahead (w1_lists.h): the first nhot item blocks take the
+    ItemLists lists;      // overflow slots, the others one record per wave
 };
 // the adversarial loss of the chain program in front of this launch: its per-row terms (ChainProgram::loss_terms) summed in a
 // fixed order by one extra workgroup (the launch's last) -> *out
@@ -732,6 +736,11 @@ __device__ __forceinline__ void grouped_dw_body(const DwGroup& grp, float* smem)
         DW_STAMP_W1(64);
         if (id == 0 && threadIdx.x == 0 && w.cnt_out && w.nitem > 0) *w.cnt_out = *w.items.ucount;
         if (id < w.ncol) { colsum_adam_body(w.ga1, w.rows, w.h, w.ld, w.bp, w.bm, w.bv1, w.bgrad, w.sc, id, smem); DW_STAMP_W1(65); }
+        else if (w.wave_form == 2 && w.lists_on) {
+            const int ib = id - w.ncol;
+            if (ib < w.nhot) w1_lists_hot_body(w.items, w.lists, reinterpret_cast<unsigned*>(smem), ib, w.nhot);
+            else w1_lists_wave_body(w.items, w.lists, ib - w.nhot, w.nitem - w.nhot);
+        }
         else if (w.wave_form == 2) w1_item_hybrid_body(w.items, reinterpret_cast<unsigned*>(smem), id - w.ncol, w.nitem);
         else if (w.wave_form) {
             if (id == w.ncol && threadIdx.x == 0) *w.hot_zero = 0;

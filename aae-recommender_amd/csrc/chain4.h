@@ -241,7 +241,12 @@ __device__ __forceinline__ f32x4 chain4_cols(const float* W4, int ns4, int N, in
 template <bool BF, bool TS = false, bool COLS = false, bool VAE = false>
 __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
     extern __shared__ __attribute__((aligned(16))) float slots[];     // [kCSlots][4][kCL], then the partial-sum scratch
-    if (P.bk.enabled && blockIdx.x == gridDim.x - 1) {                // (uniform) the piggy-backed bucket builder
+    const int il_blocks = P.il.enabled ? P.il.nblocks : 0;            // (uniform) the piggy-backed item-list builder: the last workgroups
+    if ((int)blockIdx.x >= (int)gridDim.x - il_blocks) {
+        w1_lists_build_body<kC4T>(P.il, reinterpret_cast<unsigned*>(slots), (int)blockIdx.x - ((int)gridDim.x - il_blocks), il_blocks);
+        return;
+    }
+    if (P.bk.enabled && (int)blockIdx.x == (int)gridDim.x - 1 - il_blocks) {      // (uniform) the piggy-backed bucket builder
         tile_bucket_body<kBucketMaxDocs, kC4T>(P.bk.bv, P.bk.ntiles, P.bk.tstart, P.bk.eb, P.bk.en, P.bk.ev, reinterpret_cast<int*>(slots));
         return;
     }
