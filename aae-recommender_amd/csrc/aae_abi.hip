@@ -182,8 +182,7 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     m->vae_rank_ok = m->vae && m->fused_ok && m->use_chain4 && !m->opt.no_rank_fused;
     if (m->vae_rank_ok) each_chain4_vae(limit(m->vae_rank_ok, kCSlots * kCR * kCL * sizeof(float)));
     bool& rank_ok = m->vae ? m->vae_rank_ok : m->rank_ok;
-    if (rank_ok) each_rank_x3([&](RankKernel k, int nb) { rank_ok = rank_ok && raise_lds_limit(k, rank_x3_lds_bytes(nb)); });
-    if (rank_ok) each_rank_x3v2([&](RankKernel k, int nb) { rank_ok = rank_ok && raise_lds_limit(k, rank_x3v2_lds_bytes(nb)); });
+    if (rank_ok) each_rank([&](const RankPick& r) { rank_ok = rank_ok && raise_lds_limit(r.kernel, r.lds); });
     m->w1_big_lds = raise_lds_limit(w1_item_update_kernel, sizeof(int) * w1_items_lds_words(16384));
     (void)hipGetLastError();
     m->grad_scale = 1.f;

@@ -68,81 +68,103 @@ namespace {
 // the [rows][N] scores in the scratch -> [rows][k]: register lists up to k = 32 (kernels.h), the long-list kernel beyond
 int topk_from_scores(aae_model* m, int k, int exclude_known, int32_t* idx_out_dev, float* val_out_dev, hipStream_t s) {
     if (rank_long(k)) return rank_long_dense(m, k, exclude_known, idx_out_dev, val_out_dev, s);
-    if (k <= 10)
-        hipLaunchKernelGGL(topk_rows_kernel<10>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
-                           exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    else if (k <= 20)
-        hipLaunchKernelGGL(topk_rows_kernel<20>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
-                           exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
-    else
-        hipLaunchKernelGGL(topk_rows_kernel<32>, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv,
-                           exclude_known, k, reinterpret_cast<int*>(idx_out_dev), val_out_dev);
+    const TopkRowsKernel kernel = pick_topk_rows(rank_K(k));
+    if (!kernel) return fail(AAE_ESTATE, "no topk_rows kernel is compiled for this list size");
+    hipLaunchKernelGGL(kernel, dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, m->bv, exclude_known, k,
+                       reinterpret_cast<int*>(idx_out_dev), val_out_dev);
     LAUNCHCHK("topk_rows");
     return AAE_OK;
 }
-// the dense form's scores: rows of `batch` (<= max_batch) into the [max_batch][n_items] scratch
-int aae_scores_to_scratch(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* zc_dev, int64_t zc_ld, void* stream) {
-    if (!zc_dev) return aae_predict(m, batch, cond_dev, m->G.p, m->ldn, stream);
-    TRY(set_batch(m, batch));
-    return aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream);
+// the dense form's scores: the rows of `in` (<= max_batch) into the [max_batch][n_items] scratch
+int scores_to_scratch(aae_model* m, const RankInput& in, void* stream) {
+    if (in.zc) {
+        TRY(set_batch(m, &in.batch));
+        return aae_decode(m, in.zc, in.zc_ld, m->rows, m->G.p, m->ldn, stream);
+    }
+    if (in.vae) return aae_vae_predict(m, &in.batch, in.cond, in.eps, m->G.p, m->ldn, stream);
+    return aae_predict(m, &in.batch, in.cond, m->G.p, m->ldn, stream);
 }
-// The four ranking calls of an AAE / AE handle.  zc_dev != NULL: the decode form - a caller-built decoder input (code |
-// imposed conditions of any plugin kind), the second half of predict (aae.py:855-866); `batch` names the input rows whose
-// items are excluded and cond_dev is not read.
-int aae_topk(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* zc_dev, int64_t zc_ld, int k, int exclude_known,
-             int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+// The ranking calls of a model, either family (in.vae), either form (in.zc): lists ...
+int model_topk(aae_model* m, const RankInput& in, int k, int exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
     hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_rows_cap(m, k)) {   // fused: no [rows][N] matrix (abi_rank.h)
+    const int rows = in.batch.n_rows;
+    if (rows >= 1 && rows <= rank_rows_cap(m, k, in.vae)) {      // fused: no [rows][N] matrix (abi_rank.h)
+        const RankWs w = rank_ws(m, rows, k, false);
         m->phase = 0;
-        if (zc_dev) TRY(rank_decode(m, zc_dev, zc_ld, batch, k, exclude_known, idx_out_dev, val_out_dev, s));
-        else TRY(rank_predict(m, batch, cond_dev, k, exclude_known, idx_out_dev, val_out_dev, s));
+        TRY(rank_hidden(m, in, w, s));
+        TRY(rank_from_dh2(m, w.p, rank_view(&in.batch), k, exclude_known, idx_out_dev, val_out_dev, s));
         if (!rank_long(k)) return AAE_OK;
         std::vector<std::pair<int, int>> spans;        // rows whose collect list overflowed: through the score matrix
-        TRY(rank_long_overflow(m, batch, k, s, spans));
+        TRY(rank_long_overflow(m, &in.batch, w.p, s, spans));
         for (const auto& sp : spans) {
-            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
-            const size_t r0 = (size_t)sp.first;
-            TRY(aae_scores_to_scratch(m, &sub, cond_dev ? cond_dev + r0 * m->cfg.cond_inc : nullptr, zc_dev ? zc_dev + r0 * zc_ld : nullptr,
-                                      zc_ld, stream));
-            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + r0 * k, val_out_dev + r0 * k, s));
+            const RankInput sub = rank_cut(m, in, sp.first, sp.second);
+            const size_t out0 = (size_t)sp.first * k;
+            if (in.vae) TRY(vae_span_scores(m, sub, s));      // (the fused call's own program again: its bits)
+            else TRY(scores_to_scratch(m, sub, stream));
+            TRY(rank_long_dense(m, k, exclude_known, idx_out_dev + out0, val_out_dev + out0, s));
         }
         return AAE_OK;
     }
-    TRY(aae_scores_to_scratch(m, batch, cond_dev, zc_dev, zc_ld, stream));
+    TRY(scores_to_scratch(m, in, stream));
     TRY(topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s));
     m->phase = 0;
     return AAE_OK;
 }
-// ... the rank of every held-out item in the full ranking of its row (rank_full.h)
-int aae_ranks(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* zc_dev, int64_t zc_ld, const aae_batch* truth,
-              int exclude_known, int32_t* ranks_out_dev, void* stream) {
+// ... and the rank of every held-out item in the full ranking of its row (rank_full.h)
+int model_ranks(aae_model* m, const RankInput& in, const aae_batch* truth, int exclude_known, int32_t* ranks_out_dev, void* stream) {
     hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= rank_full_rows_cap(m)) {     // fused: no [rows][N] matrix (abi_rank.h)
+    const int rows = in.batch.n_rows;
+    if (rows >= 1 && rows <= rank_full_rows_cap(m, in.vae)) {      // fused: no [rows][N] matrix (abi_rank.h)
+        const RankWs w = rank_ws(m, rows, 32, true);
         m->phase = 0;
-        if (zc_dev) return rank_full_decode(m, zc_dev, zc_ld, batch, truth, exclude_known, ranks_out_dev, s);
-        return rank_full_predict(m, batch, cond_dev, truth, exclude_known, ranks_out_dev, s);
+        TRY(rank_hidden(m, in, w, s));
+        return rank_full_from_dh2(m, w.p, rank_view(&in.batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out_dev, s);
     }
-    TRY(aae_scores_to_scratch(m, batch, cond_dev, zc_dev, zc_ld, stream));
-    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), exclude_known, ranks_out_dev, s));
+    TRY(scores_to_scratch(m, in, stream));
+    TRY(rank_full_dense(m, rank_view(&in.batch), rank_view(truth), exclude_known, ranks_out_dev, s));
     m->phase = 0;
     return AAE_OK;
+}
+// an entry point's rows: the predict form (cond, eps) or the decode form (zc), from row 0 of the generator
+RankInput rank_input(bool vae, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld) {
+    return RankInput{*batch, cond_dev, eps_dev, zc_dev, zc_ld, 0, vae};
 }
 }  // namespace
 extern "C" {
 
 int aae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev, int32_t k, int32_t exclude_known,
                      int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(rank_check_k("aae_predict_topk", k, m->N));
-    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
-    TRY(rank_check_batch(batch));
-    return aae_topk(m, batch, cond_dev, nullptr, 0, k, exclude_known, idx_out_dev, val_out_dev, stream);
+    TRY(rank_check_call("aae_predict_topk", m, false, kRankFormPredict, idx_out_dev && val_out_dev, &k, cond_dev, nullptr, 0, batch, nullptr));
+    return model_topk(m, rank_input(false, batch, cond_dev, nullptr, nullptr, 0), k, exclude_known, idx_out_dev, val_out_dev, stream);
+}
+
+int aae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k,
+                    int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
+    TRY(rank_check_call("aae_decode_topk", m, false, kRankFormDecode, zc_dev && idx_out_dev && val_out_dev, &k, nullptr, nullptr, zc_ld, batch, nullptr));
+    return model_topk(m, rank_input(false, batch, nullptr, nullptr, zc_dev, zc_ld), k, exclude_known, idx_out_dev, val_out_dev, stream);
+}
+
+int aae_predict_ranks(aae_handle m, const aae_batch* batch, const float* cond_dev, const aae_batch* truth, int32_t exclude_known,
+                      int32_t* ranks_out_dev, void* stream) {
+    TRY(rank_check_call("aae_predict_ranks", m, false, kRankFormPredict, ranks_out_dev, nullptr, cond_dev, nullptr, 0, batch, truth));
+    return model_ranks(m, rank_input(false, batch, cond_dev, nullptr, nullptr, 0), truth, exclude_known, ranks_out_dev, stream);
+}
+
+int aae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
+                     int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
+    TRY(rank_check_call("aae_decode_ranks", m, false, kRankFormDecode, zc_dev && ranks_out_dev, nullptr, nullptr, nullptr, zc_ld, batch, truth));
+    return model_ranks(m, rank_input(false, batch, nullptr, nullptr, zc_dev, zc_ld), truth, exclude_known, ranks_out_dev, stream);
 }
 
 int aae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
-    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
-    TRY(rank_check_k("aae_rank_max_rows", k, m->N));
-    *rows_out = std::max(m->R, rank_rows_cap(m, k));
+    TRY(rank_check_call("aae_rank_max_rows", m, false, kRankFormRows, rows_out, &k, nullptr, nullptr, 0, nullptr, nullptr));
+    *rows_out = std::max(m->R, rank_rows_cap(m, k, false));
+    return AAE_OK;
+}
+
+int aae_rank_full_max_rows(aae_handle m, int32_t* rows_out) {
+    TRY(rank_check_call("aae_rank_full_max_rows", m, false, kRankFormRows, rows_out, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+    *rows_out = std::max(m->R, rank_full_rows_cap(m, false));
     return AAE_OK;
 }
 
@@ -152,162 +174,40 @@ int aae_rank_long_stats(aae_handle m, int64_t out[5]) {
     return AAE_OK;
 }
 
-int aae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k,
-                    int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!m || !zc_dev || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(rank_check_k("aae_decode_topk", k, m->N));
-    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
-    TRY(rank_check_batch(batch));
-    return aae_topk(m, batch, nullptr, zc_dev, zc_ld, k, exclude_known, idx_out_dev, val_out_dev, stream);
-}
-
-int aae_rank_full_max_rows(aae_handle m, int32_t* rows_out) {
-    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
-    *rows_out = std::max(m->R, rank_full_rows_cap(m));
-    return AAE_OK;
-}
-
-int aae_predict_ranks(aae_handle m, const aae_batch* batch, const float* cond_dev, const aae_batch* truth, int32_t exclude_known,
-                      int32_t* ranks_out_dev, void* stream) {
-    if (!m || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
-    TRY(rank_check_batch(batch));
-    TRY(rank_check_truth("aae_predict_ranks", batch->n_rows, truth));
-    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_predict_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
-    return aae_ranks(m, batch, cond_dev, nullptr, 0, truth, exclude_known, ranks_out_dev, stream);
-}
-
-int aae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
-                     int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
-    if (!m || !zc_dev || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
-    TRY(rank_check_batch(batch));
-    TRY(rank_check_truth("aae_decode_ranks", batch->n_rows, truth));
-    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_decode_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
-    return aae_ranks(m, batch, nullptr, zc_dev, zc_ld, truth, exclude_known, ranks_out_dev, stream);
-}
-
-}  // extern "C"
-
 // ---- the VAE: predict -> rank (reference vae.py:229-266 + evaluation.py:183-199, 20-58; abi_rank.h, the VAE's form) -------------------
-namespace {
-int vae_rank_check(const aae_model* m, const float* cond_dev, const float* eps_dev, bool decode) {
-    if (!m->vae || !m->use_chain) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
-    if (decode) return AAE_OK;
-    if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
-    if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
-    return AAE_OK;
-}
-// the dense form's scores: rows of `batch` (<= max_batch) into the [max_batch][n_items] scratch
-int vae_scores_to_scratch(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev,
-                          int64_t zc_ld, void* stream) {
-    if (!zc_dev) return aae_vae_predict(m, batch, cond_dev, eps_dev, m->G.p, m->ldn, stream);
-    TRY(set_batch(m, batch));
-    return aae_decode(m, zc_dev, zc_ld, m->rows, m->G.p, m->ldn, stream);
-}
-// zc_dev != NULL: the decode form (cond_dev / eps_dev are not read)
-int vae_topk(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld,
-             int k, int exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    hipStream_t s = S(stream);
-    const int nc = m->c, ci = m->cfg.cond_inc;
-    if (batch->n_rows >= 1 && batch->n_rows <= vae_rank_rows_cap(m, k)) {      // fused: no [rows][N] matrix
-        const int rows = batch->n_rows;
-        const VaeRankCopies c = vae_rank_copies(m, m->G.p);
-        float* base = m->G.p + c.floats;
-        const RankPlan p = rank_plan(m, rows, k, base);
-        m->phase = 0;
-        if (zc_dev) TRY(vae_rank_decode_hidden(m, zc_dev, zc_ld, rows, c, p.dh2, s));
-        else TRY(vae_rank_predict_hidden(m, batch, cond_dev, eps_dev, 0, c, p.a1, p.eh1, p.rscale, p.dh2, s));
-        TRY(rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out_dev, val_out_dev, s));
-        if (!rank_long(k)) return AAE_OK;
-        std::vector<std::pair<int, int>> spans;        // rows whose collect list overflowed: through the score matrix
-        TRY(rank_long_overflow(m, batch, k, s, spans, base));
-        for (const auto& sp : spans) {
-            const aae_batch sub = rank_sub_batch(m, batch, sp.first, sp.second);
-            const size_t r0 = (size_t)sp.first;
-            TRY(vae_rank_long_span(m, &sub, cond_dev ? cond_dev + r0 * ci : nullptr, eps_dev ? eps_dev + r0 * nc : nullptr,
-                                   zc_dev ? zc_dev + r0 * zc_ld : nullptr, zc_ld, sp.first, k, exclude_known, idx_out_dev + r0 * k,
-                                   val_out_dev + r0 * k, s));
-        }
-        return AAE_OK;
-    }
-    TRY(vae_scores_to_scratch(m, batch, cond_dev, eps_dev, zc_dev, zc_ld, stream));
-    TRY(topk_from_scores(m, k, exclude_known, idx_out_dev, val_out_dev, s));
-    m->phase = 0;
-    return AAE_OK;
-}
-int vae_ranks(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld,
-              const aae_batch* truth, int exclude_known, int32_t* ranks_out_dev, void* stream) {
-    hipStream_t s = S(stream);
-    if (batch->n_rows >= 1 && batch->n_rows <= vae_rank_full_rows_cap(m)) {
-        const int rows = batch->n_rows;
-        const VaeRankCopies c = vae_rank_copies(m, m->G.p);
-        const RankPlan p = rank_plan(m, rows, 32, m->G.p + c.floats, true);
-        m->phase = 0;
-        if (zc_dev) TRY(vae_rank_decode_hidden(m, zc_dev, zc_ld, rows, c, p.dh2, s));
-        else TRY(vae_rank_predict_hidden(m, batch, cond_dev, eps_dev, 0, c, p.a1, p.eh1, p.rscale, p.dh2, s));
-        return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out_dev, s);
-    }
-    TRY(vae_scores_to_scratch(m, batch, cond_dev, eps_dev, zc_dev, zc_ld, stream));
-    TRY(rank_full_dense(m, rank_view(batch), rank_view(truth), exclude_known, ranks_out_dev, s));
-    m->phase = 0;
-    return AAE_OK;
-}
-}  // namespace
-extern "C" {
-
 int aae_vae_predict_topk(aae_handle m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, int32_t k,
                          int32_t exclude_known, int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!m || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(vae_rank_check(m, cond_dev, eps_dev, false));
-    TRY(rank_check_k("aae_vae_predict_topk", k, m->N));
-    TRY(rank_check_batch(batch));
-    return vae_topk(m, batch, cond_dev, eps_dev, nullptr, 0, k, exclude_known, idx_out_dev, val_out_dev, stream);
+    TRY(rank_check_call("aae_vae_predict_topk", m, true, kRankFormPredict, idx_out_dev && val_out_dev, &k, cond_dev, eps_dev, 0, batch, nullptr));
+    return model_topk(m, rank_input(true, batch, cond_dev, eps_dev, nullptr, 0), k, exclude_known, idx_out_dev, val_out_dev, stream);
 }
 
 int aae_vae_decode_topk(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int32_t k, int32_t exclude_known,
                         int32_t* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!m || !zc_dev || !idx_out_dev || !val_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(vae_rank_check(m, nullptr, nullptr, true));
-    TRY(rank_check_k("aae_vae_decode_topk", k, m->N));
-    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
-    TRY(rank_check_batch(batch));
-    return vae_topk(m, batch, nullptr, nullptr, zc_dev, zc_ld, k, exclude_known, idx_out_dev, val_out_dev, stream);
+    TRY(rank_check_call("aae_vae_decode_topk", m, true, kRankFormDecode, zc_dev && idx_out_dev && val_out_dev, &k, nullptr, nullptr, zc_ld, batch, nullptr));
+    return model_topk(m, rank_input(true, batch, nullptr, nullptr, zc_dev, zc_ld), k, exclude_known, idx_out_dev, val_out_dev, stream);
 }
 
 int aae_vae_predict_ranks(aae_handle m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, const aae_batch* truth,
                           int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
-    if (!m || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(vae_rank_check(m, cond_dev, eps_dev, false));
-    TRY(rank_check_batch(batch));
-    TRY(rank_check_truth("aae_vae_predict_ranks", batch->n_rows, truth));
-    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_vae_predict_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
-    return vae_ranks(m, batch, cond_dev, eps_dev, nullptr, 0, truth, exclude_known, ranks_out_dev, stream);
+    TRY(rank_check_call("aae_vae_predict_ranks", m, true, kRankFormPredict, ranks_out_dev, nullptr, cond_dev, eps_dev, 0, batch, truth));
+    return model_ranks(m, rank_input(true, batch, cond_dev, eps_dev, nullptr, 0), truth, exclude_known, ranks_out_dev, stream);
 }
 
 int aae_vae_decode_ranks(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
                          int32_t exclude_known, int32_t* ranks_out_dev, void* stream) {
-    if (!m || !zc_dev || !ranks_out_dev) return fail(AAE_EINVAL, "NULL argument");
-    TRY(vae_rank_check(m, nullptr, nullptr, true));
-    if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
-    TRY(rank_check_batch(batch));
-    TRY(rank_check_truth("aae_vae_decode_ranks", batch->n_rows, truth));
-    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, "aae_vae_decode_ranks: truth needs max_row_nnz: the entries of its longest row (an upper bound)");
-    return vae_ranks(m, batch, nullptr, nullptr, zc_dev, zc_ld, truth, exclude_known, ranks_out_dev, stream);
+    TRY(rank_check_call("aae_vae_decode_ranks", m, true, kRankFormDecode, zc_dev && ranks_out_dev, nullptr, nullptr, nullptr, zc_ld, batch, truth));
+    return model_ranks(m, rank_input(true, batch, nullptr, nullptr, zc_dev, zc_ld), truth, exclude_known, ranks_out_dev, stream);
 }
 
 int aae_vae_rank_max_rows(aae_handle m, int32_t k, int32_t* rows_out) {
-    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
-    TRY(vae_rank_check(m, nullptr, nullptr, true));
-    TRY(rank_check_k("aae_vae_rank_max_rows", k, m->N));
-    *rows_out = std::max(m->R, vae_rank_rows_cap(m, k));
+    TRY(rank_check_call("aae_vae_rank_max_rows", m, true, kRankFormRows, rows_out, &k, nullptr, nullptr, 0, nullptr, nullptr));
+    *rows_out = std::max(m->R, rank_rows_cap(m, k, true));
     return AAE_OK;
 }
 
 int aae_vae_rank_full_max_rows(aae_handle m, int32_t* rows_out) {
-    if (!m || !rows_out) return fail(AAE_EINVAL, "NULL argument");
-    TRY(vae_rank_check(m, nullptr, nullptr, true));
-    *rows_out = std::max(m->R, vae_rank_full_rows_cap(m));
+    TRY(rank_check_call("aae_vae_rank_full_max_rows", m, true, kRankFormRows, rows_out, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+    *rows_out = std::max(m->R, rank_full_rows_cap(m, true));
     return AAE_OK;
 }
 

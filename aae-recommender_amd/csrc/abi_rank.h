@@ -15,6 +15,13 @@
 // Full ranking (rank_full.h; aae_predict_ranks / aae_decode_ranks): no candidate lists; instead
 //   tgt_i, tgt_v, tcount [rows][kFullSlots]   the held-out items of this round, their logits, the cells ranked before them
 // Launches: gather, chain, known-item mask, then per round of 8 held-out items a row: setup, rank (pick), rank (count), finish.
+// One host path for both kinds of handle and both forms of a call (the drivers model_topk / model_ranks, abi_predict.h):
+//   RankInput + rank_cut    the rows of a call - batch, cond, eps, zc, generator row - and a span of them: the only place that
+//                           knows their strides
+//   rank_ws, rank_cap       the workspace's one layout (a VAE handle's weight copies in front of the plan) and its row limits
+//   rank_hidden             the hidden half: the program builder of this handle and form -> p.dh2
+//   rank_from_dh2 / rank_full_from_dh2      p.dh2 -> lists / ranks
+//   rank_check_call         the argument check of the eight entry points and the four *_max_rows
 #pragma once
 
 namespace {
@@ -74,57 +81,87 @@ size_t rank_ws_floats(const aae_model* m) {
     return m->G.floats();
 }
 
-// most rows one fused call can rank in `have` floats of workspace
-int rank_rows_fit(const aae_model* m, int k, size_t have) {
+// A VAE handle keeps no k-major copies of its layers (its training programs run on chain.h, whose optimiser epilogues would
+// have to keep them in step): a rank call derives the F4 copies of the two small matrices into the head of its workspace -
+// ~60 k floats at the headline widths, two launches - and lays its plan out behind them.  An AAE / AE handle has no head.
+struct VaeRankCopies { float* w3; float* v1; float* d4; size_t floats; };
+
+VaeRankCopies vae_rank_copies(const aae_model* m, float* base) {
+    VaeRankCopies c; memset(&c, 0, sizeof(c));
+    if (!m->vae) return c;
+    auto f4 = [](const Ten& W) { return (size_t)((W.cols + 3) / 4 + kW4Pad) * 4 * W.rows; };          // (+ the zero k-chunk rows, chain4.h)
+    auto d4 = [](const Ten& W) { return (size_t)((W.rows + 3) / 4) * 4 * W.cols; };
+    const Ten &W3 = m->P[P_W3], &V1 = m->P[P_V1];
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return base ? base + o : nullptr; };
+    c.w3 = take(f4(W3)); c.v1 = take(f4(V1));
+    c.d4 = take(std::max(d4(W3), d4(V1)));       // (interleave4_kernel writes the dX copy too: nobody reads it)
+    c.floats = off;
+    return c;
+}
+
+// a fused call's workspace, the only layout of it: the head, the plan behind it
+struct RankWs { VaeRankCopies c; RankPlan p; };
+RankWs rank_ws(const aae_model* m, int rows, int k, bool full) {
+    RankWs w;
+    w.c = vae_rank_copies(m, m->G.p);
+    w.p = rank_plan(m, rows, k, m->G.p + w.c.floats, full);
+    return w;
+}
+
+// most rows one fused call (full: one fused full-ranking call, k = 32) can rank in `have` floats behind the head
+int rank_rows_fit(const aae_model* m, int k, bool full, size_t have) {
     if (k < 1 || k > kLongKMax) return 0;
     const int ntiles = (m->N + kTI - 1) / kTI;
     int lo = 0, hi = kRankMaxRows;          // (the plan's size is monotone in rows up to rounding: bisect)
     while (lo < hi) {
         const int mid = (lo + hi + 1) / 2;
-        const RankPlan p = rank_plan(m, mid, k, nullptr);
+        const RankPlan p = rank_plan(m, mid, k, nullptr, full);
         // (k > 32: the floor needs k candidates per row - fewer workgroups per row block than that and every row would overflow)
         const bool floor_ok = !rank_long(k) || p.wgs * 32 >= k || p.wgs == ntiles;
         if (p.floats <= have && floor_ok) lo = mid; else hi = mid - 1;
     }
     return lo;
 }
-// ... one fused full-ranking call
-int rank_full_rows_fit(const aae_model* m, size_t have) {
-    int lo = 0, hi = kRankMaxRows;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) / 2;
-        if (rank_plan(m, mid, 32, nullptr, true).floats <= have) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+// vae: the aae_vae_* family asks - a VAE handle ranks fused through those calls alone, any other handle through the aae_* ones
+// (0: the fused path does not apply)
+int rank_cap(const aae_model* m, int k, bool full, bool vae) {
+    const size_t have = rank_ws_floats(m), head = vae_rank_copies(m, nullptr).floats;
+    return (vae ? m->vae_rank_ok : m->rank_ok) && have > head ? rank_rows_fit(m, k, full, have - head) : 0;
 }
-// (0: the fused path does not apply to this handle)
-int rank_rows_cap(const aae_model* m, int k) { return m->rank_ok ? rank_rows_fit(m, k, rank_ws_floats(m)) : 0; }
-int rank_full_rows_cap(const aae_model* m) { return m->rank_ok ? rank_full_rows_fit(m, rank_ws_floats(m)) : 0; }
+int rank_rows_cap(const aae_model* m, int k, bool vae) { return rank_cap(m, k, false, vae); }
+int rank_full_rows_cap(const aae_model* m, bool vae) { return rank_cap(m, 32, true, vae); }
 
-// one launch of a rank kernel: rank_x3v2 / rank_x3 by rank_v2_nb (kernel_pick.h), or the K = 32 kernel's front end with
+// one launch of a rank kernel: the lists' kernel of this (NB, K) (kernel_pick.h), or the K = 32 kernel's front end with
 // another epilogue: collect (rank_long.h), pick / count (rank_full.h)
 int launch_rank(const RankArgs& a, int nb, int K, int epi, int grid, hipStream_t s) {
     const bool win = x3_big_span(a.N, a.ldv);      // (dec.lin3 beyond 2^31 bytes: the moving-window instantiations, dec_fused.h)
-    const bool v2 = epi == kRankLists && rank_v2_nb(nb, K);
-    const RankKernel kernel = v2 ? pick_rank_x3v2(nb, K, win) : pick_rank_x3(nb, epi != kRankLists ? 1 : K, win, epi);
-    if (!kernel) return fail(AAE_ESTATE, "no rank kernel is compiled for this hidden width and list size");
-    const uint32_t lds = (uint32_t)(v2 ? rank_x3v2_lds_bytes(nb) : rank_x3_lds_bytes(nb));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kNT), lds, s, a);
-    LAUNCHCHK(v2 ? "rank_x3v2" : epi == kRankCollect ? "rank_x3 (collect)" : epi == kRankPick ? "rank_x3 (pick)"
-                 : epi == kRankCount ? "rank_x3 (count)" : "rank_x3");
+    const RankPick r = epi == kRankLists ? pick_rank_lists(nb, K, win) : pick_rank_epilogue(nb, epi, win);
+    if (!r.kernel) return fail(AAE_ESTATE, "no rank kernel is compiled for this hidden width and list size");
+    hipLaunchKernelGGL(r.kernel, dim3(grid), dim3(kNT), (uint32_t)r.lds, s, a);
+    LAUNCHCHK(r.name);
+    return AAE_OK;
+}
+
+// the known-item mask of the plan's rows, and what every rank launch over them is given (the pointers a plan does not lay
+// out are NULL)
+int rank_mask_and_args(aae_model* m, const RankPlan& p, const BatchView& bv, int exclude_known, RankArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(known_mask_kernel, dim3(p.rows), dim3(256), 0, s, bv, exclude_known ? p.known : (unsigned*)nullptr, p.kw,
+                       p.dh2, m->ldh, m->h);
+    LAUNCHCHK("known_mask");
+    memset(&a, 0, sizeof(a));
+    a.dh2 = p.dh2; a.ldh = m->ldh; a.V3a = m->P[P_V3].p; a.ldv = m->ldh; a.N = m->N; a.B = p.rows;
+    a.nblk = p.nblk; a.Bb = p.bb; a.known = exclude_known ? p.known : nullptr; a.kw = p.kw;
+    a.cand_v = p.cand_v; a.cand_i = p.cand_i; a.mm = p.mm; a.one_term = m->bf16 ? 1 : 0;
+    a.tgt_i = p.tgt_i; a.tgt_v = p.tgt_v; a.tcount = p.tcount;
     return AAE_OK;
 }
 
 // dh2 (workspace) of `rows` rows -> [rows][k] ids and scaled scores
 int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, int exclude_known, int32_t* idx_out,
                   float* val_out, hipStream_t s) {
-    hipLaunchKernelGGL(known_mask_kernel, dim3(p.rows), dim3(256), 0, s, bv, exclude_known ? p.known : (unsigned*)nullptr, p.kw,
-                       p.dh2, m->ldh, m->h);
-    LAUNCHCHK("known_mask");
-    RankArgs a; memset(&a, 0, sizeof(a));
-    a.dh2 = p.dh2; a.ldh = m->ldh; a.V3a = m->P[P_V3].p; a.ldv = m->ldh; a.N = m->N; a.B = p.rows;
-    a.nblk = p.nblk; a.Bb = p.bb; a.known = exclude_known ? p.known : nullptr; a.kw = p.kw;
-    a.cand_v = p.cand_v; a.cand_i = p.cand_i; a.mm = p.mm; a.one_term = m->bf16 ? 1 : 0;
+    RankArgs a;
+    TRY(rank_mask_and_args(m, p, bv, exclude_known, a, s));
     a.dbg = m->opt.rank_skip;
     const int grid = p.wgs * p.nblk;
     {
@@ -155,14 +192,8 @@ int rank_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, int k, i
 // dh2 (workspace) of `rows` rows -> the rank of every stored entry of the rows' truth, CSR order (rank_full.h)
 int rank_full_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, const BatchView& tv, int max_truth, int exclude_known,
                        int32_t* ranks_out, hipStream_t s) {
-    hipLaunchKernelGGL(known_mask_kernel, dim3(p.rows), dim3(256), 0, s, bv, exclude_known ? p.known : (unsigned*)nullptr, p.kw,
-                       p.dh2, m->ldh, m->h);
-    LAUNCHCHK("known_mask");
-    RankArgs a; memset(&a, 0, sizeof(a));
-    a.dh2 = p.dh2; a.ldh = m->ldh; a.V3a = m->P[P_V3].p; a.ldv = m->ldh; a.N = m->N; a.B = p.rows;
-    a.nblk = p.nblk; a.Bb = p.bb; a.known = exclude_known ? p.known : nullptr; a.kw = p.kw;
-    a.one_term = m->bf16 ? 1 : 0;
-    a.tgt_i = p.tgt_i; a.tgt_v = p.tgt_v; a.tcount = p.tcount;
+    RankArgs a;
+    TRY(rank_mask_and_args(m, p, bv, exclude_known, a, s));
     const int grid = p.wgs * p.nblk;
     ProfScope ps(m, AAE_K_RANK, s);
     for (int g = 0; g * kFullSlots < max_truth; ++g) {      // 8 held-out items a row and round
@@ -263,14 +294,6 @@ int rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* cond_
     return launch_chain(m, cb, s);
 }
 
-// predict -> rank for batch->n_rows <= rank_rows_cap rows
-int rank_predict(aae_model* m, const aae_batch* batch, const float* cond_dev, int k, int exclude_known, int32_t* idx_out,
-                 float* val_out, hipStream_t s) {
-    const RankPlan p = rank_plan(m, batch->n_rows, k, m->G.p);
-    TRY(rank_predict_hidden(m, batch, cond_dev, p, s));
-    return rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out, val_out, s);
-}
-
 // the same from a decoder input the caller built: zc_dev [rows][zc_ld] -> p.dh2
 int rank_decode_hidden(aae_model* m, const float* zc_dev, int64_t zc_ld, int rows, const RankPlan& p, hipStream_t s) {
     const int cp = m->cp;
@@ -286,41 +309,18 @@ int rank_decode_hidden(aae_model* m, const float* zc_dev, int64_t zc_ld, int row
     return launch_chain(m, cb, s);
 }
 
-int rank_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, int k, int exclude_known,
-                int32_t* idx_out, float* val_out, hipStream_t s) {
-    const RankPlan p = rank_plan(m, batch->n_rows, k, m->G.p);
-    TRY(rank_decode_hidden(m, zc_dev, zc_ld, batch->n_rows, p, s));
-    return rank_from_dh2(m, p, rank_view(batch), k, exclude_known, idx_out, val_out, s);
-}
-
-// full ranking of batch->n_rows <= rank_full_rows_cap rows against their truth rows
-int rank_full_predict(aae_model* m, const aae_batch* batch, const float* cond_dev, const aae_batch* truth, int exclude_known,
-                      int32_t* ranks_out, hipStream_t s) {
-    const RankPlan p = rank_plan(m, batch->n_rows, 32, m->G.p, true);
-    TRY(rank_predict_hidden(m, batch, cond_dev, p, s));
-    return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out, s);
-}
-int rank_full_decode(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth,
-                     int exclude_known, int32_t* ranks_out, hipStream_t s) {
-    const RankPlan p = rank_plan(m, batch->n_rows, 32, m->G.p, true);
-    TRY(rank_decode_hidden(m, zc_dev, zc_ld, batch->n_rows, p, s));
-    return rank_full_from_dh2(m, p, rank_view(batch), rank_view(truth), truth->max_row_nnz, exclude_known, ranks_out, s);
-}
-
 // k > 32, the dense form: [rows][ldn] scores in the scratch -> [rows][k]
 int rank_long_dense(aae_model* m, int k, int exclude_known, int32_t* idx_out, float* val_out, hipStream_t s) {
     ProfScope ps(m, AAE_K_RANK, s);
     return dense_topk(m->G.p, m->ldn, m->N, m->bv, m->rows, k, exclude_known, idx_out, val_out, s);
 }
 
-// After a fused k > 32 call: the rows' entry counts (synchronises `s`), the handle's statistics, and the spans of at most
-// max_batch rows that hold a row whose list overflowed - the caller ranks those through the score matrix.
-int rank_long_overflow(aae_model* m, const aae_batch* b, int k, hipStream_t s, std::vector<std::pair<int, int>>& spans,
-                       float* base = nullptr) {
+// After a fused k > 32 call over plan `p`: the rows' entry counts (synchronises `s`), the handle's statistics, and the spans
+// of at most max_batch rows that hold a row whose list overflowed - the caller ranks those through the score matrix.
+int rank_long_overflow(aae_model* m, const aae_batch* b, const RankPlan& p, hipStream_t s, std::vector<std::pair<int, int>>& spans) {
     const int rows = b->n_rows;
     // (a span keeps to the dense path's per-batch bounds: max_batch rows, max_nnz entries)
     const int span = std::max(1, std::min(m->R, b->max_row_nnz > 0 ? m->cfg.max_nnz / b->max_row_nnz : m->R));
-    const RankPlan p = rank_plan(m, rows, k, base ? base : m->G.p);      // (base: a workspace that starts behind the scratch's head)
     std::vector<int> cnt(rows);
     HIPCHK(hipMemcpyAsync(cnt.data(), p.count, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -335,18 +335,36 @@ int rank_long_overflow(aae_model* m, const aae_batch* b, int k, hipStream_t s, s
     return AAE_OK;
 }
 
-// rows [off, off + n) of a batch as a batch of their own, within the per-batch bounds of the dense path
-aae_batch rank_sub_batch(const aae_model* m, const aae_batch* b, int off, int n) {
-    aae_batch c = *b;
-    if (c.rows_dev) c.rows_dev += off; else c.row_start += off;
-    c.n_rows = n; c.generation = 0;
-    if (b->max_row_nnz > 0) c.nnz_bound = (int32_t)std::min<int64_t>((int64_t)n * b->max_row_nnz, b->nnz_bound);
+// The rows of a model's ranking call.  zc != NULL: the decode form - a caller-built decoder input (code | imposed conditions
+// of any plugin kind), the second half of predict (aae.py:855-866); `batch` names the input rows whose items are excluded and
+// cond / eps are not read.
+struct RankInput {
+    aae_batch batch;
+    const float* cond;          // predict form: [rows][cond_inc] (NULL without a condition)
+    const float* eps;           // ... of the aae_vae_* calls: [rows][n_code] (NULL: the counter generator, rows counted from grow0)
+    const float* zc; int64_t zc_ld;
+    int grow0;                  // the generator row of row 0
+    bool vae;                   // the aae_vae_* family was called (its checks have seen a VAE handle)
+};
+
+// rows [off, off + n) of a call as a call of their own, within the per-batch bounds of the dense path: the one place that
+// knows the strides of a call's inputs
+RankInput rank_cut(const aae_model* m, const RankInput& in, int off, int n) {
+    RankInput c = in;
+    aae_batch& b = c.batch;
+    if (b.rows_dev) b.rows_dev += off; else b.row_start += off;
+    b.n_rows = n; b.generation = 0;
+    if (b.max_row_nnz > 0) b.nnz_bound = (int32_t)std::min<int64_t>((int64_t)n * b.max_row_nnz, b.nnz_bound);
+    const size_t r0 = (size_t)off;
+    auto from_r0 = [r0](const float* p, size_t ld) { return p ? p + r0 * ld : nullptr; };
+    c.cond = from_r0(c.cond, m->cfg.cond_inc); c.eps = from_r0(c.eps, m->c); c.zc = from_r0(c.zc, c.zc_ld);
+    c.grow0 += off;
     return c;
 }
 
 // ---- argument checks of every ranking entry point, the handle-free ones included: `who` (the entry point) opens the message ----
-int rank_check_batch(const aae_batch* b) {
-    if (!b || !b->indptr_dev || !b->indices_dev || !b->values_dev) return fail(AAE_EINVAL, "batch pointers are NULL");
+int rank_check_batch(const char* who, const aae_batch* b) {
+    if (!b || !b->indptr_dev || !b->indices_dev || !b->values_dev) return fail(AAE_EINVAL, std::string(who) + ": batch pointers are NULL");
     return AAE_OK;
 }
 int rank_check_k(const char* who, int k, int n_items) {
@@ -365,35 +383,36 @@ int rank_check_truth(const char* who, int n_rows, const aae_batch* truth) {
     return AAE_OK;
 }
 
+// The one check of the model's ranking entry points - the eight calls and the four *_max_rows.  form: what the entry point
+// takes; ptrs: its handle and every pointer that must not be NULL were given; k: NULL for a full-ranking call, which names
+// its truth rows instead.  Nothing is launched before it passes.
+enum { kRankFormRows, kRankFormPredict, kRankFormDecode };      // (rows: a *_max_rows call - no batch)
+int rank_check_call(const char* who, const aae_model* m, bool vae, int form, bool ptrs, const int32_t* k, const float* cond_dev,
+                    const float* eps_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth) {
+    const std::string w(who);
+    if (!m || !ptrs) return fail(AAE_EINVAL, w + ": NULL argument");
+    if (vae && (!m->vae || !m->use_chain)) return fail(AAE_ESTATE, w + ": model was not created in VAE mode (cfg.model_kind = 3)");
+    auto predict_args = [&]() {
+        if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, w + ": cond_inc > 0 needs cond_dev");
+        if (vae && m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, w + ": rng_mode inject needs eps_dev");
+        return AAE_OK;
+    };
+    // (the aae_vae_* calls name a missing cond / eps before a k out of range, the aae_* calls behind it)
+    if (form == kRankFormPredict && vae) TRY(predict_args());
+    if (k) TRY(rank_check_k(who, *k, m->N));
+    if (form == kRankFormPredict && !vae) TRY(predict_args());
+    if (form == kRankFormRows) return AAE_OK;
+    if (form == kRankFormDecode && zc_ld < m->cp) return fail(AAE_EINVAL, w + ": zc_ld < n_code + cond_inc");
+    TRY(rank_check_batch(who, batch));
+    if (k) return AAE_OK;
+    TRY(rank_check_truth(who, batch->n_rows, truth));
+    if (truth->max_row_nnz < 1) return fail(AAE_EINVAL, w + ": truth needs max_row_nnz: the entries of its longest row (an upper bound)");
+    return AAE_OK;
+}
+
 // ---- the VAE's form (aae_vae_predict_topk / _ranks / _decode_topk / _decode_ranks; reference vae.py:229-266) -------------
 // The same workspace, the same ranking passes over dec.lin3 (= fc4); the hidden half is the VAE's forward in ONE program on the
 // 4-row kernel: eh1 -> [mu | logvar] = [fc21; fc22] eh1 -> z = mu + eps * exp(logvar / 2) -> condition block -> dh2 = act(fc3 zc).
-// A VAE handle keeps no k-major copies of its layers (its training programs run on chain.h, whose optimiser epilogues would
-// have to keep them in step): a rank call derives the F4 copies of the two small matrices into the head of its workspace -
-// ~60 k floats at the headline widths, two launches - and lays its plan out behind them.
-struct VaeRankCopies { float* w3; float* v1; float* d4; size_t floats; };
-
-VaeRankCopies vae_rank_copies(const aae_model* m, float* base) {
-    auto f4 = [](const Ten& W) { return (size_t)((W.cols + 3) / 4 + kW4Pad) * 4 * W.rows; };          // (+ the zero k-chunk rows, chain4.h)
-    auto d4 = [](const Ten& W) { return (size_t)((W.rows + 3) / 4) * 4 * W.cols; };
-    const Ten &W3 = m->P[P_W3], &V1 = m->P[P_V1];
-    VaeRankCopies c;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return base ? base + o : nullptr; };
-    c.w3 = take(f4(W3)); c.v1 = take(f4(V1));
-    c.d4 = take(std::max(d4(W3), d4(V1)));       // (interleave4_kernel writes the dX copy too: nobody reads it)
-    c.floats = off;
-    return c;
-}
-
-int vae_rank_rows_cap(const aae_model* m, int k) {
-    const size_t have = rank_ws_floats(m), head = vae_rank_copies(m, nullptr).floats;
-    return m->vae_rank_ok && have > head ? rank_rows_fit(m, k, have - head) : 0;
-}
-int vae_rank_full_rows_cap(const aae_model* m) {
-    const size_t have = rank_ws_floats(m), head = vae_rank_copies(m, nullptr).floats;
-    return m->vae_rank_ok && have > head ? rank_full_rows_fit(m, have - head) : 0;
-}
 
 // the F4 copies from the parameters as they stand (behind join_deferred: nothing else writes or reads the scratch)
 int vae_rank_derive(aae_model* m, const VaeRankCopies& c, hipStream_t s) {
@@ -457,19 +476,28 @@ int vae_rank_decode_hidden(aae_model* m, const float* zc_dev, int64_t zc_ld, int
     return launch_chain(m, cb, s);
 }
 
-// A row of a fused k > 32 call whose collect list overflowed: rows [0, sub->n_rows) of `sub` (<= max_batch) through the score
-// matrix.  The hidden half runs the fused call's own program on the handle's per-batch buffers - the same eps rows (eps_dev /
-// generator rows from grow0), the same dh2 bits - then fc4 + sigmoid into the scratch, which the copies' head is part of: they
-// are derived again per span.
-int vae_rank_long_span(aae_model* m, const aae_batch* sub, const float* cond_dev, const float* eps_dev, const float* zc_dev, int64_t zc_ld,
-                       int grow0, int k, int exclude_known, int32_t* idx_out, float* val_out, hipStream_t s) {
-    TRY(set_batch(m, sub));
-    const VaeRankCopies c = vae_rank_copies(m, m->G.p);
-    if (zc_dev) TRY(vae_rank_decode_hidden(m, zc_dev, zc_ld, m->rows, c, m->dh2.p, s));
-    else TRY(vae_rank_predict_hidden(m, sub, cond_dev, eps_dev, grow0, c, m->a1.p, m->eh1.p, m->rscale, m->dh2.p, s));
+// ---- the hidden half of a fused call, either kind of handle, either form: rows of `in` -> w.p.dh2 [rows][ldh] (w.p.a1 / eh1 /
+// rscale: [rows] scratch of the predict form's first layer) ---------------------------------------------------------------
+int rank_hidden(aae_model* m, const RankInput& in, const RankWs& w, hipStream_t s) {
+    const RankPlan& p = w.p;
+    const int rows = in.batch.n_rows;
+    if (!in.vae) return in.zc ? rank_decode_hidden(m, in.zc, in.zc_ld, rows, p, s) : rank_predict_hidden(m, &in.batch, in.cond, p, s);
+    if (in.zc) return vae_rank_decode_hidden(m, in.zc, in.zc_ld, rows, w.c, p.dh2, s);
+    return vae_rank_predict_hidden(m, &in.batch, in.cond, in.eps, in.grow0, w.c, p.a1, p.eh1, p.rscale, p.dh2, s);
+}
+
+// A span of a fused k > 32 aae_vae_* call that holds a row whose collect list overflowed: the rows of `sub` (<= max_batch)
+// -> their scores in the scratch.  The hidden half runs the fused call's own program on the handle's per-batch buffers - the
+// same eps rows (eps / generator rows from grow0), the same dh2 bits - then fc4 + sigmoid into the scratch, which the copies'
+// head is part of: they are derived again per span.
+int vae_span_scores(aae_model* m, const RankInput& sub, hipStream_t s) {
+    TRY(set_batch(m, &sub.batch));
+    RankWs w; memset(&w, 0, sizeof(w));
+    w.c = vae_rank_copies(m, m->G.p);
+    w.p.a1 = m->a1.p; w.p.eh1 = m->eh1.p; w.p.rscale = m->rscale; w.p.dh2 = m->dh2.p;
+    TRY(rank_hidden(m, sub, w, s));
     EpiSigmoid e; e.out = m->G.p; e.ld = m->ldn;
-    TRY(linear_fwd(m->dh2.p, m->ldh, m->rows, m->P[P_V3], e, s, gmode(m)));
-    return rank_long_dense(m, k, exclude_known, idx_out, val_out, s);
+    return linear_fwd(m->dh2.p, m->ldh, m->rows, m->P[P_V3], e, s, gmode(m));
 }
 
 }  // namespace

@@ -78,34 +78,41 @@ template <class F> void each_dec_opt_blocks_x3(F&& f) {
     for (int nb : kPickNb) for (int i = 0; i < 4; ++i) if (DecKernel k = pick_dec_opt_blocks_x3(nb, i & 1, i & 2)) f(k);
 }
 
-// ---- rank_x3.h.  Which of the two rank kernels a call takes: the v2 wave mapping where its registers do not spill (the
-// other list sizes keep rank_x3_kernel, the r4 mapping).  Both are compiled for every (NB, K).
-inline bool rank_v2_nb(int nb, int K) { return K == 10 || (K == 20 && nb < 13); }
+// ---- rank_x3.h.  Which of the two rank kernels keeps the lists of a (NB, K): the v2 wave mapping where its registers do
+// not spill, rank_x3_kernel (the r4 mapping) for the other list sizes.  The choice is static, so each (NB, K) is compiled
+// in the one form it is launched in.
+constexpr bool rank_v2_nb(int nb, int K) { return K == 10 || (K == 20 && nb < 13); }
+// a rank launch: the kernel, its dynamic LDS, and the name a launch error carries
+struct RankPick { RankKernel kernel; size_t lds; const char* name; };
+inline RankPick pick_rank_lists(int nb, int K, bool win) {
+    const bool v2 = rank_v2_nb(nb, K);
+    const RankKernel kernel = pick_nb<RankKernel>(nb, [&](auto NB) { return pick_k<RankKernel>(K, [&](auto KK) {
+        return pick_flags<RankKernel>([](auto WIN) -> RankKernel {
+            constexpr int K_ = decltype(KK)::value;
+            if constexpr (rank_v2_nb(NB_, K_)) return rank_x3v2_kernel<NB_, K_, WIN()>; else return rank_x3_kernel<NB_, K_, WIN(), kRankLists>; }, win); }); });
+    return {kernel, v2 ? rank_x3v2_lds_bytes(nb) : rank_x3_lds_bytes(nb), v2 ? "rank_x3v2" : "rank_x3"};
+}
 // K = 1 is the front end of the epilogues that keep no lists - collect (rank_long.h), pick and count (rank_full.h): they exist
 // with it alone, and it not without one of them
-inline RankKernel pick_rank_x3(int nb, int K, bool win, int epi) {
-    return pick_nb<RankKernel>(nb, [&](auto NB) { return pick_of<RankKernel, 1, 10, 20, 32>(K, [&](auto KK) {
-        return pick_of<RankKernel, kRankLists, kRankCollect, kRankPick, kRankCount>(epi, [&](auto EPI) {
-            return pick_flags<RankKernel>([](auto WIN) -> RankKernel {
-                constexpr int K_ = decltype(KK)::value, EPI_ = decltype(EPI)::value;
-                if constexpr ((K_ == 1) != (EPI_ != kRankLists)) return nullptr; else return rank_x3_kernel<NB_, K_, WIN(), EPI_>; }, win); }); }); });
-}
-inline RankKernel pick_rank_x3v2(int nb, int K, bool win) {
-    return pick_nb<RankKernel>(nb, [&](auto NB) { return pick_k<RankKernel>(K, [&](auto KK) {
-        return pick_flags<RankKernel>([](auto WIN) -> RankKernel { return rank_x3v2_kernel<NB_, decltype(KK)::value, WIN()>; }, win); }); });
+inline RankPick pick_rank_epilogue(int nb, int epi, bool win) {
+    const RankKernel kernel = pick_nb<RankKernel>(nb, [&](auto NB) { return pick_of<RankKernel, kRankCollect, kRankPick, kRankCount>(epi, [&](auto EPI) {
+        return pick_flags<RankKernel>([](auto WIN) -> RankKernel { return rank_x3_kernel<NB_, 1, WIN(), decltype(EPI)::value>; }, win); }); });
+    return {kernel, rank_x3_lds_bytes(nb), epi == kRankCollect ? "rank_x3 (collect)" : epi == kRankPick ? "rank_x3 (pick)" : "rank_x3 (count)"};
 }
 inline MergeKernel pick_rank_merge(int K) {
     return pick_k<MergeKernel>(K, [](auto KK) -> MergeKernel { return rank_merge_kernel<KK()>; });
 }
-// f(kernel, nb): the LDS of a rank kernel goes with its NB (rank_x3_lds_bytes / rank_x3v2_lds_bytes)
-template <class F> void each_rank_x3(F&& f) {
+template <class F> void each_rank(F&& f) {
     for (int nb : kPickNb) for (int win = 0; win < 2; ++win) {
-        for (int K : kPickK) f(pick_rank_x3(nb, K, win, kRankLists), nb);
-        for (int epi : {kRankCollect, kRankPick, kRankCount}) f(pick_rank_x3(nb, 1, win, epi), nb);
+        for (int K : kPickK) f(pick_rank_lists(nb, K, win));
+        for (int epi : {kRankCollect, kRankPick, kRankCount}) f(pick_rank_epilogue(nb, epi, win));
     }
 }
-template <class F> void each_rank_x3v2(F&& f) {
-    for (int nb : kPickNb) for (int win = 0; win < 2; ++win) for (int K : kPickK) f(pick_rank_x3v2(nb, K, win), nb);
+
+// ---- kernels.h: the register lists of the dense form, k <= 32 (K = rank_K(k)).  Static LDS: no limit to raise
+using TopkRowsKernel = void (*)(float*, int, int, BatchView, int, int, int*, float*);
+inline TopkRowsKernel pick_topk_rows(int K) {
+    return pick_k<TopkRowsKernel>(K, [](auto KK) -> TopkRowsKernel { return topk_rows_kernel<KK()>; });
 }
 
 // ---- rank_long.h / rank_full.h, the dense forms, and cooc.h: one member per score type (DenseScore) - float, what every

@@ -4,8 +4,8 @@
 // items are not rankable (exclude_known), the better score first, the smaller id at equal scores.  Only nnz(truth) integers
 // leave the GPU; the [rows, n_items] matrix is never sorted, and in the fused form it never exists.
 //
-//   fused form (handles with rank_ok), behind the gather, the chain program and known_mask_kernel of rank_predict /
-//   rank_decode (abi_rank.h).  The front end of rank_x3_kernel<NB, 1> - the kernel every list of k > 20 comes from, so the
+//   fused form (handles with rank_ok), behind the gather, the chain program and known_mask_kernel of a fused ranking
+//   call (abi_rank.h).  The front end of rank_x3_kernel<NB, 1> - the kernel every list of k > 20 comes from, so the
 //   logits carry the same bits as the ones those lists were ordered by - with two more epilogues, kFullSlots = 8 held-out
 //   items per row and pair of launches:
 //     1. rank_full_setup_kernel          the rows' next 8 held-out ids into tgt_i (-1: none), their counters zeroed

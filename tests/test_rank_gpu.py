@@ -227,3 +227,69 @@ def test_fused_rank_degenerate_shapes(N, h, c, R, rows, k):
         if n_ok:
             kth = np.sort(sc[free])[-n_ok]
             assert np.all(sc[got] >= kth - 2e-6)
+
+
+RANK_ENTRY_POINTS = [fam + form + kind for fam in ("aae_", "aae_vae_") for form in ("predict_", "decode_") for kind in ("topk", "ranks")]
+
+
+@pytest.fixture(scope="module")
+def refusal_handles():
+    """A tiny AAE handle and a VAE handle in inject mode, both with a condition, and one set of valid arguments for every
+    model ranking entry point: 12 input rows, their truth rows, and a truth of 11 rows."""
+    from aaerec._hip import HipAAE, DeviceCSR
+    from tools.synth import init_params
+    N, h, c, inc, R, rows = 64, 8, 3, 2, 16, 12
+    r = np.random.default_rng(11)
+    aae = HipAAE(N, h, c, cond_inc=inc, max_batch=R, rng_mode="device", seed=1)
+    aae.load_params(init_params(N, h, c, cond_inc=inc, seed=3))
+    vae = HipAAE(N, h, c, cond_inc=inc, max_batch=R, rng_mode="inject", dropout=(0.0, 0.0), vae=True)
+    vae.load_params({f"{name}.{part}": r.uniform(-0.3, 0.3, shape if part == "weight" else shape[:1]).astype(np.float32)
+                     for name, shape in (("enc.lin1", (h, N)), ("enc.lin3", (2 * c, h)), ("dec.lin1", (h, c + inc)), ("dec.lin3", (N, h)))
+                     for part in ("weight", "bias")})
+    ip, idx, val, _ = _corpus(r, N, rows, 10)
+    tp, tidx, tval, _ = _corpus(r, N, rows, 4)
+    dev = aae.device
+    csr, truth = DeviceCSR.from_arrays(ip, idx, val, N, dev), DeviceCSR.from_arrays(tp, tidx, tval, N, dev)
+    args = dict(batch=aae._batch(csr, 0, rows), truth=aae._batch(truth, 0, rows, bounded=False), truth_11=aae._batch(truth, 0, rows - 1, bounded=False),
+                cond=torch.zeros(rows, inc, device=dev), eps=torch.zeros(rows, c, device=dev), zc=torch.zeros(rows, c + inc, device=dev),
+                zc_narrow=torch.zeros(rows, c + inc - 1, device=dev), k=5, idx=torch.empty(rows, N + 1, dtype=torch.int32, device=dev),
+                val=torch.empty(rows, N + 1, device=dev), ranks=torch.empty(int(tp[-1]), dtype=torch.int32, device=dev))
+    return aae, vae, args, (csr, truth)
+
+
+def _rank_entry(dev, name, a):
+    """Calls the entry point `name` on the handle with the arguments of `a`, in the order of include/aaerec_hip.h."""
+    from aaerec import _hip
+    vae, topk = name.startswith("aae_vae_"), name.endswith("topk")
+    lead = [a["zc"], a["zc"].shape[1], a["batch"]] if "decode" in name else [a["batch"], a["cond"]] + ([a["eps"]] if vae else [])
+    call = [dev.handle] + lead + [a["k"] if topk else a["truth"], 1] + ([a["idx"], a["val"]] if topk else [a["ranks"]]) + [dev._stream()]
+    with dev._on_device():
+        _hip._check(getattr(dev.lib, name)(*map(_hip._arg, call)))
+
+
+@pytest.mark.parametrize("name", RANK_ENTRY_POINTS)
+def test_the_ranking_entry_points_refuse_bad_arguments_by_name(refusal_handles, name):
+    """Each of the eight model ranking entry points refuses a k out of range, a missing cond, a missing eps in inject mode, a
+    zc narrower than n_code + cond_inc, a truth of another row count, and an aae_vae_* call on an AAE handle: AaeHipError,
+    the message opening with the entry point's name.  The same arguments unchanged are accepted."""
+    from aaerec._hip import AaeHipError
+    aae, vae, good, _ = refusal_handles
+    is_vae, topk, decode = name.startswith("aae_vae_"), name.endswith("topk"), "decode" in name
+    dev = vae if is_vae else aae
+    _rank_entry(dev, name, good)
+    torch.cuda.synchronize()
+    bad = []
+    if topk:
+        bad += [("k = 0", dev, dict(k=0)), ("k = n_items + 1", dev, dict(k=dev.N + 1))]
+    if decode:
+        bad += [("narrow zc", dev, dict(zc=good["zc_narrow"]))]
+    else:
+        bad += [("no cond", dev, dict(cond=None))] + ([("no eps", dev, dict(eps=None))] if is_vae else [])
+    if not topk:
+        bad += [("truth of 11 rows", dev, dict(truth=good["truth_11"]))]
+    if is_vae:
+        bad += [("an AAE handle", aae, {})]
+    for what, handle, change in bad:
+        with pytest.raises(AaeHipError, match=rf"error -?\d+: {name}: ") as e:
+            _rank_entry(handle, name, {**good, **change})
+        print(name, what, "->", e.value)

@@ -209,29 +209,32 @@ def test_saturated_scores_give_a_valid_long_list():
         assert len(set(ids[row].tolist())) == k and not (set(ids[row].tolist()) & set(docs[row].tolist()))
 
 
-def test_overflowing_collect_lists_take_the_exact_fallback():
+@pytest.mark.parametrize("inc", [0, 7])
+def test_overflowing_collect_lists_take_the_exact_fallback(inc):
     """RANK_COLLECT_CAP set to a handful of entries: every row's list overflows and is ranked through the score matrix -
-    the same scores, a valid list; unset, no row of the same call overflows."""
+    the same scores, a valid list; unset, no row of the same call overflows.  With a condition (inc = 7) the spans that start
+    at rows 64 and 128 read their own condition rows: a wrong offset would show."""
     from aaerec import _hip
     k, rows, R = 100, 150, 64
     _hip.set_option("RANK_COLLECT_CAP", 8)
     try:
-        small, csr, docs, _ = _model(3, 20000, 100, 30, 0, R, rows, steps=0)     # (no training: both handles hold the same weights)
+        small, csr, docs, cdev = _model(3, 20000, 100, 30, inc, R, rows, steps=0)     # (no training: both handles hold the same weights)
     finally:
         _hip.set_option("RANK_COLLECT_CAP", None)
-    dev, csr2, docs2, _ = _model(3, 20000, 100, 30, 0, R, rows, steps=0)
+    dev, csr2, docs2, cdev2 = _model(3, 20000, 100, 30, inc, R, rows, steps=0)
     assert min(small.rank_max_rows(k), dev.rank_max_rows(k)) >= rows
-    ids, vals = (t.cpu().numpy() for t in dev.predict_topk(csr2, 0, rows, k))
+    ids, vals = (t.cpu().numpy() for t in dev.predict_topk(csr2, 0, rows, k, cond=cdev2))
     st = dev.rank_long_stats()
     assert st["calls"] == 1 and st["overflow_rows"] == 0, st
-    ids_s, vals_s = (t.cpu().numpy() for t in small.predict_topk(csr, 0, rows, k))
+    ids_s, vals_s = (t.cpu().numpy() for t in small.predict_topk(csr, 0, rows, k, cond=cdev))
     st = small.rank_long_stats()
     assert st["calls"] == 1 and st["overflow_rows"] == rows, st
-    full = _dense(small, csr, rows, R)
+    full = _dense(small, csr, rows, R, cdev)
     _assert_lists(ids_s, vals_s, full, docs, k, True, 2e-6, "overflow")
     np.testing.assert_allclose(vals_s, vals, atol=2e-6)
     z = torch.cat([small.encode(csr, s, min(R, rows - s)) for s in range(0, rows, R)])
-    ids_d, vals_d = (t.cpu().numpy() for t in small.decode_topk(z, csr, 0, k))
+    zc = z if cdev is None else torch.cat([z, cdev], 1)
+    ids_d, vals_d = (t.cpu().numpy() for t in small.decode_topk(zc, csr, 0, k))
     _assert_lists(ids_d, vals_d, full, docs, k, True, 2e-6, "overflow decode_topk")
 
 
