@@ -110,7 +110,7 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     if (need > arena_bytes) { delete m; return fail(AAE_ENOMEM, "arena smaller than aae_arena_bytes()"); }
     m->base = static_cast<char*>(arena_dev); m->bytes = need;
     m->alpha_mode = cfg->activation == AAE_ACT_SELU;
-    m->vae = cfg->model_kind == 3; m->vae_bwd = false; m->vae_cut = false;
+    m->vae = cfg->model_kind == 3; m->vae_cut = false;
     m->bf16 = cfg->dtype == 1;
     m->blocked_ok = cfg->blocked_output == 1;
     m->blocked_any = m->opt.blocked_any;

@@ -515,6 +515,21 @@ struct DwBuilder {
     }
 };
 
+// The ae phase's weight-gradient jobs of the running batch, in the order every grouped launch of them keeps: the decoder's
+// hidden pair V2, V1, then the encoder's group W3, W2 + the first layer's bias (and per-item update) by enc_optim.
+void dw_add_decoder(DwBuilder& dw, aae_model* m) {
+    dw.add(m, m->gb0.p, m->ldh, m->dh1.p, m->ldh, m->rows, P_V2, O_DEC);
+    dw.add(m, m->gb1.p, m->ldh, m->zc.p, m->ldc, m->rows, P_V1, O_DEC);
+}
+// (dL/d(a1) is read where chain_ae_backward left it: ga1_ptr - gb3 unless the first layer is external in export mode,
+//  where only its bias blocks ride here)
+int dw_add_encoder(DwBuilder& dw, aae_model* m, hipStream_t s) {
+    dw.add(m, m->ga3.p, m->ldz, m->eh2.p, m->ldh, m->rows, P_W3, O_ENC);
+    dw.add(m, m->gb2.p, m->ldh, m->eh1.p, m->ldh, m->rows, P_W2, O_ENC);
+    TRY(dw.add_first_layer(m, ga1_ptr(m), O_ENC, s)); m->w1_merged = true;
+    return AAE_OK;
+}
+
 // the head items a wave-form first-layer update left on its hot list: the workgroup form over that list (w1_update.h)
 int launch_w1_hot(aae_model* m, hipStream_t s) {
     if (!m->w1_hot_pending) return AAE_OK;
@@ -609,6 +624,14 @@ int build_tile_buckets(aae_model* m, hipStream_t s) {
     }
     LAUNCHCHK("tile buckets");
     m->buckets_valid = true;
+    return AAE_OK;
+}
+// ... on the side stream, beside the step's opening launches instead of in front of their first reader; ev_bk is that
+// reader's wait (bk_pending).  When this pays is the caller's condition.
+int build_tile_buckets_aside(aae_model* m) {
+    TRY(build_tile_buckets(m, m->side));
+    HIPCHK(hipEventRecord(m->ev_bk, m->side));
+    m->bk_pending = true;
     return AAE_OK;
 }
 // the tile buckets of the running batch exist and are visible to stream s (the first layer's update reads them, w1_update.h)
@@ -816,39 +839,40 @@ int encoder_first_layer_update(aae_model* m, const float* ga1, int which, hipStr
     return launch_w1_items(m, ga1, 0, 0, which, s);
 }
 
-// done_ev: an event that rides on the launch's completion signal (the side stream's "the step has begun" mark)
+// The first layer's gather on the chain path, one launch: a1 = (bias +) x * enc.lin1^T of the running batch; act_out != NULL:
+// dropout d + activation -> act_out (NULL: the partial form of an item slice, aae_first_layer_forward).
 // head: tell the side stream that the main stream has passed this launch (ev_head rides on its completion signal)
-int gather_first_layer(aae_model* m, bool train, const uint8_t* mk1, uint32_t sid1, hipStream_t s, bool head = false,
-                       bool open_step = false) {
-    const int B = m->rows, h = m->h;
-    DropSpec d1 = make_drop(m, 0, train, mk1, nullptr, B, h, sid1);
+// (the per-layer path's and the rank calls' gathers are launches of their own: always 16 waves, no step to open)
+int launch_gather(aae_model* m, const float* bias, float* act_out, const DropSpec& d, bool head, bool open_step, const char* what,
+                  hipStream_t s) {
     ProfScope ps(m, AAE_K_ENC_GATHER, s);
-    size_t shm = (size_t)16 * r4(h) * sizeof(float);
-    // wide batches: four waves per document (eight documents per CU instead of two; a document is ~20 entries: five per wave).
+    const size_t shm = (size_t)16 * r4(m->h) * sizeof(float);
+    // wide batches: four waves per document (eight documents per CU instead of two; a document is ~20 entries: five per wave;
+    // an item slice holds 1 / world of a document's entries).
     // ms/step, 16 | 4 waves: C3 at batch 512 0.651 | 0.646, C4 (1 000 rows) 0.389 | 0.381; C2's shape at batch 500 0.327 | 0.331,
     // C3 at batch 100 0.239 | 0.251 (tools/debug/gather4_ab.sh)
     constexpr int g4_rows = 512;
-    if (B >= g4_rows) {
-        hipExtLaunchKernelGGL(enc_gather_kernel_t<4>, dim3(B), dim3(256), (uint32_t)(shm / 4), s, nullptr, head ? m->ev_head : nullptr, 0, m->bv,
-                              (const float*)m->P[P_W1T].p, m->ldw1, (const float*)m->P[P_B1].p, h, (int)m->cfg.normalize_inputs,
-                              m->a1.p, m->eh1.p, m->ldh, (int)m->cfg.activation, d1, (uint64_t)m->cfg.seed,
-                              (const long long*)m->step_ctr, m->rscale, m->doc_l1,
-                              AdvanceJob{m->sc, m->step_ctr, m->lazy ? m->tab : nullptr, m->losses, open_step ? 1 : 0,
-                                         head ? m->stamp2 : nullptr, head ? m->ucount2 : nullptr},
-                              (long long)(open_step ? m->hstep : -1));
-    } else
-    hipExtLaunchKernelGGL(enc_gather_kernel, dim3(B), dim3(1024), (uint32_t)shm, s, nullptr, head ? m->ev_head : nullptr, 0, m->bv,
-                          (const float*)m->P[P_W1T].p, m->ldw1, (const float*)m->P[P_B1].p, h, (int)m->cfg.normalize_inputs,
-                          m->a1.p, m->eh1.p, m->ldh, (int)m->cfg.activation, d1, (uint64_t)m->cfg.seed,
-                          (const long long*)m->step_ctr, m->rscale, m->doc_l1,
-                          // open_step: the step-opening bookkeeping rides in this launch (advance_step_body) and the
-                          // workgroups take the step number from the host (m->hstep == *step_ctr once the step is open)
-                          // head: the prefetch's first launch (new stamp, empty list) rides here as well - the catch-up behind it then
-                          // starts a launch earlier, ahead of the output layer's critical launch instead of beside its first workgroups
-                          AdvanceJob{m->sc, m->step_ctr, m->lazy ? m->tab : nullptr, m->losses, open_step ? 1 : 0,
-                                     head ? m->stamp2 : nullptr, head ? m->ucount2 : nullptr},
-                          (long long)(open_step ? m->hstep : -1));
-    LAUNCHCHK("enc_gather");
+    const bool four = m->rows >= g4_rows;
+    // open_step: the step-opening bookkeeping rides in this launch (advance_step_body) and the
+    // workgroups take the step number from the host (m->hstep == *step_ctr once the step is open)
+    // head: the prefetch's first launch (new stamp, empty list) rides here as well - the catch-up behind it then
+    // starts a launch earlier, ahead of the output layer's critical launch instead of beside its first workgroups
+    const AdvanceJob adv{m->sc, m->step_ctr, m->lazy ? m->tab : nullptr, m->losses, open_step ? 1 : 0,
+                         head ? m->stamp2 : nullptr, head ? m->ucount2 : nullptr};
+    hipExtLaunchKernelGGL(four ? enc_gather_kernel_t<4> : enc_gather_kernel_t<16>, dim3(m->rows), dim3(four ? 256 : 1024),
+                          (uint32_t)(four ? shm / 4 : shm), s, nullptr, head ? m->ev_head : nullptr, 0, m->bv,
+                          (const float*)m->P[P_W1T].p, m->ldw1, bias, m->h, (int)m->cfg.normalize_inputs,
+                          m->a1.p, act_out, m->ldh, (int)m->cfg.activation, d, (uint64_t)m->cfg.seed,
+                          (const long long*)m->step_ctr, m->rscale, m->doc_l1, adv, (long long)(open_step ? m->hstep : -1));
+    LAUNCHCHK(what);
+    return AAE_OK;
+}
+
+// the whole first layer of this handle's own: bias, dropout (train), activation -> eh1
+int gather_first_layer(aae_model* m, bool train, const uint8_t* mk1, uint32_t sid1, hipStream_t s, bool head = false,
+                       bool open_step = false) {
+    const DropSpec d1 = make_drop(m, 0, train, mk1, nullptr, m->rows, m->h, sid1);
+    TRY(launch_gather(m, m->P[P_B1].p, m->eh1.p, d1, head, open_step, "enc_gather", s));
     m->pf_bumped = head;
     return AAE_OK;
 }

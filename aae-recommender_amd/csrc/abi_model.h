@@ -100,7 +100,6 @@ struct aae_model {
     // activations
     Ten a1, eh1, eh2, zc, dh1, dh2, G, slabs, gb0, gb1, gb2, gb3, gzc, ga3, zin, xh1, xh2, dout, zsave, da2;
     Ten ga1x;                // export mode: see aae_create
-    bool only_output_layer;  // aae_output_layer_step: stop after the output layer, dL/d(dh2) summed into da2
     const float* doc_l1;     // aae_set_doc_l1: L1 norms of the complete documents (a handle that holds an item slice of them)
     bool ext_first;          // aae_set_first_layer_external: AAE_T_ACT_A1 comes from the caller, dL/d(a1) goes back to it
     bool own_first;          // ... but the layer's rows of THIS handle's items live here and are trained here (aae_shard_step: the
@@ -108,14 +107,12 @@ struct aae_model {
     bool ae_only;            // plain AutoEncoder (reference aae.py:221-458): no disc_step / gen_step
     bool vae;                // VAE (reference vae.py:47-266): P_W3 = [fc21; fc22] (2c rows), no V2/W2, KL term
     bool bf16;               // cfg.dtype = 1: bf16 matrix-core inputs for the GEMM-shaped products (fp32 accumulate / master / Adam)
-    bool vae_bwd;            // aae_vae_step is running: aae_ae_decode_backward continues with the VAE's backward
-    bool vae_cut;            // ... cut at the condition boundary (aae_vae_encode / _decode_backward / _encoder_backward)
+    bool vae_cut;            // the VAE step is cut at the condition boundary (aae_vae_encode / _decode_backward / _encoder_backward)
     Ten mulv, gmulv, veps;   // VAE: [mu | logvar], its gradient, eps of the step
     bool use_chain;          // row-blocked layer chains (chain.h) instead of one GEMM launch per layer
     bool use_chain4;         // ... with 4 rows per workgroup (chain4.h) where a program allows it
     bool act_nm;             // cfg.activation is one of the r6 classes (AAE_ACT_SOFTPLUS ..): its layer programs run on chain_kernel<.., true> only
     bool dec_hidden_done;    // the ae forward already ran the decoder's hidden layers (fused aae_step)
-    bool fuse_enc_bwd;       // aae_step: run the encoder backward in the decoder-backward program
     bool enc_bwd_done;
     int max_slabs;
     float* bce_partials; int bce_partials_cap;
@@ -532,6 +529,24 @@ DropSpec make_drop(const aae_model* m, int layer, bool train, const uint8_t* ma,
 }
 
 inline int grid1d(size_t n, int block = 256) { return (int)std::min<size_t>((n + block - 1) / block, 2048); }
+
+// split-K over the items of a [B, N] x [N, h] product into slabs (the dense first layer, the unfused dA2 = G * V3): enough
+// slices to put ~2 048 workgroups on the chip; returns the items per slice (a multiple of 64), *splits = the slices used
+inline int split_k_items(const aae_model* m, int B, int* splits) {
+    const int tiles = ((B + 63) / 64) * ((m->h + 63) / 64);
+    const int want = std::max(1, std::min(m->max_slabs, 2048 / tiles));
+    const int kps = ((m->N + want - 1) / want + 63) / 64 * 64;
+    *splits = (m->N + kps - 1) / kps;
+    return kps;
+}
+
+// What one decode-backward call does beyond the plain phase (decode_backward, abi_output_layer.h): set by the entry point
+// that makes the call and handed down, never stored on the handle
+struct DecodeMode {
+    bool only_output_layer = false;   // aae_output_layer_step: ACT_DH2 is the input; stop after the output layer, dL/d(dh2) summed into da2
+    bool vae = false;                 // aae_vae_step / aae_vae_decode_backward: continue with the VAE's backward
+    bool enc_too = false;             // aae_step: run the encoder backward in the decoder-backward program
+};
 
 
 }  // namespace

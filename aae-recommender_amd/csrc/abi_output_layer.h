@@ -11,6 +11,7 @@ struct DecLaunch {
     int ntiles, grid;           // 32-item tiles of the layer; workgroups of a launch on the whole chip
     bool win;                   // dec.lin3 beyond 2^31 bytes: the kernels' moving-window instantiations (dec_fused.h)
     size_t fused_lds;           // LDS of dec_fused.h's / dec_fused_bf16.h's own kernels
+    DecodeMode mode;            // of the decode-backward call this launch belongs to
     bool want_ts, ts_obk;       // debug (AAE_DEC_TS): phase timeline of one tile / of dec_opt_blocks_x3_kernel ("obk")
 };
 unsigned long long* dec_ts_dev = nullptr;      // debug (AAE_DEC_TS): the kernels' 128 timestamps
@@ -208,7 +209,7 @@ int output_layer_split(aae_model* m, const DecLaunch& L, int* n_loss_partials, i
     // an item slice's next batch (named ahead): its distinct items and their deferred-Adam catch-up behind the
     // deferred launch on the same stream (ordered behind this step's head by ev_crit; rows of the running batch
     // are skipped there, the step's own updates bring them to the same step)
-    if (m->only_output_layer && m->pf_armed && m->mark2 && m->lazy) TRY(launch_prefetch(m, false));
+    if (L.mode.only_output_layer && m->pf_armed && m->mark2 && m->lazy) TRY(launch_prefetch(m, false));
     return AAE_OK;
 }
 
@@ -237,14 +238,14 @@ int reduce_slabs(aae_model* m, const DecLaunch& L, int crit_slabs, int n_loss_pa
         hipLaunchKernelGGL(slab_partial_kernel, dim3((unsigned)((n4 + 255) / 256), ny), dim3(256), 0, s, src, n, slab_stride, n4, dst, dst_stride,
                            loss ? m->bce_partials : (const float*)nullptr, loss ? n_loss_partials : 0, loss ? 1.0f / ((float)B * (float)N) : 0.f, m->losses, 0);
     };
-    if (m->only_output_layer && crit_slabs <= 64) {
+    if (L.mode.only_output_layer && crit_slabs <= 64) {
         // (row blocks in one launch: 256 / nblk slabs - one pass sums them straight into dL/d(dh2), with the loss)
         sum_slabs(m->slabs.p, crit_slabs, m->da2.p, 0, 1, true);
         LAUNCHCHK("slabs -> da2");
         return AAE_OK;
     }
     sum_slabs(m->slabs.p, crit_slabs, part, slab_stride, 16, true);
-    if (m->only_output_layer) {
+    if (L.mode.only_output_layer) {
         sum_slabs(part, 16, m->da2.p, 0, 1, false);
         LAUNCHCHK("slab_partial -> da2");
     } else if (!m->use_chain) {
@@ -257,13 +258,14 @@ int reduce_slabs(aae_model* m, const DecLaunch& L, int crit_slabs, int n_loss_pa
 }
 
 // ---- fused path (dec_fused.h), single or split launch, then the slab reduction
-int output_layer_fused(aae_model* m, int B, float gscale, const DropSpec& d2, const float** chain_part, size_t* chain_stride, hipStream_t s) {
+int output_layer_fused(aae_model* m, const DecodeMode& mode, int B, float gscale, const DropSpec& d2, const float** chain_part, size_t* chain_stride, hipStream_t s) {
     if (m->bk_pending) {            // built on the side stream while this step's forward ran (aae_first_layer_forward)
         HIPCHK(hipStreamWaitEvent(s, m->ev_bk, 0));
         m->bk_pending = false;
     }
     if (!m->buckets_valid) TRY(build_tile_buckets(m, s));   // (else: the extra workgroup of this step's first chain launch did)
     DecLaunch L;
+    L.mode = mode;
     // row blocks of the fused output layer: one launch covers at most 112 rows; larger batches (cfg.blocked_output) run as
     // nblk launches of the split form over equal row blocks
     L.nblk = m->have_batch ? row_blocks(m) : 1; L.Bb = (B + L.nblk - 1) / L.nblk;
@@ -295,7 +297,7 @@ int output_layer_fused(aae_model* m, int B, float gscale, const DropSpec& d2, co
 }
 
 // ---- unfused path: three GEMMs through G = dL/dlogits [B][N]
-int output_layer_unfused(aae_model* m, int B, float gscale, const DropSpec& d2, hipStream_t s) {
+int output_layer_unfused(aae_model* m, const DecodeMode& mode, int B, float gscale, const DropSpec& d2, hipStream_t s) {
     const int N = m->N, h = m->h;
     {
         EpiBce e; e.G = m->G.p; e.ldg = m->ldn; e.gscale = gscale; e.partials = m->bce_partials;
@@ -311,10 +313,8 @@ int output_layer_unfused(aae_model* m, int B, float gscale, const DropSpec& d2, 
     }
     // dA2 = G * V3 (K = N items, split-K slabs), then back through act2/drop2
     {
-        int tiles = ((B + 63) / 64) * ((h + 63) / 64);
-        int splits = std::max(1, std::min(m->max_slabs, 2048 / tiles));
-        int kps = ((N + splits - 1) / splits + 63) / 64 * 64;
-        splits = (N + kps - 1) / kps;
+        int splits;
+        const int kps = split_k_items(m, B, &splits);
         GemmShape g{m->G.p, m->P[P_V3].p, B, h, N, m->ldn, m->ldh, kps};
         EpiSlab e; e.out = m->slabs.p; e.ld = m->ldh; e.slab_stride = (size_t)m->R * m->ldh;
         {
@@ -322,7 +322,7 @@ int output_layer_unfused(aae_model* m, int B, float gscale, const DropSpec& d2, 
             (void)launch_gemm_mode<0, 0, true>(gmode(m), g, e, splits, s);
         }
         LAUNCHCHK("dA2 gemm");
-        if (m->only_output_layer) {
+        if (mode.only_output_layer) {
             const size_t n4 = (size_t)B * m->ldh / 4;
             hipLaunchKernelGGL(slab_partial_kernel, dim3((unsigned)((n4 + 255) / 256), 1), dim3(256), 0, s, m->slabs.p, splits,
                                e.slab_stride, n4, m->da2.p, (size_t)0, (const float*)nullptr, 0, 0.f, m->losses, 0);
@@ -338,7 +338,7 @@ int output_layer_unfused(aae_model* m, int B, float gscale, const DropSpec& d2, 
     // side stream, behind the rest of the step (G and dh2 stay untouched until the next step's join).
     // (not for the item slices of the vocabulary-sharded scheme: there the background GEMM slowed the replica handle's
     // kernels by more than it saved - 0.496 -> 0.560 ms of per-rank compute at world 8, tools/vocab_rank_time.py)
-    if (m->side && m->cfg.grad_mode == AAE_GRAD_FUSED && !m->bf16 && !m->only_output_layer) {
+    if (m->side && m->cfg.grad_mode == AAE_GRAD_FUSED && !m->bf16 && !mode.only_output_layer) {
         HIPCHK(hipEventRecord(m->ev_crit, s));
         HIPCHK(hipStreamWaitEvent(m->side, m->ev_crit, 0));
         {
@@ -357,9 +357,9 @@ int output_layer_unfused(aae_model* m, int B, float gscale, const DropSpec& d2, 
 }
 
 // ---- the decoder's hidden layers, backward (VAE cut / VAE / chain program / per-layer GEMMs)
-int decoder_hidden_backward(aae_model* m, const float* chain_part, size_t chain_stride, const DropSpec& d1, float* dzc_out, hipStream_t s) {
+int decoder_hidden_backward(aae_model* m, const DecodeMode& mode, const float* chain_part, size_t chain_stride, const DropSpec& d1, float* dzc_out, hipStream_t s) {
     const int B = m->rows, h = m->h, cp = m->cp;
-    if (m->use_chain && m->vae_bwd && m->vae_cut) {
+    if (m->use_chain && mode.vae && m->vae_cut) {
         // cut at the condition boundary: stop at dL/d(decoder input); fc3's weight gradient + optimiser here, the rest
         // of the backward pass comes with the caller's dL/dz (aae_vae_encoder_backward)
         TRY(chain_vae_backward_dec(m, chain_part, chain_stride, dzc_out, s));
@@ -367,7 +367,7 @@ int decoder_hidden_backward(aae_model* m, const float* chain_part, size_t chain_
         dw.add(m, m->gb0.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);
         return dw.launch(s);
     }
-    if (m->use_chain && m->vae_bwd) {
+    if (m->use_chain && mode.vae) {
         TRY(chain_vae_backward(m, chain_part, chain_stride, s));
         DwBuilder dw;
         dw.add(m, m->gb0.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);
@@ -378,15 +378,12 @@ int decoder_hidden_backward(aae_model* m, const float* chain_part, size_t chain_
     if (m->use_chain) {
         // decoder hidden backward (+ the encoder backward when called from aae_step) in one program,
         // then every small weight gradient + optimiser update in one grouped launch
-        const bool enc_too = m->fuse_enc_bwd;
+        const bool enc_too = mode.enc_too;
         TRY(chain_ae_backward(m, true, enc_too, chain_part, chain_stride, nullptr, 0, dzc_out, O_ENC, s, 16, enc_too));
         DwBuilder dw;
-        dw.add(m, m->gb0.p, m->ldh, m->dh1.p, m->ldh, B, P_V2, O_DEC);
-        dw.add(m, m->gb1.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);
+        dw_add_decoder(dw, m);
         if (enc_too) {
-            dw.add(m, m->ga3.p, m->ldz, m->eh2.p, m->ldh, B, P_W3, O_ENC);
-            dw.add(m, m->gb2.p, m->ldh, m->eh1.p, m->ldh, B, P_W2, O_ENC);
-            TRY(dw.add_first_layer(m, m->gb3.p, O_ENC, s)); m->w1_merged = true;
+            TRY(dw_add_encoder(dw, m, s));
             m->enc_bwd_done = true;
         }
         return dw.launch(s);
@@ -408,21 +405,17 @@ int decoder_hidden_backward(aae_model* m, const float* chain_part, size_t chain_
     return AAE_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int aae_ae_decode_backward(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_rng_inject* inj,
-                           float* dzc_out, void* stream) {
-    if (!m) return fail(AAE_EINVAL, "handle is NULL");
+// ---- the decode-backward phase: decoder hidden layers forward (unless they ran, or ACT_DH2 is the input), the output layer,
+// the decoder's hidden layers backward.  mode: what the entry point that makes the call wants beyond the plain phase
+int decode_backward(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_rng_inject* inj, float* dzc_out,
+                    const DecodeMode& mode, hipStream_t s) {
     if (m->phase != 1) return fail(AAE_ESTATE, "aae_ae_decode_backward without aae_ae_encode");
     remember_inject(m, inj, false);
-    hipStream_t s = S(stream);
-    const int B = m->rows, N = m->N, h = m->h, cp = m->cp;
+    const int B = m->rows, N = m->N, h = m->h;
     if (zc_dev) TRY(stage_zc(m, zc_dev, zc_ld, B, s));
     const uint8_t* mk2 = m->inj.masks_dev[2];
     const uint8_t* mk3 = m->inj.masks_dev[3];
-    if (m->only_output_layer) { /* ACT_DH2 is the input */ }
+    if (mode.only_output_layer) { /* ACT_DH2 is the input */ }
     else if (m->use_chain) { if (!m->dec_hidden_done) TRY(chain_dec_hidden(m, true, B, s)); }
     else TRY(decoder_hidden_forward(m, true, mk2, mk3, B, s));
     TRY(join_output_layer(m, s));       // a deferred launch of the step before that was left running at this step's opening (late join)
@@ -430,11 +423,21 @@ int aae_ae_decode_backward(aae_handle m, const float* zc_dev, int64_t zc_ld, con
     DropSpec d1 = make_drop(m, 0, true, mk2, nullptr, B, h, 2);
     DropSpec d2 = make_drop(m, 1, true, mk3, nullptr, B, h, 3);
     const float* chain_part = nullptr; size_t chain_stride = 0;
-    if (fused_decoder_applies(m)) TRY(output_layer_fused(m, B, gscale, d2, &chain_part, &chain_stride, s));
-    else TRY(output_layer_unfused(m, B, gscale, d2, s));
-    if (!m->only_output_layer) TRY(decoder_hidden_backward(m, chain_part, chain_stride, d1, dzc_out, s));
+    if (fused_decoder_applies(m)) TRY(output_layer_fused(m, mode, B, gscale, d2, &chain_part, &chain_stride, s));
+    else TRY(output_layer_unfused(m, mode, B, gscale, d2, s));
+    if (!mode.only_output_layer) TRY(decoder_hidden_backward(m, mode, chain_part, chain_stride, d1, dzc_out, s));
     m->phase = 2;
     return AAE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aae_ae_decode_backward(aae_handle m, const float* zc_dev, int64_t zc_ld, const aae_rng_inject* inj,
+                           float* dzc_out, void* stream) {
+    if (!m) return fail(AAE_EINVAL, "handle is NULL");
+    return decode_backward(m, zc_dev, zc_ld, inj, dzc_out, DecodeMode{}, S(stream));
 }
 
 }  // extern "C"

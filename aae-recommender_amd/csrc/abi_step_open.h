@@ -2,15 +2,59 @@
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
 #pragma once
 
-extern "C" {
+namespace {
 
 // ---- the step ----------------------------------------------------------------------------
 // The aae_rng_inject handed to a phase stays in force for the later phases of the same step;
 // its device buffers must stay valid until the step's kernels have run.
-static void remember_inject(aae_model* m, const aae_rng_inject* inj, bool reset) {
+void remember_inject(aae_model* m, const aae_rng_inject* inj, bool reset) {
     if (inj) m->inj = *inj;
     else if (reset) memset(&m->inj, 0, sizeof(m->inj));
 }
+
+// The step-opening bookkeeping as a launch of its own (where it does not ride in the opening gather: AdvanceJob).
+// ahead: the batch's item list was built while the step before ran - its stamp and count stay as they are
+int launch_advance(aae_model* m, hipStream_t s, bool ahead = false) {
+    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
+                       ahead ? (int*)nullptr : m->stamp, ahead ? (int*)nullptr : m->ucount, m->losses);
+    LAUNCHCHK("advance_step");
+    return AAE_OK;
+}
+
+// The plain opening of a step on `batch` (aae_decoder_step, aae_vae_step, aae_vae_encode(train), aae_output_layer_step(batch)):
+// no batch named ahead, nothing left running from the step before.  What a caller reads of the first layer
+// (lazy_prepare) and its own dec_hidden_done follow at the caller.
+int open_step_plain(aae_model* m, const aae_batch* batch, const aae_rng_inject* inj, hipStream_t s) {
+    TRY(set_batch(m, batch));
+    remember_inject(m, inj, true);
+    TRY(join_deferred(m, s));       // the previous step's optimiser pass over DEC_V3 reads the step scalars and dh2
+    m->hstep++; m->pf_armed = false;
+    TRY(launch_advance(m, s));
+    m->enc_bwd_done = false;
+    return AAE_OK;
+}
+
+// The list of this batch's distinct items and their catch-up were built while the previous step ran (the caller named
+// the batch with aae_prefetch_batch): the second list set becomes the step's.  Called with hstep counting this step.
+bool take_lists_built_ahead(aae_model* m, const aae_batch* batch) {
+    const bool ahead = m->pf_built && m->pf_step == m->hstep && same_batch(m->pf_built_batch, *batch) && m->lazy;
+    m->pf_built = false;
+    if (ahead) { std::swap(m->mark, m->mark2); std::swap(m->ulist, m->ulist2); std::swap(m->ucount, m->ucount2); std::swap(m->stamp, m->stamp2); }
+    return ahead;
+}
+
+// the caller's condition block [rows][cond_inc] -> behind z in zc (the decoder backward and dec.lin1's weight gradient read it there)
+int stage_cond(aae_model* m, const float* cond_dev, hipStream_t s) {
+    if (m->cfg.cond_inc <= 0) return AAE_OK;
+    hipLaunchKernelGGL(copy2d_kernel, dim3(grid1d((size_t)m->rows * m->cfg.cond_inc)), dim3(256), 0, s, cond_dev,
+                       m->cfg.cond_inc, m->zc.p + m->c, m->ldc, m->rows, m->cfg.cond_inc, 1.0f);
+    LAUNCHCHK("copy cond");
+    return AAE_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_inject* inj, float* z_out, bool with_dec,
                           const float* cond_dev, void* stream) {
@@ -21,21 +65,15 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
     TRY(join_step_open(m, s));      // the previous step's optimiser pass over DEC_V3 reads the step scalars and dh2 (or its
                                     // own copies of them: it then runs on into this step's forward pass - late join)
     m->hstep++;
-    // the list of this batch's distinct items and their catch-up were built while the previous step ran
-    const bool ahead = m->pf_built && m->pf_step == m->hstep && same_batch(m->pf_built_batch, *batch) && m->lazy;
-    m->pf_built = false;
+    const bool ahead = take_lists_built_ahead(m, batch);
     const bool end_marked = m->end_marked, spec_ok = m->spec_tab_ok;      // (of the step before; this step's advance renews the table entry)
     m->end_marked = false; m->pf_this_step = false; m->spec_tab_ok = m->lazy;
-    if (ahead) { std::swap(m->mark, m->mark2); std::swap(m->ulist, m->ulist2); std::swap(m->ucount, m->ucount2); std::swap(m->stamp, m->stamp2); }
     // With the batch's list built ahead nothing sits between the step-opening bookkeeping and the first gather: it rides
     // in that launch (one launch floor, ~4.5 us, less per step)
-    constexpr bool fold_ok = true;
     // (noise_gen: aae_set_input_noise_gen is pending - the step's noise is drawn, abi_dae.h; a dense step either way)
     const bool noise_gen = m->noise_gen_next; const float noise_gen_scale = m->noise_gen_scale; m->noise_gen_next = false;
-    const bool fold_advance = fold_ok && ahead && m->use_chain && !m->ext_first && m->noise_next == nullptr && !noise_gen;
-    if (!fold_advance)
-    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
-                       ahead ? (int*)nullptr : m->stamp, ahead ? (int*)nullptr : m->ucount, m->losses);
+    const bool fold_advance = ahead && m->use_chain && !m->ext_first && m->noise_next == nullptr && !noise_gen;
+    if (!fold_advance) TRY(launch_advance(m, s, ahead));
     m->dense_step = m->noise_next != nullptr || noise_gen;
     const float* noise = m->noise_next; m->noise_next = nullptr;
     if (m->dense_step) {
@@ -56,10 +94,8 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
         LAUNCHCHK("dense_input");
         }
         const int B = m->rows, h = m->h, N = m->N;
-        int tiles = ((B + 63) / 64) * ((h + 63) / 64);
-        int splits = std::max(1, std::min(m->max_slabs, 2048 / tiles));
-        int kps = ((N + splits - 1) / splits + 63) / 64 * 64;
-        splits = (N + kps - 1) / kps;
+        int splits;
+        const int kps = split_k_items(m, B, &splits);
         GemmShape g{m->Xn.p, m->P[P_W1T].p, B, h, N, m->ldn, m->ldw1, kps};
         EpiSlab e; e.out = m->slabs.p; e.ld = m->ldh; e.slab_stride = (size_t)m->R * m->ldh;
         (void)launch_gemm_mode<0, 0, true>(gmode(m), g, e, splits, s);
@@ -72,7 +108,7 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
         m->dec_hidden_done = false; m->enc_bwd_done = false;
         TRY(chain_ae_forward(m, with_dec, cond_dev, z_out, s));
         m->phase = 1;
-        if (m->pf_armed) m->pf_armed = false;
+        m->pf_armed = false;
         return AAE_OK;
     }
     if (m->ext_first) {
@@ -92,14 +128,8 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
     // rows the builder rides in the step's first chain launch.)  The side stream is in order behind the previous step's
     // deferred launch, which waited for that step's output layer - the alternate bucket set's last readers are older.
     // (Not on the three-GEMM path: there the side stream holds the previous step's dV3 GEMM for most of this step.)
-    {
-        constexpr bool bk_ahead = true;
-        if (bk_ahead && m->side && m->ev_bk && m->last_out_split && m->rows > 16 * kMB && !m->buckets_valid && fused_decoder_applies(m)) {
-            TRY(build_tile_buckets(m, m->side));
-            HIPCHK(hipEventRecord(m->ev_bk, m->side));
-            m->bk_pending = true;
-        }
-    }
+    if (m->side && m->ev_bk && m->last_out_split && m->rows > 16 * kMB && !m->buckets_valid && fused_decoder_applies(m))
+        TRY(build_tile_buckets_aside(m));
     const bool pf = m->pf_armed && m->side && m->mark2 && m->lazy && m->use_chain;
     if (m->pf_armed && !pf) m->pf_armed = false;
     if (m->use_chain) {

@@ -9,17 +9,11 @@ int aae_decoder_step(aae_handle m, const aae_batch* batch, const float* zin_dev,
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
     if (!zin_dev) return fail(AAE_EINVAL, "zin_dev is NULL");
     if (zin_ld < m->cp) return fail(AAE_EINVAL, "zin_ld < n_code + cond_inc");
-    TRY(set_batch(m, batch));
-    remember_inject(m, inj, true);
     hipStream_t s = S(stream);
-    TRY(join_deferred(m, s));       // the previous step's optimiser pass over DEC_V3 reads the step scalars and dh2
-    m->hstep++; m->pf_armed = false;
-    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
-                       m->stamp, m->ucount, m->losses);
-    LAUNCHCHK("advance_step");
-    m->dec_hidden_done = false; m->enc_bwd_done = false; m->fuse_enc_bwd = false;
+    TRY(open_step_plain(m, batch, inj, s));
+    m->dec_hidden_done = false;
     m->phase = 1;
-    TRY(aae_ae_decode_backward(m, zin_dev, zin_ld, nullptr, dzin_out, stream));
+    TRY(decode_backward(m, zin_dev, zin_ld, nullptr, dzin_out, DecodeMode{}, s));
     m->phase = 0;
     return AAE_OK;
 }
@@ -31,22 +25,14 @@ int aae_vae_step(aae_handle m, const aae_batch* batch, const float* cond_dev, co
     if (!m->use_chain) return fail(AAE_ESTATE, "VAE mode needs the layer-chain kernels");
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
-    TRY(set_batch(m, batch));
-    remember_inject(m, nullptr, true);
     hipStream_t s = S(stream);
-    TRY(join_deferred(m, s));
-    m->hstep++; m->pf_armed = false;
-    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
-                       m->stamp, m->ucount, m->losses);
-    LAUNCHCHK("advance_step");
+    TRY(open_step_plain(m, batch, nullptr, s));
     if (m->lazy) TRY(lazy_prepare(m, -1, false, s));
     TRY(gather_first_layer(m, false, nullptr, 0, s));                 // eh1 = act(fc1(normalize(x))), vae.py:111-113
     TRY(chain_vae_forward(m, cond_dev, eps_dev, m->rows, s));
-    m->dec_hidden_done = true; m->enc_bwd_done = false; m->fuse_enc_bwd = false;
-    m->vae_bwd = true; m->vae_cut = false; m->phase = 1;
-    const int rc = aae_ae_decode_backward(m, nullptr, 0, nullptr, nullptr, stream);
-    m->vae_bwd = false;
-    if (rc != AAE_OK) return rc;
+    m->dec_hidden_done = true; m->vae_cut = false; m->phase = 1;
+    DecodeMode mode; mode.vae = true;
+    TRY(decode_backward(m, nullptr, 0, nullptr, nullptr, mode, s));
     TRY(encoder_first_layer_update(m, m->gb3.p, O_ENC, s, m->w1_merged));
     m->phase = 0;
     return AAE_OK;
@@ -84,20 +70,21 @@ int aae_vae_encode(aae_handle m, const aae_batch* batch, const float* eps_dev, f
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
     if (!m->vae || !m->use_chain) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
     if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
-    TRY(set_batch(m, batch));
-    remember_inject(m, nullptr, true);
     hipStream_t s = S(stream);
-    TRY(join_deferred(m, s));
     if (train) {
-        m->hstep++; m->pf_armed = false;
-        hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
-                           m->stamp, m->ucount, m->losses);
-        LAUNCHCHK("advance_step");
+        TRY(open_step_plain(m, batch, nullptr, s));
         if (m->lazy) TRY(lazy_prepare(m, -1, false, s));
-    } else if (m->lazy) TRY(lazy_prepare(m, 0, true, s));
+    } else {
+        // no step is opened: the batch through the weights as they are (its rows of the first layer caught up through this step)
+        TRY(set_batch(m, batch));
+        remember_inject(m, nullptr, true);
+        TRY(join_deferred(m, s));
+        if (m->lazy) TRY(lazy_prepare(m, 0, true, s));
+        m->enc_bwd_done = false;
+    }
     TRY(gather_first_layer(m, false, nullptr, 0, s));
     TRY(chain_vae_encode(m, eps_dev, z_out_dev, m->rows, s));
-    m->dec_hidden_done = false; m->enc_bwd_done = false; m->fuse_enc_bwd = false;
+    m->dec_hidden_done = false;
     m->phase = train ? 1 : 0; m->vae_cut = train != 0;
     return AAE_OK;
 }
@@ -109,10 +96,9 @@ int aae_vae_decode_backward(aae_handle m, const float* zc_dev, int64_t zc_ld, fl
     hipStream_t s = S(stream);
     TRY(stage_zc(m, zc_dev, zc_ld, m->rows, s));
     TRY(chain_vae_dec_hidden(m, m->rows, s));
-    m->dec_hidden_done = true; m->vae_bwd = true;
-    const int rc = aae_ae_decode_backward(m, nullptr, 0, nullptr, dzc_out_dev, stream);
-    m->vae_bwd = false;
-    return rc;
+    m->dec_hidden_done = true;
+    DecodeMode mode; mode.vae = true;
+    return decode_backward(m, nullptr, 0, nullptr, dzc_out_dev, mode, s);
 }
 
 int aae_vae_encoder_backward(aae_handle m, const float* dz_dev, int64_t dz_ld, void* stream) {
@@ -139,9 +125,7 @@ int aae_ae_encoder_backward(aae_handle m, const float* dz_dev, int64_t dz_ld, vo
         if (!m->enc_bwd_done) {
             TRY(chain_ae_backward(m, false, true, nullptr, 0, dz_dev, (int)dz_ld, nullptr, O_ENC, s));
             DwBuilder dw;
-            dw.add(m, m->ga3.p, m->ldz, m->eh2.p, m->ldh, m->rows, P_W3, O_ENC);
-            dw.add(m, m->gb2.p, m->ldh, m->eh1.p, m->ldh, m->rows, P_W2, O_ENC);
-            TRY(dw.add_first_layer(m, ga1_ptr(m), O_ENC, s)); m->w1_merged = true;
+            TRY(dw_add_encoder(dw, m, s));
             TRY(dw.launch(s));
         }
         if (!m->ext_first || m->own_first) TRY(encoder_first_layer_update(m, m->gb3.p, O_ENC, s, m->w1_merged));
@@ -161,14 +145,8 @@ int aae_ae_forward(aae_handle m, const aae_batch* batch, const float* cond_dev, 
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
     if (!m->use_chain || m->vae) return fail(AAE_ESTATE, "aae_ae_forward needs the layer-chain kernels (and no VAE mode)");
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
-    hipStream_t s = S(stream);
     TRY(ae_encode_impl(m, batch, inj, nullptr, true, cond_dev, stream));
-    if (m->cfg.cond_inc > 0) {
-        hipLaunchKernelGGL(copy2d_kernel, dim3(grid1d((size_t)m->rows * m->cfg.cond_inc)), dim3(256), 0, s, cond_dev,
-                           m->cfg.cond_inc, m->zc.p + m->c, m->ldc, m->rows, m->cfg.cond_inc, 1.0f);
-        LAUNCHCHK("copy cond");
-    }
-    return AAE_OK;
+    return stage_cond(m, cond_dev, S(stream));
 }
 
 // aae_output_layer_step: the decoder's output layer alone over the handle's items - logits from AAE_T_ACT_DH2, BCE
@@ -180,24 +158,15 @@ int aae_output_layer_step(aae_handle m, const aae_batch* batch, void* stream) {
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
     if (m->vae) return fail(AAE_ESTATE, "aae_output_layer_step: not in VAE mode");
     hipStream_t s = S(stream);
-    if (batch || m->opt_pending) TRY(join_deferred(m, s));      // (batch = NULL: a prefetch started by this step keeps running)
-    if (batch) {
-        TRY(set_batch(m, batch));
-        remember_inject(m, nullptr, true);
-        m->hstep++; m->pf_armed = false;
-        hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
-                           m->stamp, m->ucount, m->losses);
-        LAUNCHCHK("advance_step");
-        m->enc_bwd_done = false; m->fuse_enc_bwd = false;
-    } else if (m->phase != 1 || !m->dec_hidden_done) {
-        return fail(AAE_ESTATE, "aae_output_layer_step(batch = NULL) without aae_ae_forward");
+    if (batch) TRY(open_step_plain(m, batch, nullptr, s));
+    else {
+        if (m->opt_pending) TRY(join_deferred(m, s));      // (a prefetch started by this step keeps running)
+        if (m->phase != 1 || !m->dec_hidden_done) return fail(AAE_ESTATE, "aae_output_layer_step(batch = NULL) without aae_ae_forward");
     }
     m->dec_hidden_done = true;
     m->phase = 1;
-    m->only_output_layer = true;
-    int rc = aae_ae_decode_backward(m, nullptr, 0, nullptr, nullptr, stream);
-    m->only_output_layer = false;
-    TRY(rc);
+    DecodeMode mode; mode.only_output_layer = true;
+    TRY(decode_backward(m, nullptr, 0, nullptr, nullptr, mode, s));
     m->phase = batch ? 0 : 2;
     return AAE_OK;
 }
@@ -211,14 +180,10 @@ int aae_ae_backward(aae_handle m, const float* dA2_dev, int64_t dA2_ld, void* st
     if ((m->phase != 1 && m->phase != 2) || !m->dec_hidden_done) return fail(AAE_ESTATE, "aae_ae_backward without aae_ae_forward");
     if (dA2_dev && dA2_ld != m->ldh) return fail(AAE_EINVAL, "aae_ae_backward: dA2_ld must equal the leading dimension of AAE_T_ACT_DH2");
     hipStream_t s = S(stream);
-    const int B = m->rows;
     TRY(chain_ae_backward(m, true, true, dA2_dev ? dA2_dev : m->da2.p, 0, nullptr, 0, nullptr, O_ENC, s, 1));
     DwBuilder dw;
-    dw.add(m, m->gb0.p, m->ldh, m->dh1.p, m->ldh, B, P_V2, O_DEC);
-    dw.add(m, m->gb1.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);
-    dw.add(m, m->ga3.p, m->ldz, m->eh2.p, m->ldh, B, P_W3, O_ENC);
-    dw.add(m, m->gb2.p, m->ldh, m->eh1.p, m->ldh, B, P_W2, O_ENC);
-    TRY(dw.add_first_layer(m, ga1_ptr(m), O_ENC, s)); m->w1_merged = true;      // (external first layer: its bias blocks only)
+    dw_add_decoder(dw, m);
+    TRY(dw_add_encoder(dw, m, s));      // (external first layer: its bias blocks only)
     TRY(dw.launch(s));
     m->enc_bwd_done = true;
     m->phase = 2;
@@ -249,36 +214,23 @@ int aae_first_layer_forward(aae_handle m, const aae_batch* batch, const float* b
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
     if (m->vae || m->cfg.grad_mode != AAE_GRAD_FUSED) return fail(AAE_ESTATE, "aae_first_layer_forward: fused optimiser, no VAE mode");
     hipStream_t s = S(stream);
-    bool pf = false, fold_advance = false;
+    bool fold_advance = false;
     if (batch) {
         TRY(join_deferred(m, s));       // (batch = NULL: a deferred optimiser launch of the output layer keeps running - it
                                         //  touches dec.lin3, its moments, the stored dL/dlogits and dh2, nothing of this layer)
         TRY(set_batch(m, batch));
         remember_inject(m, nullptr, true);
         m->hstep++;
-        // (as in aae_step: the list of this batch's distinct items and their catch-up were built while the previous step
-        //  ran, if the caller named the batch with aae_prefetch_batch)
-        const bool ahead = m->pf_built && m->pf_step == m->hstep && same_batch(m->pf_built_batch, *batch) && m->lazy;
-        m->pf_built = false;
-        if (ahead) { std::swap(m->mark, m->mark2); std::swap(m->ulist, m->ulist2); std::swap(m->ucount, m->ucount2); std::swap(m->stamp, m->stamp2); }
-        constexpr bool fold_ok = true;
-        fold_advance = fold_ok && ahead;          // (as in aae_step: nothing between the bookkeeping and the gather)
-        if (!fold_advance)
-        hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, m->sc, m->step_ctr, m->lazy ? m->tab : nullptr,
-                           ahead ? (int*)nullptr : m->stamp, ahead ? (int*)nullptr : m->ucount, m->losses);
-        LAUNCHCHK("advance_step");
+        const bool ahead = take_lists_built_ahead(m, batch);
+        fold_advance = ahead;          // (as in aae_step: nothing between the bookkeeping and the gather)
+        if (!fold_advance) TRY(launch_advance(m, s, ahead));
         if (m->lazy && !ahead) TRY(lazy_prepare(m, -1, false, s));
-        m->enc_bwd_done = false; m->fuse_enc_bwd = false; m->dense_step = false;
+        m->enc_bwd_done = false; m->dense_step = false;
         // The output layer's tile buckets depend on the batch only: they are built on the side stream beside this
         // handle's list building and gather (and the caller's forward pass) instead of in front of the critical launch.
         // The side stream is in order behind the last deferred launch, which waited for the last critical launch - the
         // last reader of the bucket arrays; without such a launch to order it the build stays where it was.
-        constexpr bool bk_ahead = true;
-        if (bk_ahead && m->side && m->ev_bk && m->last_out_split && fused_decoder_applies(m)) {
-            TRY(build_tile_buckets(m, m->side));
-            HIPCHK(hipEventRecord(m->ev_bk, m->side));
-            m->bk_pending = true;
-        }
+        if (m->side && m->ev_bk && m->last_out_split && fused_decoder_applies(m)) TRY(build_tile_buckets_aside(m));
         // (a batch named with aae_prefetch_batch stays armed: its list and catch-up are enqueued behind this step's
         //  deferred optimiser launch - aae_output_layer_step - where they need no mark on this stream; a mark riding on
         //  the gather below cost the stream more than the 16 us it moved away)
@@ -286,29 +238,8 @@ int aae_first_layer_forward(aae_handle m, const aae_batch* batch, const float* b
     } else if (!m->have_batch) {
         return fail(AAE_ESTATE, "aae_first_layer_forward(batch = NULL) without a running batch");
     }
-    {
-        ProfScope ps(m, AAE_K_ENC_GATHER, s);
-        const size_t shm = (size_t)16 * r4(m->h) * sizeof(float);
-        DropSpec none; memset(&none, 0, sizeof(none));
-        // (four waves per document for wide batches, as gather_first_layer: an item slice holds 1 / world of a document's entries)
-        constexpr int g4_rows = 512;
-        if (m->rows >= g4_rows)
-        hipExtLaunchKernelGGL(enc_gather_kernel_t<4>, dim3(m->rows), dim3(256), (uint32_t)(shm / 4), s, nullptr, pf ? m->ev_head : nullptr, 0,
-                              m->bv, (const float*)m->P[P_W1T].p, m->ldw1, bias_dev, m->h, (int)m->cfg.normalize_inputs,
-                              m->a1.p, (float*)nullptr, m->ldh, (int)m->cfg.activation, none, (uint64_t)m->cfg.seed,
-                              (const long long*)m->step_ctr, m->rscale, m->doc_l1,
-                              AdvanceJob{m->sc, m->step_ctr, m->lazy ? m->tab : nullptr, m->losses, fold_advance ? 1 : 0},
-                              (long long)(fold_advance ? m->hstep : -1));
-        else
-        hipExtLaunchKernelGGL(enc_gather_kernel, dim3(m->rows), dim3(1024), (uint32_t)shm, s, nullptr, pf ? m->ev_head : nullptr, 0,
-                              m->bv, (const float*)m->P[P_W1T].p, m->ldw1, bias_dev, m->h, (int)m->cfg.normalize_inputs,
-                              m->a1.p, (float*)nullptr, m->ldh, (int)m->cfg.activation, none, (uint64_t)m->cfg.seed,
-                              (const long long*)m->step_ctr, m->rscale, m->doc_l1,
-                              AdvanceJob{m->sc, m->step_ctr, m->lazy ? m->tab : nullptr, m->losses, fold_advance ? 1 : 0},
-                              (long long)(fold_advance ? m->hstep : -1));
-        LAUNCHCHK("enc_gather (partial)");
-    }
-    if (pf) TRY(launch_prefetch(m));
+    DropSpec none; memset(&none, 0, sizeof(none));
+    TRY(launch_gather(m, bias_dev, nullptr, none, false, fold_advance, "enc_gather (partial)", s));
     if (batch) { m->phase = 1; m->dec_hidden_done = true; }       // aae_output_layer_step(batch = NULL) may follow on this handle
     return AAE_OK;
 }
@@ -428,15 +359,9 @@ int aae_step(aae_handle m, const aae_batch* batch, const float* cond_dev, const 
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     hipStream_t s = S(stream);
     TRY(ae_encode_impl(m, batch, inj, nullptr, true, cond_dev, stream));
-    if (m->cfg.cond_inc > 0) {
-        hipLaunchKernelGGL(copy2d_kernel, dim3(grid1d((size_t)m->rows * m->cfg.cond_inc)), dim3(256), 0, s, cond_dev,
-                           m->cfg.cond_inc, m->zc.p + m->c, m->ldc, m->rows, m->cfg.cond_inc, 1.0f);
-        LAUNCHCHK("copy cond");
-    }
-    m->fuse_enc_bwd = true;
-    int rc = aae_ae_decode_backward(m, nullptr, 0, nullptr, nullptr, stream);
-    m->fuse_enc_bwd = false;
-    TRY(rc);
+    TRY(stage_cond(m, cond_dev, s));
+    DecodeMode mode; mode.enc_too = true;
+    TRY(decode_backward(m, nullptr, 0, nullptr, nullptr, mode, s));
     TRY(aae_ae_encoder_backward(m, nullptr, 0, stream));
     if (!m->ae_only) TRY(aae_disc_gen(m, nullptr, stream));
     return AAE_OK;

@@ -281,11 +281,7 @@ int aae_shard_step(aae_handle m, const aae_collectives* c, const aae_batch* batc
     m->dec_hidden_done = false; m->enc_bwd_done = false;
     TRY(chain_ae_forward(m, true, cond_dev, nullptr, s));           // every row of the batch: dropout + activation on a1, hidden layers -> dh2
     m->phase = 1;
-    if (m->cfg.cond_inc > 0) {
-        hipLaunchKernelGGL(copy2d_kernel, dim3(grid1d((size_t)m->rows * m->cfg.cond_inc)), dim3(256), 0, s, cond_dev,
-                           m->cfg.cond_inc, m->zc.p + m->c, m->ldc, m->rows, m->cfg.cond_inc, 1.0f);
-        LAUNCHCHK("copy cond");
-    }
+    TRY(stage_cond(m, cond_dev, s));
     m->grad_scale = item_share;
     const int rc = aae_output_layer_step(m, nullptr, stream);       // its items' logits, BCE, dV3 + dec_optim, dL/d(dh2) partial
     m->grad_scale = 1.f;

@@ -232,15 +232,144 @@ def test_split_phase_equals_fused_step():
         check_state(fx, m, s, "split")
 
 
-def test_abi_rejects_bad_calls():
-    from aaerec._hip import AaeHipError
-    fx = Fixture("step_nodrop_gauss")
-    m = make_model(fx)
-    with pytest.raises(AaeHipError):
-        m.disc_gen()                       # no ae phase before
-    csr = csr_of(fx, m, 0)
-    with pytest.raises(AaeHipError):
-        m.step(csr, 0, fx.cfg["B"] + 1)    # more rows than max_batch
+# ---- calls out of order: each is refused by a host-side check, with its text, and the handle carries on ----------------
+# A sequence below is one step through its phase calls; at(point) runs between them.  The handle under test gets a refused
+# call at the case's points, its twin none.
+def _seq_whole(fx, m, s, at):
+    csr = csr_of(fx, m, s)
+    at("open")
+    m.step(csr, 0, csr.shape[0], masks=fx.masks(s), z_real=fx.z[f"step{s}.z_real"])
+
+
+def _seq_split(fx, m, s, at):
+    csr = csr_of(fx, m, s)
+    cond = fx.cond_inputs(s)
+    at("open")
+    z = m.ae_encode(csr, 0, csr.shape[0], masks=fx.masks(s), z_real=fx.z[f"step{s}.z_real"])
+    at("encoded")
+    dzc = m.ae_decode_backward(torch.cat([z, torch.as_tensor(cond[0], device=m.device)], 1) if cond else z)
+    at("decoded")
+    m.ae_encoder_backward(dzc[:, :fx.cfg["c"]])
+    at("encoder_done")
+    m.disc_step()
+    m.gen_step()
+
+
+def _seq_cut(fx, m, s, at):
+    csr = csr_of(fx, m, s)
+    at("open")
+    m.ae_forward(csr, 0, csr.shape[0], masks=fx.masks(s), z_real=fx.z[f"step{s}.z_real"])
+    m.output_layer_step()
+    at("output_done")
+    m.ae_backward()
+    at("backward_done")
+    m.disc_gen()
+
+
+def _seq_vae(fx, m, s, at):
+    csr = csr_of(fx, m, s)
+    at("open")
+    z = m.vae_encode(csr, 0, csr.shape[0], eps=fx.z[f"step{s}.eps"], train=True)
+    at("encoded")
+    dzc = m.vae_decode_backward(z)
+    at("decoded")
+    m.vae_encoder_backward(dzc[:, :fx.cfg["c"]])
+
+
+def _zeros(m, cols):
+    return torch.zeros(m.max_batch, cols, device=m.device)
+
+
+def _step_on_an_external_first_layer(fx, m, s):
+    m.set_first_layer_external(True)
+    try:
+        m.step(csr_of(fx, m, s), 0, fx.cfg["B"])
+    finally:
+        m.set_first_layer_external(False)
+
+
+# name: (fixture, sequence, the points of a step at which the call is made, the call (fx, m, s), the text it is refused with
+#        [, the steps it is made in: both of the two unless given])
+BAD_CALLS = {
+    "disc_step_before_the_ae_phases": ("step_nodrop_gauss", _seq_split, ("open", "encoded", "decoded"),
+                                       lambda fx, m, s: m.disc_gen(), "aae_disc_step before the ae phases of the step"),
+    "gen_step_before_disc_step": ("step_nodrop_gauss", _seq_split, ("open", "encoder_done"),
+                                  lambda fx, m, s: m.gen_step(), "aae_gen_step before aae_disc_step"),
+    "ae_decode_backward_without_ae_encode": ("step_cond_concat", _seq_split, ("open", "decoded"),
+                                             lambda fx, m, s: m.ae_decode_backward(_zeros(m, fx.cfg["c"] + fx.cfg["cond_inc"])),
+                                             "aae_ae_decode_backward without aae_ae_encode"),
+    "ae_encoder_backward_without_ae_decode_backward": ("step_cond_concat", _seq_split, ("open", "encoded"),
+                                                       lambda fx, m, s: m.ae_encoder_backward(_zeros(m, fx.cfg["c"])),
+                                                       "aae_ae_encoder_backward without aae_ae_decode_backward"),
+    "output_layer_step_without_ae_forward": ("step_nodrop_gauss", _seq_cut, ("open", "output_done"),
+                                             lambda fx, m, s: m.output_layer_step(),
+                                             "aae_output_layer_step(batch = NULL) without aae_ae_forward"),
+    "ae_backward_without_ae_forward": ("step_nodrop_gauss", _seq_cut, ("open", "backward_done"),
+                                       lambda fx, m, s: m.ae_backward(), "aae_ae_backward without aae_ae_forward"),
+    "vae_decode_backward_without_vae_encode": ("step_vae", _seq_vae, ("open", "decoded"),
+                                               lambda fx, m, s: m.vae_decode_backward(_zeros(m, fx.cfg["c"])),
+                                               "aae_vae_decode_backward without aae_vae_encode(train)"),
+    "vae_encoder_backward_without_vae_decode_backward": ("step_vae", _seq_vae, ("open", "encoded"),
+                                                         lambda fx, m, s: m.vae_encoder_backward(_zeros(m, fx.cfg["c"])),
+                                                         "aae_vae_encoder_backward without aae_vae_decode_backward"),
+    # (only a handle that never saw a batch has none running: the first step's opening)
+    "first_layer_forward_without_a_running_batch": ("step_nodrop_gauss", _seq_whole, ("open",),
+                                                    lambda fx, m, s: m.first_layer_forward(),
+                                                    "aae_first_layer_forward(batch = NULL) without a running batch", (0,)),
+    "step_on_an_external_first_layer": ("step_nodrop_gauss", _seq_whole, ("open",), _step_on_an_external_first_layer,
+                                        "aae_step: the first layer is external (aae_set_first_layer_external): drive the phases"),
+    "more_rows_than_max_batch": ("step_nodrop_gauss", _seq_whole, ("open",),
+                                 lambda fx, m, s: m.step(csr_of(fx, m, s), 0, fx.cfg["B"] + 1), "batch n_rows outside [1, max_batch]"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(BAD_CALLS))
+def test_abi_rejects_bad_calls(name, monkeypatch):
+    """Every phase call out of order is refused with its text by a host-side check - also in the middle of a split step, which
+    then continues - and leaves nothing behind: after two steps the handle holds the parameter and loss bytes of a twin that
+    never saw a refusal.  (AAE_SPLIT_ANY: the split form's loss is reproducible at the fixtures' sizes.)"""
+    import re
+    from aaerec._hip import AaeHipError, HipAAE
+    monkeypatch.setenv("AAE_SPLIT_ANY", "1")
+    fixture, sequence, points, call, text = BAD_CALLS[name][:5]
+    steps = BAD_CALLS[name][5] if len(BAD_CALLS[name]) > 5 else (0, 1)
+    fx = Fixture(fixture)
+
+    def new_handle():
+        if fixture != "step_vae":
+            return make_model(fx)
+        c = fx.cfg
+        m = HipAAE(c["N"], c["h"], c["c"], cond_inc=c["cond_inc"], max_batch=c["B"], rng_mode="inject", gen_lr=c["gen_lr"],
+                   reg_lr=c["gen_lr"], dropout=(0.0, 0.0), vae=True)
+        m.load_params(_vae_params(fx, "init"))
+        return m
+
+    m, twin = new_handle(), new_handle()
+    refused = []
+    for s in range(2):
+        def at(point):
+            if point not in points or s not in steps:
+                return
+            with pytest.raises(AaeHipError, match=re.escape(text)):
+                call(fx, m, s)
+            refused.append((s, point))
+        sequence(fx, m, s, at)
+        sequence(fx, twin, s, lambda point: None)
+        got, want = np.array(m.losses(), dtype=np.float32), np.array(twin.losses(), dtype=np.float32)
+        if fixture == "step_vae":
+            # The KL sum is not reproducible from run to run on any build: chain.h's COP_REPARAM_BWD adds one partial per wave
+            # with a float atomic, in the order the waves arrive (two runs of ONE library differ in it, tools/step_bits.py).
+            # Every partial is a fixed-order sum of terms >= 0, so two orders of adding W of them differ by at most
+            # 2 (W - 1) 2^-24 of the sum; W = 16 waves per 16-row workgroup.  Its gradient does not pass through the sum: the
+            # parameters and the reconstruction loss are held to their bytes like everywhere else.
+            waves = 16 * ((fx.cfg["B"] + 15) // 16)
+            assert abs(float(got[1]) - float(want[1])) <= 2 * (waves - 1) * 2.0 ** -24 * max(got[1], want[1]), (name, s, got, want)
+            got[1] = want[1] = 0.0
+        assert got.tobytes() == want.tobytes(), (name, s, got, want)
+    assert len(refused) == len(steps) * len(points)
+    got, want = m.state_dict(), twin.state_dict()
+    for k in want:
+        assert got[k].tobytes() == want[k].tobytes(), (name, k)
 
 
 @pytest.mark.parametrize("prefetch", [False, True, "early"])
