@@ -58,6 +58,7 @@ T_ENC_W1T, T_ENC_B1, T_ENC_W2, T_ENC_W3, T_DEC_V1, T_DEC_V2, T_DEC_V3, T_DISC_D1
 T_ADAM_ENC, T_ADAM_GEN, T_ADAM_DEC, T_ADAM_DISC, T_GRAD = 16, 32, 48, 64, 80
 T_ACT_Z, T_ACT_LOSSES, T_ACT_A1, T_ACT_DZC, T_ACT_DH2, T_ACT_DA2 = 96, 97, 98, 99, 100, 101
 T_ACT_GA1 = 102
+T_W1_TSYNC = 103
 CAT_SUM, CAT_MEAN = 0, 1
 CAT_SPARSE_ADAM, CAT_ADAM = 0, 1
 O_ENC, O_DEC, O_GEN, O_DISC = 0, 1, 2, 3
@@ -264,6 +265,7 @@ _PROTOS = {
     "aae_set_split": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 K_ENC_GATHER, K_DEC_BCE_FWD, K_DEC_DA2, K_DEC_DV3_ADAM, K_ENC_W1_ADAM, K_DEC_FUSED, K_CHAIN, K_DEC_CRIT, K_DEC_OPT, K_RANK, K_COLLECTIVE = range(11)
+K_UNIQ_ITEMS, K_W1_CATCHUP = 11, 12
 
 _lib = None
 

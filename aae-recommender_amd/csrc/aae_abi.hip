@@ -73,7 +73,7 @@ int aae_abi_version(void) { return AAE_ABI_VERSION; }
 
 int aae_set_option(const char* name, const char* value) {
     if (!name || !*name) return fail(AAE_EINVAL, "option name is empty");
-    static const char* known[] = {"NO_CHAIN", "CHAIN16", "SPLIT_ANY", "BLOCKED_ANY", "EARLY_ANY", "NO_LATE_JOIN", "NO_ITEM_COUNT", "NO_ITEM_LISTS", "W1_SERIAL",
+    static const char* known[] = {"NO_CHAIN", "CHAIN16", "SPLIT_ANY", "BLOCKED_ANY", "EARLY_ANY", "NO_LATE_JOIN", "NO_ITEM_COUNT", "NO_ITEM_LISTS", "NO_INLINE_PREFETCH", "INLINE_PF_DISC8", "W1_SERIAL",
                                   "NO_RANK_FUSED", "CHAIN_KSLICES", "X16_ROWS", "DW_KSPLIT_ROWS", "DEC_TS", "CHAIN_TS", "DW_TS", "DEC_SKIP", "CHAIN_SKIP", "RANK_SKIP",
                                   "RANK_COLLECT_CAP"};
     bool ok = false;
@@ -288,7 +288,15 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
             // 0.2520 / 0.2423 / 0.2341 / 0.2255 / 0.2262 / 0.2270 / 0.2281 / 0.2330 ms/step on 72 / 80 / 88 / 96 / 104 / 112 / 120 /
             // 128 / 136 (the launch before it: 0.2434 / 0.2327 / 0.2294 / 0.2313 and 0.2438 / 0.2326 / 0.2289 / 0.2314 on 104 / 112 /
             // 120 / 128).  104 and 112 tie and 96 is over the edge: 112, 7/16 of the chip
-            const int cap = m->late_enabled ? m->n_cu * 7 / 16 : m->n_cu * 9 / 16;
+            // With the next batch's item list and catch-up inside the step's own chain launches (abi_chains.h: inline_prefetch_applies;
+            // nothing of them is left on the side stream in front of this launch or beside the critical one) the optimum moved down
+            // once more - same box, C3, two passes: 0.2420 / 0.2324 / 0.2237 / 0.2206 / 0.2175 / 0.2183 / 0.2188 / 0.2227 / 0.2258 and
+            // 0.2420 / 0.2323 / 0.2236 / 0.2203 / 0.2176 / 0.2184 / 0.2191 / 0.2221 / 0.2258 ms/step on 80 / 88 / 96 / 100 / 104 /
+            // 108 / 112 / 120 / 128 (the side-stream route on the same build: 0.2214-0.2217 / 0.2233-0.2236 on 112 / 120; the build
+            // before it: 0.2345 / 0.2273 / 0.2214 / 0.2232 on 96 / 104 / 112 / 120): 104, 13/32 of the chip, for the handles that
+            // take that route; the others keep 112.  C2 in bf16 keeps its 40 (0.1629 / 0.1470 / 0.1488 / 0.1498 on 32 / 40 / 48 / 56).
+            // (profiles/inline_prefetch_width_sweep.txt)
+            const int cap = !m->late_enabled ? m->n_cu * 9 / 16 : inline_prefetch_handle(m) ? m->n_cu * 13 / 32 : m->n_cu * 7 / 16;
             m->split_wgs = std::max(1, std::min(w, cap));
         }
     }
@@ -466,6 +474,9 @@ int aae_tensor_info(aae_handle h, int id, aae_tensor* out) {
     else if (id == AAE_T_ACT_DZC) { tmp = h->gzc; tmp.cols = h->cp; t = &tmp; }
     else if (id == AAE_T_ACT_LOSSES) {
         tmp.rows = 1; tmp.cols = 4; tmp.ld = 4; tmp.off = (size_t)((char*)h->losses - h->base); t = &tmp;
+    }
+    else if (id == AAE_T_W1_TSYNC && h->lazy) {
+        tmp.rows = 1; tmp.cols = h->N; tmp.ld = h->N; tmp.off = (size_t)((char*)h->tsync - h->base); t = &tmp;
     }
     if (!t) return fail(AAE_EINVAL, "unknown tensor id");
     out->byte_offset = t->off; out->rows = t->rows; out->cols = t->cols; out->ld = t->ld;

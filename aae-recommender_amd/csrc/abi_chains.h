@@ -320,6 +320,7 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
     if (four && m->x16_ok && cb.P.rows >= (cb.x16_rows > 0 ? cb.x16_rows : m->x16_rows) && !cb.P.bk.enabled && !cb.P.il.enabled && x16_program_ok(cb.P)) {
         ChainProgram X = cb.P;
         if (x16_remap_slots(X)) {
+            cb.P.uq.enabled = cb.P.cu.enabled = 0;      // (no job rides on the wide-batch kernel: the caller sends its kernel instead)
             // the look-ahead chains of the weight prefetch: per workgroup class, every op's next linear op
             X.x16_row_lo = 1 << 30;
             for (int i = 0; i < X.nops; ++i) if (X.ops[i].row_lo > 0) X.x16_row_lo = X.ops[i].row_lo;
@@ -347,6 +348,11 @@ int launch_chain(aae_model* m, ChainBuilder& cb, hipStream_t s) {
     // so the row workgroups are placed first.  The lists count as built from here on: stream order is the dependency
     if (cb.P.il.enabled && !four) cb.P.il.enabled = 0;
     if (cb.P.il.enabled) { grid += cb.P.il.nblocks; m->il_set ^= 1; m->item_lists_valid = true; }
+    // the next batch's list / catch-up (piggyback_next_list, piggyback_next_catchup): last of all; a launch that cannot carry
+    // its job clears it, and the caller sends the kernel of that name behind the launch instead
+    if (!four || ts_kernel || cb.vae4) cb.P.uq.enabled = cb.P.cu.enabled = 0;
+    if (cb.P.cu.enabled) { cb.P.uq.enabled = 0; grid += cb.P.cu.nblocks; }
+    else if (cb.P.uq.enabled) grid += cb.P.uq.nblocks;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(four ? kC4T : kCT), kCSlots * kCR * kCL * sizeof(float), s, cb.P);
     LAUNCHCHK("chain_kernel");
     return want_ts ? print_chain_timeline(cb.P, ts_dev, false, four, s) : AAE_OK;
@@ -712,6 +718,85 @@ static void piggyback_item_lists(aae_model* m, ChainBuilder& cb) {
     j.enabled = 1;
 }
 
+// ---- the batch named ahead (aae_prefetch_batch): its distinct-item list and catch-up inside the running step's chain launches ----
+// What the side stream's two launches (launch_prefetch) read and write - the second list set; the first layer's rows, moments
+// and tsync of items of the NEXT batch that are not in the running one; the running step's entry of the optimiser table - no
+// launch of the running step writes, so stream order behind the opening gather is all the ordering they need.  Where the whole
+// step is one call (aae_step) on batches of one fused launch, they ride as extra workgroups of the step's own chain launches,
+// on CUs the deferred launch leaves idle: the list in the ae phase's backward launch, the catch-up in the generator's (and, by
+// aae_options::inline_pf_disc8, part of it in the discriminator's) - no mark on the opening gather, no wait in front of the
+// next one, and nothing beside the critical launch.
+// (the handle's part: what aae_create knows - it sets the deferred launch's width by it; then the step's)
+bool inline_prefetch_handle(const aae_model* m) {
+    return !m->opt.no_inline_prefetch && !m->ae_only && !m->vae && m->use_chain4 && m->lazy && m->cfg.grad_mode == AAE_GRAD_FUSED &&
+           m->cfg.optimizer == AAE_OPT_ADAM && !m->early_any && !m->opt.chain_ts;
+}
+bool inline_prefetch_applies(const aae_model* m) {
+    return inline_prefetch_handle(m) && m->whole_step && !m->dense_step && !m->ext_first && m->rows <= 16 * kMB &&
+           m->pf_batch.n_rows <= 16 * kMB && !(m->x16_ok && 2 * m->rows >= m->x16_rows);
+}
+static BatchView view_of(const aae_batch& b) {
+    BatchView bv; bv.indptr = b.indptr_dev; bv.indices = b.indices_dev; bv.values = b.values_dev;
+    bv.rows = b.rows_dev; bv.row_start = b.row_start; bv.n_rows = b.n_rows;
+    return bv;
+}
+static void piggyback_next_list(aae_model* m, ChainBuilder& cb) {
+    if (!m->inl_step || m->inl_uniq_out) return;
+    UniqJob& j = cb.P.uq;
+    j.bv = view_of(m->inl_batch); j.mark = m->mark2; j.stamp = m->stamp2; j.ulist = m->ulist2; j.ucount = m->ucount2;
+    j.nblocks = (m->inl_batch.n_rows + kC4W - 1) / kC4W;      // one wave per document
+    j.enabled = 1;
+}
+// ... behind the launch that was to carry it: the kernel of that name where it could not
+static int next_list_sent(aae_model* m, const ChainBuilder* cb, hipStream_t s) {
+    if (!m->inl_step || m->inl_uniq_out) return AAE_OK;
+    if (!cb || !cb->P.uq.enabled) {
+        ProfScope ps(m, AAE_K_UNIQ_ITEMS, s);
+        const aae_batch& b = m->inl_batch;
+        const int mr = b.max_row_nnz > 0 ? b.max_row_nnz : 1024;
+        const int gy = std::max(1, std::min(16, std::max(1, std::min(64, (mr + 15) / 16)) / 16 + 1));
+        hipLaunchKernelGGL(uniq_items_kernel, dim3(b.n_rows, gy), dim3(256), 0, s, view_of(b), m->mark2, m->stamp2, m->ulist2, m->ucount2);
+        LAUNCHCHK("uniq_items (next batch)");
+    }
+    m->inl_uniq_out = true;
+    return AAE_OK;
+}
+// eighths [inl_cu8, hi8) of the list: rows of the running batch are skipped, the others brought through the running step
+static void piggyback_next_catchup(aae_model* m, ChainBuilder& cb, int hi8) {
+    if (!m->inl_step || !m->inl_uniq_out || m->inl_cu8 >= hi8) return;
+    CatchupJob& j = cb.P.cu;
+    j.a = W1Catchup{m->ulist2, m->ucount2, m->N, m->tsync, m->P[P_W1T].p, m->M[0][P_W1T].p, m->V[0][P_W1T].p, m->M[1][P_W1T].p,
+                    m->V[1][P_W1T].p, m->ldw1, m->h, m->tab, m->mark, m->stamp};
+    j.upto = (int)m->hstep; j.lo8 = m->inl_cu8; j.hi8 = hi8;
+    // one workgroup per CU (a chain workgroup's LDS): the CUs neither the deferred launch nor the program's rows hold, and no
+    // more than the share of the largest list a batch of this size is sized for, kC4T / 256 rows a pass
+    const int bound = std::min(m->cfg.max_nnz, std::max(256, m->inl_batch.n_rows * 32));
+    const int share = std::max(1, (bound * (hi8 - m->inl_cu8) / 8 + kC4T / 256 - 1) / (kC4T / 256));
+    const int idle = m->n_cu - (m->opt_pending ? m->split_wgs : 0) - (cb.P.rows + kR4 - 1) / kR4 - 8;
+    j.nblocks = std::max(8, std::min(idle, share));
+    j.enabled = 1;
+}
+static void next_catchup_sent(aae_model* m, const ChainBuilder& cb) {
+    if (cb.P.cu.enabled) m->inl_cu8 = cb.P.cu.hi8;
+}
+// behind the generator's launch, the last that carries any of it: what no launch carried goes out as the kernels of that name
+// (rows already brought to this step are skipped: a whole-list launch is right whatever rode before), and the lists count as
+// built for the next step - take_lists_built_ahead hands them over as it does the side stream's
+static int inline_prefetch_done(aae_model* m, hipStream_t s) {
+    if (!m->inl_step) return AAE_OK;
+    if (m->inl_cu8 < 8) {
+        ProfScope ps(m, AAE_K_W1_CATCHUP, s);
+        const int grid = std::min(m->cfg.max_nnz, std::max(256, m->inl_batch.n_rows * 32));
+        hipLaunchKernelGGL(w1_catchup_kernel, dim3(grid), dim3(256), 0, s, m->ulist2, m->ucount2, m->N, m->tsync,
+                           m->P[P_W1T].p, m->M[0][P_W1T].p, m->V[0][P_W1T].p, m->M[1][P_W1T].p, m->V[1][P_W1T].p,
+                           m->ldw1, m->h, m->tab, m->step_ctr, 0, m->mark, m->stamp, m->hstep);
+        LAUNCHCHK("w1_catchup (next batch)");
+    }
+    m->inl_step = false;
+    m->pf_built = true; m->pf_step = m->hstep + 1; m->pf_built_batch = m->inl_batch;
+    return AAE_OK;
+}
+
 // ae forward after the gather: encoder tail (+ optionally the decoder's two hidden layers)
 int chain_ae_forward(aae_model* m, bool with_dec, const float* cond_dev, float* z_out, hipStream_t s) {
     const int B = m->rows, h = m->h, c = m->c, cp = m->cp;
@@ -807,8 +892,9 @@ int chain_ae_backward(aae_model* m, bool dec_part, bool enc_part, const float* p
         x2.d = make_drop(m, 0, true, I.masks_dev[which == O_GEN ? 8 : 0], nullptr, B, h, which == O_GEN ? 8 : 0);
         cop_out(x2, ga1_ptr(m), m->ldh);
     }
-    if (item_lists) piggyback_item_lists(m, cb);
-    return launch_chain(m, cb, s);
+    if (item_lists) { piggyback_item_lists(m, cb); piggyback_next_list(m, cb); }
+    TRY(launch_chain(m, cb, s));
+    return item_lists ? next_list_sent(m, &cb, s) : AAE_OK;
 }
 
 // first encoder layer's weight gradient (sparse scatter), bias gradient and their optimiser
@@ -843,8 +929,9 @@ int encoder_first_layer_update(aae_model* m, const float* ga1, int which, hipStr
 // dropout d + activation -> act_out (NULL: the partial form of an item slice, aae_first_layer_forward).
 // head: tell the side stream that the main stream has passed this launch (ev_head rides on its completion signal)
 // (the per-layer path's and the rank calls' gathers are launches of their own: always 16 waves, no step to open)
+// bump_next: the new stamp + empty list alone (the list and catch-up ride in this step's own launches: no mark to leave)
 int launch_gather(aae_model* m, const float* bias, float* act_out, const DropSpec& d, bool head, bool open_step, const char* what,
-                  hipStream_t s) {
+                  hipStream_t s, bool bump_next = false) {
     ProfScope ps(m, AAE_K_ENC_GATHER, s);
     const size_t shm = (size_t)16 * r4(m->h) * sizeof(float);
     // wide batches: four waves per document (eight documents per CU instead of two; a document is ~20 entries: five per wave;
@@ -858,7 +945,7 @@ int launch_gather(aae_model* m, const float* bias, float* act_out, const DropSpe
     // head: the prefetch's first launch (new stamp, empty list) rides here as well - the catch-up behind it then
     // starts a launch earlier, ahead of the output layer's critical launch instead of beside its first workgroups
     const AdvanceJob adv{m->sc, m->step_ctr, m->lazy ? m->tab : nullptr, m->losses, open_step ? 1 : 0,
-                         head ? m->stamp2 : nullptr, head ? m->ucount2 : nullptr};
+                         head || bump_next ? m->stamp2 : nullptr, head || bump_next ? m->ucount2 : nullptr};
     hipExtLaunchKernelGGL(four ? enc_gather_kernel_t<4> : enc_gather_kernel_t<16>, dim3(m->rows), dim3(four ? 256 : 1024),
                           (uint32_t)(four ? shm / 4 : shm), s, nullptr, head ? m->ev_head : nullptr, 0, m->bv,
                           (const float*)m->P[P_W1T].p, m->ldw1, bias, m->h, (int)m->cfg.normalize_inputs,
@@ -870,9 +957,9 @@ int launch_gather(aae_model* m, const float* bias, float* act_out, const DropSpe
 
 // the whole first layer of this handle's own: bias, dropout (train), activation -> eh1
 int gather_first_layer(aae_model* m, bool train, const uint8_t* mk1, uint32_t sid1, hipStream_t s, bool head = false,
-                       bool open_step = false) {
+                       bool open_step = false, bool bump_next = false) {
     const DropSpec d1 = make_drop(m, 0, train, mk1, nullptr, m->rows, m->h, sid1);
-    TRY(launch_gather(m, m->P[P_B1].p, m->eh1.p, d1, head, open_step, "enc_gather", s));
+    TRY(launch_gather(m, m->P[P_B1].p, m->eh1.p, d1, head, open_step, "enc_gather", s, bump_next));
     m->pf_bumped = head;
     return AAE_OK;
 }
@@ -904,8 +991,12 @@ int launch_prefetch(aae_model* m, bool wait_head = true, bool early = false) {
     else if (wait_head) HIPCHK(hipStreamWaitEvent(q, m->ev_head, 0));      // (else: the caller enqueues behind work that is ordered behind the step's head)
     if (early || !(wait_head && m->pf_bumped)) hipLaunchKernelGGL(bump_stamp_kernel, dim3(1), dim3(1), 0, q, m->stamp2, m->ucount2);
     m->pf_bumped = false;
-    hipLaunchKernelGGL(uniq_items_kernel, dim3(b.n_rows, gy), dim3(256), 0, q, bv, m->mark2, m->stamp2, m->ulist2, m->ucount2);
+    {
+        ProfScope ps(m, AAE_K_UNIQ_ITEMS, q);
+        hipLaunchKernelGGL(uniq_items_kernel, dim3(b.n_rows, gy), dim3(256), 0, q, bv, m->mark2, m->stamp2, m->ulist2, m->ucount2);
+    }
     if (m->cfg.optimizer == AAE_OPT_ADAM) {
+        ProfScope ps(m, AAE_K_W1_CATCHUP, q);
         const int grid = std::min(m->cfg.max_nnz, std::max(256, b.n_rows * 32));
         hipLaunchKernelGGL(w1_catchup_kernel, dim3(grid), dim3(256), 0, q, m->ulist2, m->ucount2, m->N, m->tsync,
                            m->P[P_W1T].p, m->M[0][P_W1T].p, m->V[0][P_W1T].p, m->M[1][P_W1T].p, m->V[1][P_W1T].p,
@@ -1069,7 +1160,9 @@ int chain_disc_step(aae_model* m, hipStream_t s) {
         cop_out(x3, m->gb0.p, m->ldh);
         ChainOp& x2 = cb.add(cop_dx(m, P_D2, 5, 6, h, h, CEPI_ACTBWD, s)); x2.yslot = 1; x2.d = d1.d;
         cop_out(x2, m->gb1.p, m->ldh);
+        piggyback_next_catchup(m, cb, m->opt.inline_pf_disc8);
         TRY(launch_chain(m, cb, s));
+        next_catchup_sent(m, cb);
     }
     DwBuilder dw;
     dw.add(m, m->ga3.p, 4, m->xh2.p, m->ldh, 2 * B, P_D3, O_DISC);
@@ -1114,7 +1207,11 @@ int chain_gen_step(aae_model* m, hipStream_t s) {
     cop_out(w3, m->gb2.p, m->ldh);
     ChainOp& w2 = cb.add(cop_dx(m, P_W2, 7, 8, h, h, CEPI_ACTBWD, s)); w2.yslot = 1; w2.d = e1.d;
     cop_out(w2, ga1_ptr(m), m->ldh);
+    TRY(next_list_sent(m, nullptr, s));      // (a step whose backward launch did not carry the list)
+    piggyback_next_catchup(m, cb, 8);
     TRY(launch_chain(m, cb, s));
+    next_catchup_sent(m, cb);
+    TRY(inline_prefetch_done(m, s));
     DwBuilder dw;
     dw.add(m, m->ga3.p, m->ldz, m->eh2.p, m->ldh, B, P_W3, O_GEN);
     dw.add(m, m->gb2.p, m->ldh, m->eh1.p, m->ldh, B, P_W2, O_GEN);

@@ -60,6 +60,7 @@ int set_batch(aae_model* m, const aae_batch* b) {
     m->bv.indptr = b->indptr_dev; m->bv.indices = b->indices_dev; m->bv.values = b->values_dev;
     m->bv.rows = b->rows_dev; m->bv.row_start = b->row_start; m->bv.n_rows = b->n_rows;
     m->rows = b->n_rows; m->have_batch = true; m->buckets_valid = false; m->item_lists_valid = false; m->w1_merged = false;
+    m->inl_step = false;
     {   // 16 entries per workgroup pass; unknown row bound -> 64 strided chunks
         int mr = b->max_row_nnz > 0 ? b->max_row_nnz : 1024;
         m->chunks = std::max(1, std::min(64, (mr + 15) / 16));
@@ -72,10 +73,14 @@ int set_batch(aae_model* m, const aae_batch* b) {
 int lazy_prepare(aae_model* m, int upto_off, bool bump, hipStream_t s) {
     if (bump) hipLaunchKernelGGL(bump_stamp_kernel, dim3(1), dim3(1), 0, s, m->stamp, m->ucount);
     int gy = std::max(1, std::min(16, m->chunks / 16 + 1));
-    hipLaunchKernelGGL(uniq_items_kernel, dim3(m->rows, gy), dim3(256), 0, s, m->bv, m->mark, m->stamp, m->ulist,
-                       m->ucount);
+    {
+        ProfScope ps(m, AAE_K_UNIQ_ITEMS, s);
+        hipLaunchKernelGGL(uniq_items_kernel, dim3(m->rows, gy), dim3(256), 0, s, m->bv, m->mark, m->stamp, m->ulist,
+                           m->ucount);
+    }
     LAUNCHCHK("uniq_items");
     if (m->cfg.optimizer == AAE_OPT_ADAM) {
+        ProfScope ps(m, AAE_K_W1_CATCHUP, s);
         int grid = std::min(m->cfg.max_nnz, std::max(256, m->rows * 32));
         hipLaunchKernelGGL(w1_catchup_kernel, dim3(grid), dim3(256), 0, s, m->ulist, m->ucount, m->N, m->tsync,
                            m->P[P_W1T].p, m->M[0][P_W1T].p, m->V[0][P_W1T].p, m->M[1][P_W1T].p, m->V[1][P_W1T].p,
@@ -88,6 +93,7 @@ int lazy_prepare(aae_model* m, int upto_off, bool bump, hipStream_t s) {
 // lazy Adam: every row of W1T (and its four moment tensors) through the current step
 int lazy_flush(aae_model* m, hipStream_t s) {
     if (!m->lazy || m->cfg.optimizer != AAE_OPT_ADAM) return AAE_OK;
+    ProfScope ps(m, AAE_K_W1_CATCHUP, s);
     hipLaunchKernelGGL(w1_catchup_kernel, dim3(std::min(m->N, 8192)), dim3(256), 0, s, (const int*)nullptr,
                        (const int*)nullptr, m->N, m->tsync, m->P[P_W1T].p, m->M[0][P_W1T].p, m->V[0][P_W1T].p,
                        m->M[1][P_W1T].p, m->V[1][P_W1T].p, m->ldw1, m->h, m->tab, m->step_ctr, 0);

@@ -39,6 +39,7 @@ enum { O_ENC = 0, O_DEC = 1, O_GEN = 2, O_DISC = 3 };
 // per process, so a test may create two handles with different switches.  What is left forces a PATH (the parity suites replay
 // every fixture on each of them) or is a diagnostic of a debug run; the tuning knobs and the on/off switches of r1-r5's
 // experiments are gone with their decisions taken (HISTORY.md has the numbers).
+constexpr int kInlinePfDisc8 = 0;      // (aae_options::inline_pf_disc8's default)
 struct aae_options {
     // paths (tests)
     bool no_chain;          // NO_CHAIN: one GEMM launch per hidden layer instead of the layer-chain programs
@@ -48,6 +49,9 @@ struct aae_options {
     bool early_any;         // EARLY_ANY: the next batch's item list started from the step before, at every batch size
     bool no_late_join;      // NO_LATE_JOIN: a step waits for the deferred launch of the step before at its opening
     bool no_item_lists;     // NO_ITEM_LISTS: the first layer's update collects every item's rows itself (no per-batch row lists, w1_lists.h)
+    bool no_inline_prefetch; // NO_INLINE_PREFETCH: the next batch's item list and catch-up on the side stream (launch_prefetch) also where workgroups
+                            // of the step's own chain launches would build them (abi_chains.h: inline_prefetch_applies)
+    int inline_pf_disc8;    // INLINE_PF_DISC8: eighths of that list whose catch-up rides in the discriminator's launch, the rest in the generator's (0 .. 8)
     bool no_item_count;     // NO_ITEM_COUNT: first-layer item workgroups sized by the bound, not by the device's last count
     bool w1_serial;         // W1_SERIAL: data-parallel import of the peers' first-layer rows one launch per peer
     bool no_rank_fused;     // NO_RANK_FUSED: predict -> rank as two kernels over the [rows, N] score matrix
@@ -70,6 +74,7 @@ inline void read_options(aae_options& o) {
     o.no_chain = on("NO_CHAIN"); o.chain16 = on("CHAIN16"); o.split_any = on("SPLIT_ANY"); o.blocked_any = on("BLOCKED_ANY");
     o.early_any = on("EARLY_ANY"); o.no_late_join = on("NO_LATE_JOIN"); o.no_item_count = on("NO_ITEM_COUNT");
     o.no_item_lists = on("NO_ITEM_LISTS");
+    o.no_inline_prefetch = on("NO_INLINE_PREFETCH"); o.inline_pf_disc8 = std::max(0, std::min(num("INLINE_PF_DISC8", kInlinePfDisc8), 8));
     o.w1_serial = on("W1_SERIAL"); o.no_rank_fused = on("NO_RANK_FUSED"); o.chain_kslices = on("CHAIN_KSLICES");
     o.x16_rows = num("X16_ROWS", 1024); o.dw_ksplit_rows = num("DW_KSPLIT_ROWS", -1);
     o.rank_collect_cap = std::max(0, std::min(num("RANK_COLLECT_CAP", 0), 4096));
@@ -180,6 +185,11 @@ struct aae_model {
     aae_batch pf_batch, pf_built_batch; bool pf_armed; bool pf_built; long long pf_step; long long hstep;
     bool pf_pending; hipEvent_t ev_head, ev_pf;
     bool pf_bumped = false;  // the running step's gather bumped the next batch's stamp (launch_prefetch skips its own launch)
+    // The same list and catch-up built by workgroups of the running step's own chain launches instead (abi_chains.h: inline_prefetch_applies):
+    // stream order is the only ordering they need - no side stream, no mark, nothing pending.  whole_step: the call is aae_step (every
+    // carrying launch follows); inl_step: this step carries them, for inl_batch; inl_uniq_out: the list is enqueued; inl_cu8: eighths
+    // of the list whose catch-up is enqueued
+    bool whole_step = false, inl_step = false, inl_uniq_out = false; int inl_cu8 = 0; aae_batch inl_batch;
     bool pf_after_opt = false;                             // the pending prefetch was enqueued behind the pending deferred launch
     hipEvent_t ev_bk = nullptr; bool bk_pending = false;   // the tile buckets of the running batch, built on the side stream (aae_first_layer_forward)
     bool last_out_split = false;                           // the last output-layer pass ran as critical + deferred launch(es)

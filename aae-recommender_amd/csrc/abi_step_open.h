@@ -138,9 +138,15 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
         // (wide batches only: at 100 rows the 3 200 small workgroups of the catch-up, started this early, sit on the CUs the forward
         //  chain's 25 workgroups need whole - C3 0.2386 -> 0.2420 ms/step; C4, 1 000 rows: 0.3932 -> 0.3826; AAE_EARLY_ANY: tests)
         const bool early = pf && ahead && end_marked && spec_ok && m->early_enabled && (m->rows > 16 * kMB || m->early_any);
+        // ... or inside this step's own chain launches (abi_chains.h: inline_prefetch_applies): the gather opens the list, leaves no
+        // mark, and nothing is pending for the next step's opening to wait for
+        const bool inl = pf && !early && inline_prefetch_applies(m);
         if (early) TRY(launch_prefetch(m, true, true));
-        TRY(gather_first_layer(m, true, m->inj.masks_dev[0], 0, s, pf && !early, fold_advance));
-        if (pf && !early) TRY(launch_prefetch(m));
+        TRY(gather_first_layer(m, true, m->inj.masks_dev[0], 0, s, pf && !early && !inl, fold_advance, inl));
+        if (inl) {
+            m->inl_step = true; m->inl_uniq_out = false; m->inl_cu8 = 0; m->inl_batch = m->pf_batch;
+            m->pf_armed = false;
+        } else if (pf && !early) TRY(launch_prefetch(m));
         TRY(chain_ae_forward(m, with_dec, cond_dev, z_out, s));
         m->phase = 1;
         return AAE_OK;

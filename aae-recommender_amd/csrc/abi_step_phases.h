@@ -358,7 +358,10 @@ int aae_step(aae_handle m, const aae_batch* batch, const float* cond_dev, const 
     if (m->ext_first) return fail(AAE_ESTATE, "aae_step: the first layer is external (aae_set_first_layer_external): drive the phases");
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     hipStream_t s = S(stream);
-    TRY(ae_encode_impl(m, batch, inj, nullptr, true, cond_dev, stream));
+    m->whole_step = true;           // (every launch of the step follows in this call: the next batch's list and catch-up may ride in them)
+    const int rc = ae_encode_impl(m, batch, inj, nullptr, true, cond_dev, stream);
+    m->whole_step = false;
+    TRY(rc);
     TRY(stage_cond(m, cond_dev, s));
     DecodeMode mode; mode.enc_too = true;
     TRY(decode_backward(m, nullptr, 0, nullptr, nullptr, mode, s));

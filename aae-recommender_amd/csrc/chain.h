@@ -99,6 +99,9 @@ struct ChainProgram {
                                         // of ops[] moves every op descriptor's offset in the kernel-argument segment (and with it the width of the
                                         // scalar loads that fetch it: +0.3 us per launch of every chain kernel, measured)
     ItemListJob il;                     // chain4.h: enabled = the launch's last il.nblocks workgroups build the batch's item row lists (w1_lists.h)
+    UniqJob uq;                         // chain4.h: enabled = uq.nblocks workgroups behind those list the distinct items of the batch named ahead ...
+    CatchupJob cu;                      // ... and cu.nblocks workgroups, last of all, catch its first-layer rows up (kernels.h; never both in one launch:
+                                        // the catch-up reads a finished list, so it rides in a later launch of the step)
 };
 
 // Workgroup barrier that orders LDS traffic only: global stores of finished activations (consumed by

@@ -241,12 +241,30 @@ __device__ __forceinline__ f32x4 chain4_cols(const float* W4, int ns4, int N, in
 template <bool BF, bool TS = false, bool COLS = false, bool VAE = false>
 __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
     extern __shared__ __attribute__((aligned(16))) float slots[];     // [kCSlots][4][kCL], then the partial-sum scratch
-    const int il_blocks = P.il.enabled ? P.il.nblocks : 0;            // (uniform) the piggy-backed item-list builder: the last workgroups
-    if ((int)blockIdx.x >= (int)gridDim.x - il_blocks) {
-        w1_lists_build_body<kC4T>(P.il, reinterpret_cast<unsigned*>(slots), (int)blockIdx.x - ((int)gridDim.x - il_blocks), il_blocks);
+    // (uniform) the piggy-backed jobs, behind the row workgroups in block order: [bucket builder][item lists][next batch: list | catch-up]
+    // (the timeline and VAE members carry no next-batch job: launch_chain sends none their way)
+    const int nx_blocks = (TS || VAE) ? 0 : P.cu.enabled ? P.cu.nblocks : P.uq.enabled ? P.uq.nblocks : 0;
+    const int il_end = (int)gridDim.x - nx_blocks;
+    if constexpr (!TS && !VAE) {
+        if ((int)blockIdx.x >= il_end) {
+            static_assert((kC4T / 256) * kLazyReplay * sizeof(LazyTab) <= kCSlots * kCR * kCL * sizeof(float),
+                          "the catch-up's staged table entries (one set per row in flight) fit a chain workgroup's LDS");
+            const int vb = (int)blockIdx.x - il_end;
+            if (P.cu.enabled) {
+                w1_catchup_body<kC4T>(P.cu.a, P.cu.upto, reinterpret_cast<LazyTab*>(slots), vb, nx_blocks, P.cu.lo8, P.cu.hi8);
+            } else {        // one wave per document
+                const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+                uniq_items_body(P.uq.bv, P.uq.mark, P.uq.stamp, P.uq.ulist, P.uq.ucount, vb * kC4W + wv, nx_blocks * kC4W, 0, 1, (int)threadIdx.x & 63, 64);
+            }
+            return;
+        }
+    }
+    const int il_blocks = P.il.enabled ? P.il.nblocks : 0;            // the item-list builder
+    if ((int)blockIdx.x >= il_end - il_blocks) {
+        w1_lists_build_body<kC4T>(P.il, reinterpret_cast<unsigned*>(slots), (int)blockIdx.x - (il_end - il_blocks), il_blocks);
         return;
     }
-    if (P.bk.enabled && (int)blockIdx.x == (int)gridDim.x - 1 - il_blocks) {      // (uniform) the piggy-backed bucket builder
+    if (P.bk.enabled && (int)blockIdx.x == il_end - 1 - il_blocks) {      // the piggy-backed bucket builder
         tile_bucket_body<kBucketMaxDocs, kC4T>(P.bk.bv, P.bk.ntiles, P.bk.tstart, P.bk.eb, P.bk.en, P.bk.ev, reinterpret_cast<int*>(slots));
         return;
     }

@@ -655,18 +655,29 @@ __global__ __launch_bounds__(256) void adv_loss_kernel(const float* __restrict__
 // (kLazyReplay / kLazyTabCap / LazyTab: defined at the top of this file, next to advance_step_body)
 
 // distinct items of the batch -> ulist (order arbitrary), *ucount
+// The body, for a caller that is told its place: "block" bx of nbx takes the documents bx, bx + nbx, .., part by of nby of each
+// one's entries, with nt threads (tid the thread's index among them).  No barrier: a wave may call it on its own.
+__device__ __forceinline__ void uniq_items_body(const BatchView& bv, int* __restrict__ mark, const int* __restrict__ stamp_p,
+                                                int* __restrict__ ulist, int* __restrict__ ucount, int bx, int nbx, int by,
+                                                int nby, int tid, int nt) {
+    const int stamp = *stamp_p;
+    for (int b = bx; b < bv.n_rows; b += nbx) {
+        const int dc = bv.doc(b);
+        const int64_t lo = bv.indptr[dc], hi = bv.indptr[dc + 1];
+        for (int64_t e = lo + (int64_t)by * nt + tid; e < hi; e += (int64_t)nby * nt) {
+            const int idx = bv.indices[e];
+            if (atomicExch(&mark[idx], stamp) != stamp) ulist[atomicAdd(ucount, 1)] = idx;
+        }
+    }
+}
 __global__ __launch_bounds__(256) void uniq_items_kernel(BatchView bv, int* __restrict__ mark,
                                                          const int* __restrict__ stamp_p, int* __restrict__ ulist,
                                                          int* __restrict__ ucount) {
-    const int b = blockIdx.x;
-    const int dc = bv.doc(b);
-    const int64_t lo = bv.indptr[dc], hi = bv.indptr[dc + 1];
-    const int stamp = *stamp_p;
-    for (int64_t e = lo + (int64_t)blockIdx.y * 256 + threadIdx.x; e < hi; e += (int64_t)gridDim.y * 256) {
-        const int idx = bv.indices[e];
-        if (atomicExch(&mark[idx], stamp) != stamp) ulist[atomicAdd(ucount, 1)] = idx;
-    }
+    uniq_items_body(bv, mark, stamp_p, ulist, ucount, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, (int)gridDim.y, (int)threadIdx.x, 256);
 }
+// ... as the last nblocks workgroups of a chain launch (chain4.h): the batch named ahead (aae_prefetch_batch), into the second list
+// set, one wave per document
+struct UniqJob { int enabled, nblocks; BatchView bv; int* mark; const int* stamp; int* ulist; int* ucount; };
 
 // stab: the per-step scalars of steps t0+1 .. t0+nl, staged in LDS by the caller (a chain of dependent scalar
 // loads from the global table cost ~50 ns per replayed step - the whole kernel's time at 192 steps)
@@ -691,7 +702,50 @@ __device__ __forceinline__ void lazy_replay(float& p, float& m1, float& v1, floa
     }
 }
 
-// rows = ulist[0..*ucount) (or every row when ulist == NULL); one workgroup per row.
+// rows = ulist[0..*ucount) (or every row when ulist == NULL); one 256-thread group per row.
+// upto = the step the rows are brought to.  skip_mark (the catch-up of the NEXT batch's rows while a step runs): rows of the
+// RUNNING batch are left alone - the step's own two updates bring them to `upto`
+struct W1Catchup {
+    const int* ulist; const int* ucount; int n_rows_all; int* tsync;
+    float* W; float* M1; float* V1; float* M3; float* V3; int ld, h;
+    const LazyTab* tab; const int* skip_mark; const int* skip_stamp;
+};
+// The body, for a caller that is told its place: workgroup vblock of vgrid, NT threads = NT / 256 rows per pass (one row per
+// 256-thread quarter), grid-stride over eighths [lo8, hi8) of the list (a list dealt over two launches: each row to one of them,
+// by list index).  stab: [NT / 256][kLazyReplay] in LDS.  Every row is the same operations in the same order wherever it runs.
+template <int NT>
+__device__ __forceinline__ void w1_catchup_body(const W1Catchup& a, int upto, LazyTab* stab, int vblock, int vgrid, int lo8, int hi8) {
+    static_assert(NT % 256 == 0, "w1_catchup_body: whole 256-thread quarters");
+    constexpr int Q = NT / 256;
+    const int q = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8), t = (int)threadIdx.x & 255;
+    LazyTab* st = stab + q * kLazyReplay;
+    const int cnt = a.ulist ? *a.ucount : a.n_rows_all;
+    const int r_lo = (int)(((long long)cnt * lo8) >> 3), r_hi = (int)(((long long)cnt * hi8) >> 3);
+    const int skip = a.skip_mark ? *a.skip_stamp : 0;
+    for (int base = r_lo + vblock * Q; base < r_hi; base += vgrid * Q) {
+        const int r = base + q;
+        int row = 0, t0 = upto;
+        if (r < r_hi) {
+            row = a.ulist ? a.ulist[r] : r;
+            t0 = (a.skip_mark && a.skip_mark[row] == skip) ? upto : a.tsync[row];
+        }
+        if (t0 < upto) {
+            const int nl = min(upto - t0, kLazyReplay);
+            for (int j = t; j < nl; j += 256) st[j] = a.tab[(t0 + 1 + j) & (kLazyTabCap - 1)];
+        }
+        __syncthreads();
+        if (t0 < upto) {
+            for (int c = t; c < a.h; c += 256) {
+                const size_t o = (size_t)row * a.ld + c;
+                float p = a.W[o], m1 = a.M1[o], v1 = a.V1[o], m3 = a.M3[o], v3 = a.V3[o];
+                lazy_replay(p, m1, v1, m3, v3, t0, upto, st);
+                a.W[o] = p; a.M1[o] = m1; a.V1[o] = v1; a.M3[o] = m3; a.V3[o] = v3;
+            }
+        }
+        __syncthreads();                       // every thread has read tsync[row]
+        if (t == 0 && t0 < upto) a.tsync[row] = upto;
+    }
+}
 // upto = *step_ctr + upto_off  (training gather: -1 = through the previous step; export/predict: 0)
 __global__ __launch_bounds__(256) void w1_catchup_kernel(const int* __restrict__ ulist, const int* __restrict__ ucount,
                                                          int n_rows_all, int* __restrict__ tsync,
@@ -704,28 +758,12 @@ __global__ __launch_bounds__(256) void w1_catchup_kernel(const int* __restrict__
     // (upto_abs >= 0: the step number from the host - the early prefetch runs beside the launch that advances *step_ctr)
     __shared__ LazyTab stab[kLazyReplay];
     const int upto = upto_abs >= 0 ? (int)upto_abs : (int)*step_ctr + upto_off;
-    const int cnt = ulist ? *ucount : n_rows_all;
-    // skip_mark (the prefetch of the NEXT batch's rows while a step runs): rows of the RUNNING batch are left alone -
-    // the step's own two updates bring them to `upto`
-    const int skip = skip_mark ? *skip_stamp : 0;
-    for (int r = blockIdx.x; r < cnt; r += gridDim.x) {
-        const int row = ulist ? ulist[r] : r;
-        const int t0 = (skip_mark && skip_mark[row] == skip) ? upto : tsync[row];
-        if (t0 < upto) {
-            const int nl = min(upto - t0, kLazyReplay);
-            for (int j = threadIdx.x; j < nl; j += 256) stab[j] = tab[(t0 + 1 + j) & (kLazyTabCap - 1)];
-            __syncthreads();
-            for (int c = threadIdx.x; c < h; c += 256) {
-                const size_t o = (size_t)row * ld + c;
-                float p = W[o], m1 = M1[o], v1 = V1[o], m3 = M3[o], v3 = V3[o];
-                lazy_replay(p, m1, v1, m3, v3, t0, upto, stab);
-                W[o] = p; M1[o] = m1; V1[o] = v1; M3[o] = m3; V3[o] = v3;
-            }
-        }
-        __syncthreads();                       // every thread has read tsync[row]
-        if (threadIdx.x == 0 && t0 < upto) tsync[row] = upto;
-    }
+    const W1Catchup a{ulist, ucount, n_rows_all, tsync, W, M1, V1, M3, V3, ld, h, tab, skip_mark, skip_stamp};
+    w1_catchup_body<256>(a, upto, stab, (int)blockIdx.x, (int)gridDim.x, 0, 8);
 }
+// ... as the last nblocks workgroups of a chain launch (chain4.h): the catch-up of the batch named ahead through the RUNNING
+// step (upto: the host's step number, by value), eighths [lo8, hi8) of its list
+struct CatchupJob { int enabled, nblocks; W1Catchup a; int upto, lo8, hi8; };
 
 // optimiser step on the touched rows with the scattered gradient; clears the gradient rows.
 // mark_synced: this was gen_optim (the second update of the step) -> tsync[row] = current step

@@ -163,6 +163,8 @@ enum {
     AAE_T_ACT_DH2 = 100,   /* the decoder's last hidden activation [rows][n_hidden + 1] (last column = 1: the bias input) */
     AAE_T_ACT_DA2 = 101,   /* dL/d(ACT_DH2) written by aae_output_layer_step, same layout */
     AAE_T_ACT_GA1 = 102,   /* dL/d(ACT_A1) of the last encoder backward [rows][n_hidden] */
+    AAE_T_W1_TSYNC = 103,  /* deferred first-layer Adam: int32 [1][n_items] (behind the float view), the last step whose two updates a row
+                            * of ENC_W1T has received; read it behind aae_join (a catch-up of the batch named ahead may be writing it) */
     AAE_T_ACT_DZC = 99     /* dL/d(decoder input) of the last ae phase [rows][n_code + cond_inc]: columns n_code.. are
                             * the gradient of the condition block handed to aae_step (trainable conditions) */
 };
@@ -866,6 +868,9 @@ enum { AAE_K_ENC_GATHER = 0,   /* sparse row gather of the first encoder layer *
                                 * k > 32: also floor + collect + sort, and the dense form's long-list kernel */
        AAE_K_COLLECTIVE,       /* a collective of aae_dp_step / aae_shard_step: event pair on the step's stream around the table's call
                                 * (what the rank waits: the transfer AND the slowest rank's arrival) */
+       AAE_K_UNIQ_ITEMS,       /* uniq_items_kernel as a launch of its own: a batch's distinct-item list (a list built by workgroups of
+                                * a layer-chain launch is no launch and is not counted) */
+       AAE_K_W1_CATCHUP,       /* w1_catchup_kernel as a launch of its own: the deferred first-layer Adam replayed on listed (or all) rows */
        AAE_K_N };
 /* on = 0: off; 1: every kernel id above; otherwise a selection: bit (k + 1) of `on` times kernel id k
  * (an event pair costs a few microseconds of stream time, so a timed run selects only what it reports) */
