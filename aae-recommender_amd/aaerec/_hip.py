@@ -61,6 +61,7 @@ T_ACT_GA1 = 102
 T_W1_TSYNC = 103
 CAT_SUM, CAT_MEAN = 0, 1
 CAT_SPARSE_ADAM, CAT_ADAM = 0, 1
+BAG_SUM, BAG_MEAN_WIDTH, BAG_MEAN_COUNT, BAG_MAX_PAD0, BAG_MAX = range(5)
 O_ENC, O_DEC, O_GEN, O_DISC = 0, 1, 2, 3
 MODEL_AAE, MODEL_AE, MODEL_VAE = 0, 1, 3          # cfg.model_kind
 DTYPE_F32, DTYPE_BF16 = 0, 1                      # cfg.dtype
@@ -196,6 +197,11 @@ _PROTOS = {
                                  C.c_int64, C.c_void_p]),
     "aae_cat_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_void_p]),
+    "aae_bag_encode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_bag_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                 C.c_void_p]),
     "aae_csr_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_cooc_scores": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p]),
@@ -416,6 +422,35 @@ def cat_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, mean=False, grad
                                              table.shape[0], table.shape[1], _ptr(idx), idx.shape[0], idx.shape[1],
                                              CAT_MEAN if mean else CAT_SUM, _ptr(dout), dout.stride(0),
                                              CAT_ADAM if grad_scratch is not None else CAT_SPARSE_ADAM, float(lr), int(step),
+                                             C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+
+
+def bag_encode(table, idx, out, reduce=BAG_SUM, padding_idx=-1):
+    """A bag of table rows per row of idx, reduced into out [rows, dim] (aae_bag_encode: nn.EmbeddingBag's sum / mean / max
+    and CategoricalCondition's hid.max(1)[0]).  reduce: one of BAG_*; padding_idx -1: no padding row.  `out` may be a
+    column slice of the step's condition block."""
+    _cat_args(table, idx, out)
+    with torch.cuda.device(table.device):
+        _check(load_library().aae_bag_encode(_ptr(table), table.shape[0], table.shape[1], _ptr(idx), idx.shape[0],
+                                             idx.shape[1], int(reduce), int(padding_idx), _ptr(out), out.stride(0),
+                                             C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+
+
+def bag_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, reduce=BAG_SUM, padding_idx=-1, grad_scratch=None,
+               sparse=False):
+    """Backward of bag_encode from dout [rows, dim] plus the optimiser step: dense Adam over the whole table, or
+    (sparse=True) SparseAdam over the rows the batch names.  grad_scratch (zeros [vocab, dim], left zero): needed by dense
+    Adam and by the two max modes.  The winners of the max modes are recomputed from the table: it must be what bag_encode
+    read.  step counts from 1."""
+    _cat_args(table, idx, dout)
+    for t in (exp_avg, exp_avg_sq) + ((grad_scratch,) if grad_scratch is not None else ()):
+        if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
+            raise TypeError("aaerec: optimiser state must match the embedding table")
+    with torch.cuda.device(table.device):
+        _check(load_library().aae_bag_update(_ptr(table), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(grad_scratch),
+                                             table.shape[0], table.shape[1], _ptr(idx), idx.shape[0], idx.shape[1],
+                                             int(reduce), int(padding_idx), _ptr(dout), dout.stride(0),
+                                             CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step),
                                              C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
 
 

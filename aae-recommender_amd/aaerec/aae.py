@@ -305,7 +305,7 @@ class AdversarialAutoEncoder:
 
     def _is_device_native(self):
         """Every condition is a concatenated block the kernels can produce and train themselves: a constant block or
-        a CategoricalCondition with its table on this GPU."""
+        a CategoricalCondition / EmbeddingBagCondition with its table on this GPU (its own device_native decides)."""
         dev = self.hip.device if self.hip is not None else \
             torch.device(self.device if self.device is not None else "cuda:{}".format(torch.cuda.current_device()))
         return all(getattr(c, "constant_concat", False) or (hasattr(c, "device_native") and c.device_native(dev))

@@ -11,8 +11,9 @@ graph so trainable conditions (embedding tables with their own optimiser) keep l
 Conditions whose encoded input is a constant block that is concatenated
 (`PretrainedWordEmbeddingCondition`, anything with `constant_concat = True`) take the fully
 fused kernel path instead: their block is copied next to z on the device.  So does a
-`CategoricalCondition` whose table lives on the GPU: its lookup, backward and SparseAdam / Adam step
-are two small kernels of the library around the fused step (`device_native`).
+`CategoricalCondition` (every `reduce`) or an `EmbeddingBagCondition` (modes sum / mean / max) whose table
+lives on the GPU: its lookup, backward and SparseAdam / Adam step are two small kernels of the library
+around the fused step (`device_native`).
 """
 import itertools as it
 from abc import ABC, abstractmethod
@@ -247,7 +248,9 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
         self.embedding_dim = embedding_dim
 
     def encode(self, inputs):
-        return self.embedding_bag(inputs)
+        if not torch.is_tensor(inputs):
+            inputs = torch.as_tensor(np.asarray(inputs))
+        return self.embedding_bag(inputs.to(self.embedding_bag.weight.device))
 
     def zero_grad(self):
         self.optimizer.zero_grad()
@@ -257,6 +260,67 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
 
     def size_increment(self):
         return self.embedding_dim
+
+    # ---- device-native training path (libaaerec_hip: aae_bag_encode / aae_bag_update) ------------------------
+    # With the table in HBM (nn.EmbeddingBag's own device= keyword, or .embedding_bag.cuda()) the bag reduction, its
+    # backward and the Adam step run in the library's kernels around the fused step, as CategoricalCondition's do.  The
+    # optimiser state lives in self.optimizer.state in torch's own layout (step as a tensor, exp_avg, exp_avg_sq), so
+    # state_dict(), checkpoints and a later torch-side step see the same tensors.
+    _BAG_MODES = {"sum": 0, "mean": 2, "max": 4}          # _hip.BAG_SUM / BAG_MEAN_COUNT / BAG_MAX
+
+    def device_native(self, device):
+        bag = self.embedding_bag
+        w = bag.weight
+        return (w.is_cuda and w.device == torch.device(device) and bag.mode in self._BAG_MODES and bag.max_norm is None
+                and not bag.scale_grad_by_freq and not bag.sparse and self.embedding_dim <= 256)
+
+    def _index_block(self, inputs, device):
+        if torch.is_tensor(inputs):
+            if inputs.dim() != 2 or inputs.is_floating_point():
+                raise ValueError("EmbeddingBagCondition: the device-native route takes 2-D integer input [rows, width]")
+            if inputs.is_cuda:
+                return inputs.to(device=device, dtype=torch.int32).contiguous()
+            inputs = inputs.numpy()
+        arr = np.asarray(inputs)
+        if arr.ndim != 2 or arr.dtype.kind not in "iu":
+            raise ValueError("EmbeddingBagCondition: the device-native route takes 2-D integer input [rows, width]")
+        from . import _hip
+        return _hip.upload(np.ascontiguousarray(arr, dtype=np.int32), device)
+
+    def padded_width(self, inputs):
+        """Width of a batch: the second dimension of its [rows, width] input (nothing is padded)."""
+        return int(inputs.shape[1]) if hasattr(inputs, "shape") else len(inputs[0])
+
+    def _padding_idx(self):
+        p = self.embedding_bag.padding_idx
+        return -1 if p is None else int(p)
+
+    def encode_into(self, out, inputs, width=None):
+        """encode(inputs) written into `out` ([rows, embedding_dim], may be a column slice of a wider block).  width is
+        accepted for the protocol's sake: 2-D input has one width, and no mode divides by it."""
+        from . import _hip
+        w = self.embedding_bag.weight
+        self._idx = self._index_block(inputs, w.device)
+        _hip.bag_encode(w.data, self._idx, out, reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx())
+
+    def update_from(self, dout, inputs=None):
+        """zero_grad + backward + step (dense Adam) from dL/d(encoded block) of the rows last handed to encode_into, or
+        of `inputs` (data parallel: every rank applies the gathered gradient of the whole batch).  The winners of
+        mode='max' are recomputed from the table, which nothing has touched since encode_into."""
+        from . import _hip
+        w = self.embedding_bag.weight
+        if inputs is not None:
+            self._idx = self._index_block(inputs, w.device)
+        st = self.optimizer.state[w]
+        if "exp_avg" not in st:
+            st["step"] = torch.tensor(0.0)
+            st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(w.data), torch.zeros_like(w.data)
+        if getattr(self, "_grad_scratch", None) is None:
+            self._grad_scratch = torch.zeros_like(w.data)
+        st["step"] += 1
+        _hip.bag_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
+                        int(st["step"]), reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx(),
+                        grad_scratch=self._grad_scratch)
 
 
 class CategoricalCondition(ConcatenationBasedConditioning):
@@ -337,7 +401,8 @@ class CategoricalCondition(ConcatenationBasedConditioning):
     # step see the same tensors.
     def device_native(self, device):
         w = self.embedding.weight if self.embedding is not None else None
-        return (w is not None and w.is_cuda and w.device == torch.device(device) and self.reduce in (None, "sum", "mean")
+        return (w is not None and w.is_cuda and w.device == torch.device(device)
+                and self.reduce in (None, "sum", "mean", "max")
                 and not self.embedding_params and self.embedding_dim <= 256)
 
     def _index_block(self, inputs, device, width=None):
@@ -361,7 +426,10 @@ class CategoricalCondition(ConcatenationBasedConditioning):
         from . import _hip
         w = self.embedding.weight
         self._idx = self._index_block(inputs, w.device, width)
-        _hip.cat_encode(w.data, self._idx, out, mean=self.reduce == "mean")
+        if self.reduce == "max":        # hid.max(1)[0]: a padding slot is a candidate of value 0 (aae_bag_*, AAE_BAG_MAX_PAD0)
+            _hip.bag_encode(w.data, self._idx, out, reduce=_hip.BAG_MAX_PAD0, padding_idx=self.padding_idx)
+        else:
+            _hip.cat_encode(w.data, self._idx, out, mean=self.reduce == "mean")
 
     def update_from(self, dout, inputs=None):
         """zero_grad + backward + step from dL/d(encoded block) of the rows last handed to encode_into, or of
@@ -374,9 +442,14 @@ class CategoricalCondition(ConcatenationBasedConditioning):
         if "exp_avg" not in st:
             st["step"] = 0 if self.sparse else torch.tensor(0.0)
             st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(w.data), torch.zeros_like(w.data)
-        if not self.sparse and getattr(self, "_grad_scratch", None) is None:
+        if (not self.sparse or self.reduce == "max") and getattr(self, "_grad_scratch", None) is None:
             self._grad_scratch = torch.zeros_like(w.data)
         st["step"] += 1
+        if self.reduce == "max":        # the winners are recomputed from the table: nothing has touched it since encode_into
+            _hip.bag_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
+                            int(st["step"]), reduce=_hip.BAG_MAX_PAD0, padding_idx=self.padding_idx,
+                            grad_scratch=self._grad_scratch, sparse=self.sparse)
+            return
         _hip.cat_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
                         int(st["step"]), mean=self.reduce == "mean",
                         grad_scratch=None if self.sparse else self._grad_scratch)

@@ -46,6 +46,7 @@
 #include "chain4.h"
 #include "chain16x3.h"
 #include "cond_embed.h"
+#include "cond_bag.h"
 #include "w1_update.h"
 #include "dae_corrupt.h"
 

@@ -367,6 +367,33 @@ int aae_cat_encode(const float* table_dev, int32_t vocab, int32_t dim, const int
 int aae_cat_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
                    int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce,
                    const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream);
+/* EmbeddingBagCondition (condition.py:372-394: nn.EmbeddingBag, modes sum / mean / max, over 2-D input) and
+ * CategoricalCondition(reduce="max") (hid.max(1)[0]): bags of table rows with a free padding row and the two max
+ * reductions (csrc/cond_bag.h).  Handle-free like aae_cat_*: every buffer is the caller's, launches go to `stream`.
+ *   padding_idx  -1: no padding row (nn.EmbeddingBag's default; index 0 is an ordinary, trainable row);
+ *                >= 0: that row is left out of the reduction and never receives a gradient.
+ *                An index outside [0, vocab) is handled like a padding slot.
+ *   reduce  AAE_BAG_SUM         sum of the bag
+ *           AAE_BAG_MEAN_WIDTH  sum / width, padding counted                             (hid.mean(1))
+ *           AAE_BAG_MEAN_COUNT  sum / number of non-padding slots; an empty bag gives 0  (nn.EmbeddingBag(mode="mean"))
+ *           AAE_BAG_MAX_PAD0    column-wise maximum in which a padding slot is a candidate of value 0: a row shorter than
+ *                               the padded width gives max(..., 0), an all-padding row 0   (hid.max(1)[0])
+ *           AAE_BAG_MAX         column-wise maximum of the non-padding slots; an empty bag gives 0
+ *                                                                                        (nn.EmbeddingBag(mode="max"))
+ *   Tie rule (max modes): the gradient of (row r, column d) goes to the FIRST slot of row r that attains the maximum in
+ *   column d; in AAE_BAG_MAX_PAD0 to nobody when that slot is a padding slot.
+ *   Recompute contract: aae_bag_update recomputes the winners from the table - the caller must not modify the table
+ *   between the aae_bag_encode and the aae_bag_update of a step.  No argmax buffer crosses the step.
+ *   optimizer: AAE_CAT_SPARSE_ADAM / AAE_CAT_ADAM as in aae_cat_update.  grad_scratch_dev [vocab][dim] (zero on the
+ *   first call, left zero) is needed by AAE_CAT_ADAM and, with either optimiser, by the two max modes.
+ *   Limits: dim <= 256, width >= 1, rows * width <= 2^22; the update's duplicate scan is quadratic in rows * width.
+ *   Deterministic: no float atomics, the first slot naming a table row sums its contributions in slot order. */
+enum { AAE_BAG_SUM = 0, AAE_BAG_MEAN_WIDTH = 1, AAE_BAG_MEAN_COUNT = 2, AAE_BAG_MAX_PAD0 = 3, AAE_BAG_MAX = 4 };
+int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,
+                   int32_t width, int32_t reduce, int32_t padding_idx, float* out_dev, int64_t out_ld, void* stream);
+int aae_bag_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                   int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
+                   const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream);
 /* PretrainedWordEmbeddingCondition's preprocessing (condition.py:345-369 -> ub.py:52-57, EmbeddedVectorizer.transform:
  * `sparse_scores @ self.embedding`): out_dev[r][0:dim] = sum over the CSR entries e of row r of
  * values[e] * table_dev[indices[e]][0:dim], accumulated in CSR order.  indptr int64 [n_rows + 1] (absolute offsets

@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
-"""Host-level fit() throughput (docs/s) of the conditioned model variants at the headline widths:
-no condition, a constant concatenated block (pretrained-embedding style), a trainable categorical condition
-(embedding on CPU = the reference's default, and on the GPU).  Everything runs through AdversarialAutoEncoder.fit."""
+"""Host-level throughput of the conditioned model variants at the headline widths.
+
+    python tools/cond_rate.py        fit() in docs/s: no condition, a constant concatenated block (pretrained-embedding style), a
+                                     trainable categorical condition (embedding on CPU = the reference's default, and on the GPU)
+    python tools/cond_rate.py bag    partial_fit() in ms/step at batch 100 behind the conditions the bag kernels train
+                                     (csrc/cond_bag.h): CategoricalCondition(reduce="max") under SparseAdam and Adam,
+                                     EmbeddingBagCondition in its default mode and in mode="max" - on the native route and,
+                                     forced by a subclass whose device_native returns False, on the bridged one
+Everything runs through AdversarialAutoEncoder."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aae-recommender_amd"))
@@ -55,22 +61,78 @@ def rate(tag, conditions, data, epochs=25):
     print(f"{tag:34s} {epochs * DOCS / dt:10.0f} docs/s   ({1e3 * dt / (epochs * DOCS / B):.3f} ms/step, build {t2 - t1:.2f} s)", flush=True)
 
 
-rate("no condition", None, None)
-vec = rng.standard_normal((DOCS, 50)).astype(np.float32)
-rate("constant concat (50)", C.ConditionList([("title", ConstConcat(50))]), [vec])
-authors = [[int(a) for a in rng.integers(0, 5000, rng.integers(1, 5))] for _ in range(DOCS)]
-for on_gpu in (False, True):
-    cat = C.CategoricalCondition(32, use_cuda=True, embedding_on_gpu=on_gpu, reduce="sum")
-    cl = C.ConditionList([("authors", cat)])
-    data = cl.fit_transform([authors])
-    rate(f"categorical (32, emb on {'gpu' if on_gpu else 'cpu'})", cl, data, epochs=25 if on_gpu else 2)
-    both = C.ConditionList([("title", ConstConcat(50)), ("authors", C.CategoricalCondition(
-        32, use_cuda=True, embedding_on_gpu=on_gpu, reduce="sum"))])
-    d2 = both.fit_transform([vec, authors])
-    rate(f"concat + categorical (emb on {'gpu' if on_gpu else 'cpu'})", both, d2, epochs=25 if on_gpu else 2)
+def partial_fit_rates(rounds=9, warm=2):
+    """Median over `rounds` passes of 64 partial_fit calls (after `warm` passes), every pass closed by a synchronize."""
+    batches = [X[i:i + B] for i in range(0, DOCS, B)]
+    authors = [[int(a) for a in rng.integers(0, 5000, rng.integers(1, 5))] for _ in range(DOCS)]
+    # (a LongTensor on the GPU: the form nn.EmbeddingBag itself takes, so the bridged route needs no conversion)
+    bags = torch.from_numpy(rng.integers(0, 5000, size=(DOCS, 4)).astype(np.int64)).cuda()
 
-# the same condition forced through the torch-autograd bridge (the step cut at the condition boundary)
-cat = C.CategoricalCondition(32, use_cuda=True, reduce="sum")
-cat.device_native = lambda device: False
-cl = C.ConditionList([("authors", cat)])
-rate("categorical (emb on gpu, autograd bridge)", cl, cl.fit_transform([authors]))
+    def cat(sparse):
+        def make(bridged):
+            cls = C.CategoricalCondition
+            if bridged:
+                cls = type("Bridged", (cls,), {"device_native": lambda self, device: False})
+            cond = cls(32, use_cuda=True, reduce="max", sparse=sparse)
+            return cond, cond.fit_transform(authors)
+        return make
+
+    def bag(**kw):
+        def make(bridged):
+            cls = C.EmbeddingBagCondition
+            if bridged:
+                cls = type("Bridged", (cls,), {"device_native": lambda self, device: False})
+            cond = cls(5001, 32, **kw)
+            cond.embedding_bag.cuda()
+            return cond, bags
+        return make
+
+    def ms_per_step(make, bridged):
+        cond, data = make(bridged)
+        m = AdversarialAutoEncoder(n_hidden=h, n_code=c, batch_size=B, n_epochs=1, conditions=C.ConditionList([("authors", cond)]),
+                                   verbose=False, seed=1)
+        times = []
+        for r in range(warm + rounds):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i, b in enumerate(batches):
+                m.partial_fit(b, condition_data=[data[i * B:(i + 1) * B]])
+            torch.cuda.synchronize()
+            times.append(1e3 * (time.perf_counter() - t0) / len(batches))
+        native = m._is_device_native()
+        assert not (bridged and native)
+        return float(np.median(times[warm:])), native
+    print(f"partial_fit, N={N} h={h} c={c} batch {B}: median ms/step of {rounds} passes of {DOCS // B} steps")
+    print(f"{'condition':44s} {'native':>10s} {'bridged':>10s}")
+    for tag, make in (("CategoricalCondition(32, max, SparseAdam)", cat(True)), ("CategoricalCondition(32, max, Adam)", cat(False)),
+                      ("EmbeddingBagCondition(5001, 32)  [mean]", bag()), ("EmbeddingBagCondition(5001, 32, mode=max)", bag(mode="max"))):
+        t_nat, native = ms_per_step(make, False)
+        t_br, _ = ms_per_step(make, True)
+        note = "" if native else "   (no native route in this build: both columns are the bridged route)"
+        print(f"{tag:44s} {t_nat:10.3f} {t_br:10.3f}{note}", flush=True)
+
+
+def fit_rates():
+    rate("no condition", None, None)
+    vec = rng.standard_normal((DOCS, 50)).astype(np.float32)
+    rate("constant concat (50)", C.ConditionList([("title", ConstConcat(50))]), [vec])
+    authors = [[int(a) for a in rng.integers(0, 5000, rng.integers(1, 5))] for _ in range(DOCS)]
+    for on_gpu in (False, True):
+        cat = C.CategoricalCondition(32, use_cuda=True, embedding_on_gpu=on_gpu, reduce="sum")
+        cl = C.ConditionList([("authors", cat)])
+        data = cl.fit_transform([authors])
+        rate(f"categorical (32, emb on {'gpu' if on_gpu else 'cpu'})", cl, data, epochs=25 if on_gpu else 2)
+        both = C.ConditionList([("title", ConstConcat(50)), ("authors", C.CategoricalCondition(
+            32, use_cuda=True, embedding_on_gpu=on_gpu, reduce="sum"))])
+        d2 = both.fit_transform([vec, authors])
+        rate(f"concat + categorical (emb on {'gpu' if on_gpu else 'cpu'})", both, d2, epochs=25 if on_gpu else 2)
+
+    # the same condition forced through the torch-autograd bridge (the step cut at the condition boundary)
+    cat = C.CategoricalCondition(32, use_cuda=True, reduce="sum")
+    cat.device_native = lambda device: False
+    cl = C.ConditionList([("authors", cat)])
+    rate("categorical (emb on gpu, autograd bridge)", cl, cl.fit_transform([authors]))
+
+
+if __name__ == "__main__":
+    partial_fit_rates() if "bag" in sys.argv[1:] else fit_rates()
