@@ -176,6 +176,14 @@ _PROTOS = {
                                        C.c_void_p, C.c_void_p]),
     "aae_vae_rank_max_rows": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "aae_vae_rank_full_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "aae_predict_loss": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
+    "aae_decode_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
+    "aae_vae_predict_loss": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch),
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_vae_decode_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.c_void_p,
+                                      C.c_void_p]),
+    "aae_loss_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "aae_vae_loss_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "aae_encode": (C.c_int, [C.c_void_p, C.POINTER(AaeBatch), C.c_void_p, C.c_void_p]),
     "aae_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_apply_updates": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -1960,6 +1968,47 @@ class HipAAE:
         zc = zc.detach().to(self.device, torch.float32).contiguous()
         return self._ranks(self.lib.aae_vae_decode_ranks, self.vae_rank_full_max_rows(), csr, row_start, zc.shape[0], truth_csr,
                            exclude_known, zc=zc)
+
+    # ---- the held-out loss: per-row sums on the device, no score matrix (csrc/loss_eval.h) ----------------
+    def loss_max_rows(self):
+        """Rows one predict_loss / decode_loss call (a VAE handle: vae_predict_loss / vae_decode_loss) may take."""
+        if self.vae:
+            return self._max_rows("vae_loss", self.lib.aae_vae_loss_max_rows)
+        return self._max_rows("loss", self.lib.aae_loss_max_rows)
+
+    def _loss(self, entry, name, csr, row_start, n_rows, targets, per_row=(), zc=None, mid=(), n_out=1):
+        """A loss call of the handle: n_out float64 device tensors [n_rows].  targets: a DeviceCSR of csr's shape (None: csr)."""
+        if targets is not None and tuple(targets.shape) != tuple(csr.shape):
+            raise ValueError(f"{name}: targets has shape {tuple(targets.shape)}, the input rows {tuple(csr.shape)}")
+        b = self._batch(csr, row_start, n_rows, bounded=n_rows <= self.max_batch)
+        t = None if targets is None else self._batch(targets, row_start, n_rows, bounded=False)
+        outs = tuple(torch.empty(n_rows, dtype=torch.float64, device=self.device) for _ in range(n_out))
+        with self._on_device():
+            _check(entry(*map(_arg, self._lead(b, 0, n_rows, per_row, zc)), *mid, None if t is None else C.byref(t),
+                         *map(_ptr, outs), self._stream()))
+        return outs if n_out > 1 else outs[0]
+
+    def predict_loss(self, csr, row_start, n_rows, cond=None, targets=None):
+        """float64 device tensor [n_rows]: per row the BCE of predict() against `targets` (None: the input rows), SUMMED over
+        the items (aae_predict_loss).  Eval mode; nothing is copied to the host.  n_rows <= loss_max_rows()."""
+        return self._loss(self.lib.aae_predict_loss, "predict_loss", csr, row_start, n_rows, targets, (self._cond_rows(cond),))
+
+    def decode_loss(self, zc, csr, row_start, targets=None):
+        """The same for decode(zc): the input rows csr[row_start : row_start + len(zc)] (aae_decode_loss)."""
+        zc = zc.detach().to(self.device, torch.float32).contiguous()
+        return self._loss(self.lib.aae_decode_loss, "decode_loss", csr, row_start, zc.shape[0], targets, zc=zc)
+
+    def vae_predict_loss(self, csr, row_start, n_rows, cond=None, eps=None, row0=0, targets=None):
+        """(row_bce, row_kl) float64 device tensors [n_rows] of a VAE handle (aae_vae_predict_loss): the BCE sums of
+        vae_predict for the same rows and eps ([n_rows, n_code]; None: the device generator, whose rows count from row0)
+        and the rows' KL terms."""
+        return self._loss(self.lib.aae_vae_predict_loss, "vae_predict_loss", csr, row_start, n_rows, targets,
+                          (self._cond_rows(cond), self._eps_rows(eps, n_rows)), mid=(C.c_int64(int(row0)),), n_out=2)
+
+    def vae_decode_loss(self, zc, csr, row_start, targets=None):
+        """The BCE sums of the VAE's decode(zc) (aae_vae_decode_loss)."""
+        zc = zc.detach().to(self.device, torch.float32).contiguous()
+        return self._loss(self.lib.aae_vae_decode_loss, "vae_decode_loss", csr, row_start, zc.shape[0], targets, zc=zc)
 
     def encode(self, csr, row_start, n_rows):
         b = self._batch(csr, row_start, n_rows)

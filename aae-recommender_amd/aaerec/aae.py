@@ -692,9 +692,49 @@ def _predict_ranks(self, X, Y, condition_data=None, exclude_known=True, metrics=
         lambda csr, start, zc: self.hip.decode_ranks(zc, csr, start, truth, exclude_known=exclude_known)), Ys, metrics)
 
 
+def loss_targets(targets, shape, device, who="eval_loss"):
+    """The target rows of an eval_loss call as a DeviceCSR (None: the inputs themselves are the targets): a matrix of the
+    inputs' shape with values in [0, 1], duplicates summed and indices sorted."""
+    if targets is None:
+        return None
+    Ts = sp.csr_matrix(targets, copy=True) if not sp.issparse(targets) else targets.tocsr(copy=True)
+    if Ts.shape != tuple(shape):
+        raise ValueError("{}: targets has shape {}, the inputs {}".format(who, Ts.shape, tuple(shape)))
+    Ts.sum_duplicates()
+    Ts.sort_indices()
+    _validate_targets(Ts)
+    return _hip.DeviceCSR(Ts, device)
+
+
+def finish_loss(parts, shape, per_row):
+    """The per-row BCE sums (float64 device parts of a chunked call) as eval_loss returns them: the rows' sums on the host,
+    or the mean over rows x items - the number losses()[0] reports for a training batch.  One copy to the host."""
+    rows = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float64)
+    if per_row:
+        return rows.cpu().numpy()
+    return float(rows.sum().item() / (shape[0] * shape[1])) if shape[0] else 0.0
+
+
+def _eval_loss(self, X, condition_data=None, targets=None, per_row=False):
+    """The model's loss on rows it was not trained on, eval mode (no dropout, no corruption), without the [n, N] score
+    matrix: the mean over rows x items of F.binary_cross_entropy(predict(X) + 1e-12, T + 1e-12) - what losses()[0] reports
+    for a training batch - with T = targets (None: X, the reference's choice; any matrix of X's shape with values in [0, 1],
+    e.g. X + the held-out items).  per_row: the float64 sums over the items of every row instead.  Conditions as in
+    predict_topk(): see _rank_chunks."""
+    Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+    tdev = loss_targets(targets, Xs.shape, self.hip.device)
+    if tdev is None:
+        _validate_targets(Xs)
+    return finish_loss(self._rank_chunks(
+        Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.loss_max_rows()),
+        lambda csr, start, n, cond: self.hip.predict_loss(csr, start, n, cond=cond, targets=tdev),
+        lambda csr, start, zc: self.hip.decode_loss(zc, csr, start, targets=tdev)), Xs.shape, per_row)
+
+
 AdversarialAutoEncoder._rank_chunks = _rank_chunks
 AdversarialAutoEncoder.predict_topk = _predict_topk
 AdversarialAutoEncoder.predict_ranks = _predict_ranks
+AdversarialAutoEncoder.eval_loss = _eval_loss
 
 
 def _take(c, idx, rows_dev=None):
@@ -895,6 +935,17 @@ class DecodingRecommender(Recommender):
         parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_ranks(zc, csr, start, truth))
         return ranking.finish_ranks(parts, Ys, metrics)
 
+    def eval_loss(self, test_set, targets=None, per_row=False):
+        """The mean BCE of predict(test_set) against the test bags (targets: any matrix of their shape instead), on the
+        device (aae_decode_loss): what partial_fit logs for a training batch.  per_row: the rows' float64 sums."""
+        X = test_set.tocsr()
+        tdev = loss_targets(targets, X.shape, self.hip.device)
+        if tdev is None:
+            _validate_targets(X)
+        chunk = ranking.chunk_rows(self.batch_size, self.hip.loss_max_rows())
+        parts = self._rank_chunks(test_set, chunk, lambda zc, csr, start: self.hip.decode_loss(zc, csr, start, targets=tdev))
+        return finish_loss(parts, X.shape, per_row)
+
 
 def _validate_targets(X):
     """The reference's F.binary_cross_entropy rejects targets outside [0,1] (duplicate items in a
@@ -967,3 +1018,11 @@ class AAERecommender(Recommender):
         if self.conditions:
             condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
         return self.model.predict_ranks(X, y_true, condition_data=condition_data, metrics=metrics)
+
+    def eval_loss(self, test_set, targets=None):
+        """The model's mean BCE on the test bags (targets: any matrix of their shape instead), computed on the device."""
+        X = test_set.tocsr()
+        condition_data = None
+        if self.conditions:
+            condition_data = self.conditions.transform(test_set.get_attributes(self.conditions.keys()))
+        return self.model.eval_loss(X, condition_data=condition_data, targets=targets)

@@ -219,3 +219,8 @@ class DAERecommender(Recommender):
         """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag; with metrics,
         [(mean, std)] per name."""
         return self.dae.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set), metrics=metrics)
+
+    def eval_loss(self, test_set, targets=None):
+        """The model's mean BCE on the test bags as they are - no corruption - (targets: any matrix of their shape instead),
+        computed on the device (AdversarialAutoEncoder.eval_loss)."""
+        return self.dae.eval_loss(test_set.tocsr(), condition_data=self._conditions_of(test_set), targets=targets)

@@ -19,7 +19,7 @@ import scipy.sparse as sp
 import torch
 
 from . import _hip, ranking
-from .aae import TORCH_OPTIMIZERS, AdversarialAutoEncoder, _take, _validate_targets
+from .aae import TORCH_OPTIMIZERS, AdversarialAutoEncoder, _take, _validate_targets, loss_targets
 from .base import Recommender
 from .condition import _check_conditions
 
@@ -53,6 +53,7 @@ class VAE:
         self.rng_mode = rng_mode
         self.training = True
         self.last_loss = None
+        self.last_test_loss = None
         code_inc = int(conditions.size_increment()) if conditions else 0
         if n_code + code_inc + 1 > DEC_IN_MAX:
             raise ValueError("the VAE's decoder input [z | conditions | 1] is n_code + conditions.size_increment() + 1 = "
@@ -189,27 +190,79 @@ class VAE:
         self.loss()
         return self
 
-    def predict(self, X, condition_data=None):
+    def predict(self, X, condition_data=None, test_loss=False):
+        """test_loss: also evaluate the reference's loss_function on every batch (vae.py:243-264) - on the device, with the
+        eps rows the batch's scores were made from -, print its `====> Test set loss:` line and keep the value in
+        last_test_loss."""
         use_condition = _check_conditions(self.conditions, condition_data)
         self.eval()
         if self.conditions:
             self.conditions.eval()
         Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+        if test_loss:
+            _validate_targets(Xs)
         csr = _hip.DeviceCSR(Xs, self.device)
         pred = _hip.HostRows(Xs.shape[0], Xs.shape[1], self.device)
+        bce, kl = [], []
         with torch.no_grad():
             for start in range(0, Xs.shape[0], self.batch_size):
                 n = min(self.batch_size, Xs.shape[0] - start)
                 cond = None
                 c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
+                eps = self._eps(n)
                 if use_condition and not self._cond_native:
-                    z = self.hip.vae_encode(csr, start, n, eps=self._eps(n), train=False)
-                    pred.put(start, self.hip.decode(self.conditions.encode_impose(z, c_batch)))
+                    z = self.hip.vae_encode(csr, start, n, eps=eps, train=False)
+                    zc = self.conditions.encode_impose(z, c_batch)
+                    pred.put(start, self.hip.decode(zc))
+                    if test_loss:
+                        bce.append(self.hip.vae_decode_loss(zc, csr, start))
+                        kl.append(self._kl_rows(csr, start, n))
                     continue
                 if use_condition:
                     cond = self._cond(c_batch)
-                pred.put(start, self.hip.vae_predict(csr, start, n, cond=cond, eps=self._eps(n)))
+                pred.put(start, self.hip.vae_predict(csr, start, n, cond=cond, eps=eps))
+                if test_loss:       # (the device generator counts a batch's rows from 0 in vae_predict: row0 = 0 repeats its draws)
+                    b, k = self.hip.vae_predict_loss(csr, start, n, cond=cond, eps=eps, row0=0)
+                    bce.append(b)
+                    kl.append(k)
+        if test_loss:
+            self.last_test_loss = self._test_loss(torch.cat(bce).cpu().numpy(), torch.cat(kl).cpu().numpy(), Xs.shape[1])
+            print('====> Test set loss: {:.4f}'.format(self.last_test_loss))
         return pred.numpy()
+
+    # ---- the loss on held-out rows (aae_vae_predict_loss / aae_vae_decode_loss) --------------------------------
+    def _kl_rows(self, csr, start, n):
+        """The rows' KL terms where the decoder input is a plugin's: they depend on the encoder alone, so the predict form
+        with a zero condition block and zero draws answers them (its BCE sums are dropped)."""
+        ci = self.hip.cfg.cond_inc
+        cond = torch.zeros(n, ci, device=self.device) if ci else None
+        return self.hip.vae_predict_loss(csr, start, n, cond=cond, eps=torch.zeros(n, self.n_code, device=self.device))[1]
+
+    def _test_loss(self, row_bce, row_kl, n_items):
+        """The reference's test loss from the per-row sums: sum over the batches of batch_size rows of (mean BCE of the
+        batch + its KL sum), over the number of rows (vae.py:243-263)."""
+        total, n_rows, bs = 0.0, len(row_bce), self.batch_size
+        for s0 in range(0, n_rows, bs):
+            b = row_bce[s0:s0 + bs]
+            total += b.sum() / (len(b) * n_items) + row_kl[s0:s0 + bs].sum()
+        return float(total / n_rows) if n_rows else 0.0
+
+    def eval_loss(self, X, condition_data=None, targets=None, per_row=False):
+        """The reference's test loss of the model on rows it was not trained on (vae.py:243-264: per batch of batch_size rows
+        mean BCE + KL sum, summed, over the rows), without the [n, N] score matrix.  targets: None = X, or any matrix of X's
+        shape with values in [0, 1].  per_row: (row_bce, row_kl) instead, the float64 sums over the items / the code of every
+        row.  eps as predict_topk() draws it; on the device generator every row of the call has its own draw (row0)."""
+        Xs = sp.csr_matrix(X) if not sp.issparse(X) else X.tocsr()
+        tdev = loss_targets(targets, Xs.shape, self.device)
+        if tdev is None:
+            _validate_targets(Xs)
+        parts = self._rank_chunks(
+            Xs, condition_data, ranking.chunk_rows(self.batch_size, self.hip.loss_max_rows()),
+            lambda csr, start, n, cond, eps: self.hip.vae_predict_loss(csr, start, n, cond=cond, eps=eps, row0=start, targets=tdev),
+            lambda csr, start, zc: (self.hip.vae_decode_loss(zc, csr, start, targets=tdev), self._kl_rows(csr, start, zc.shape[0])))
+        cat = lambda i: (torch.cat([p[i] for p in parts]) if parts else torch.zeros(0, dtype=torch.float64)).cpu().numpy()  # noqa: E731
+        row_bce, row_kl = cat(0), cat(1)
+        return (row_bce, row_kl) if per_row else self._test_loss(row_bce, row_kl, Xs.shape[1])
 
     # ---- ranking on the device (aae_vae_predict_topk / aae_vae_predict_ranks) ----------------------------------
     def _rank_chunks(self, Xs, condition_data, chunk, fused, decode):
@@ -323,3 +376,7 @@ class VAERecommender(Recommender):
         """CSR with y_true's pattern: the rank of every held-out item in the full ranking of its test bag; with metrics,
         [(mean, std)] per name."""
         return self.model.predict_ranks(test_set.tocsr(), y_true, condition_data=self._conditions_of(test_set), metrics=metrics)
+
+    def eval_loss(self, test_set, targets=None):
+        """The reference's test loss of the model on the test bags (VAE.eval_loss), computed on the device."""
+        return self.model.eval_loss(test_set.tocsr(), condition_data=self._conditions_of(test_set), targets=targets)

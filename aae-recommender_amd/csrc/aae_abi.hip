@@ -34,6 +34,7 @@
 #include "rank_x3.h"
 #include "rank_long.h"
 #include "rank_full.h"
+#include "loss_eval.h"
 #include "cooc.h"
 #include "spgemm.h"
 #include "sptrans.h"

@@ -1012,14 +1012,15 @@ int launch_prefetch(aae_model* m, bool wait_head = true, bool early = false) {
 // ---- VAE (reference vae.py:47-266) -----------------------------------------------------------
 // forward: eh1 (the gather's act(fc1 x)) -> [mu | logvar] = [fc21; fc22] eh1 -> z = mu + eps * exp(logvar/2)
 // -> (constant condition block) -> dh2 = act(fc3 z): the input of the vocabulary-wide output layer fc4
-int chain_vae_forward(aae_model* m, const float* cond_dev, const float* eps_dev, int rows, hipStream_t s) {
+// (grow0: the generator row of row 0 - 0 for the step and for predict; a chunked loss evaluation names its chunk's first row)
+int chain_vae_forward(aae_model* m, const float* cond_dev, const float* eps_dev, int rows, hipStream_t s, int grow0 = 0) {
     const int h = m->h, c = m->c, cp = m->cp;
     ChainBuilder cb(m, rows);
     ChainOp& l = cb.add(cop_load(m->eh1.p, m->ldh, 0, h)); l.one_col = h;
     ChainOp& ml = cb.add(cop_fwd(m, P_W3, 0, 1, h + 1, 2 * c, CEPI_NONE, s));
     cop_out(ml, m->mulv.p, (int)m->mulv.ld);
     ChainOp& rp = cb.add(cop(COP_REPARAM, 1, 2, c));
-    rp.W = eps_dev; rp.ldw = c; rp.aux = 12; rp.aux_ptr = m->veps.p; rp.aux_ld = (int)m->veps.ld;
+    rp.W = eps_dev; rp.ldw = c; rp.aux = 12; rp.aux_ptr = m->veps.p; rp.aux_ld = (int)m->veps.ld; rp.grow0 = grow0;
     if (wide_dec_in(m)) {
         // the condition's first columns behind z (208 columns in all) -> zc; the later parts pass through slot 4
         ChainOp& ca = cb.add(cop_load(cond_dev, m->cfg.cond_inc, 2, kCWide - c)); ca.dst_col0 = c;

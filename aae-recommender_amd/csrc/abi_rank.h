@@ -15,12 +15,16 @@
 // Full ranking (rank_full.h; aae_predict_ranks / aae_decode_ranks): no candidate lists; instead
 //   tgt_i, tgt_v, tcount [rows][kFullSlots]   the held-out items of this round, their logits, the cells ranked before them
 // Launches: gather, chain, known-item mask, then per round of 8 held-out items a row: setup, rank (pick), rank (count), finish.
+// Held-out loss (loss_eval.h; aae_predict_loss / aae_decode_loss / aae_vae_*): no lists, no target slots; instead
+//   lpart [rows][wgs] doubles, csum [rows][kLossChunksMax] doubles, (VAE) mulv [rows][2 n_code]
+// Launches: gather, chain, TARGET mask, rank (loss), loss_targets, loss_finish, (VAE, predict form) vae_kl_rows.
 // One host path for both kinds of handle and both forms of a call (the drivers model_topk / model_ranks, abi_predict.h):
 //   RankInput + rank_cut    the rows of a call - batch, cond, eps, zc, generator row - and a span of them: the only place that
 //                           knows their strides
 //   rank_ws, rank_cap       the workspace's one layout (a VAE handle's weight copies in front of the plan) and its row limits
 //   rank_hidden             the hidden half: the program builder of this handle and form -> p.dh2
 //   rank_from_dh2 / rank_full_from_dh2      p.dh2 -> lists / ranks
+//   loss_from_dh2                           p.dh2 -> the rows' BCE sums against a target CSR (loss_eval.h; model_loss)
 //   rank_check_call         the argument check of the eight entry points and the four *_max_rows
 #pragma once
 
@@ -33,8 +37,12 @@ struct RankPlan {
     float *a1, *eh1, *dh2, *rscale, *cand_v, *mm; int* cand_i; unsigned* known;
     int cap; float* tau; int* count; unsigned long long* list;      // k > 32 (rank_long.h)
     int* tgt_i; float* tgt_v; int* tcount;                          // full ranking (rank_full.h)
+    double *lpart, *csum; float* mulv;                              // held-out loss (loss_eval.h); mulv: a VAE handle's [mu | logvar]
     size_t floats;
 };
+
+// what a plan lays out behind the hidden half and the mask: candidate lists, the full ranking's slots, the loss's sums
+enum { kPlanLists = 0, kPlanFull = 1, kPlanLoss = 2 };
 
 inline bool rank_long(int k) { return k > 32; }
 inline int rank_collect_cap(const aae_model* m) { return m->opt.rank_collect_cap > 0 ? m->opt.rank_collect_cap : kLongCap; }
@@ -42,7 +50,7 @@ inline int rank_collect_cap(const aae_model* m) { return m->opt.rank_collect_cap
 inline int rank_K(int k) { return k <= 10 ? 10 : k <= 20 ? 20 : 32; }
 
 // lays the workspace out for `rows` rows (base == NULL: measures only)
-RankPlan rank_plan(const aae_model* m, int rows, int k, float* base, bool full = false) {
+RankPlan rank_plan(const aae_model* m, int rows, int k, float* base, int layout = kPlanLists) {
     RankPlan p; memset(&p, 0, sizeof(p));
     p.rows = rows; p.K = rank_K(k);
     const int ntiles = (m->N + kTI - 1) / kTI;
@@ -55,7 +63,14 @@ RankPlan rank_plan(const aae_model* m, int rows, int k, float* base, bool full =
     p.a1 = take((size_t)rows * m->ldh); p.eh1 = take((size_t)rows * m->ldh); p.dh2 = take((size_t)rows * m->ldh);
     p.rscale = take(rows);
     p.known = reinterpret_cast<unsigned*>(take((size_t)rows * p.kw));
-    if (full) {     // (no lists: the pick / count epilogues leave no candidates)
+    if (layout == kPlanLoss) {     // (no lists, no slots: doubles - every offset is a multiple of 64 floats)
+        p.lpart = reinterpret_cast<double*>(take((size_t)rows * p.wgs * 2));
+        p.csum = reinterpret_cast<double*>(take((size_t)rows * kLossChunksMax * 2));
+        if (m->vae) p.mulv = take((size_t)rows * 2 * m->c);
+        p.floats = off;
+        return p;
+    }
+    if (layout == kPlanFull) {     // (no lists: the pick / count epilogues leave no candidates)
         p.tgt_i = reinterpret_cast<int*>(take((size_t)rows * kFullSlots));
         p.tgt_v = take((size_t)rows * kFullSlots);
         p.tcount = reinterpret_cast<int*>(take((size_t)rows * kFullSlots));
@@ -102,21 +117,22 @@ VaeRankCopies vae_rank_copies(const aae_model* m, float* base) {
 
 // a fused call's workspace, the only layout of it: the head, the plan behind it
 struct RankWs { VaeRankCopies c; RankPlan p; };
-RankWs rank_ws(const aae_model* m, int rows, int k, bool full) {
+RankWs rank_ws(const aae_model* m, int rows, int k, int layout) {
     RankWs w;
     w.c = vae_rank_copies(m, m->G.p);
-    w.p = rank_plan(m, rows, k, m->G.p + w.c.floats, full);
+    w.p = rank_plan(m, rows, k, m->G.p + w.c.floats, layout);
     return w;
 }
 
-// most rows one fused call (full: one fused full-ranking call, k = 32) can rank in `have` floats behind the head
-int rank_rows_fit(const aae_model* m, int k, bool full, size_t have) {
+// most rows one fused call (layout: kPlanFull - one fused full-ranking call - and kPlanLoss - one fused loss call - ask with
+// k = 32) can take in `have` floats behind the head
+int rank_rows_fit(const aae_model* m, int k, int layout, size_t have) {
     if (k < 1 || k > kLongKMax) return 0;
     const int ntiles = (m->N + kTI - 1) / kTI;
     int lo = 0, hi = kRankMaxRows;          // (the plan's size is monotone in rows up to rounding: bisect)
     while (lo < hi) {
         const int mid = (lo + hi + 1) / 2;
-        const RankPlan p = rank_plan(m, mid, k, nullptr, full);
+        const RankPlan p = rank_plan(m, mid, k, nullptr, layout);
         // (k > 32: the floor needs k candidates per row - fewer workgroups per row block than that and every row would overflow)
         const bool floor_ok = !rank_long(k) || p.wgs * 32 >= k || p.wgs == ntiles;
         if (p.floats <= have && floor_ok) lo = mid; else hi = mid - 1;
@@ -125,15 +141,16 @@ int rank_rows_fit(const aae_model* m, int k, bool full, size_t have) {
 }
 // vae: the aae_vae_* family asks - a VAE handle ranks fused through those calls alone, any other handle through the aae_* ones
 // (0: the fused path does not apply)
-int rank_cap(const aae_model* m, int k, bool full, bool vae) {
+int rank_cap(const aae_model* m, int k, int layout, bool vae) {
     const size_t have = rank_ws_floats(m), head = vae_rank_copies(m, nullptr).floats;
-    return (vae ? m->vae_rank_ok : m->rank_ok) && have > head ? rank_rows_fit(m, k, full, have - head) : 0;
+    return (vae ? m->vae_rank_ok : m->rank_ok) && have > head ? rank_rows_fit(m, k, layout, have - head) : 0;
 }
-int rank_rows_cap(const aae_model* m, int k, bool vae) { return rank_cap(m, k, false, vae); }
-int rank_full_rows_cap(const aae_model* m, bool vae) { return rank_cap(m, 32, true, vae); }
+int rank_rows_cap(const aae_model* m, int k, bool vae) { return rank_cap(m, k, kPlanLists, vae); }
+int rank_full_rows_cap(const aae_model* m, bool vae) { return rank_cap(m, 32, kPlanFull, vae); }
+int rank_loss_rows_cap(const aae_model* m, bool vae) { return rank_cap(m, 32, kPlanLoss, vae); }
 
 // one launch of a rank kernel: the lists' kernel of this (NB, K) (kernel_pick.h), or the K = 32 kernel's front end with
-// another epilogue: collect (rank_long.h), pick / count (rank_full.h)
+// another epilogue: collect (rank_long.h), pick / count (rank_full.h), loss (loss_eval.h)
 int launch_rank(const RankArgs& a, int nb, int K, int epi, int grid, hipStream_t s) {
     const bool win = x3_big_span(a.N, a.ldv);      // (dec.lin3 beyond 2^31 bytes: the moving-window instantiations, dec_fused.h)
     const RankPick r = epi == kRankLists ? pick_rank_lists(nb, K, win) : pick_rank_epilogue(nb, epi, win);
@@ -153,7 +170,7 @@ int rank_mask_and_args(aae_model* m, const RankPlan& p, const BatchView& bv, int
     a.dh2 = p.dh2; a.ldh = m->ldh; a.V3a = m->P[P_V3].p; a.ldv = m->ldh; a.N = m->N; a.B = p.rows;
     a.nblk = p.nblk; a.Bb = p.bb; a.known = exclude_known ? p.known : nullptr; a.kw = p.kw;
     a.cand_v = p.cand_v; a.cand_i = p.cand_i; a.mm = p.mm; a.one_term = m->bf16 ? 1 : 0;
-    a.tgt_i = p.tgt_i; a.tgt_v = p.tgt_v; a.tcount = p.tcount;
+    a.tgt_i = p.tgt_i; a.tgt_v = p.tgt_v; a.tcount = p.tcount; a.lpart = p.lpart;
     return AAE_OK;
 }
 
@@ -205,6 +222,41 @@ int rank_full_from_dh2(aae_model* m, const RankPlan& p, const BatchView& bv, con
                            reinterpret_cast<int*>(ranks_out));
         LAUNCHCHK("rank_full_finish");
     }
+    return AAE_OK;
+}
+
+// the chunks loss_targets_kernel cuts the target rows into: kLossChunk entries each, by the longest row (0: not given)
+int loss_chunks(int max_row_nnz) {
+    return max_row_nnz > 0 ? std::max(1, std::min(kLossChunksMax, (max_row_nnz + kLossChunk - 1) / kLossChunk)) : kLossChunksMax;
+}
+
+// dh2 (workspace) of `rows` rows -> row_bce [rows]: the sum over the items of the row's cell losses against its targets `tv`
+// (loss_eval.h).  The mask of the plan holds the TARGET entries: the loss epilogue skips them, loss_targets charges them.
+int loss_from_dh2(aae_model* m, const RankPlan& p, const BatchView& tv, int max_row_nnz, double* row_bce_out, hipStream_t s) {
+    RankArgs a;
+    TRY(rank_mask_and_args(m, p, tv, 1, a, s));
+    const int chunks = loss_chunks(max_row_nnz);
+    ProfScope ps(m, AAE_K_RANK, s);
+    TRY(launch_rank(a, m->fused_nb, 1, kRankLoss, p.wgs * p.nblk, s));
+    hipLaunchKernelGGL(pick_loss_targets(), dim3(p.rows, chunks), dim3(256), 0, s, tv, (const float*)p.dh2, m->ldh,
+                       (const float*)m->P[P_V3].p, m->ldh, m->h + 1, m->N, m->bf16 ? 1 : 0, p.csum);
+    LAUNCHCHK("loss_targets");
+    hipLaunchKernelGGL(pick_loss_finish(), dim3((p.rows + 255) / 256), dim3(256), 0, s, (const double*)p.lpart, p.wgs,
+                       (const double*)p.csum, chunks, p.rows, row_bce_out);
+    LAUNCHCHK("loss_finish");
+    return AAE_OK;
+}
+// [mu | logvar] of `rows` rows -> row_kl [rows]
+int loss_kl_rows(const float* mulv, int ld, int nc, int rows, double* row_kl_out, hipStream_t s) {
+    hipLaunchKernelGGL(pick_vae_kl_rows(), dim3((rows + 3) / 4), dim3(256), 0, s, mulv, ld, nc, rows, row_kl_out);
+    LAUNCHCHK("vae_kl_rows");
+    return AAE_OK;
+}
+// the model's dense form: the LOGITS of the m->rows rows of the call in the [max_batch][n_items] scratch -> row_bce
+int loss_rows_dense(aae_model* m, const BatchView& tv, double* row_bce_out, hipStream_t s) {
+    ProfScope ps(m, AAE_K_RANK, s);
+    hipLaunchKernelGGL(pick_loss_rows_dense(), dim3(m->rows), dim3(256), 0, s, m->G.p, m->ldn, m->N, tv, row_bce_out);
+    LAUNCHCHK("loss_rows_dense");
     return AAE_OK;
 }
 
@@ -442,15 +494,18 @@ void vae_rank_dec_hidden(aae_model* m, ChainBuilder& cb, const VaeRankCopies& c,
 
 // rows of `batch` -> dh2 [rows][ldh].  eps_dev: row 0 of the batch (NULL: the counter generator, rows counted from grow0);
 // a1 / eh1 / rscale: [rows] scratch of the first layer
+// mulv: where a loss call keeps [mu | logvar] [rows][2 n_code] for its KL term (NULL: nobody reads them)
 int vae_rank_predict_hidden(aae_model* m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, int grow0,
-                            const VaeRankCopies& c, float* a1, float* eh1, float* rscale, float* dh2, hipStream_t s) {
+                            const VaeRankCopies& c, float* a1, float* eh1, float* rscale, float* dh2, hipStream_t s,
+                            float* mulv = nullptr) {
     const int rows = batch->n_rows, h = m->h, nc = m->c, cp = m->cp;
     TRY(rank_first_layer(m, batch, a1, eh1, rscale, s));
     TRY(vae_rank_derive(m, c, s));
     ChainBuilder cb(m, rows);
     cb.vae4 = true;
     ChainOp& l = cb.add(cop_load(eh1, m->ldh, 0, h)); l.one_col = h;
-    cb.add(vae_cop_fwd(m, P_W3, c.w3, 0, 1, h + 1, 2 * nc, CEPI_NONE));
+    ChainOp& ml = cb.add(vae_cop_fwd(m, P_W3, c.w3, 0, 1, h + 1, 2 * nc, CEPI_NONE));
+    if (mulv) cop_out(ml, mulv, 2 * nc);
     ChainOp& rp = cb.add(cop(COP_REPARAM, 1, 2, nc));
     rp.W = eps_dev; rp.ldw = nc; rp.aux = 12; rp.grow0 = grow0;        // (stream id 12: chain_vae_forward's draws)
     if (wide_dec_in(m)) {
@@ -483,7 +538,7 @@ int rank_hidden(aae_model* m, const RankInput& in, const RankWs& w, hipStream_t 
     const int rows = in.batch.n_rows;
     if (!in.vae) return in.zc ? rank_decode_hidden(m, in.zc, in.zc_ld, rows, p, s) : rank_predict_hidden(m, &in.batch, in.cond, p, s);
     if (in.zc) return vae_rank_decode_hidden(m, in.zc, in.zc_ld, rows, w.c, p.dh2, s);
-    return vae_rank_predict_hidden(m, &in.batch, in.cond, in.eps, in.grow0, w.c, p.a1, p.eh1, p.rscale, p.dh2, s);
+    return vae_rank_predict_hidden(m, &in.batch, in.cond, in.eps, in.grow0, w.c, p.a1, p.eh1, p.rscale, p.dh2, s, p.mulv);
 }
 
 // A span of a fused k > 32 aae_vae_* call that holds a row whose collect list overflowed: the rows of `sub` (<= max_batch)

@@ -537,9 +537,9 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                 if (lrow < nrows && col < n) {
                     float eps;
                     if (op.W) eps = op.W[(size_t)(r0 + lrow) * op.ldw + col];
-                    else {      // the counter generator, stream id = op.aux, the row of the call (every program of this kernel starts at the call's row 0)
+                    else {      // the counter generator, stream id = op.aux, the row of the call + op.grow0 (0 but for a chunk of a loss evaluation)
                         const uint64_t k = key ^ ((uint64_t)(uint32_t)op.aux * 0xA0761D6478BD642Full);
-                        eps = draw_gauss(k, (uint32_t)(r0 + lrow), col);
+                        eps = draw_gauss(k, (uint32_t)(r0 + lrow + op.grow0), col);
                     }
                     op.aux_ptr[(size_t)(r0 + lrow) * op.aux_ld + col] = eps;
                     const float mu = src[lrow * kCL + col], lv = src[lrow * kCL + n + col];

@@ -92,12 +92,12 @@ inline RankPick pick_rank_lists(int nb, int K, bool win) {
             if constexpr (rank_v2_nb(NB_, K_)) return rank_x3v2_kernel<NB_, K_, WIN()>; else return rank_x3_kernel<NB_, K_, WIN(), kRankLists>; }, win); }); });
     return {kernel, v2 ? rank_x3v2_lds_bytes(nb) : rank_x3_lds_bytes(nb), v2 ? "rank_x3v2" : "rank_x3"};
 }
-// K = 1 is the front end of the epilogues that keep no lists - collect (rank_long.h), pick and count (rank_full.h): they exist
-// with it alone, and it not without one of them
+// K = 1 is the front end of the epilogues that keep no lists - collect (rank_long.h), pick and count (rank_full.h), loss
+// (loss_eval.h): they exist with it alone, and it not without one of them
 inline RankPick pick_rank_epilogue(int nb, int epi, bool win) {
-    const RankKernel kernel = pick_nb<RankKernel>(nb, [&](auto NB) { return pick_of<RankKernel, kRankCollect, kRankPick, kRankCount>(epi, [&](auto EPI) {
+    const RankKernel kernel = pick_nb<RankKernel>(nb, [&](auto NB) { return pick_of<RankKernel, kRankCollect, kRankPick, kRankCount, kRankLoss>(epi, [&](auto EPI) {
         return pick_flags<RankKernel>([](auto WIN) -> RankKernel { return rank_x3_kernel<NB_, 1, WIN(), decltype(EPI)::value>; }, win); }); });
-    return {kernel, rank_x3_lds_bytes(nb), epi == kRankCollect ? "rank_x3 (collect)" : epi == kRankPick ? "rank_x3 (pick)" : "rank_x3 (count)"};
+    return {kernel, rank_x3_lds_bytes(nb), epi == kRankCollect ? "rank_x3 (collect)" : epi == kRankPick ? "rank_x3 (pick)" : epi == kRankCount ? "rank_x3 (count)" : "rank_x3 (loss)"};
 }
 inline MergeKernel pick_rank_merge(int K) {
     return pick_k<MergeKernel>(K, [](auto KK) -> MergeKernel { return rank_merge_kernel<KK()>; });
@@ -105,7 +105,7 @@ inline MergeKernel pick_rank_merge(int K) {
 template <class F> void each_rank(F&& f) {
     for (int nb : kPickNb) for (int win = 0; win < 2; ++win) {
         for (int K : kPickK) f(pick_rank_lists(nb, K, win));
-        for (int epi : {kRankCollect, kRankPick, kRankCount}) f(pick_rank_epilogue(nb, epi, win));
+        for (int epi : {kRankCollect, kRankPick, kRankCount, kRankLoss}) f(pick_rank_epilogue(nb, epi, win));
     }
 }
 
@@ -195,6 +195,13 @@ inline auto pick_rand_ranks() { return rand_ranks_kernel; }
 inline auto pick_metric_rows() { return metric_rows_kernel; }
 inline auto pick_metric_finish() { return metric_finish_kernel; }
 inline auto pick_ranks_from_lists() { return ranks_from_lists_kernel; }
+
+// ---- loss_eval.h: the held-out loss behind the loss epilogue of rank_x3_kernel (above), its dense form, the VAE's KL rows.
+// Static LDS: no limit to raise
+inline auto pick_loss_targets() { return loss_targets_kernel; }
+inline auto pick_loss_finish() { return loss_finish_kernel; }
+inline auto pick_loss_rows_dense() { return loss_rows_dense_kernel; }
+inline auto pick_vae_kl_rows() { return vae_kl_rows_kernel; }
 
 // ---- lowrank.h: the CSR x row-major-dense product - the projection of the ranking calls and aae_spmm_f32 alike
 using SpmmKernel = void (*)(LowRankView, BatchView, float*, long long);

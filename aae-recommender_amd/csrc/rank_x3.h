@@ -38,11 +38,20 @@ struct RankArgs {
     const int* tgt_i;                   // [B][kFullSlots] their item ids, -1: slot unused
     float* tgt_v;                       // [B][kFullSlots] their logits (PICK writes, COUNT reads); -inf: the item is a known one
     int* tcount;                        // [B][kFullSlots] cells that rank before the item (COUNT adds)
+    // the LOSS epilogue of rank_x3_kernel (loss_eval.h): `known` is the bitmap of the row's TARGET entries
+    double* lpart;                      // [B][wgs] the workgroup's sum of the row's zero-target cell losses, target cells skipped
 };
 
 // the epilogues of rank_x3_kernel
-constexpr int kRankLists = 0, kRankCollect = 1, kRankPick = 2, kRankCount = 3;
+constexpr int kRankLists = 0, kRankCollect = 1, kRankPick = 2, kRankCount = 3, kRankLoss = 4;
 constexpr int kFullSlots = 8;       // held-out items per row one PICK + COUNT pair of launches answers (rank_full.h)
+
+// The loss of one cell of the output layer, from its LOGIT - the one definition behind every held-out loss (loss_eval.h: the
+// loss epilogue below, loss_targets_kernel, loss_rows_dense_kernel): a cell without a target entry is the training step's
+// zero-target form (bce_elem_t0: softplus, 100 from kBceSatLogit on), a target entry the reference's form (bce_elem: + 1e-12,
+// the clamps at -100, the cut-off).  The gradients those functions also form are dead code here.
+__device__ __forceinline__ float loss_cell_t0(float l) { float g, loss; bce_elem_t0(l, 0.f, g, loss); return loss; }
+__device__ __forceinline__ float loss_cell_target(float l, float t) { float g, loss; bce_elem(l, t, 0.f, g, loss); return loss; }
 
 // One workgroup per row: the row's known items -> its bitmap (known != NULL), and the bias input of the output layer: column
 // h of the row's dh2 = 1, the padding columns behind it = 0 (the chain program stores the layer's h outputs only; the
@@ -59,7 +68,7 @@ __global__ __launch_bounds__(256) void known_mask_kernel(BatchView bv, unsigned*
     const int64_t lo = bv.indptr[dc], hi = bv.indptr[dc + 1];
     for (int64_t e = lo + tid; e < hi; e += 256) {
         const int i = bv.indices[e];
-        atomicOr(&k[i >> 5], 1u << (i & 31));
+        if ((unsigned)(i >> 5) < (unsigned)kw) atomicOr(&k[i >> 5], 1u << (i & 31));
     }
 }
 
@@ -83,9 +92,12 @@ inline size_t rank_x3_lds_bytes(int NB) {          // (128-row blocks as well: i
 // EPI = kRankCollect (rank_long.h): the same products with another epilogue - no lists, no extremes: every rankable cell at or
 // above the row's floor goes to the row's list in the workspace.  kRankPick / kRankCount (rank_full.h): the cells that ARE the
 // row's held-out items store their logit; every cell is compared with the row's held-out logits and counted where it ranks first.
+// kRankLoss (loss_eval.h): no lists either - the zero-target loss of every cell whose bit in `known` (here: the row's TARGET
+// entries) is clear, four cells in fp32, then onto the thread's fp64 sum; the row's 8 threads add up by lane shuffles and one
+// plain store writes lpart[row][workgroup].  A target cell adds nothing: loss_targets_kernel charges it whole.
 template <int NB, int K, bool WIN = false, int EPI = kRankLists>      // WIN: dec.lin3 beyond 2^31 bytes (dec_fused.h X3WindowT)
 __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
-    constexpr bool COLLECT = EPI == kRankCollect, FULL = EPI == kRankPick || EPI == kRankCount;
+    constexpr bool COLLECT = EPI == kRankCollect, FULL = EPI == kRankPick || EPI == kRankCount, LOSS = EPI == kRankLoss;
     const bool one = a.one_term != 0;
     constexpr int KC1 = (NB + 1) / 2, NKS = (KC1 + 1) / 2;
     constexpr int NKR = NKS > kXRegSteps ? kXRegSteps : NKS, NKL = NKS - NKR;
@@ -186,17 +198,21 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
         f_l[s] = EPI == kRankCount ? a.tgt_v[(size_t)crow * TS + s] : INFINITY;
         f_c[s] = 0;
     }
+    double l_sum = 0.0;                         // LOSS: this thread's cells over the workgroup's tiles
 
     // the epilogue of one finished tile: the thread's four cells
     auto epilogue = [&](int i0, unsigned kword) {
         if (!erow || (a.dbg & 2)) return;
         const float4 lA = *reinterpret_cast<const float4*>(raw + eb * kRRS + 4 * eq);
         const float4 lB = *reinterpret_cast<const float4*>(raw + kGR * kRRS + eb * kRRS + 4 * eq);
+        float l4 = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int n = 4 * eq + j, item = i0 + n;
             const float v = (&lA.x)[j] + (&lB.x)[j];       // the LOGIT: sigmoid is monotone - applied to the winners only (merge)
-            if constexpr (COLLECT) {
+            if constexpr (LOSS) {
+                if (item < N && !((kword >> n) & 1u)) l4 += loss_cell_t0(v);
+            } else if constexpr (COLLECT) {
                 if (item < N && !((kword >> n) & 1u) && v >= c_tau) {
                     const int pos = atomicAdd(c_count, 1);
                     if (pos < a.cap) {
@@ -228,6 +244,7 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
                 }
             }
         }
+        if constexpr (LOSS) l_sum += (double)l4;
     };
     __syncthreads();
 
@@ -289,6 +306,13 @@ __global__ __launch_bounds__(kNT) void rank_x3_kernel(RankArgs a) {
     lds_barrier();
     if (prev_i0 >= 0) epilogue(prev_i0, kw_prev);
     if constexpr (COLLECT || EPI == kRankPick) return;
+    if constexpr (LOSS) {
+        // the 8 threads of a row add up in a fixed order (lanes 8 eb .. 8 eb + 7 of one wave); one plain store per (row, workgroup)
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) l_sum += __shfl_xor(l_sum, o, 64);
+        if (erow && eq == 0) a.lpart[(size_t)(erow0 + eb) * wgs + wgi] = l_sum;
+        return;
+    }
     if constexpr (EPI == kRankCount) {
         // the 8 threads of a row add their counts up; one integer atomic per (row, slot, workgroup): the sum does not depend on order
 #pragma unroll

@@ -506,6 +506,37 @@ int aae_vae_decode_ranks(aae_handle h, const float* zc_dev, int64_t zc_ld, const
                          int32_t exclude_known, int32_t* ranks_out_dev, void* stream);
 int aae_vae_rank_max_rows(aae_handle h, int32_t k, int32_t* rows_out);
 int aae_vae_rank_full_max_rows(aae_handle h, int32_t* rows_out);
+/* The loss of the model on rows it was not trained on (csrc/loss_eval.h; reference aae.py:176-177, 693-695 - the BCE of
+ * F.binary_cross_entropy(x_hat + 1e-12, target + 1e-12) - and vae.py:243-264, loss_function on every test batch), eval mode: no
+ * dropout, the weights as they stand, nothing of the handle changes.  Per row of the call
+ *   row_bce_dev[i] (double) = the SUM over the n_items cells of row i of the cell loss against `targets`
+ * - divide by rows * n_items for the mean the training step reports in aae_read_losses()[0].  `targets` is a batch with the row
+ * addressing of `batch` (row i of the one belongs to row i of the other), values in [0, 1], an item at most once per row;
+ * NULL = `batch` itself, the reference's choice.  A cell without a target entry is charged softplus(logit) (100 from
+ * logit >= 24 ln 2 on, the reference's fp32 saturation), a target entry the reference's form from one logit.
+ * Where the fused ranking form applies (aae_loss_max_rows rows per call, far more than max_batch) the [rows, n_items] matrix
+ * never exists: one pass over dec.lin3 with the loss epilogue of the rank kernel, the target cells skipped there and charged
+ * by a dot product per entry.  Otherwise (<= max_batch rows) the LOGITS go to the [max_batch][n_items] scratch and one
+ * workgroup per row sums the same two cell functions.  Sums are fp64 in a fixed order: nothing varies from run to run; two
+ * ways of chunking the same rows agree to n_items * 2^-53 relative (calls on one side of 224 rows, as aae_predict_ranks).
+ * Nothing synchronises.
+ *   aae_decode_loss       the same behind a decoder input the caller built (as aae_decode_topk).
+ *   aae_vae_predict_loss  a VAE handle (any other: AAE_ESTATE): eps_dev as in aae_vae_predict_topk; row0 = the counter
+ *                         generator's row of the call's first row (the ranking calls count from 0 in every call: pass the
+ *                         chunk's first row here and a chunked evaluation draws what one call over all rows draws);
+ *                         row_kl_dev[i] (double) = -0.5 sum_c (1 + logvar - mu^2 - exp(logvar)) of row i.
+ *   aae_vae_decode_loss   the VAE's decode(zc): no KL term (the caller has the code).
+ *   aae_loss_max_rows / aae_vae_loss_max_rows   rows ONE call may take (>= max_batch). */
+int aae_predict_loss(aae_handle h, const aae_batch* batch, const float* cond_dev, const aae_batch* targets, double* row_bce_dev,
+                     void* stream);
+int aae_decode_loss(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* targets,
+                    double* row_bce_dev, void* stream);
+int aae_vae_predict_loss(aae_handle h, const aae_batch* batch, const float* cond_dev, const float* eps_dev, int64_t row0,
+                         const aae_batch* targets, double* row_bce_dev, double* row_kl_dev, void* stream);
+int aae_vae_decode_loss(aae_handle h, const float* zc_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* targets,
+                        double* row_bce_dev, void* stream);
+int aae_loss_max_rows(aae_handle h, int32_t* rows_out);
+int aae_vae_loss_max_rows(aae_handle h, int32_t* rows_out);
 /* The item co-occurrence baseline (reference baselines.py:22-43, Countbased: predict = X @ C, C = X^T X of the training set;
  * csrc/cooc.h).  Handle-free like aae_cat_encode / aae_csr_embed: every buffer is the caller's, the launches go to `stream`,
  * nothing synchronises.  `cooc` is C in CSR form with INTEGER values: indptr int64 [n_rows + 1], indices int32 with the columns
