@@ -114,6 +114,7 @@ __device__ __forceinline__ void chain_barrier() { asm volatile("s_waitcnt lgkmcn
 // this kernel's scalar-register pressure it re-issued ~8 dependent s_load + s_waitcnt per ELEMENT
 // (~0.5 us per 16x16 block).  The empty asm makes each value opaque, i.e. it has to stay in a register.
 template <class T> __device__ __forceinline__ T chain_pin(T v) { asm volatile("" : "+s"(v)); return v; }
+template <class T> __device__ __forceinline__ T chain_pin_v(T v) { asm volatile("" : "+v"(v)); return v; }     // (a per-lane value)
 
 struct EpiCtx {
     int epi, act, den, drng, split, width, goa, gob;
@@ -156,17 +157,17 @@ __device__ __forceinline__ int chain_keep(const EpiCtx& c, int row, int col) {  
     return m[(size_t)r * c.width + col] != 0;
 }
 
+}  // namespace aae
+#include "chain_ops.h"     // the non-linear ops' arithmetic, shared with chain4.h and chain16x3.h
+namespace aae {
+
 template <bool NM = false>      // (NM: with the non-monotone activations' derivative, device_common.h)
 __device__ __forceinline__ float chain_epi(const EpiCtx& c, int grow, int lrow, int col, float v) {
     if (c.epi == CEPI_DROPACT) {
         if (c.den) v = chain_keep(c, grow, col) ? v * c.mk + c.ak : c.ad;
         return act_fwd<NM>(c.act, v);
     }
-    if (c.epi == CEPI_ACTBWD) {
-        v *= act_grad_from_y<NM>(c.act, c.y[lrow * kCL + col]);
-        if (c.den) v *= chain_keep(c, grow, col) ? c.mk : 0.f;
-        return v;
-    }
+    if (c.epi == CEPI_ACTBWD) return chain_actbwd<NM>(c, grow, col, v, c.y[lrow * kCL + col]);
     if (c.epi == CEPI_SIGMOID) return sigmoidf_(v);
     return v;
 }
@@ -385,6 +386,10 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
         float* dst = slots + op.dst * kCR * kCL;
         const float* src = slots + op.src * kCR * kCL;
         const int kind = op.kind;
+        // The non-linear ops' copy of the thread index, opaque: the rows, columns and addresses they derive from it are computed
+        // inside the op.  Derived from `tid`, hipcc hoists every such expression out of the op loop and holds it across the linear
+        // ops' weight registers - 9 to 16 spilled registers per member of this kernel.
+        const int otid = chain_pin_v(tid), olane = otid & 63;
 
         if (kind == COP_LINEAR || kind == COP_LINEAR_DX) {
             // output blocks of 16 columns: wave w takes blocks w, w+8 (N <= 208 -> <= 13 blocks)
@@ -438,10 +443,10 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
             chain_load_block(op.W, op.ldw, op.out_row0 + r0, nrows, op.N, dst, op.dst_col0, op.scale);
         } else if (kind == COP_SLABSUM) {
             // sum of op.aux (<= 16) partial slabs: every slab load of a thread is in flight at once
-            const int lrow = tid >> kRS, rowc = min(lrow, max(nrows, 1) - 1), nf4 = (op.N + 3) >> 2;
+            const int lrow = otid >> kRS, rowc = min(lrow, max(nrows, 1) - 1), nf4 = (op.N + 3) >> 2;
 #pragma unroll
             for (int j = 0; j < kJ; ++j) {
-                const int c4 = (tid & (kTPR - 1)) + kTPR * j, c4c = min(c4, nf4 - 1);
+                const int c4 = (otid & (kTPR - 1)) + kTPR * j, c4c = min(c4, nf4 - 1);
                 float4 v[16];
 #pragma unroll
                 for (int z = 0; z < 16; ++z)
@@ -457,15 +462,11 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                     const EpiCtx sec = chain_epi_ctx(CEPI_ACTBWD, op, P, key, slots);
                     const float4 y4 = *reinterpret_cast<const float4*>(op.aux_ptr + (size_t)(r0 + rowc) * op.aux_ld + c4c * 4);
                     const int gr = r0 + lrow;
-                    // (the mask / generator lookup only for cells of the block that exist: an injected mask tensor
-                    // ends with the batch's last row)
-                    const bool den = sec.den && lrow < nrows;
-                    const float k0 = (den && c4 * 4 + 0 < op.N) ? (chain_keep(sec, gr, c4 * 4 + 0) ? sec.mk : 0.f) : 1.f;
-                    const float k1 = (den && c4 * 4 + 1 < op.N) ? (chain_keep(sec, gr, c4 * 4 + 1) ? sec.mk : 0.f) : 1.f;
-                    const float k2 = (den && c4 * 4 + 2 < op.N) ? (chain_keep(sec, gr, c4 * 4 + 2) ? sec.mk : 0.f) : 1.f;
-                    const float k3 = (den && c4 * 4 + 3 < op.N) ? (chain_keep(sec, gr, c4 * 4 + 3) ? sec.mk : 0.f) : 1.f;
-                    acc4.x *= act_grad_from_y<NM>(sec.act, y4.x) * k0; acc4.y *= act_grad_from_y<NM>(sec.act, y4.y) * k1;
-                    acc4.z *= act_grad_from_y<NM>(sec.act, y4.z) * k2; acc4.w *= act_grad_from_y<NM>(sec.act, y4.w) * k3;
+                    const bool in = lrow < nrows;
+                    acc4.x *= chain_actbwd_factor<NM>(sec, gr, c4 * 4 + 0, in && c4 * 4 + 0 < op.N, y4.x);
+                    acc4.y *= chain_actbwd_factor<NM>(sec, gr, c4 * 4 + 1, in && c4 * 4 + 1 < op.N, y4.y);
+                    acc4.z *= chain_actbwd_factor<NM>(sec, gr, c4 * 4 + 2, in && c4 * 4 + 2 < op.N, y4.z);
+                    acc4.w *= chain_actbwd_factor<NM>(sec, gr, c4 * 4 + 3, in && c4 * 4 + 3 < op.N, y4.w);
                 }
                 const bool ok = lrow < nrows;
                 if (!ok || c4 * 4 + 0 >= op.N) acc4.x = 0.f;
@@ -477,62 +478,54 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
         } else if (kind == COP_DROPACT || kind == COP_ACTBWD) {
             const EpiCtx ec = chain_epi_ctx(kind == COP_DROPACT ? CEPI_DROPACT : CEPI_ACTBWD, op, P, key, slots);
             const int epiN = chain_pin(op.N);
-            const int lrow = tid >> kRS;
-            for (int col = tid & (kTPR - 1); col < kCL; col += kTPR)
+            const int lrow = otid >> kRS;
+            for (int col = otid & (kTPR - 1); col < kCL; col += kTPR)
                 dst[lrow * kCL + col] = (lrow < nrows && col < epiN)
                     ? chain_epi<NM>(ec, r0 + lrow, lrow, col, src[lrow * kCL + col]) : 0.f;
         } else if (kind == COP_FINAL_FWD) {
-            // one wave per pair of rows; softmax / sigmoid / identity over N columns, in place on dst
+            // one wave per row; softmax / sigmoid / identity over N columns, in place on dst
+            static_assert(kCL <= 256, "final_act_*4: four cells of a lane cover a slot row");
+            const int n = op.N, fkind = op.aux;
             for (int lrow = wave; lrow < kCR; lrow += kCW) {
                 float* zr = dst + lrow * kCL;
-                if (op.aux == 1) {
-                    float mx = -INFINITY;
-                    for (int j = lane; j < op.N; j += 64) mx = fmaxf(mx, zr[j]);
-                    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-                    float sum = 0.f;
-                    for (int j = lane; j < op.N; j += 64) sum += expf(zr[j] - mx);
-                    sum = wave_sum(sum);
-                    for (int j = lane; j < op.N; j += 64) zr[j] = expf(zr[j] - mx) / sum;
-                } else if (op.aux == 2) {
-                    for (int j = lane; j < op.N; j += 64) zr[j] = sigmoidf_(zr[j]);
-                }
+                float z[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) z[j] = olane + 64 * j < n ? zr[olane + 64 * j] : 0.f;
+                final_act_fwd4(z, n, fkind, olane);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (fkind && olane + 64 * j < n) zr[olane + 64 * j] = z[j];
             }
         } else if (kind == COP_FINAL_BWD) {
             const float* zs = slots + op.yslot * kCR * kCL;
+            const int n = op.N, fkind = op.aux;
             for (int lrow = wave; lrow < kCR; lrow += kCW) {
-                const float* zr = zs + lrow * kCL;
-                const float* gr = src + lrow * kCL;
-                float* o = dst + lrow * kCL;
-                if (op.aux == 1) {
-                    float dot = 0.f;
-                    for (int j = lane; j < op.N; j += 64) dot += gr[j] * zr[j];
-                    dot = wave_sum(dot);
-                    for (int j = lane; j < op.N; j += 64) o[j] = zr[j] * (gr[j] - dot);
-                } else if (op.aux == 2) {
-                    for (int j = lane; j < op.N; j += 64) o[j] = gr[j] * zr[j] * (1.f - zr[j]);
-                } else {
-                    for (int j = lane; j < op.N; j += 64) o[j] = gr[j];
+                float g[4], z[4], o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool in = olane + 64 * j < n;
+                    g[j] = in ? src[lrow * kCL + olane + 64 * j] : 0.f;
+                    z[j] = (in && fkind) ? zs[lrow * kCL + olane + 64 * j] : 0.f;
                 }
-                // a following forward-pattern layer (dX on a transposed weight copy) reads whole 16-column k-chunks
-                for (int j = op.N + lane; j < kCL; j += 64) o[j] = 0.f;
+                final_act_bwd4(g, z, n, fkind, olane, o);
+                // (zero beyond n: a following forward-pattern layer - dX on a transposed weight copy - reads whole 16-column k-chunks)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (olane + 64 * j < kCL) dst[lrow * kCL + olane + 64 * j] = olane + 64 * j < n ? o[j] : 0.f;
             }
         } else if (kind == COP_PRIOR) {
-            const int lrow = tid >> kRS, grow = r0 + lrow, n = op.N;
+            const int lrow = otid >> kRS, grow = r0 + lrow, n = op.N;
             const uint64_t k = key ^ (100ull * 0xA0761D6478BD642Full);
-            for (int col = tid & (kTPR - 1); col < kCL; col += kTPR) {
+            for (int col = otid & (kTPR - 1); col < kCL; col += kTPR) {
                 float v = 0.f;
                 if (lrow < nrows && col < n) {
                     if (grow >= op.row_split) v = op.W[(size_t)grow * op.ldw + col];
                     else if (op.aux_ptr) v = op.aux_ptr[(size_t)grow * op.aux_ld + col] * op.scale;
-                    else if (op.aux == 0) v = draw_gauss(k, (uint32_t)(grow + op.grow0), col) * op.scale;
-                    else if (op.aux == 1) v = draw_class(k, (uint32_t)(grow + op.grow0), n) == col ? op.scale : 0.f;   // categorical: one-hot of a uniform class per row
-                    // bernoulli: the reference's randint(0, 1) is always 0 (aae.py:86-88)
+                    else v = prior_cell(k, (uint32_t)(grow + op.grow0), col, n, op.aux, op.scale);
                 }
                 dst[lrow * kCL + col] = v;
             }
         } else if (kind == COP_REPARAM) {
-            const int lrow = tid >> kRS, n = op.N;
-            for (int col = tid & (kTPR - 1); col < kCL; col += kTPR) {
+            const int lrow = otid >> kRS, n = op.N;
+            for (int col = otid & (kTPR - 1); col < kCL; col += kTPR) {
                 float zv = 0.f;
                 if (lrow < nrows && col < n) {
                     float eps;
@@ -542,16 +535,15 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                         eps = draw_gauss(k, (uint32_t)(r0 + lrow + op.grow0), col);
                     }
                     op.aux_ptr[(size_t)(r0 + lrow) * op.aux_ld + col] = eps;
-                    const float mu = src[lrow * kCL + col], lv = src[lrow * kCL + n + col];
-                    zv = mu + eps * expf(0.5f * lv);
+                    zv = reparam_cell(src[lrow * kCL + col], src[lrow * kCL + n + col], eps);
                 }
                 dst[lrow * kCL + col] = zv;
             }
         } else if (kind == COP_REPARAM_BWD) {
             const float* ml = slots + op.yslot * kCR * kCL;
-            const int lrow = tid >> kRS, n = op.N >> 1;          // op.N = 2n columns are produced (and stored)
+            const int lrow = otid >> kRS, n = op.N >> 1;          // op.N = 2n columns are produced (and stored)
             float kl = 0.f;
-            for (int col = tid & (kTPR - 1); col < kCL; col += kTPR) {
+            for (int col = otid & (kTPR - 1); col < kCL; col += kTPR) {
                 float o = 0.f;
                 if (lrow < nrows && col < 2 * n) {
                     const int j = col < n ? col : col - n;
@@ -575,35 +567,21 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
             // barriers for a layer whose arithmetic is 16 dot products and 16 scaled copies of one weight row
             static_assert(kCT == 1024 && kTPR == 64, "COP_DISC_HEAD maps one wavefront to one row");
             const EpiCtx ec = chain_epi_ctx(CEPI_ACTBWD, op, P, key, slots);
-            const int lrow = tid >> kRS, grow = r0 + lrow, t = tid & (kTPR - 1);
+            const int lrow = otid >> kRS, grow = r0 + lrow, t = otid & (kTPR - 1);
             const int Kk = chain_pin(op.K), Nn = chain_pin(op.N);
-            float wv[4], part = 0.f;
+            float wv[4], xv[4], dx[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = t + 64 * j;
                 wv[j] = op.W[min(k, Kk - 1)];
-                if (k < Kk) part += src[lrow * kCL + k] * wv[j];
+                xv[j] = k < Kk ? src[lrow * kCL + k] : 0.f;
             }
-            const float logit = wave_sum(part);
-            float gv = 0.f;
-            if (lrow < nrows) {
-                const float dv = sigmoidf_(logit);
-                const int Bsplit = op.row_split;
-                const float invB = 1.f / (float)Bsplit;
-                float l, gg;
-                if (op.aux == 0 && grow >= Bsplit) { l = logf(1.f - dv + kTiny); gg = invB / (1.f - dv + kTiny); }
-                else { l = logf(dv + kTiny); gg = -invB / (dv + kTiny); }
-                gv = gg * dv * (1.f - dv) * op.scale;
-                if (t == 0) {
-                    if (P.loss_terms) P.loss_terms[grow] = -l * invB;
-                    else atomicAdd(P.loss_out + P.loss_slot, -l * invB);
-                    if (op.aux_ptr) op.aux_ptr[(size_t)grow * op.aux_ld] = gv;
-                }
-            }
+            disc_head_row(xv, wv, Kk, t, lrow < nrows, grow, op.aux, op.row_split, op.scale, P.loss_terms, P.loss_out + P.loss_slot,
+                          op.aux_ptr, op.aux_ld, dx);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = t + 64 * j;
-                if (k < kCL) dst[lrow * kCL + k] = (lrow < nrows && k < Nn) ? chain_epi<NM>(ec, grow, lrow, k, gv * wv[j]) : 0.f;
+                if (k < kCL) dst[lrow * kCL + k] = (lrow < nrows && k < Nn) ? chain_epi<NM>(ec, grow, lrow, k, dx[j]) : 0.f;
             }
         } else if (kind == COP_ADV) {
             // src col 0 = D(x) of each row.  mode 0: rows < row_split real, others fake; mode 1: all fake(gen)
@@ -611,15 +589,12 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                 const int lrow = tid, g = r0 + lrow;
                 float gv = 0.f;
                 if (lrow < nrows) {
-                    const float dv = src[lrow * kCL];
                     const int B = op.row_split;
                     const float invB = 1.f / (float)B;
-                    float l, gg;
-                    if (op.aux == 0 && g >= B) { l = logf(1.f - dv + kTiny); gg = invB / (1.f - dv + kTiny); }
-                    else { l = logf(dv + kTiny); gg = -invB / (dv + kTiny); }
-                    gv = gg * dv * (1.f - dv) * op.scale;
-                    if (P.loss_terms) P.loss_terms[g] = -l * invB;
-                    else atomicAdd(P.loss_out + P.loss_slot, -l * invB);
+                    const AdvTerm t = adv_term(src[lrow * kCL], op.aux == 0 && g >= B, invB, op.scale);
+                    gv = t.gv;
+                    if (P.loss_terms) P.loss_terms[g] = -t.l * invB;
+                    else atomicAdd(P.loss_out + P.loss_slot, -t.l * invB);
                 }
                 dst[lrow * kCL] = gv;
             }

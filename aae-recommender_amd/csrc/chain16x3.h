@@ -206,12 +206,8 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                     if (col < N && lr < nrows) {
                         v = acc[q];
                         if (acc_in) v += x16_get(dst, lr, col);           // the layer's earlier k-part: this lane's own cell
-                        if (ec.epi == CEPI_ACTBWD) {
-                            v *= act_grad_from_y<false>(ec.act, ygp ? yv[q] : x16_get(ys, lr, col));
-                            if (ec.den) v *= chain_keep(ec, r0 + lr, col) ? ec.mk : 0.f;
-                        } else {
-                            v = chain_epi<false>(ec, r0 + lr, lr, col, v);
-                        }
+                        if (ec.epi == CEPI_ACTBWD) v = chain_actbwd<false>(ec, r0 + lr, col, v, ygp ? yv[q] : x16_get(ys, lr, col));
+                        else v = chain_epi<false>(ec, r0 + lr, lr, col, v);
                         store(lr, col, v);
                     }
                     // (columns >= N read as zero for the next layer; the constant-1 column of an augmented layer input rides here)
@@ -247,8 +243,7 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                     const bool cell = wave < nrows && ecol < opN;
                     if (epi_k == CEPI_ACTBWD) {
                         const float y = qaux_ptr[(size_t)(r0 + rowc) * qaux_ld + cc];
-                        const float kp = (sec.den && cell) ? (chain_keep(sec, r0 + wave, ecol) ? sec.mk : 0.f) : 1.f;
-                        acc *= act_grad_from_y<false>(sec.act, y) * kp;
+                        acc *= chain_actbwd_factor<false>(sec, r0 + wave, ecol, cell, y);
                     }
                     acc = cell ? acc : 0.f;
                     store(wave, ecol, acc);
@@ -279,20 +274,8 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
             // one wave per row: softmax / sigmoid / identity over opN (<= 208) columns, in place on dst
             float z[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = lane + 64 * j < opN ? x16_get(dst, wave, lane + 64 * j) : -INFINITY;
-            if (qaux == 1) {
-                float mx = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-                for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) if (lane + 64 * j < opN) { z[j] = expf(z[j] - mx); sum += z[j]; }
-                sum = wave_sum(sum);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) z[j] = z[j] / sum;
-            } else if (qaux == 2) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) z[j] = sigmoidf_(z[j]);
-            }
+            for (int j = 0; j < 4; ++j) z[j] = lane + 64 * j < opN ? x16_get(dst, wave, lane + 64 * j) : 0.f;
+            final_act_fwd4(z, opN, qaux, lane);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int ecol = lane + 64 * j;
@@ -304,28 +287,20 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
             if (one_col >= 0 && lane == 0) x16_put(dst, wave, one_col, wave < nrows ? 1.f : 0.f);
         } else if (kind == COP_FINAL_BWD) {
             const char* zs = ximg + yslot_k * kX16SlotB;
-            float g[4], zz[4];
+            float g[4], zz[4], ga[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool in = lane + 64 * j < opN;
                 g[j] = in ? x16_get(src, wave, lane + 64 * j) : 0.f;
                 zz[j] = (in && qaux) ? x16_get(zs, wave, lane + 64 * j) : 0.f;
             }
-            float dot = 0.f;
-            if (qaux == 1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dot += g[j] * zz[j];
-                dot = wave_sum(dot);
-            }
+            final_act_bwd4(g, zz, opN, qaux, lane, ga);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int ecol = lane + 64 * j;
                 if (ecol < kX16Kp) {
-                    float o = 0.f;
-                    if (ecol < opN) {
-                        o = qaux == 1 ? zz[j] * (g[j] - dot) : qaux == 2 ? g[j] * zz[j] * (1.f - zz[j]) : g[j];
-                        store(wave, ecol, o);
-                    }
+                    const float o = ecol < opN ? ga[j] : 0.f;
+                    if (ecol < opN) store(wave, ecol, o);
                     x16_put(dst, wave, ecol, o);       // (zero beyond opN: a following layer reads whole k-steps)
                 }
             }
@@ -340,16 +315,7 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                     if (wave < nrows && ecol < n) {
                         if (grow >= qrow_split) v = qfake_slot >= 0 ? x16_get(ximg + qfake_slot * kX16SlotB, wave, ecol) : qW[(size_t)grow * qldw + ecol];
                         else if (qaux_ptr) v = qaux_ptr[(size_t)grow * qaux_ld + ecol] * qscale;
-                        else if (qaux == 0) {          // gauss: Box-Muller on two words of the counter generator
-                            const uint32_t u1 = hash_cell(k, (uint32_t)(grow + qgrow0), (uint32_t)(2 * ecol));
-                            const uint32_t u2 = hash_cell(k, (uint32_t)(grow + qgrow0), (uint32_t)(2 * ecol + 1));
-                            const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
-                            const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
-                            v = sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2) * qscale;
-                        } else if (qaux == 1) {        // categorical: one-hot of a uniform class per row
-                            const uint32_t u = hash_cell(k, (uint32_t)(grow + qgrow0), 0xFFFFFFFFu);
-                            v = ((int)(u % (uint32_t)n) == ecol) ? qscale : 0.f;
-                        }                                // bernoulli: the reference's randint(0, 1) is always 0 (aae.py:86-88)
+                        else v = prior_cell(k, (uint32_t)(grow + qgrow0), ecol, n, qaux, qscale);
                         store(wave, ecol, v);
                     }
                     x16_put(dst, wave, ecol, ecol == one_col ? (wave < nrows ? 1.f : 0.f) : v);
@@ -360,29 +326,15 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
             const EpiCtx ec = chain_epi_ctx(CEPI_ACTBWD, op, P, key, reinterpret_cast<const float*>(ximg));
             const int lrow = wave, grow = r0 + lrow;
             const int Kk = opK, Nn = opN;
-            float wv[4], dot = 0.f;
+            float wv[4], xv[4], dx[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = lane + 64 * j;
                 wv[j] = qW[min(k, Kk - 1)];
-                if (k < Kk) dot += x16_get(src, lrow, k) * wv[j];
+                xv[j] = k < Kk ? x16_get(src, lrow, k) : 0.f;
             }
-            const float logit = wave_sum(dot);
-            float gv = 0.f;
-            if (lrow < nrows) {
-                const float dv = sigmoidf_(logit);
-                const int Bsplit = qrow_split;
-                const float invB = 1.f / (float)Bsplit;
-                float l, gg;
-                if (qaux == 0 && grow >= Bsplit) { l = logf(1.f - dv + kTiny); gg = invB / (1.f - dv + kTiny); }
-                else { l = logf(dv + kTiny); gg = -invB / (dv + kTiny); }
-                gv = gg * dv * (1.f - dv) * qscale;
-                if (lane == 0) {
-                    if (P.loss_terms) P.loss_terms[grow] = -l * invB;
-                    else atomicAdd(P.loss_out + P.loss_slot, -l * invB);
-                    if (qaux_ptr) qaux_ptr[(size_t)grow * qaux_ld] = gv;
-                }
-            }
+            disc_head_row(xv, wv, Kk, lane, lrow < nrows, grow, qaux, qrow_split, qscale, P.loss_terms, P.loss_out + P.loss_slot,
+                          qaux_ptr, qaux_ld, dx);
             const char* ys = ximg + yslot_k * kX16SlotB;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -390,8 +342,7 @@ __global__ __launch_bounds__(kX16T) void chain16x3_kernel(ChainProgram P) {
                 if (k < kX16Kp) {
                     float v = 0.f;
                     if (lrow < nrows && k < Nn) {
-                        v = gv * wv[j] * act_grad_from_y<false>(ec.act, x16_get(ys, lrow, k));
-                        if (ec.den) v *= chain_keep(ec, grow, k) ? ec.mk : 0.f;
+                        v = chain_actbwd<false>(ec, grow, k, dx[j], x16_get(ys, lrow, k));
                         store(lrow, k, v);
                     }
                     x16_put(dst, lrow, k, v);

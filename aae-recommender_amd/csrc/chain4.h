@@ -348,12 +348,8 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     if (ccol < N && crow < nrows) {
                         v = crow == 0 ? cs[0] : crow == 1 ? cs[1] : crow == 2 ? cs[2] : cs[3];
                         if (acc_in) v += dst[crow * kCL + ccol];
-                        if (ec.epi == CEPI_ACTBWD) {
-                            v *= act_grad_from_y<false>(ec.act, ygp ? yv1 : (slots + yslot_k * kR4 * kCL)[crow * kCL + ccol]);
-                            if (ec.den) v *= chain_keep(ec, r0 + crow, ccol) ? ec.mk : 0.f;
-                        } else {
-                            v = chain_epi<false>(ec, r0 + crow, crow, ccol, v);
-                        }
+                        if (ec.epi == CEPI_ACTBWD) v = chain_actbwd<false>(ec, r0 + crow, ccol, v, ygp ? yv1 : (slots + yslot_k * kR4 * kCL)[crow * kCL + ccol]);
+                        else v = chain_epi<false>(ec, r0 + crow, crow, ccol, v);
                     }
                     if (ccol < kCL) dst[crow * kCL + ccol] = ccol == one_col ? (crow < nrows ? 1.f : 0.f) : v;
                 }
@@ -409,12 +405,8 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     else sum_slices(std::integral_constant<int, kC4W>{});
                     if (acc_in) v += dst[erow * kCL + ecol];          // (uniform) the layer's earlier k-part: this thread's own cell
                     // (the epilogue's y slot holds 4-row blocks here: index it with this kernel's row stride)
-                    if (ec.epi == CEPI_ACTBWD) {
-                        v *= act_grad_from_y<false>(ec.act, ygp ? yv[eh] : (slots + yslot_k * kR4 * kCL)[erow * kCL + ecol]);
-                        if (ec.den) v *= chain_keep(ec, r0 + erow, ecol) ? ec.mk : 0.f;
-                    } else {
-                        v = chain_epi<false>(ec, r0 + erow, erow, ecol, v);
-                    }
+                    if (ec.epi == CEPI_ACTBWD) v = chain_actbwd<false>(ec, r0 + erow, ecol, v, ygp ? yv[eh] : (slots + yslot_k * kR4 * kCL)[erow * kCL + ecol]);
+                    else v = chain_epi<false>(ec, r0 + erow, erow, ecol, v);
                 }
                 // (columns >= N read as zero for the next layer; the constant-1 column of an augmented layer input rides here
                 //  instead of in a write + barrier of its own behind every op)
@@ -446,9 +438,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                 if (epi_k == CEPI_ACTBWD) {
                     const EpiCtx sec = chain_epi_ctx(CEPI_ACTBWD, op, P, key, slots);
                     const float y = qaux_ptr[(size_t)(r0 + rowc) * qaux_ld + cc];
-                    const bool cell = erow < nrows && ecol < opN;
-                    const float kp = (sec.den && cell) ? (chain_keep(sec, r0 + erow, ecol) ? sec.mk : 0.f) : 1.f;
-                    acc *= act_grad_from_y<false>(sec.act, y) * kp;
+                    acc *= chain_actbwd_factor<false>(sec, r0 + erow, ecol, erow < nrows && ecol < opN, y);
                 }
                 dst[erow * kCL + ecol] = (erow < nrows && ecol < opN) ? acc : 0.f;
             }
@@ -461,10 +451,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                 if (erow < nrows && ecol < opN) {
                     v = src[erow * kCL + ecol];
                     if (kind == COP_DROPACT) v = chain_epi<false>(ec, r0 + erow, erow, ecol, v);
-                    else {
-                        v *= act_grad_from_y<false>(ec.act, (slots + qyslot * kR4 * kCL)[erow * kCL + ecol]);
-                        if (ec.den) v *= chain_keep(ec, r0 + erow, ecol) ? ec.mk : 0.f;
-                    }
+                    else v = chain_actbwd<false>(ec, r0 + erow, ecol, v, (slots + qyslot * kR4 * kCL)[erow * kCL + ecol]);
                 }
                 dst[erow * kCL + ecol] = ecol == one_col ? (erow < nrows ? 1.f : 0.f) : v;
             }
@@ -472,34 +459,27 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
         } else if (kind == COP_FINAL_FWD) {
             if (wave < kR4) {                           // one wave per row; softmax / sigmoid / identity, in place on dst
                 float* zr = dst + wave * kCL;
-                if (qaux == 1) {
-                    float mx = -INFINITY;
-                    for (int j = lane; j < opN; j += 64) mx = fmaxf(mx, zr[j]);
-                    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-                    float sum = 0.f;
-                    for (int j = lane; j < opN; j += 64) sum += expf(zr[j] - mx);
-                    sum = wave_sum(sum);
-                    for (int j = lane; j < opN; j += 64) zr[j] = expf(zr[j] - mx) / sum;
-                } else if (qaux == 2) {
-                    for (int j = lane; j < opN; j += 64) zr[j] = sigmoidf_(zr[j]);
-                }
+                float z[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) z[j] = lane + 64 * j < opN ? zr[lane + 64 * j] : 0.f;
+                final_act_fwd4(z, opN, qaux, lane);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (qaux && lane + 64 * j < opN) zr[lane + 64 * j] = z[j];
             }
         } else if (kind == COP_FINAL_BWD) {
             if (wave < kR4) {
                 const float* zr = slots + qyslot * kR4 * kCL + wave * kCL;
                 const float* gr = src + wave * kCL;
-                float* o = dst + wave * kCL;
-                if (qaux == 1) {
-                    float dot = 0.f;
-                    for (int j = lane; j < opN; j += 64) dot += gr[j] * zr[j];
-                    dot = wave_sum(dot);
-                    for (int j = lane; j < opN; j += 64) o[j] = zr[j] * (gr[j] - dot);
-                } else if (qaux == 2) {
-                    for (int j = lane; j < opN; j += 64) o[j] = gr[j] * zr[j] * (1.f - zr[j]);
-                } else {
-                    for (int j = lane; j < opN; j += 64) o[j] = gr[j];
+                float g[4], z[4], o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool in = lane + 64 * j < opN;
+                    g[j] = in ? gr[lane + 64 * j] : 0.f;
+                    z[j] = (in && qaux) ? zr[lane + 64 * j] : 0.f;
                 }
-                for (int j = opN + lane; j < kCL; j += 64) o[j] = 0.f;
+                final_act_bwd4(g, z, opN, qaux, lane, o);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (lane + 64 * j < kCL) dst[wave * kCL + lane + 64 * j] = lane + 64 * j < opN ? o[j] : 0.f;
             }
         } else if (kind == COP_PRIOR) {
             if (ecol < kCL)
@@ -511,16 +491,7 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                 if (erow < nrows && ecol < n) {
                     if (grow >= qrow_split) v = qfake_slot >= 0 ? (slots + qfake_slot * kR4 * kCL)[erow * kCL + ecol] : qW[(size_t)grow * qldw + ecol];
                     else if (qaux_ptr) v = qaux_ptr[(size_t)grow * qaux_ld + ecol] * qscale;
-                    else if (qaux == 0) {          // gauss: Box-Muller on two words of the counter generator
-                        const uint32_t u1 = hash_cell(k, (uint32_t)(grow + qgrow0), (uint32_t)(2 * ecol));
-                        const uint32_t u2 = hash_cell(k, (uint32_t)(grow + qgrow0), (uint32_t)(2 * ecol + 1));
-                        const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
-                        const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
-                        v = sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2) * qscale;
-                    } else if (qaux == 1) {        // categorical: one-hot of a uniform class per row
-                        const uint32_t u = hash_cell(k, (uint32_t)(grow + qgrow0), 0xFFFFFFFFu);
-                        v = ((int)(u % (uint32_t)n) == ecol) ? qscale : 0.f;
-                    }                                // bernoulli: the reference's randint(0, 1) is always 0 (aae.py:86-88)
+                    else v = prior_cell(k, (uint32_t)(grow + qgrow0), ecol, n, qaux, qscale);
                 }
                 dst[erow * kCL + ecol] = v;
             }
@@ -530,41 +501,20 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                 const EpiCtx ec = chain_epi_ctx(CEPI_ACTBWD, op, P, key, slots);
                 const int lrow = wave, grow = r0 + lrow;
                 const int Kk = opK, Nn = opN;
-                float wv[4], dot = 0.f;
+                float wv[4], xv[4], dx[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int k = lane + 64 * j;
                     wv[j] = qW[min(k, Kk - 1)];
-                    if (k < Kk) dot += src[lrow * kCL + k] * wv[j];
+                    xv[j] = k < Kk ? src[lrow * kCL + k] : 0.f;
                 }
-                const float logit = wave_sum(dot);
-                float gv = 0.f;
-                if (lrow < nrows) {
-                    const float dv = sigmoidf_(logit);
-                    const int Bsplit = qrow_split;
-                    const float invB = 1.f / (float)Bsplit;
-                    float l, gg;
-                    if (qaux == 0 && grow >= Bsplit) { l = logf(1.f - dv + kTiny); gg = invB / (1.f - dv + kTiny); }
-                    else { l = logf(dv + kTiny); gg = -invB / (dv + kTiny); }
-                    gv = gg * dv * (1.f - dv) * qscale;
-                    if (lane == 0) {
-                        if (P.loss_terms) P.loss_terms[grow] = -l * invB;       // (summed by the weight-gradient launch behind the program)
-                        else atomicAdd(P.loss_out + P.loss_slot, -l * invB);
-                        if (qaux_ptr) qaux_ptr[(size_t)grow * qaux_ld] = gv;
-                    }
-                }
+                disc_head_row(xv, wv, Kk, lane, lrow < nrows, grow, qaux, qrow_split, qscale, P.loss_terms, P.loss_out + P.loss_slot,
+                              qaux_ptr, qaux_ld, dx);
                 const float* ys = slots + qyslot * kR4 * kCL;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int k = lane + 64 * j;
-                    if (k < kCL) {
-                        float v = 0.f;
-                        if (lrow < nrows && k < Nn) {
-                            v = gv * wv[j] * act_grad_from_y<false>(ec.act, ys[lrow * kCL + k]);
-                            if (ec.den) v *= chain_keep(ec, grow, k) ? ec.mk : 0.f;
-                        }
-                        dst[lrow * kCL + k] = v;
-                    }
+                    if (k < kCL) dst[lrow * kCL + k] = (lrow < nrows && k < Nn) ? chain_actbwd<false>(ec, grow, k, dx[j], ys[lrow * kCL + k]) : 0.f;
                 }
             }
         }   // COP_STORE: only the stores below.  (COP_ADV / COP_REPARAM_BWD: the VAE's training programs stay on chain.h's kernel)
@@ -581,17 +531,12 @@ __global__ __launch_bounds__(kC4T) void chain4_kernel(ChainProgram P) {
                     if (erow < nrows && ecol < opN) {
                         float eps;
                         if (qW) eps = qW[(size_t)(r0 + erow) * qldw + ecol];
-                        else {      // Box-Muller on two words of the counter generator (stream id = qaux)
+                        else {      // the counter generator, stream id = qaux
                             const uint64_t k = key ^ ((uint64_t)(uint32_t)qaux * 0xA0761D6478BD642Full);
-                            const uint32_t u1 = hash_cell(k, (uint32_t)(r0 + erow + qgrow0), (uint32_t)(2 * ecol));
-                            const uint32_t u2 = hash_cell(k, (uint32_t)(r0 + erow + qgrow0), (uint32_t)(2 * ecol + 1));
-                            const float f1 = ((float)(u1 >> 8) + 1.0f) * (1.0f / 16777216.0f);     // (0, 1]
-                            const float f2 = (float)(u2 >> 8) * (1.0f / 16777216.0f);
-                            eps = sqrtf(-2.0f * logf(f1)) * cosf(6.283185307179586f * f2);
+                            eps = draw_gauss(k, (uint32_t)(r0 + erow + qgrow0), ecol);
                         }
                         if (qaux_ptr) qaux_ptr[(size_t)(r0 + erow) * qaux_ld + ecol] = eps;
-                        const float mu = src[erow * kCL + ecol], lv = src[erow * kCL + opN + ecol];
-                        zv = mu + eps * expf(0.5f * lv);
+                        zv = reparam_cell(src[erow * kCL + ecol], src[erow * kCL + opN + ecol], eps);
                     }
                     dst[erow * kCL + ecol] = ecol == one_col ? (erow < nrows ? 1.f : 0.f) : zv;
                 }

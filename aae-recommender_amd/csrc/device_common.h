@@ -202,8 +202,9 @@ __device__ __forceinline__ uint32_t hash_cell(uint64_t key, uint32_t row, uint32
 }
 
 // The two draws behind every sample of a step, from the words of one stream (k = rng_key(seed, step, 0) ^ stream id *
-// 0xA0761D6478BD642F: stream 100 the prior, 12 the VAE's eps), for prior_kernel (kernels.h) and chain.h's COP_PRIOR / COP_REPARAM
-// ops.  chain4.h and chain16x3.h keep their own copies; tests/test_device_rng_gpu.py holds every copy to the same restatement.
+// 0xA0761D6478BD642F: stream 100 the prior, 12 the VAE's eps, 14 the DAE's noise).  Every kernel that samples calls these:
+// prior_kernel (kernels.h), the COP_PRIOR / COP_REPARAM ops of the three chain kernels, dae_corrupt.h;
+// tests/test_device_rng_gpu.py holds each of those paths to the host restatement tests/device_rng.py.
 // Standard normal for cell (row, col): Box-Muller on the top 24 bits of the words of columns 2 col and 2 col + 1.
 __device__ __forceinline__ float draw_gauss(uint64_t k, uint32_t row, int col) {
     const uint32_t u1 = hash_cell(k, row, (uint32_t)(2 * col));
@@ -215,6 +216,25 @@ __device__ __forceinline__ float draw_gauss(uint64_t k, uint32_t row, int col) {
 // Uniform class in [0, n) for a row: the word of column 0xFFFFFFFF.
 __device__ __forceinline__ int draw_class(uint64_t k, uint32_t row, int n) {
     return (int)(hash_cell(k, row, 0xFFFFFFFFu) % (uint32_t)n);
+}
+// Cell (row, col) of z_real ~ prior (PRIOR_SAMPLERS, aae.py:78-94) times prior_scale, n columns wide; k: the key of stream 100,
+// row: of the GLOBAL batch.  kind 0 gauss, 1 categorical (the one-hot of a uniform class per row), 2 bernoulli: the
+// reference's randint(0, 1) is always 0 (aae.py:86-88).
+__device__ __forceinline__ float prior_cell(uint64_t k, uint32_t row, int col, int n, int kind, float scale) {
+    if (kind == 0) return draw_gauss(k, row, col) * scale;
+    if (kind == 1) return draw_class(k, row, n) == col ? scale : 0.f;
+    return 0.f;
+}
+
+// One row's term of the adversarial losses (aae.py:726-727, 738) from dv = D(x): l = log(D + T) of a real row (and of
+// gen_step's rows) | log(1 - D + T) of disc_step's fake rows - the loss is -mean l, invB = 1 / B -, and gv = scale * dLoss /
+// d(the discriminator's last pre-activation): -1/B / (D + T) * D (1 - D) | +1/B / (1 - D + T) * D (1 - D).
+struct AdvTerm { float l, gv; };
+__device__ __forceinline__ AdvTerm adv_term(float dv, bool fake, float invB, float scale) {
+    float l, gg;
+    if (fake) { l = logf(1.f - dv + kTiny); gg = invB / (1.f - dv + kTiny); }
+    else { l = logf(dv + kTiny); gg = -invB / (dv + kTiny); }
+    return {l, gg * dv * (1.f - dv) * scale};
 }
 
 // returns keep in {0,1}

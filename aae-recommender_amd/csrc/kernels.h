@@ -528,6 +528,10 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------
 // encoder output activation (PRIOR_ACTIVATIONS, aae.py:97-101): rows of width c, in place.
 // One wave per row.  fwd: z = softmax(a) | sigmoid(a) | a.   bwd: ga from gz and z.
+// These two walk global rows of ANY width and so keep their loops: the one restatement left of final_act_fwd4 /
+// final_act_bwd4 (chain_ops.h, the chain kernels' form for rows of up to 256 columns) - same terms, same order (a lane's
+// columns ascending, then the wave).  tests/test_device_rng_gpu.py's
+// test_one_seed_gives_one_run_on_the_per_layer_path_and_the_chain_path and the no_chain paths of the parity suites tie them.
 // ---------------------------------------------------------------------------------------
 __global__ void final_act_fwd_kernel(float* __restrict__ z, int rows, int c, int ld, int kind,
                                      float* __restrict__ copy_out, int ld_copy) {
@@ -583,20 +587,15 @@ __global__ void fill_col_kernel(float* dst, int ld, int rows, int col, float v) 
 }
 
 // z_real ~ prior (PRIOR_SAMPLERS, aae.py:78-94) from the counter generator, times prior_scale: the per-layer path's launch
-// of what the layer-chain programs draw in their COP_PRIOR op (chain.h, chain4.h, chain16x3.h) - the SAME draw, word for word
-// (stream 100 of hash_cell, the top 24 bits of a word), so a seed gives one run on either path
-// (tests/test_device_rng_gpu.py holds all four copies to tests/device_rng.py)
+// of what the layer-chain programs draw in their COP_PRIOR op (chain.h, chain4.h, chain16x3.h) - the SAME draw (prior_cell,
+// device_common.h, on stream 100), so a seed gives one run on either path (tests/test_device_rng_gpu.py holds all four
+// callers to tests/device_rng.py)
 __global__ void prior_kernel(float* __restrict__ z, int ld, int rows, int c, int prior, float scale, uint64_t seed,
                              const long long* step_ctr, int grow0) {
     const uint64_t k = rng_key(seed, (uint64_t)*step_ctr, 0) ^ (100ull * 0xA0761D6478BD642Full);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < rows * c; i += gridDim.x * blockDim.x) {
         int r = i / c, j = i - r * c;
-        const uint32_t gr = (uint32_t)(r + grow0);       // keyed by the row of the global batch
-        float v = 0.f;
-        if (prior == 0) v = draw_gauss(k, gr, j) * scale;
-        else if (prior == 1) v = draw_class(k, gr, c) == j ? scale : 0.f;      // categorical: one-hot of a uniform class per row
-        // bernoulli: the reference's randint(0, 1) is always 0 (aae.py:86-88)
-        z[(size_t)r * ld + j] = v;
+        z[(size_t)r * ld + j] = prior_cell(k, (uint32_t)(r + grow0), j, c, prior, scale);     // keyed by the row of the global batch
     }
 }
 
@@ -616,12 +615,9 @@ __global__ __launch_bounds__(256) void adv_loss_kernel(const float* __restrict__
     const float invB = 1.f / (float)B;
     const int rows = mode == 0 ? 2 * B : B;
     for (int r = threadIdx.x; r < rows; r += 256) {
-        float dv = dout[(size_t)r * ldo];
-        float g, l;
-        if (mode == 0 && r >= B) { l = logf(1.f - dv + kTiny); g = invB / (1.f - dv + kTiny); }
-        else { l = logf(dv + kTiny); g = -invB / (dv + kTiny); }
-        ga[(size_t)r * lda] = g * dv * (1.f - dv) * gscale;
-        acc += (double)l;
+        const AdvTerm t = adv_term(dout[(size_t)r * ldo], mode == 0 && r >= B, invB, gscale);
+        ga[(size_t)r * lda] = t.gv;
+        acc += (double)t.l;
     }
     red[threadIdx.x] = acc;
     __syncthreads();

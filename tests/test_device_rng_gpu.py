@@ -2,10 +2,11 @@
 NumPy restatement of the counter generator: two handles with the same parameters, one drawing its dropout masks, prior
 sample and eps in the kernels, the other handed them - the three losses after every step and the whole state_dict() at the
 end must agree.  The injected path is the one every fixture, fuzzer and sweep of the suite already pins to the reference, so
-this holds every copy of the keep rule (drop_keep, chain_keep, the GEMM epilogues, the discriminator head), of the Box-Muller
-/ categorical draw (prior_kernel and the COP_PRIOR op of chain.h, chain4.h, chain16x3.h), of the reparametrisation draw
-(COP_REPARAM of chain.h and chain4.h), the step value of the forward and of the recomputed backward masks, the stream ids
-and the row offsets to ONE definition.
+this holds every copy of the keep rule (drop_keep, chain_keep, the GEMM epilogues), every caller of the one Box-Muller /
+categorical draw (draw_gauss / draw_class through prior_cell, device_common.h: prior_kernel and the COP_PRIOR op of chain.h,
+chain4.h, chain16x3.h; the reparametrisation draw of COP_REPARAM in chain.h and chain4.h) - the key, row and column each of
+them hands it -, the step value of the forward and of the recomputed backward masks, the stream ids and the row offsets to
+ONE definition.
 
 Shape: N = 700, h = 48, c = 12, B = 37 (no multiple of the 4- or 16-row blocks), B = 1, and B = 40 (a multiple of 4: the
 discriminator program then carries the encoder's evaluation pass as a prefix of its upper rows).  Three steps per case: the

@@ -11,6 +11,8 @@ the loss series and a predict of the first batch; the other four hashes say whic
 
 Widths every kernel family is compiled for (hidden 200, code 50), 2 000 items, rows 24 (one row block) / 130 (two row blocks, the
 bucket build on the side stream; blocked_output) / 512 (the four-wave gather); data from tools/synth.py, fixed seeds, device rng.
+At rows 24 and 130 the AAE step also runs on each of the other layer-chain kernels (X16_ROWS, CHAIN16, CHAIN_KSLICES) and with the
+categorical and bernoulli priors (softmax and sigmoid encoder outputs); at rows 24 with GELU, on the chain and the per-layer path.
 
     python tools/step_bits.py [--list] [--only SUBSTRING] [--mark]
 --mark launches a cumsum kernel of torch's between the cases, so that a kernel trace of the run can be cut by case.
@@ -48,13 +50,15 @@ class Ctx:
         return (s % NBATCH) * self.B
 
     def model(self, options=(), params=None, **kw):
-        for o in options:
-            _hip.set_option(o, "1")
+        """options: names (set to "1") or (name, value) pairs, in force while the handle is created"""
+        options = [(o, "1") if isinstance(o, str) else o for o in options]
+        for o, v in options:
+            _hip.set_option(o, v)
         try:
             kw.setdefault("blocked_output", self.B > 112)
             m = HipAAE(N, H, CODE, max_batch=self.B, rng_mode="device", seed=1, **kw)
         finally:
-            for o in options:
+            for o, _ in options:
                 _hip.set_option(o, None)
         m.load_params(params if params is not None else init_params(N, H, CODE, cond_inc=kw.get("cond_inc", 0), seed=3))
         if self.csr is None:
@@ -277,6 +281,18 @@ def cases(rows):
     for kind, kw in (("aae", {}), ("ae", {"ae_only": True})):
         for tag, options in paths:
             out.append((f"step_{kind}_{tag}", plain_step(options, **kw)))
+    # the other layer-chain kernels (default: the 4-row one below 128 rows), the priors other than gauss - with them the softmax
+    # and sigmoid encoder outputs - and one activation class that only the 16-row fp32 kernel and the per-layer path carry
+    x16, chain16, no_chain = ("x16", (("X16_ROWS", "16"),)), ("chain16", (("CHAIN16", "1"),)), ("no_chain", ("NO_CHAIN",))
+    if rows in (24, 130):
+        for tag, options in (x16, chain16, ("kslices", (("CHAIN_KSLICES", "1"),))):
+            out.append((f"step_aae_{tag}", plain_step(options)))
+        for prior in ("categorical", "bernoulli"):
+            for tag, options in [("default", ()), x16, chain16] + [no_chain] * (rows == 24):
+                out.append((f"step_aae_{prior}_{tag}", plain_step(options, prior=prior)))
+    if rows == 24:
+        for tag, options in (("default", ()), no_chain):
+            out.append((f"step_aae_gelu_{tag}", plain_step(options, activation="GELU")))
     out += [("step_cond20", plain_step(cond_inc=20)),
             ("step_hints", hinted_step()), ("step_hints_early_any", hinted_step(("EARLY_ANY",))),
             ("step_bf16", plain_step(dtype="bf16")),
