@@ -34,6 +34,7 @@ COOC_TILE = 16384         # items per LDS tile of the co-occurrence score kernel
 SPGEMM_HASH_PRODUCTS = 4096   # most products of a row the sparse product keeps in an LDS hash table (AAE_SPGEMM_HASH_PRODUCTS; csrc/spgemm.h)
 SPGEMM_STAGE = 512        # entries of a row of A its tile kernel stages in LDS at a time (AAE_SPGEMM_STAGE)
 SPTRANS_LDS = 4096        # longest row of a transpose sorted in LDS in one go (AAE_SPTRANS_LDS; csrc/sptrans.h): longer ones merge through a scratch
+IRGAN_DIM_MAX, IRGAN_POS_MAX, IRGAN_BATCH_MAX, IRGAN_TILE = 64, 2048, 1024, 128      # AAE_IRGAN_* (csrc/irgan.h)
 LOWRANK_DIMS_MAX = 4096   # widest hidden vector of the truncated-SVD projection kernel (AAE_LOWRANK_DIMS_MAX; csrc/lowrank.h)
 METRIC_MAX = 32           # most metric specs of one aae_metric_rows call (AAE_METRIC_MAX; csrc/rank_metrics.h)
 METRIC_ROW_MAX = 4096     # longest row of held-out ranks the metric kernel sorts in LDS (AAE_METRIC_ROW_MAX)
@@ -122,6 +123,12 @@ class AaeRankRows(C.Structure):
 
 class AaeLowRank(C.Structure):
     _fields_ = [("vt_dev", C.c_void_p), ("ld", C.c_int64), ("n_features", C.c_int32), ("dims", C.c_int32)]
+
+
+class AaeIrganNet(C.Structure):
+    _fields_ = [("user_emb_dev", C.c_void_p), ("item_emb_dev", C.c_void_p), ("item_bias_dev", C.c_void_p),
+                ("m_user_emb_dev", C.c_void_p), ("m_item_emb_dev", C.c_void_p), ("m_item_bias_dev", C.c_void_p),
+                ("users", C.c_int32), ("items", C.c_int32), ("dim", C.c_int32)]
 
 
 _PROTOS = {
@@ -253,6 +260,19 @@ _PROTOS = {
                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aae_lowrank_ranks": (C.c_int, [C.POINTER(AaeLowRank), C.c_int32, C.POINTER(AaeBatch), C.POINTER(AaeBatch), C.POINTER(AaeBatch),
                                     C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "aae_irgan_scratch_bytes": (C.c_int, [C.POINTER(AaeIrganNet), C.POINTER(C.c_size_t)]),
+    "aae_irgan_scores": (C.c_int, [C.POINTER(AaeIrganNet), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_irgan_topk": (C.c_int, [C.POINTER(AaeIrganNet), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AaeBatch), C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aae_irgan_ranks": (C.c_int, [C.POINTER(AaeIrganNet), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AaeBatch), C.POINTER(AaeBatch),
+                                  C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "aae_irgan_d_steps": (C.c_int, [C.POINTER(AaeIrganNet), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aae_irgan_sample_neg": (C.c_int, [C.POINTER(AaeIrganNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
+                                       C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aae_irgan_g_steps": (C.c_int, [C.POINTER(AaeIrganNet), C.POINTER(AaeIrganNet), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_float, C.c_float, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "aae_dense_to_csr": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.POINTER(C.c_int32 * 4), C.c_void_p]),
     "aae_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -1091,6 +1111,124 @@ def lowrank_ranks(lr, n_items, csr, items_csr, row_start, n_rows, truth_csr, n_t
             _csr_batch(truth_csr, row_start, n_rows, rows))
     return _ranks_call(load_library().aae_lowrank_ranks, lr.device, torch.cuda.device(lr.device), n_truth, exclude_known,
                        lead, (hidden, hidden.stride(0), scratch, scratch.stride(0)))
+
+
+# ---- IRGAN (aae_irgan_*; csrc/irgan.h) -------------------------------------------------------------------------------
+IRGAN_KEYS = ("user_emb", "item_emb", "item_bias", "m_user_emb", "m_item_emb", "m_item_bias")
+
+
+class DeviceIrganNet:
+    """One net of IRGAN in HBM: user_emb [users, dim], item_emb [items, dim], item_bias [items] and their momentum buffers, fp32,
+    contiguous.  arrays: the six by IRGAN_KEYS (a missing momentum buffer is zeros)."""
+
+    def __init__(self, arrays, device):
+        self.device = torch.device(device)
+        u, v, b = (np.asarray(arrays[k], dtype=np.float32) for k in IRGAN_KEYS[:3])
+        if u.ndim != 2 or v.ndim != 2 or b.ndim != 1 or u.shape[1] != v.shape[1] or v.shape[0] != b.shape[0]:
+            raise ValueError("aaerec: user_emb [users, dim], item_emb [items, dim] and item_bias [items] do not fit together")
+        self.users, self.dim, self.items = int(u.shape[0]), int(u.shape[1]), int(v.shape[0])
+        self.t = {}
+        for k, p in zip(IRGAN_KEYS, (u, v, b, u, v, b)):
+            a = np.asarray(arrays[k], dtype=np.float32) if arrays.get(k) is not None else np.zeros_like(p)
+            if a.shape != p.shape:
+                raise ValueError("aaerec: {} has shape {}, not {}".format(k, a.shape, p.shape))
+            self.t[k] = upload(np.ascontiguousarray(a), self.device).contiguous()
+
+    def struct(self):
+        s = AaeIrganNet()
+        for k in IRGAN_KEYS:
+            setattr(s, k + "_dev", self.t[k].data_ptr())
+        s.users, s.items, s.dim = self.users, self.items, self.dim
+        return s
+
+    def arrays(self):
+        return {k: self.t[k].cpu().numpy() for k in IRGAN_KEYS}
+
+
+def irgan_scratch(net, slots=1):
+    """The uint8 scratch of the training calls of `net`: aae_irgan_scratch_bytes, with room for `slots` users' softmax tables
+    (aae_irgan_sample_neg works on that many users per launch)."""
+    n = C.c_size_t()
+    s = net.struct()
+    _check(load_library().aae_irgan_scratch_bytes(C.byref(s), C.byref(n)))
+    tiles = (net.items + IRGAN_TILE - 1) // IRGAN_TILE
+    extra = (max(1, int(slots)) - 1) * tiles * (24 + 4 * IRGAN_TILE)
+    return torch.empty(n.value + extra + 256, dtype=torch.uint8, device=net.device)
+
+
+def _irgan_scratch_arg(scratch):
+    off = (-scratch.data_ptr()) % 256
+    return C.c_void_p(scratch.data_ptr() + off), C.c_size_t(scratch.numel() - off)
+
+
+def irgan_scores(net, users, pos=None, out=None):
+    """float32 device tensor [len(users), items]: the logits of the int32 device tensor `users`, 0 at the training positives
+    `pos` = (indptr int64 [users + 1], ascending item ids int32) device tensors, or None (aae_irgan_scores)."""
+    n = int(users.numel())
+    out = _scratch(net.device, n, net.items, out, torch.float32, "out", True)
+    s = net.struct()
+    with torch.cuda.device(net.device):
+        _check(load_library().aae_irgan_scores(C.byref(s), _ptr(users), n, _ptr(pos[0]) if pos else None, _ptr(pos[1]) if pos else None,
+                                               _ptr(out), out.stride(0), _stream_of(net.device)))
+    return out[:n, :net.items]
+
+
+def irgan_topk(net, users, pos, known_csr, row_start, n_rows, k, exclude_known=True, scratch=None):
+    """(ids int32 [n_rows, k], scaled scores float32 [n_rows, k]) - device tensors - of rows [row_start, row_start + n_rows) of
+    the DeviceCSR `known_csr` (the test rows' known items), row r scored as user users[r] (aae_irgan_topk)."""
+    scratch = _scratch(net.device, n_rows, net.items, scratch, torch.float32, "scratch", True)
+    lead = (net.struct(), users, pos[0] if pos else None, pos[1] if pos else None, _csr_batch(known_csr, row_start, n_rows))
+    return _list_call(load_library().aae_irgan_topk, net.device, torch.cuda.device(net.device), n_rows, k, exclude_known, lead,
+                      (scratch, scratch.stride(0)))
+
+
+def irgan_ranks(net, users, pos, known_csr, row_start, n_rows, truth_csr, n_truth, exclude_known=True, scratch=None):
+    """int32 device tensor [n_truth]: the 1-based ranks of the stored entries of the truth rows, CSR order (aae_irgan_ranks)."""
+    scratch = _scratch(net.device, n_rows, net.items, scratch, torch.float32, "scratch", True)
+    lead = (net.struct(), users, pos[0] if pos else None, pos[1] if pos else None, _csr_batch(known_csr, row_start, n_rows),
+            _csr_batch(truth_csr, row_start, n_rows))
+    return _ranks_call(load_library().aae_irgan_ranks, net.device, torch.cuda.device(net.device), n_truth, exclude_known, lead,
+                       (scratch, scratch.stride(0)))
+
+
+def irgan_d_steps(net, lines, batch_size, n_steps, lr, momentum, lam, scratch, losses=False):
+    """n_steps D steps over the int32 device tensor `lines` [n, 3] (aae_irgan_d_steps); the fp64 device tensor of the steps'
+    losses when asked for."""
+    out = torch.empty(n_steps, dtype=torch.float64, device=net.device) if losses else None
+    s = net.struct()
+    p, nb = _irgan_scratch_arg(scratch)
+    with torch.cuda.device(net.device):
+        _check(load_library().aae_irgan_d_steps(C.byref(s), _ptr(lines), int(lines.shape[0]), int(batch_size), int(n_steps), float(lr),
+                                                float(momentum), float(lam), _ptr(out), p, nb, _stream_of(net.device)))
+    return out
+
+
+def irgan_sample_neg(net, users, line_off, max_pos, temperature, seed, draw, lines, scratch):
+    """generate_for_d: column 2 of the int32 device tensor `lines` [n, 3] for the users of the int32 device tensor `users`,
+    user q owning lines [line_off[q], line_off[q + 1]) (int64 device tensor) (aae_irgan_sample_neg)."""
+    s = net.struct()
+    p, nb = _irgan_scratch_arg(scratch)
+    with torch.cuda.device(net.device):
+        _check(load_library().aae_irgan_sample_neg(C.byref(s), _ptr(users), _ptr(line_off), int(users.numel()), int(max_pos),
+                                                   float(temperature), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), _ptr(lines),
+                                                   int(lines.shape[0]), p, nb, _stream_of(net.device)))
+
+
+def irgan_g_steps(gen, dis, users, pos, max_pos, lr, momentum, scratch, samples=None, sample_off=None, seed=0, draw=0, losses=False,
+                  samples_out=None):
+    """One G step per entry of the int32 device tensor `users`; samples injected (int32 `samples`, int64 `sample_off`) or drawn
+    by (seed, draw), and then written to the int32 `samples_out` at `sample_off` if that is given (aae_irgan_g_steps).  The fp64
+    device tensor of the steps' losses when asked for."""
+    n = int(users.numel())
+    out = torch.empty(n, dtype=torch.float64, device=gen.device) if losses else None
+    g, d = gen.struct(), dis.struct()
+    p, nb = _irgan_scratch_arg(scratch)
+    with torch.cuda.device(gen.device):
+        _check(load_library().aae_irgan_g_steps(C.byref(g), C.byref(d), _ptr(users), n, _ptr(pos[0]), _ptr(pos[1]), int(max_pos),
+                                                _ptr(samples), _ptr(sample_off), _ptr(samples_out), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                int(draw),
+                                                float(lr), float(momentum), _ptr(out), p, nb, _stream_of(gen.device)))
+    return out
 
 
 # state_dict key <-> (net, layer)

@@ -43,6 +43,7 @@
 #include "randrank.h"
 #include "rank_metrics.h"
 #include "lowrank.h"
+#include "irgan.h"
 #include "chain.h"
 #include "chain4.h"
 #include "chain16x3.h"
@@ -511,6 +512,7 @@ int aae_sync(aae_handle h, void* stream) {
 #include "abi_random.h"
 #include "abi_metrics.h"
 #include "abi_lowrank.h"
+#include "abi_irgan.h"
 #include "abi_data_parallel.h"
 
 #include "dp_step.h"

@@ -811,6 +811,73 @@ int aae_lowrank_ranks(const aae_lowrank* lowrank, int32_t n_items, const aae_bat
  * not written.  AAE_EINVAL as above. */
 int aae_spmm_f32(const aae_batch* rows, const float* dense_dev, int64_t ld, int32_t n_cols, int32_t width, float* out_dev,
                  int64_t ld_out, void* stream);
+/* IRGAN (reference irgan/cf_gan.py, gen_model.py, dis_model.py; csrc/irgan.h).  Handle-free like the calls above: every buffer is
+ * the caller's, the launches go to `stream`, nothing synchronises.  A net is three fp32 tensors and their momentum buffers:
+ * user_emb [users][dim], item_emb [items][dim], item_bias [items], rows contiguous; dim in [1, AAE_IRGAN_DIM_MAX].
+ *   logit(u, j) = item_bias[j] + sum_d user_emb[u][d] * item_emb[j][d]      (one fmaf chain, d ascending, from the bias)
+ * Momentum SGD as torch.optim.SGD(lr, momentum): buf = momentum * buf + grad, p -= lr * buf, on EVERY element of all three tensors
+ * on every step (the reference's gradients are dense).  fp32 parameters and products, no float atomics, duplicates summed in list
+ * order, reductions over the items in one fixed order with fp64 sums: the same inputs give the same bits.
+ * scratch_dev / scratch_bytes of the training calls: 256-byte aligned, at least aae_irgan_scratch_bytes(net) (a fixed region and
+ * the softmax tables of one user); aae_irgan_sample_neg works on as many users at once as further table slots fit.
+ * aae_irgan_scores     out_dev [n_rows][ld] fp32 (ld as in aae_lowrank_scores): logit(users_dev[r], j), and exactly 0 where j is a
+ *                      training positive of that user - pos_indptr_dev int64 [users + 1] / pos_items_dev int32, ascending ids per
+ *                      user, both NULL for none.  A user id outside [0, users) gives a row of zeros.
+ * aae_irgan_topk       scores of the known->n_rows users into scratch_dev [rows][scratch_ld], then the dense form of
+ * aae_irgan_ranks      aae_predict_topk / aae_predict_ranks over it exactly as aae_lowrank_topk / _ranks: `known` names the known
+ *                      items of the TEST rows (masked when exclude_known), min-max scaling, the smaller id at equal scores, -1 / 0
+ *                      tails, k in [1, min(1024, items)].
+ * aae_irgan_d_steps    n_steps consecutive D steps over lines_dev int32 [n_lines][3] = (user, positive, negative): step s takes
+ *                      lines [s batch_size, min((s + 1) batch_size, n_lines)), each line the triples (u, pos, 1), (u, neg, 0);
+ *                      loss = mean BCE-with-logits + lambda (mean(user_emb^2) + mean(item_emb^2) + mean(item_bias^2)), written
+ *                      to losses_out_dev [n_steps] fp64 when that is not NULL.  batch_size in [1, AAE_IRGAN_BATCH_MAX].
+ * aae_irgan_sample_neg generate_for_d for users users_dev[0 .. n_users): user q owns lines [line_off_dev[q], line_off_dev[q + 1])
+ *                      (at most max_pos <= AAE_IRGAN_POS_MAX of them) and gets one negative per line, written to column 2, drawn
+ *                      from softmax(logit / temperature) by the keyed generator: stream 16, keyed by (seed, draw, user id, index
+ *                      of the line within the user) - the same lines under any chunking of the users (sampler: csrc/irgan.h).
+ * aae_irgan_g_steps    one G step per entry of users_dev [n_steps], in order: p = softmax(logit), n = 2 |pos| samples - injected
+ *                      (samples_dev int32, step s at sample_off_dev[s], int64 [n_steps + 1]) or, both NULL, drawn from the mixture
+ *                      0.8 p + 0.2 uniform(pos) on stream 17 keyed by (seed, draw, user id, sample index) -, reward_s = 2
+ *                      (sigmoid(dis logit) - 1/2) p_s / pn_s with pn_s = 0.8 p_s + 0.2 / |pos| [s in pos], loss = -mean(log(max(p_s,
+ *                      1e-8)) reward_s) to losses_out_dev [n_steps] fp64 if given; samples_out_dev (with sample_off_dev), if given,
+ *                      receives the samples every step used.  pos_*: the ascending positives by user id, at
+ *                      most max_pos per user; a user without positives takes no step.
+ * AAE_EINVAL (with aae_last_error) before anything touches the device: a NULL pointer, dim outside [1, 64], users or items not
+ * positive, k out of range, a bad ld or base, batch_size outside [1, 1024], n_steps beyond the lines, max_pos above 2048, a
+ * temperature that is not positive, a scratch that is too small or misaligned. */
+#define AAE_IRGAN_DIM_MAX 64
+#define AAE_IRGAN_POS_MAX 2048
+#define AAE_IRGAN_BATCH_MAX 1024
+#define AAE_IRGAN_TILE 128
+typedef struct aae_irgan_net {
+    float* user_emb_dev;      /* [users][dim] */
+    float* item_emb_dev;      /* [items][dim] */
+    float* item_bias_dev;     /* [items] */
+    float* m_user_emb_dev;    /* the momentum buffers, same shapes (the training calls; the scoring calls do not read them) */
+    float* m_item_emb_dev;
+    float* m_item_bias_dev;
+    int32_t users;
+    int32_t items;
+    int32_t dim;
+} aae_irgan_net;
+int aae_irgan_scratch_bytes(const aae_irgan_net* net, size_t* bytes_out);
+int aae_irgan_scores(const aae_irgan_net* gen, const int32_t* users_dev, int32_t n_rows, const int64_t* pos_indptr_dev,
+                     const int32_t* pos_items_dev, float* out_dev, int64_t ld, void* stream);
+int aae_irgan_topk(const aae_irgan_net* gen, const int32_t* users_dev, const int64_t* pos_indptr_dev, const int32_t* pos_items_dev,
+                   const aae_batch* known, int32_t k, int32_t exclude_known, float* scratch_dev, int64_t scratch_ld,
+                   int32_t* idx_out_dev, float* val_out_dev, void* stream);
+int aae_irgan_ranks(const aae_irgan_net* gen, const int32_t* users_dev, const int64_t* pos_indptr_dev, const int32_t* pos_items_dev,
+                    const aae_batch* known, const aae_batch* truth, int32_t exclude_known, float* scratch_dev, int64_t scratch_ld,
+                    int32_t* ranks_out_dev, void* stream);
+int aae_irgan_d_steps(const aae_irgan_net* dis, const int32_t* lines_dev, int64_t n_lines, int32_t batch_size, int32_t n_steps, float lr,
+                      float momentum, float lambda, double* losses_out_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+int aae_irgan_sample_neg(const aae_irgan_net* gen, const int32_t* users_dev, const int64_t* line_off_dev, int32_t n_users, int32_t max_pos,
+                         float temperature, uint64_t seed, int64_t draw, int32_t* lines_dev, int64_t n_lines, void* scratch_dev,
+                         size_t scratch_bytes, void* stream);
+int aae_irgan_g_steps(const aae_irgan_net* gen, const aae_irgan_net* dis, const int32_t* users_dev, int32_t n_steps,
+                      const int64_t* pos_indptr_dev, const int32_t* pos_items_dev, int32_t max_pos, const int32_t* samples_dev,
+                      const int64_t* sample_off_dev, int32_t* samples_out_dev, uint64_t seed, int64_t draw, float lr, float momentum,
+                      double* losses_out_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
 /* split form for generic conditions */
 int aae_encode(aae_handle h, const aae_batch* batch, float* z_out_dev, void* stream);
 int aae_decode(aae_handle h, const float* zc_dev, int64_t zc_ld, int32_t n_rows,

@@ -1455,6 +1455,120 @@ def gen_challenge():
     print("challenge_metrics:", n, "rows, lengths", min(lengths), "-", max(lengths), "names", names, "bytes", os.path.getsize(path))
 
 
+IRGAN_CASES = {
+    # name: (users, items, (fewest, most) items per user, batch_size, seed)
+    "irgan_small": (7, 40, (1, 4), 4, 91),
+    "irgan_dup": (5, 9, (3, 6), 16, 92),
+}
+
+
+def gen_irgan(only=None):
+    """The reference's IRGAN (irgan/cf_gan.py) on two toy problems, on the CPU, in a temporary working directory (fit writes
+    dis-train.txt where it stands).  np.random.choice is wrapped to record every result; generate_for_d is wrapped to record the
+    lines it wrote; both nets' step() to record every loss; the states are snapshot at the first all_logits call behind a
+    generate_for_d (the end of a D-epoch block) and at the first generate_for_d of the next epoch / the end of fit (the end of
+    a G-epoch block).  n_epochs=2, d_epochs=6 (generate_for_d runs twice per epoch), g_epochs=2, lr=0.05, emb_dim=5 (the
+    reference's all_rating hard-codes it).  irgan_*.npz hold arrays only.
+
+    ONE INTERVENTION: fit reads its batches with linecache.getline, which never looks at the file again once it has cached it, so
+    in a fresh process every D step of the reference trains on the FIRST dis-train.txt it wrote (and, in a process that has run
+    another model, on that model's) while generate_for_d goes on drawing and writing new ones.  That depends on what the process
+    did before, not on the model; the wrapper clears linecache behind every generate_for_d, so the recorded run trains on the
+    lines it has just generated - what cf_gan.py's loop is written to do, and what aaerec/irgan.py does."""
+    import linecache
+    import tempfile
+    import_reference()
+    import irgan.cf_gan as ref_gan
+    for name, (users, items, (lo, hi), batch_size, seed) in IRGAN_CASES.items():
+        if only is not None and name != only:
+            continue
+        rng = np.random.RandomState(seed)
+        X = {u: rng.choice(items, size=rng.randint(lo, hi + 1), replace=False).tolist() for u in range(users)}
+        torch.manual_seed(seed)
+        np.random.seed(seed)
+        n_epochs, d_epochs, g_epochs, lr = 2, 6, 2, 0.05
+        model = ref_gan.IRGAN(users, items, batch_size=batch_size, emb_dim=5, lr=lr, n_epochs=n_epochs, d_epochs=d_epochs,
+                              g_epochs=g_epochs, verbose=False)
+        G, D = model.generator, model.discriminator
+
+        def state(out, prefix):
+            for tag, net, params in (("g", G, G.g_params), ("d", D, D.d_param)):
+                for key, p in zip(("user_emb", "item_emb", "item_bias"), params):
+                    buf = net.optimizer.state[p].get("momentum_buffer") if p in net.optimizer.state else None
+                    out["%s.%s.%s" % (prefix, tag, key)] = p.detach().numpy().copy()
+                    out["%s.%s.m_%s" % (prefix, tag, key)] = np.zeros_like(p.detach().numpy()) if buf is None else buf.numpy().copy()
+
+        out = {}
+        state(out, "init")
+        draws, line_sets, d_losses, g_losses, blocks = [], [], [], [], []
+        pending = [False]          # a generate_for_d has run since the last G step
+        calls = [0]
+        per_epoch = (d_epochs + 4) // 5
+        real_choice, real_gen, real_logits = np.random.choice, model.generate_for_d, G.all_logits
+        real_dstep, real_gstep = D.step, G.step
+
+        def rec_choice(*a, **k):
+            r = real_choice(*a, **k)
+            draws.append(np.asarray(r, dtype=np.int64).copy())
+            return r
+
+        def rec_gen(filename, condition_data=None):
+            if calls[0] and calls[0] % per_epoch == 0:
+                state(out, "block%d" % len(blocks)); blocks.append(1)       # (the G-epoch block of the epoch before)
+            calls[0] += 1
+            real_gen(filename, condition_data)
+            linecache.clearcache()      # (see the docstring: fit then reads the file it has just written)
+            with open(filename) as fh:
+                line_sets.append(np.asarray([[int(v) for v in ln.split()] for ln in fh.read().split("\n")], dtype=np.int32))
+            pending[0] = True
+
+        def rec_logits(*a, **k):
+            if pending[0]:
+                pending[0] = False
+                state(out, "block%d" % len(blocks)); blocks.append(0)       # (a D-epoch block)
+            return real_logits(*a, **k)
+
+        def rec_dstep(loss):
+            d_losses.append(float(loss.item()))
+            return real_dstep(loss)
+
+        def rec_gstep(loss):
+            g_losses.append(float(loss.item()))
+            return real_gstep(loss)
+
+        np.random.choice = rec_choice
+        model.generate_for_d = rec_gen
+        object.__setattr__(G, "all_logits", rec_logits)
+        object.__setattr__(D, "step", rec_dstep)
+        object.__setattr__(G, "step", rec_gstep)
+        here = os.getcwd()
+        try:
+            with tempfile.TemporaryDirectory() as tmp:
+                os.chdir(tmp)
+                model.fit(X)
+        finally:
+            os.chdir(here)
+            np.random.choice = real_choice
+        state(out, "block%d" % len(blocks)); blocks.append(1)
+        assert blocks == [0, 1] * n_epochs and len(line_sets) == per_epoch * n_epochs, (blocks, len(line_sets))
+        rating = G.all_rating(list(range(users))).detach().numpy()
+        pred = np.stack([model.simple_test_one_user((rating[u], u)) for u in range(users)])
+        lens = [len(X[u]) for u in range(users)]
+        out.update(cfg=np.asarray(json.dumps(dict(users=users, items=items, batch_size=batch_size, emb_dim=5, lr=lr, n_epochs=n_epochs,
+                                                  d_epochs=d_epochs, g_epochs=g_epochs, momentum=0.9, n_blocks=len(blocks)))),
+                   pos_indptr=np.concatenate(([0], np.cumsum(lens))).astype(np.int64),
+                   pos_items=np.concatenate([X[u] for u in range(users)]).astype(np.int32),
+                   draw_indptr=np.concatenate(([0], np.cumsum([d.size for d in draws]))).astype(np.int64),
+                   draws=np.concatenate(draws).astype(np.int32),
+                   line_indptr=np.concatenate(([0], np.cumsum([ls.shape[0] for ls in line_sets]))).astype(np.int64),
+                   lines=np.concatenate(line_sets).astype(np.int32),
+                   d_losses=np.asarray(d_losses), g_losses=np.asarray(g_losses), pred=pred)
+        path = os.path.join(OUT, name + ".npz")
+        np.savez_compressed(path, **out)
+        print(name + ":", users, "users", items, "items", len(draws), "draws", len(d_losses), "D steps", len(g_losses), "G steps",
+              "bytes", os.path.getsize(path))
+
+
 ACT_NAMES = ["Softplus", "Hardtanh", "ReLU6", "CELU", "Softsign", "Hardsigmoid", "LogSigmoid", "Softshrink", "Hardshrink",
              "Identity", "GELU", "SiLU", "Mish", "Hardswish", "ELU", "LeakyReLU", "Sigmoid"]
 # added after r6: seeds go on from ACT_NAMES', whose fixtures regenerate bit for bit.  PReLU's six weights (enc.act1 .. disc.act2)
@@ -1586,6 +1700,8 @@ def main():
         gen_mi()
     if want("popular"):
         gen_popular()
+    if want("irgan"):
+        gen_irgan()
     if want("metrics"):
         gen_metric_known_answers()
     if want("challenge"):
