@@ -109,6 +109,8 @@ class _Twin:
 
     def _R(self, x):
         from oracle.aae_oracle import bf16_round
+        if not self.bf16:                            # (the fp32 fuzz's twin, tests/fuzz_path_cases.py: no rounding, the float64 cast alone)
+            return np.asarray(x).astype(np.float64)
         return bf16_round(x).astype(np.float64)      # (the same bf16 value; a product of two of these accumulates in float64)
 
     def _act(self, u):
@@ -157,24 +159,24 @@ class _Twin:
         return G, ga1, gx
 
 
-def make_pair(params, salt, decoder=False, **kw):
-    """(the rounded oracle, its twin) on copies of the same parameters"""
+def make_pair(params, salt, decoder=False, bf16=True, **kw):
+    """(the rounded oracle, its twin) on copies of the same parameters; bf16=False: the fp32 oracle and its twin"""
     from oracle import aae_oracle as O
     base = O.OracleDecoder if decoder else O.OracleAAE
     twin_cls = type("Twin" + base.__name__, (_Twin, base), {})
-    ora, twin = base(params, bf16=True, **kw), twin_cls(params, bf16=True, **kw)
+    ora, twin = base(params, bf16=bf16, **kw), twin_cls(params, bf16=bf16, **kw)
     twin.model = A.Intrinsics(salt)
     return ora, twin
 
 
-def run_pair(cfg, r, seed):
+def run_pair(cfg, r, seed, bf16=True):
     """A step case through oracle and twin: per-step losses of both, the two models, and predict of both where asked."""
     from oracle import aae_oracle as O
     from oracle.dense_torch_port import init_params
     inc = cfg["inc"]
     kw, p, lr = F.model_kwargs(cfg)
     params = init_params(cfg["N"], cfg["h"], cfg["c"], cond_inc=inc, seed=seed)
-    ora, twin = make_pair(params, seed, conditions=[O.ConcatConst(inc)] if inc else [], **kw)
+    ora, twin = make_pair(params, seed, bf16=bf16, conditions=[O.ConcatConst(inc)] if inc else [], **kw)
     twin.conditions = [O.ConcatConst(inc)] if inc else []
     la, lb = [], []
     for st in F.steps(cfg, r):
@@ -188,14 +190,14 @@ def run_pair(cfg, r, seed):
     return np.asarray(la), np.asarray(lb), ora, twin, pred
 
 
-def run_decoder_pair(seed):
+def run_decoder_pair(seed, bf16=True):
     from oracle import aae_oracle as O
     from oracle.dense_torch_port import init_params
     r, N, h, B, act = F.decoder_config(seed)
     it = F.decoder_steps(r, N, h, B, seed)
     c, p = next(it)
     params = init_params(N, h, c, seed=seed)
-    ora, twin = make_pair(params, seed, decoder=True, lr=2e-3, dropout=p, activation=act, conditions=[O.ConcatConst(c)])
+    ora, twin = make_pair(params, seed, decoder=True, bf16=bf16, lr=2e-3, dropout=p, activation=act, conditions=[O.ConcatConst(c)])
     twin.conditions = [O.ConcatConst(c)]
     la, lb, dz = [], [], []
     for s in range(3):

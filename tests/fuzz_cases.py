@@ -1,4 +1,5 @@
-"""The generator and the step loop of the randomised differential tests, shared by tests/test_fuzz_gpu.py (fp32 mode) and
+"""The generator and the step loop of the randomised differential tests, shared by tests/test_fuzz_gpu.py (fp32 mode),
+tests/test_fuzz_paths_cpu.py / tests/test_fuzz_paths_gpu.py (fp32 mode on the forced paths, tests/fuzz_path_cases.py) and
 tests/test_bf16_fuzz_cpu.py / tests/test_bf16_fuzz_gpu.py (bf16 mode, tests/bf16_cases.py): random model shapes and options,
 the batches of a three-step run with a shorter last batch, and the comparison of the device with the oracle.  One
 implementation: a configuration and its inputs are the same draws of the same generator whoever asks.  Importing this module
@@ -22,6 +23,53 @@ WIDE = [dict(N=300, h=40, c=50, B=37, inc=300), dict(N=120, h=200, c=10, B=100, 
 # The library's execution paths a handle can be forced onto (aae_set_option, read once at aae_create): option name and value
 PATHS = {"default": None, "kslices": ("CHAIN_KSLICES", 1), "chain16": ("CHAIN16", 1), "no_chain": ("NO_CHAIN", 1),
          "x16": ("X16_ROWS", 16), "split_any": ("SPLIT_ANY", 1), "blocked_any": ("BLOCKED_ANY", 1)}
+
+# The profile's kernel ids of the output layer's forms (aaerec._hip K_DEC_BCE_FWD, K_DEC_FUSED, K_DEC_CRIT, K_DEC_OPT): the
+# three-kernel path's first GEMM, the single launch, the split form's critical and deferred launches
+OUT_KERNELS = (1, 5, 7, 8)
+FUSED_ROWS, LAUNCH_ROWS, ROW_BLOCK = 109, 112, 104
+
+
+def output_form(path, rows):
+    """The form an fp32 handle of the fuzz's sizes (hidden width below 208, fewer than 16384 items, whole-step gradients) takes
+    for a batch of `rows` rows, restating csrc/abi_chains.h fused_decoder_applies and csrc/abi_output_layer.h
+    output_layer_fused: 'split' (critical + deferred launch; row-blocked beyond 112 rows), 'single' or 'three' (the three
+    GEMMs).  The single-launch LDS image of dh2 fits up to 109 rows; a batch of 110 .. 112 rows is one row block that does not
+    fit; beyond 112 rows only a blocked_output handle - the fuzz creates one on BLOCKED_ANY - stays on the fused kernels, as
+    row blocks of ceil(rows / ceil(rows / 104)) rows."""
+    if rows <= FUSED_ROWS:
+        return "split" if path == "split_any" else "single"
+    if rows <= LAUNCH_ROWS or path != "blocked_any":
+        return "three"
+    nblk = -(-rows // ROW_BLOCK)
+    return "split" if -(-rows // nblk) <= FUSED_ROWS and nblk <= 16 else "three"
+
+
+def assert_output_form(path, counters, tag):
+    """counters: per step (rows, launches of OUT_KERNELS) as check_configuration / check_decoder record them.  On SPLIT_ANY and
+    BLOCKED_ANY every step must have taken output_form()'s form and no other: a forced path that fell back silently fails here."""
+    ran = {"split": (0, 0, 1, 1), "single": (0, 1, 0, 0), "three": (1, 0, 0, 0)}
+    for step, (rows, counts) in enumerate(counters):
+        want = ran[output_form(path, rows)]
+        assert tuple(min(n, 1) for n in counts) == want, (f"{tag} {path} step {step}, {rows} rows: launches of (bce_fwd, single, critical, "
+                                                         f"deferred) {counts}, expected the {output_form(path, rows)} form {want}")
+
+
+def _forced_handle(path, make):
+    """make(blocked_output) with `path`'s option set around the creation (a handle reads its switches once, at creation)"""
+    from aaerec import _hip
+    opt = PATHS[path]
+    if opt:
+        _hip.set_option(opt[0], opt[1])
+    try:        # (BLOCKED_ANY lifts the size cap of the row-blocked output layer; the form itself is the handle's blocked_output)
+        return make(path == "blocked_any")
+    finally:
+        if opt:
+            _hip.set_option(opt[0], None)
+
+
+def _count_output_launches(dev, counters, rows):
+    counters.append((rows, tuple(dev.profile_read(k)[1] for k in OUT_KERNELS)))
 
 
 def config(seed, tiny=False):
@@ -139,10 +187,11 @@ def bf16_param_stats(got, want, lr, n_steps):
 SGD_TOL = 5e-5        # (the fp32 fuzz's; tests/bf16_cases.py has the measurement that keeps it for bf16 mode)
 
 
-def check_configuration(cfg, r, seed, bf16=False, path="default"):
-    """Three steps of the device against the oracle, the parameters after them, and predict where the configuration asks.
-    bf16: a dtype = 'bf16' handle on `path` against OracleAAE(bf16=True) at the tolerances of tests/test_bf16_gpu.py; returns
-    the observed (share, maximum) per tensor."""
+def check_configuration(cfg, r, seed, bf16=False, path="default", counters=None):
+    """Three steps of the device against the oracle, the parameters after them, and predict where the configuration asks, on
+    a handle forced onto `path`.  bf16: a dtype = 'bf16' handle against OracleAAE(bf16=True) at the tolerances of
+    tests/test_bf16_gpu.py; returns the observed (share, maximum) per tensor.  counters: a list that receives, per step,
+    (rows, launches of OUT_KERNELS) from the handle's profile."""
     import pytest
     import torch
     from aaerec import _hip
@@ -153,17 +202,15 @@ def check_configuration(cfg, r, seed, bf16=False, path="default"):
     params = init_params(N, h, c, cond_inc=inc, seed=seed)
     kw, p, lr = model_kwargs(cfg)
     if bf16:
-        opt = PATHS[path]
-        if opt:
-            _hip.set_option(opt[0], opt[1])
-        try:        # (BLOCKED_ANY lifts the size cap of the row-blocked output layer; the form itself is the handle's blocked_output)
-            dev = HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", dtype="bf16", blocked_output=path == "blocked_any", **kw)
-        finally:
-            if opt:
-                _hip.set_option(opt[0], None)     # (a handle reads its switches once, at creation)
+        dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", dtype="bf16", blocked_output=blocked, **kw))
+    elif path != "default":
+        dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", blocked_output=blocked, **kw))
     else:
         dev = HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", **kw)
     dev.load_params(params)
+    if counters is not None:
+        dev.profile_enable(True, kernels=OUT_KERNELS)
+    tag = f"{cfg}" if path == "default" else f"{cfg} {path}"
     ora = O.OracleAAE(params, conditions=[O.ConcatConst(inc)] if inc else [], bf16=bf16, **kw)
     for st in steps(cfg, r):
         s, Bs, ip, idx, val, masks, zr, cond = (st[k] for k in ("s", "Bs", "ip", "idx", "val", "masks", "zr", "cond"))
@@ -171,7 +218,7 @@ def check_configuration(cfg, r, seed, bf16=False, path="default"):
         sel = torch.as_tensor(st["pick"], device=dev.device) if st["pick"] is not None else None
         cdev = torch.as_tensor(cond, device=dev.device) if inc else None
         cut = cfg["cut"] and cut_fits(cfg)
-        if cut and bf16 and cut_refused(cfg, path):
+        if cut and cut_refused(cfg, path):
             # the library refuses the cut form here: the status and the message, and then the whole step on the same handle
             with pytest.raises(_hip.AaeHipError, match=r"error -4: aae_ae_forward needs the layer-chain kernels"):
                 dev.ae_forward(csr, 0, Bs, rows=sel, cond=cdev, masks=masks, z_real=zr)
@@ -187,7 +234,9 @@ def check_configuration(cfg, r, seed, bf16=False, path="default"):
         if bf16:
             np.testing.assert_allclose(dev.losses(), want, rtol=2e-4, atol=2e-6, err_msg=f"{cfg} {path} step {s}")
         else:
-            np.testing.assert_allclose(dev.losses(), want, rtol=5e-5, atol=2e-6, err_msg=f"{cfg} step {s}")
+            np.testing.assert_allclose(dev.losses(), want, rtol=5e-5, atol=2e-6, err_msg=f"{tag} step {s}")
+        if counters is not None:
+            _count_output_launches(dev, counters, Bs)
     got = dev.state_dict()
     stats = None
     if bf16 and cfg["opt"] == "sgd":
@@ -209,14 +258,13 @@ def check_configuration(cfg, r, seed, bf16=False, path="default"):
         # the learning rate.  So: at most 1 % of a tensor's elements (8 for the small ones) may exceed the tolerance, none by
         # more than 3 lr.
         for k, w in ora.p.items():
-            close_enough(got[k], w, 5e-5, 3 * max(lr), f"{cfg} {k}")
+            close_enough(got[k], w, 5e-5, 3 * max(lr), f"{tag} {k}")
     if cfg.get("predict"):                     # the last batch's reconstructions with the trained weights (no dropout)
         out = dev.predict(csr, 0, Bs, cond=cdev) if sel is None else None
         if out is not None:
             want = ora.predict(ip, idx, val, [cond] if inc else None)
             np.testing.assert_allclose(out.cpu().numpy(), want, atol=5e-4 if bf16 else 1e-4, err_msg=f"{cfg} predict")
-    if bf16:
-        dev.close()
+    dev.close()
     return stats
 
 
@@ -251,9 +299,10 @@ def decoder_steps(r, N, h, B, seed):
     yield (r.standard_normal((B, c)) * 0.5).astype(np.float32)
 
 
-def check_decoder(r, N, h, B, act, seed, bf16=False, dz_tol=None, decode_tol=None):
+def check_decoder(r, N, h, B, act, seed, bf16=False, dz_tol=None, decode_tol=None, path="default", counters=None):
     """aae_decoder_step (DecodingRecommender: decoder only, input block from the conditions, dL/d(input) returned) against
-    OracleDecoder; bf16: both in bf16 mode, at the tolerances of tests/test_bf16_gpu.py."""
+    OracleDecoder; bf16: both in bf16 mode, at the tolerances of tests/test_bf16_gpu.py.  path, counters: as check_configuration's
+    (fp32 handles)."""
     import torch
     from aaerec._hip import HipAAE, DeviceCSR
     from oracle import aae_oracle as O
@@ -261,9 +310,11 @@ def check_decoder(r, N, h, B, act, seed, bf16=False, dz_tol=None, decode_tol=Non
     it = decoder_steps(r, N, h, B, seed)
     c, p = next(it)
     params = init_params(N, h, c, seed=seed)
-    dev = HipAAE(N, h, c, max_batch=B, rng_mode="inject", gen_lr=2e-3, reg_lr=2e-3, dropout=p, activation=act,
-                 **(dict(dtype="bf16") if bf16 else {}))
+    mk = dict(max_batch=B, rng_mode="inject", gen_lr=2e-3, reg_lr=2e-3, dropout=p, activation=act, **(dict(dtype="bf16") if bf16 else {}))
+    dev = HipAAE(N, h, c, **mk) if path == "default" else _forced_handle(path, lambda blocked: HipAAE(N, h, c, blocked_output=blocked, **mk))
     dev.load_params(params)
+    if counters is not None:
+        dev.profile_enable(True, kernels=OUT_KERNELS)
     ora = O.OracleDecoder(params, lr=2e-3, dropout=p, activation=act, conditions=[O.ConcatConst(c)], **(dict(bf16=True) if bf16 else {}))
     for s in range(3):
         ip, idx, val, zin, masks = next(it)
@@ -279,6 +330,8 @@ def check_decoder(r, N, h, B, act, seed, bf16=False, dz_tol=None, decode_tol=Non
         else:
             np.testing.assert_allclose(dev.losses()[0], want, rtol=5e-5, atol=2e-6)
             np.testing.assert_allclose(dz.cpu().numpy(), ora.last_dzin, rtol=5e-4, atol=1e-7)     # (entries are sums with cancellation, ~1e-4 in size)
+        if counters is not None:
+            _count_output_launches(dev, counters, B)
     got = dev.state_dict()
     zp = next(it)
     stats = None
@@ -295,3 +348,65 @@ def check_decoder(r, N, h, B, act, seed, bf16=False, dz_tol=None, decode_tol=Non
             close_enough(got[k], w, 5e-5, 6e-3, f"decoder N={N} h={h} c={c} B={B} {k}")
         np.testing.assert_allclose(dev.decode(torch.as_tensor(zp, device=dev.device)).cpu().numpy(), ora.predict([zp]), atol=2e-5)
     return stats
+
+
+def vae_draws(r, seed, N, h, B):
+    """The VAE case's own draws behind decoder_config's: code and condition widths, torch-initialised fc1 .. fc4, then per step
+    the batch, eps and the condition block.  -> (c, inc, the parameters by the reference's names, the three steps)"""
+    import torch
+    c, inc = int(r.integers(2, 100)), int(r.choice([0, 0, 9, 40]))
+    inc = min(inc, 206 - c)
+    g = torch.Generator().manual_seed(seed)
+
+    def lin(o, i):
+        k = 1.0 / np.sqrt(i)
+        return ((torch.rand(o, i, generator=g) * 2 - 1) * k).numpy(), ((torch.rand(o, generator=g) * 2 - 1) * k).numpy()
+    vp = {}
+    for name, (o, i) in (("fc1", (h, N)), ("fc21", (c, h)), ("fc22", (c, h)), ("fc3", (h, c + inc)), ("fc4", (N, h))):
+        vp[name + ".weight"], vp[name + ".bias"] = lin(o, i)
+    steps_ = []
+    for s in range(3):
+        Bs = B if s < 2 else max(1, B - int(r.integers(0, min(B, 9))))
+        ip, idx, val = batch(r, N, Bs, B)
+        eps = r.standard_normal((Bs, c)).astype(np.float32)
+        cond = (r.standard_normal((Bs, inc)) * 0.4).astype(np.float32) if inc else None
+        steps_.append((Bs, ip, idx, val, eps, cond))
+    return c, inc, vp, steps_
+
+
+def check_vae(r, N, h, B, act, seed, path="default"):
+    """aae_vae_step (VAE) against OracleVAE over decoder_config's draws, on a handle forced onto `path`."""
+    import pytest
+    import torch
+    from aaerec._hip import HipAAE, DeviceCSR
+    from oracle import aae_oracle as O
+    c, inc, vp, steps_ = vae_draws(r, seed, N, h, B)
+    dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", gen_lr=2e-3, reg_lr=2e-3, dropout=(0.0, 0.0),
+                                                      activation=act, vae=True))
+    dev.load_params({"enc.lin1.weight": vp["fc1.weight"], "enc.lin1.bias": vp["fc1.bias"],
+                     "enc.lin3.weight": np.vstack([vp["fc21.weight"], vp["fc22.weight"]]),
+                     "enc.lin3.bias": np.concatenate([vp["fc21.bias"], vp["fc22.bias"]]),
+                     "dec.lin1.weight": vp["fc3.weight"], "dec.lin1.bias": vp["fc3.bias"],
+                     "dec.lin3.weight": vp["fc4.weight"], "dec.lin3.bias": vp["fc4.bias"]})
+    ora = O.OracleVAE(vp, lr=2e-3, activation=act, conditions=[O.ConcatConst(inc)] if inc else [])
+    if path == "no_chain":
+        # the VAE's hidden half is a layer program and nothing else: layer by layer the library refuses the step - the status and
+        # the message, and the parameters as they were loaded
+        from aaerec import _hip
+        Bs, ip, idx, val, eps, cond = steps_[0]
+        with pytest.raises(_hip.AaeHipError, match=r"error -4: VAE mode needs the layer-chain kernels"):
+            dev.vae_step(DeviceCSR.from_arrays(ip, idx, val, N, dev.device), 0, Bs,
+                         cond=torch.as_tensor(cond, device=dev.device) if inc else None, eps=eps)
+        assert np.array_equal(dev.state_dict()["dec.lin3.weight"], vp["fc4.weight"])
+        return
+    for Bs, ip, idx, val, eps, cond in steps_:
+        dev.vae_step(DeviceCSR.from_arrays(ip, idx, val, N, dev.device), 0, Bs,
+                     cond=torch.as_tensor(cond, device=dev.device) if inc else None, eps=eps)
+        want = ora.partial_fit(ip, idx, val, eps, [cond] if inc else None)
+        l = dev.losses()
+        np.testing.assert_allclose((l[0] + l[1]) / Bs, want, rtol=5e-5)
+    got = dev.state_dict()
+    want = {"enc.lin1.weight": ora.p["fc1.weight"], "enc.lin3.weight": np.vstack([ora.p["fc21.weight"], ora.p["fc22.weight"]]),
+            "dec.lin1.weight": ora.p["fc3.weight"], "dec.lin3.weight": ora.p["fc4.weight"], "dec.lin3.bias": ora.p["fc4.bias"]}
+    for k, w in want.items():
+        close_enough(got[k], w, 5e-5, 6e-3, f"vae N={N} h={h} c={c} inc={inc} B={B} {k}")

@@ -52,12 +52,17 @@ class Restatement:
     """aae_output_layer_step restated: logits = dh2 V3^T + b3; F.binary_cross_entropy(sigmoid + 1e-12, T + 1e-12) and its
     gradient as autograd forms it, in fp32 (oracle.aae_oracle.sigmoid: 1 / (1 + exp(-l)), pinned to torch's saturation by
     tests/test_oracle_golden.py); dA2 = G V3; dV3 = G^T dh2, db3 = sum_b G; torch.optim.Adam.  bf16: the matrix products'
-    operands rounded to bf16 as the bf16 build defines them (tests/test_bf16_gpu.py _SliceEmu)."""
+    operands rounded to bf16 as the bf16 build defines them (tests/test_bf16_gpu.py _SliceEmu).  moments (m_w, v_w, m_b, v_b)
+    and step: Adam's state as aae_load_adam sets it before the first call; optimizer 'sgd': torch.optim.SGD
+    (tests/outlayer_cases.py)."""
 
-    def __init__(self, w, b, lr, scale, bf16):
-        from oracle.aae_oracle import Adam, bf16_round
+    def __init__(self, w, b, lr, scale, bf16, moments=None, step=0, optimizer="adam"):
+        from oracle.aae_oracle import SGD, Adam, bf16_round
         self.p = {"w": w.copy(), "b": b.copy()}
-        self.opt, self.scale = Adam(lr), scale
+        self.opt, self.scale = (Adam(lr) if optimizer == "adam" else SGD(lr)), scale
+        if moments is not None and optimizer == "adam":
+            for k in ("w", "b"):
+                self.opt.m[k], self.opt.v[k], self.opt.t[k] = moments["m_" + k].copy(), moments["v_" + k].copy(), int(step)
         self.R = bf16_round if bf16 else (lambda x: x)
 
     def forward(self, dh2):

@@ -15,7 +15,7 @@ N_SEEDS = int(os.environ.get("AAE_FUZZ_SEEDS", "28"))       # (a wider hunt: AAE
 SEEDS = list(range(N_SEEDS))
 
 from fuzz_cases import (ACTS, ACTS_R6, WIDE, batch as _batch, check_configuration as _check_configuration,      # noqa: F401
-                        check_decoder, close_enough as _close_enough, config as _config, decoder_config, wide_config)
+                        check_decoder, check_vae, close_enough as _close_enough, config as _config, decoder_config, wide_config)
 # (the generator, the step loop and the comparison live in tests/fuzz_cases.py: the bf16 fuzz runs the same implementation)
 
 
@@ -166,10 +166,6 @@ def test_random_decoder_and_vae_steps_with_a_further_activation_class_match_orac
 
 
 def _decoder_vae_case(seed, act_override=None):
-    import torch
-    from aaerec._hip import HipAAE, DeviceCSR
-    from oracle import aae_oracle as O
-    from oracle.dense_torch_port import init_params
     r, N, h, B, act = decoder_config(seed)
     if act_override:
         act = act_override
@@ -177,40 +173,8 @@ def _decoder_vae_case(seed, act_override=None):
         # ---- decoder only: the input block is what the condition plugins produced (width n_code here) ----
         check_decoder(r, N, h, B, act, seed)
         return
-    # ---- VAE ----
-    c, inc = int(r.integers(2, 100)), int(r.choice([0, 0, 9, 40]))
-    inc = min(inc, 206 - c)
-    g = torch.Generator().manual_seed(seed)
-
-    def lin(o, i):
-        k = 1.0 / np.sqrt(i)
-        return ((torch.rand(o, i, generator=g) * 2 - 1) * k).numpy(), ((torch.rand(o, generator=g) * 2 - 1) * k).numpy()
-    vp = {}
-    for name, (o, i) in (("fc1", (h, N)), ("fc21", (c, h)), ("fc22", (c, h)), ("fc3", (h, c + inc)), ("fc4", (N, h))):
-        vp[name + ".weight"], vp[name + ".bias"] = lin(o, i)
-    dev = HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", gen_lr=2e-3, reg_lr=2e-3, dropout=(0.0, 0.0),
-                 activation=act, vae=True)
-    dev.load_params({"enc.lin1.weight": vp["fc1.weight"], "enc.lin1.bias": vp["fc1.bias"],
-                     "enc.lin3.weight": np.vstack([vp["fc21.weight"], vp["fc22.weight"]]),
-                     "enc.lin3.bias": np.concatenate([vp["fc21.bias"], vp["fc22.bias"]]),
-                     "dec.lin1.weight": vp["fc3.weight"], "dec.lin1.bias": vp["fc3.bias"],
-                     "dec.lin3.weight": vp["fc4.weight"], "dec.lin3.bias": vp["fc4.bias"]})
-    ora = O.OracleVAE(vp, lr=2e-3, activation=act, conditions=[O.ConcatConst(inc)] if inc else [])
-    for s in range(3):
-        Bs = B if s < 2 else max(1, B - int(r.integers(0, min(B, 9))))
-        ip, idx, val = _batch(r, N, Bs, B)
-        eps = r.standard_normal((Bs, c)).astype(np.float32)
-        cond = (r.standard_normal((Bs, inc)) * 0.4).astype(np.float32) if inc else None
-        dev.vae_step(DeviceCSR.from_arrays(ip, idx, val, N, dev.device), 0, Bs,
-                     cond=torch.as_tensor(cond, device=dev.device) if inc else None, eps=eps)
-        want = ora.partial_fit(ip, idx, val, eps, [cond] if inc else None)
-        l = dev.losses()
-        np.testing.assert_allclose((l[0] + l[1]) / Bs, want, rtol=5e-5)
-    got = dev.state_dict()
-    want = {"enc.lin1.weight": ora.p["fc1.weight"], "enc.lin3.weight": np.vstack([ora.p["fc21.weight"], ora.p["fc22.weight"]]),
-            "dec.lin1.weight": ora.p["fc3.weight"], "dec.lin3.weight": ora.p["fc4.weight"], "dec.lin3.bias": ora.p["fc4.bias"]}
-    for k, w in want.items():
-        _close_enough(got[k], w, 5e-5, 6e-3, f"vae N={N} h={h} c={c} inc={inc} B={B} {k}")
+    # ---- VAE ---- (tests/fuzz_cases.py: the forced-path fuzz runs the same implementation)
+    check_vae(r, N, h, B, act, seed)
 
 
 @pytest.mark.parametrize("scheme", ["vocab", "replicated", "vocab2", "shard"])
