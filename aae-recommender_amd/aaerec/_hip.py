@@ -217,6 +217,14 @@ _PROTOS = {
     "aae_bag_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64,
                                  C.c_void_p]),
+    "aae_bag_csr_scratch_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "aae_bag_csr_encode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_int64, C.c_void_p]),
+    "aae_bag_csr_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32,
+                                     C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
     "aae_csr_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_cooc_scores": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p]),
@@ -480,6 +488,158 @@ def bag_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, reduce=BAG_SUM, 
                                              int(reduce), int(padding_idx), _ptr(dout), dout.stride(0),
                                              CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step),
                                              C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+
+
+# ---- bags from a resident CSR (aae_bag_csr_*; csrc/cond_csr.h) -------------------------------------------------------
+BAG_CSR_SORT = 4096              # kBagCsrSort: keys one workgroup sorts in LDS, the run length the merge passes start from
+BAG_CSR_SCAN = 1024              # kBagCsrScanNT: rows the row scan takes in one round
+BAG_CSR_UPDATE_WAVES = 4096 * 4  # kBagCsrMaxGrid * kCatWaves: sorted positions the update launch takes in one grid round
+BAG_CSR_MAX_ENTRIES = 1 << 22    # kBagCsrMaxEntries: entries of a step
+
+
+def bag_csr_scratch_bytes(max_rows, max_entries):
+    """Bytes of the scratch a step of max_rows rows and at most max_entries entries needs (arithmetic: no GPU)."""
+    n = C.c_int64()
+    _check(load_library().aae_bag_csr_scratch_bytes(int(max_rows), int(max_entries), C.byref(n)))
+    return n.value
+
+
+def bags_from_lists(lists):
+    """(indptr int64 [n + 1], indices int32) of a list of value lists, entry order kept.  A value that does not fit an int32
+    names no table row: it becomes -1, which every reduction skips."""
+    lens = np.fromiter((len(row) for row in lists), dtype=np.int64, count=len(lists))
+    indptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    flat = np.fromiter((v for row in lists for v in row), dtype=np.int64, count=int(indptr[-1]))
+    return indptr, _bag_ids(flat)
+
+
+def _bag_ids(flat):
+    flat = np.asarray(flat, dtype=np.int64)
+    return np.where((flat < -2 ** 31) | (flat >= 2 ** 31), -1, flat).astype(np.int32)
+
+
+def bags_from_offsets(indices, offsets, weights=None, include_last_offset=False):
+    """(indptr, indices, weights) of nn.EmbeddingBag's 1-D call form: bag i holds indices[offsets[i]:offsets[i + 1]], the
+    last one runs to the end - or, include_last_offset, offsets already ends with len(indices)."""
+    indices = np.asarray(indices).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    indptr = offsets if include_last_offset else np.concatenate([offsets, [len(indices)]]).astype(np.int64)
+    if len(indptr) < 1 or (len(indptr) > 1 and indptr[0] != 0) or (np.diff(indptr) < 0).any() or indptr[-1] > len(indices):
+        raise ValueError("aaerec: offsets must start at 0, ascend and stay within the indices")
+    if weights is not None:
+        weights = np.asarray(weights, dtype=np.float32).reshape(-1)
+        if len(weights) != len(indices):
+            raise ValueError("aaerec: per_sample_weights must have the shape of the indices")
+    return np.ascontiguousarray(indptr), _bag_ids(indices), weights
+
+
+class DeviceBags:
+    """The value lists of a whole corpus as a CSR resident in HBM (int64 indptr, int32 indices - table rows, in list order,
+    repeats kept -, optionally float32 per-sample weights), uploaded once.  `lengths` (device int32) holds the lists'
+    lengths; entry_bound(rows) bounds the entries of any `rows` lists from the host's sorted copy, so a step needs no
+    synchronisation to size its scratch.  window() names the rows of a step."""
+
+    def __init__(self, lists, device, weights=None):
+        indptr, indices = bags_from_lists(lists)
+        self._init(indptr, indices, None if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1), device)
+
+    @classmethod
+    def from_offsets(cls, indices, offsets, device, weights=None, include_last_offset=False):
+        self = cls.__new__(cls)
+        self._init(*bags_from_offsets(indices, offsets, weights, include_last_offset), device)
+        return self
+
+    def _init(self, indptr, indices, weights, device):
+        self.device = torch.device(device)
+        self.n_docs, self.nnz = len(indptr) - 1, int(indptr[-1])
+        if weights is not None and len(weights) != len(indices):
+            raise ValueError("aaerec: per_sample_weights must have the shape of the indices")
+        lens = np.diff(indptr)
+        self._cum = np.cumsum(np.sort(lens)[::-1])           # _cum[k - 1]: the entries of the k longest lists
+        self.indptr = upload(indptr, device)
+        self.indices = upload(indices if len(indices) else np.zeros(1, dtype=np.int32), device)
+        self.weights = None if weights is None else upload(weights if len(weights) else np.zeros(1, dtype=np.float32), device)
+        self.lengths = upload(lens.astype(np.int32), device)
+        self.device = self.indptr.device                     # ('cuda' resolved to the device the arrays went to)
+        self._scratch = None
+
+    def __len__(self):
+        return self.n_docs
+
+    def entry_bound(self, rows):
+        """No `rows` lists of the corpus hold more entries than this (at least 1)."""
+        if self.n_docs == 0 or rows < 1:
+            return 1
+        return max(1, int(self._cum[min(int(rows), self.n_docs) - 1]))
+
+    def scratch(self, rows):
+        """(buffer, bytes) for a step of `rows` rows: grown when a call needs more, never per step."""
+        need = bag_csr_scratch_bytes(rows, self.entry_bound(rows))
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._scratch, self._scratch.numel()
+
+    def window(self, row_ids=None, row0=0, rows=None):
+        """The rows of a step: a device int32 tensor of row ids (a window of the epoch's permutation), or the contiguous
+        rows row0 .. row0 + rows."""
+        return BagWindow(self, row_ids, int(row0), int(row_ids.numel() if row_ids is not None else rows))
+
+
+class BagWindow:
+    """(DeviceBags, rows of a step): what a resident condition's encode_into / update_from take instead of value lists."""
+    __slots__ = ("bags", "row_ids", "row0", "rows")
+
+    def __init__(self, bags, row_ids, row0, rows):
+        if row_ids is not None and (row_ids.dtype != torch.int32 or row_ids.dim() != 1 or not row_ids.is_contiguous()
+                                    or row_ids.device != bags.device):
+            raise TypeError("aaerec: row_ids must be a contiguous int32 vector on the bags' device")
+        self.bags, self.row_ids, self.row0, self.rows = bags, row_ids, row0, rows
+
+    def __len__(self):
+        return self.rows
+
+
+def _bag_csr_args(table, view, block):
+    if not (table.is_cuda and block.is_cuda and view.bags.indptr.is_cuda):
+        raise RuntimeError("aaerec: the bag kernels take GPU tensors (there is no CPU path)")
+    if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2:
+        raise TypeError("aaerec: embedding table must be a contiguous float32 [vocab, dim] tensor")
+    if block.dtype != torch.float32 or block.dim() != 2 or block.stride(1) != 1 or block.shape[0] != view.rows \
+            or block.shape[1] != table.shape[1]:
+        raise TypeError("aaerec: block must be a float32 [rows, dim] view with unit column stride")
+
+
+def bag_csr_encode(table, view, out, reduce=BAG_SUM, padding_idx=-1):
+    """bag_encode over the rows `view` (a BagWindow) of a resident DeviceBags: the same bits as bag_encode / cat_encode on
+    those lists padded to their longest.  `out` may be a column slice of the step's condition block."""
+    _bag_csr_args(table, view, out)
+    b = view.bags
+    scratch, nbytes = b.scratch(view.rows)
+    with torch.cuda.device(table.device):
+        _check(load_library().aae_bag_csr_encode(
+            _ptr(table), table.shape[0], table.shape[1], _ptr(b.indptr), _ptr(b.indices), _ptr(b.weights), b.n_docs, b.nnz,
+            _ptr(view.row_ids), view.row0, view.rows, int(reduce), int(padding_idx), _ptr(out), out.stride(0), _ptr(scratch),
+            nbytes, C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+
+
+def bag_csr_update(table, exp_avg, exp_avg_sq, view, dout, lr, step, reduce=BAG_SUM, padding_idx=-1, grad_scratch=None,
+                   sparse=False):
+    """bag_update over the rows `view` of a resident DeviceBags: entries grouped by table row with a sort (no quadratic scan,
+    nothing on the host), summed in the padded route's order - the same bits.  Arguments as bag_update."""
+    _bag_csr_args(table, view, dout)
+    for t in (exp_avg, exp_avg_sq) + ((grad_scratch,) if grad_scratch is not None else ()):
+        if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
+            raise TypeError("aaerec: optimiser state must match the embedding table")
+    b = view.bags
+    scratch, nbytes = b.scratch(view.rows)
+    with torch.cuda.device(table.device):
+        _check(load_library().aae_bag_csr_update(
+            _ptr(table), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(grad_scratch), table.shape[0], table.shape[1], _ptr(b.indptr),
+            _ptr(b.indices), _ptr(b.weights), b.n_docs, b.nnz, _ptr(view.row_ids), view.row0, view.rows,
+            b.entry_bound(view.rows), int(reduce), int(padding_idx), _ptr(dout), dout.stride(0),
+            CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step), _ptr(scratch), nbytes,
+            C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
 
 
 def csr_embed(csr, table):

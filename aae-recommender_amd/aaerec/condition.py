@@ -295,11 +295,39 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
         p = self.embedding_bag.padding_idx
         return -1 if p is None else int(p)
 
+    @staticmethod
+    def offsets_form(inputs):
+        """True for nn.EmbeddingBag's other call form as condition data: the tuple (input_1d, offsets) or
+        (input_1d, offsets, per_sample_weights)."""
+        ndim = lambda x: x.dim() if torch.is_tensor(x) else np.ndim(x)           # noqa: E731
+        return isinstance(inputs, tuple) and len(inputs) in (2, 3) and inputs[0] is not None and inputs[1] is not None \
+            and all(x is None or ndim(x) == 1 for x in inputs)
+
+    def resident(self, inputs, device):
+        """The bags of an (input_1d, offsets[, per_sample_weights]) corpus as a _hip.DeviceBags, uploaded once
+        (include_last_offset as the module says); None for 2-D input, which stays as it is."""
+        if not self.offsets_form(inputs):
+            return None
+        from . import _hip
+        host = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)       # noqa: E731
+        weights = inputs[2] if len(inputs) == 3 else None
+        if weights is not None and self.embedding_bag.mode != "sum":
+            raise ValueError("EmbeddingBagCondition: per_sample_weights go with mode='sum' only")
+        return _hip.DeviceBags.from_offsets(host(inputs[0]), host(inputs[1]), device,
+                                            weights=None if weights is None else host(weights),
+                                            include_last_offset=self.embedding_bag.include_last_offset)
+
     def encode_into(self, out, inputs, width=None):
         """encode(inputs) written into `out` ([rows, embedding_dim], may be a column slice of a wider block).  width is
-        accepted for the protocol's sake: 2-D input has one width, and no mode divides by it."""
+        accepted for the protocol's sake: 2-D input has one width, and no mode divides by it.  inputs: a [rows, width] index
+        block, or a window of resident bags (_hip.BagWindow)."""
         from . import _hip
         w = self.embedding_bag.weight
+        if isinstance(inputs, _hip.BagWindow):
+            self._idx = inputs
+            _hip.bag_csr_encode(w.data, inputs, out, reduce=self._BAG_MODES[self.embedding_bag.mode],
+                                padding_idx=self._padding_idx())
+            return
         self._idx = self._index_block(inputs, w.device)
         _hip.bag_encode(w.data, self._idx, out, reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx())
 
@@ -310,7 +338,7 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
         from . import _hip
         w = self.embedding_bag.weight
         if inputs is not None:
-            self._idx = self._index_block(inputs, w.device)
+            self._idx = inputs if isinstance(inputs, _hip.BagWindow) else self._index_block(inputs, w.device)
         st = self.optimizer.state[w]
         if "exp_avg" not in st:
             st["step"] = torch.tensor(0.0)
@@ -318,9 +346,10 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
         if getattr(self, "_grad_scratch", None) is None:
             self._grad_scratch = torch.zeros_like(w.data)
         st["step"] += 1
-        _hip.bag_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
-                        int(st["step"]), reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx(),
-                        grad_scratch=self._grad_scratch)
+        update = _hip.bag_csr_update if isinstance(self._idx, _hip.BagWindow) else _hip.bag_update
+        update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
+               int(st["step"]), reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx(),
+               grad_scratch=self._grad_scratch)
 
 
 class CategoricalCondition(ConcatenationBasedConditioning):
@@ -405,7 +434,20 @@ class CategoricalCondition(ConcatenationBasedConditioning):
                 and self.reduce in (None, "sum", "mean", "max")
                 and not self.embedding_params and self.embedding_dim <= 256)
 
+    _CSR_MODES = {"sum": 0, "mean": 1, "max": 3}          # _hip.BAG_SUM / BAG_MEAN_WIDTH / BAG_MAX_PAD0
+
+    def resident(self, inputs, device):
+        """The transformed condition data of a whole corpus in HBM, uploaded once: the value lists as a _hip.DeviceBags
+        (reduce sum / mean / max; a step then hands encode_into a window of it), or - reduce=None, one value a document -
+        the column as an int32 tensor a step selects its rows from on the device."""
+        from . import _hip
+        if self.reduce is None:
+            return _hip.upload(np.asarray(inputs, dtype=np.int32).reshape(-1), device)
+        return _hip.DeviceBags(inputs, device)
+
     def _index_block(self, inputs, device, width=None):
+        if self.reduce is None and torch.is_tensor(inputs) and inputs.is_cuda:      # rows of the resident column
+            return inputs.to(device=device, dtype=torch.int32).reshape(-1, 1).contiguous()
         if self.reduce is None:
             arr = np.asarray(inputs, dtype=np.int32).reshape(-1, 1)
         else:
@@ -425,8 +467,12 @@ class CategoricalCondition(ConcatenationBasedConditioning):
         width: pad to at least this many values (a rank's share of a batch uses the whole batch's width)."""
         from . import _hip
         w = self.embedding.weight
+        if isinstance(inputs, _hip.BagWindow):      # resident value lists: the same bits without the padded block
+            self._idx = inputs
+            _hip.bag_csr_encode(w.data, inputs, out, reduce=self._CSR_MODES[self.reduce], padding_idx=self.padding_idx)
+            return
         self._idx = self._index_block(inputs, w.device, width)
-        if self.reduce == "max":        # hid.max(1)[0]: a padding slot is a candidate of value 0 (aae_bag_*, AAE_BAG_MAX_PAD0)
+        if self.reduce == "max":     # hid.max(1)[0]: a padding slot is a candidate of value 0 (aae_bag_*, AAE_BAG_MAX_PAD0)
             _hip.bag_encode(w.data, self._idx, out, reduce=_hip.BAG_MAX_PAD0, padding_idx=self.padding_idx)
         else:
             _hip.cat_encode(w.data, self._idx, out, mean=self.reduce == "mean")
@@ -437,7 +483,7 @@ class CategoricalCondition(ConcatenationBasedConditioning):
         from . import _hip
         w = self.embedding.weight
         if inputs is not None:
-            self._idx = self._index_block(inputs, w.device)
+            self._idx = inputs if isinstance(inputs, _hip.BagWindow) else self._index_block(inputs, w.device)
         st = self.optimizer.state[w]
         if "exp_avg" not in st:
             st["step"] = 0 if self.sparse else torch.tensor(0.0)
@@ -445,6 +491,12 @@ class CategoricalCondition(ConcatenationBasedConditioning):
         if (not self.sparse or self.reduce == "max") and getattr(self, "_grad_scratch", None) is None:
             self._grad_scratch = torch.zeros_like(w.data)
         st["step"] += 1
+        if isinstance(self._idx, _hip.BagWindow):
+            _hip.bag_csr_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
+                                int(st["step"]), reduce=self._CSR_MODES[self.reduce], padding_idx=self.padding_idx,
+                                grad_scratch=self._grad_scratch if (not self.sparse or self.reduce == "max") else None,
+                                sparse=self.sparse)
+            return
         if self.reduce == "max":        # the winners are recomputed from the table: nothing has touched it since encode_into
             _hip.bag_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
                             int(st["step"]), reduce=_hip.BAG_MAX_PAD0, padding_idx=self.padding_idx,

@@ -19,7 +19,7 @@ import scipy.sparse as sp
 import torch
 
 from . import _hip, ranking
-from .aae import TORCH_OPTIMIZERS, AdversarialAutoEncoder, _take, _validate_targets, loss_targets
+from .aae import TORCH_OPTIMIZERS, AdversarialAutoEncoder, _take, _validate_targets, loss_targets, resident_condition_data
 from .base import Recommender
 from .condition import _check_conditions
 
@@ -125,6 +125,13 @@ class VAE:
 
     _cond_fn = AdversarialAutoEncoder._cond_fn
 
+    # True: device-native trainable conditions read their data from HBM, uploaded once per fit / ranking call (aae.py:
+    # resident_condition_data); False (the default): the padded per-step route
+    resident_conditions = False
+
+    def _is_device_native(self):
+        return self._cond_native
+
     def _step(self, csr, n_rows, rows, c_batch):
         if c_batch is not None and not self._cond_native:
             # the step cut at the condition boundary (vae.py:120-130, 175-181)
@@ -171,6 +178,8 @@ class VAE:
         X = X.tocsr()
         _validate_targets(X)
         csr = _hip.DeviceCSR(X, self.device)             # the corpus stays resident in HBM
+        if use_condition:
+            condition_data = resident_condition_data(self, condition_data)
         n_docs = X.shape[0]
         self.train()
         if self.conditions:
@@ -183,8 +192,9 @@ class VAE:
             perm_dev = torch.as_tensor(perm.astype(np.int32), device=self.device)
             for start in range(0, n_docs, self.batch_size):
                 idx = perm[start:start + self.batch_size]
-                c_batch = [_take(c, idx) for c in condition_data] if use_condition else None
-                self._step(csr, len(idx), perm_dev[start:start + len(idx)], c_batch)
+                rows = perm_dev[start:start + len(idx)]
+                c_batch = [_take(c, idx, rows) for c in condition_data] if use_condition else None
+                self._step(csr, len(idx), rows, c_batch)
             if self.verbose:
                 print()
         self.loss()
@@ -202,6 +212,8 @@ class VAE:
         if test_loss:
             _validate_targets(Xs)
         csr = _hip.DeviceCSR(Xs, self.device)
+        if use_condition:
+            condition_data = resident_condition_data(self, condition_data)
         pred = _hip.HostRows(Xs.shape[0], Xs.shape[1], self.device)
         bce, kl = [], []
         with torch.no_grad():
@@ -275,6 +287,8 @@ class VAE:
         if self.conditions:
             self.conditions.eval()
         csr = _hip.DeviceCSR(Xs, self.device)
+        if use_condition:
+            condition_data = resident_condition_data(self, condition_data)
         n_rows, bs = Xs.shape[0], self.batch_size
         eps_all = None
         if self.rng_mode == "reference":

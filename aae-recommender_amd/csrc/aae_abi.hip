@@ -49,6 +49,7 @@
 #include "chain16x3.h"
 #include "cond_embed.h"
 #include "cond_bag.h"
+#include "cond_csr.h"
 #include "w1_update.h"
 #include "dae_corrupt.h"
 

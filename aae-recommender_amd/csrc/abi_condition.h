@@ -1,5 +1,5 @@
 // Entry points of the trainable categorical and embedding-bag conditions and of the CSR helpers (cond_embed.h, cond_bag.h,
-// kernels.h).
+// cond_csr.h, kernels.h).
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
 #pragma once
 
@@ -111,6 +111,138 @@ int aae_bag_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, 
     } else if (is_max) {
         hipLaunchKernelGGL(bag_sparse_adam_kernel, grid, block, 0, S(stream), u);
         LAUNCHCHK("bag_sparse_adam");
+    }
+    return AAE_OK;
+}
+
+// ---- the same bags from a resident CSR (cond_csr.h) ----------------------------------------------------------
+// scratch: two key buffers of max_entries, then the int32 arrays hdr[16], off[max_rows + 1], live[max_rows],
+// rowof[max_entries], win[max_rows][256]; rounded up to 256 bytes
+static int64_t bag_csr_bytes(int64_t max_rows, int64_t max_entries) {
+    const int64_t ints = 16 + (max_rows + 1) + max_rows + max_entries + max_rows * kCatMaxDim;
+    return (16 * max_entries + 4 * ints + 255) / 256 * 256;
+}
+
+int aae_bag_csr_scratch_bytes(int64_t max_rows, int64_t max_entries, int64_t* bytes_out) {
+    if (!bytes_out) return fail(AAE_EINVAL, "aae_bag_csr_scratch_bytes: bytes_out is NULL");
+    if (max_rows < 0 || max_entries < 0) return fail(AAE_EINVAL, "aae_bag_csr_scratch_bytes: max_rows and max_entries must be >= 0");
+    if (max_rows > INT32_MAX || max_entries > INT32_MAX)
+        return fail(AAE_EINVAL, "aae_bag_csr_scratch_bytes: max_rows and max_entries must fit an int32");
+    *bytes_out = bag_csr_bytes(max_rows, max_entries);
+    return AAE_OK;
+}
+
+static void bag_csr_carve(BagCsr& c, void* scratch_dev, int32_t rows, int64_t max_entries) {
+    c.keys_a = (unsigned long long*)scratch_dev;
+    c.keys_b = c.keys_a + max_entries;
+    c.hdr = (int*)(c.keys_b + max_entries);
+    c.off = c.hdr + 16;
+    c.live = c.off + rows + 1;
+    c.rowof = c.live + rows;
+    c.win = c.rowof + max_entries;
+    c.max_entries = (int)max_entries;
+}
+
+// the checks of both calls (who: the entry point's name); fills c
+static int bag_csr_check(const char* who, BagCsr& c, int32_t vocab, int32_t dim, const int64_t* indptr_dev,
+                         const int32_t* indices_dev, const float* weights_dev, int64_t n_docs, int64_t nnz,
+                         const int32_t* row_ids_dev, int64_t row0, int32_t rows, int64_t max_entries, int32_t reduce,
+                         int32_t padding_idx, void* scratch_dev, int64_t scratch_bytes) {
+#define BAG_CSR_FAIL(text) return fail(AAE_EINVAL, std::string(who) + ": " + text)
+    if (vocab < 1) BAG_CSR_FAIL("vocab must be >= 1");
+    if (dim < 1 || dim > kCatMaxDim) BAG_CSR_FAIL("dim must be within [1, 256]");
+    if (rows < 1) BAG_CSR_FAIL("rows must be >= 1");
+    if (!indptr_dev || !indices_dev) BAG_CSR_FAIL("indptr_dev / indices_dev is NULL");
+    if (n_docs < 1 || nnz < 0) BAG_CSR_FAIL("need n_docs >= 1 and nnz >= 0");
+    if (!row_ids_dev && (row0 < 0 || row0 + rows > n_docs)) BAG_CSR_FAIL("row0 .. row0 + rows is not inside [0, n_docs)");
+    if (max_entries < 0) BAG_CSR_FAIL("max_entries must be >= 0");
+    if (max_entries > kBagCsrMaxEntries) BAG_CSR_FAIL("max_entries: a step takes at most 2^22 entries");
+    if (reduce < AAE_BAG_SUM || reduce > AAE_BAG_MAX) BAG_CSR_FAIL("unknown reduce");
+    if (weights_dev && reduce != AAE_BAG_SUM) BAG_CSR_FAIL("weights_dev goes with reduce AAE_BAG_SUM only");
+    if (padding_idx < -1 || padding_idx >= vocab) BAG_CSR_FAIL("padding_idx must be -1 or a table row");
+    if (!scratch_dev || ((uintptr_t)scratch_dev & 7)) BAG_CSR_FAIL("scratch_dev is NULL or not 8-byte aligned");
+    if (scratch_bytes < bag_csr_bytes(rows, max_entries)) BAG_CSR_FAIL("scratch_bytes is smaller than aae_bag_csr_scratch_bytes(rows, max_entries)");
+#undef BAG_CSR_FAIL
+    c.indptr = (const long long*)indptr_dev; c.indices = indices_dev; c.weights = weights_dev;
+    c.n_docs = n_docs; c.nnz = nnz; c.row_ids = row_ids_dev; c.row0 = row0; c.rows = rows;
+    bag_csr_carve(c, scratch_dev, rows, max_entries);
+    return AAE_OK;
+}
+
+int aae_bag_csr_encode(const float* table_dev, int32_t vocab, int32_t dim, const int64_t* indptr_dev,
+                       const int32_t* indices_dev, const float* weights_dev, int64_t n_docs, int64_t nnz,
+                       const int32_t* row_ids_dev, int64_t row0, int32_t rows, int32_t reduce, int32_t padding_idx,
+                       float* out_dev, int64_t out_ld, void* scratch_dev, int64_t scratch_bytes, void* stream) {
+    BagCsr c;
+    TRY(bag_csr_check("aae_bag_csr_encode", c, vocab, dim, indptr_dev, indices_dev, weights_dev, n_docs, nnz, row_ids_dev, row0,
+                      rows, 0, reduce, padding_idx, scratch_dev, scratch_bytes));
+    if (!table_dev || !out_dev || out_ld < dim) return fail(AAE_EINVAL, "aae_bag_csr_encode: table_dev / out_dev is NULL or out_ld < dim");
+    if (reduce == AAE_BAG_MEAN_WIDTH || reduce == AAE_BAG_MAX_PAD0) {        // the two modes that see the width
+        hipLaunchKernelGGL(bagcsr_rowinfo_kernel, dim3(1), dim3(kBagCsrScanNT), 0, S(stream), c);
+        LAUNCHCHK("bagcsr_rowinfo");
+    }
+    hipLaunchKernelGGL(bagcsr_encode_kernel, dim3(rows, (dim + 63) / 64), dim3(64), 0, S(stream), c, table_dev, vocab, dim,
+                       reduce, padding_idx, out_dev, (long long)out_ld);
+    LAUNCHCHK("bagcsr_encode");
+    return AAE_OK;
+}
+
+int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                       int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev, const float* weights_dev,
+                       int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
+                       int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
+                       int32_t optimizer, double lr, int64_t step, void* scratch_dev, int64_t scratch_bytes, void* stream) {
+    BagCsrUpdate p;
+    memset(&p, 0, sizeof(p));
+    TRY(bag_csr_check("aae_bag_csr_update", p.c, vocab, dim, indptr_dev, indices_dev, weights_dev, n_docs, nnz, row_ids_dev, row0,
+                      rows, max_entries, reduce, padding_idx, scratch_dev, scratch_bytes));
+    if (max_entries < 1) return fail(AAE_EINVAL, "aae_bag_csr_update: max_entries must be >= 1");
+    if (!table_dev || !exp_avg_dev || !exp_avg_sq_dev || !dout_dev || dout_ld < dim)
+        return fail(AAE_EINVAL, "aae_bag_csr_update: table/state/dout is NULL or dout_ld < dim");
+    if (optimizer != AAE_CAT_SPARSE_ADAM && optimizer != AAE_CAT_ADAM) return fail(AAE_EINVAL, "aae_bag_csr_update: unknown optimizer");
+    const bool is_max = reduce == AAE_BAG_MAX_PAD0 || reduce == AAE_BAG_MAX;
+    if ((optimizer == AAE_CAT_ADAM || is_max) && !grad_scratch_dev)
+        return fail(AAE_EINVAL, "aae_bag_csr_update: dense Adam and the max modes need grad_scratch_dev");
+    if (step < 1) return fail(AAE_EINVAL, "aae_bag_csr_update: step counts from 1");
+    const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
+    CatUpdate& a = p.u.c;
+    a.table = table_dev; a.m = exp_avg_dev; a.v = exp_avg_sq_dev;
+    a.gdense = (optimizer == AAE_CAT_ADAM || is_max) ? grad_scratch_dev : nullptr;
+    a.d = dout_dev; a.ldd = dout_ld; a.vocab = vocab; a.dim = dim; a.rows = rows;
+    a.neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
+    p.u.reduce = reduce; p.u.pad = padding_idx;
+    hipStream_t s = S(stream);
+    const BagCsr& c = p.c;
+    hipLaunchKernelGGL(bagcsr_rowinfo_kernel, dim3(1), dim3(kBagCsrScanNT), 0, s, c);
+    hipLaunchKernelGGL(bagcsr_sort_kernel, dim3((unsigned)((max_entries + kBagCsrSort - 1) / kBagCsrSort)), dim3(kBagCsrNT), 0, s, c,
+                       vocab, padding_idx);
+    // merge passes up to the entry bound (E itself stays on the device); the sorted keys end in keys_a or keys_b
+    unsigned long long *src = c.keys_a, *dst = c.keys_b;
+    for (int64_t w = kBagCsrSort; w < max_entries; w <<= 1) {
+        hipLaunchKernelGGL(bagcsr_merge_kernel, dim3((unsigned)((max_entries + kBagCsrNT - 1) / kBagCsrNT)), dim3(kBagCsrNT), 0, s,
+                           src, dst, c.hdr, (int)w);
+        unsigned long long* t = src; src = dst; dst = t;
+    }
+    p.sorted = src;
+    if (reduce >= AAE_BAG_MEAN_COUNT)
+        hipLaunchKernelGGL(bagcsr_rowpass_kernel, dim3(rows, reduce == AAE_BAG_MEAN_COUNT ? 1 : (dim + 63) / 64), dim3(64), 0, s, c,
+                           table_dev, vocab, dim, reduce, padding_idx);
+    const int64_t want = (max_entries + kCatWaves - 1) / kCatWaves;
+    const dim3 grid((unsigned)(want < kBagCsrMaxGrid ? want : kBagCsrMaxGrid)), block(64 * kCatWaves);
+    hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, p);
+    LAUNCHCHK("bagcsr_update");
+    if (optimizer == AAE_CAT_ADAM) {
+        OptScalars sc; memset(&sc, 0, sizeof(sc));
+        sc.t = step; sc.neg_step_size = (float)(-(lr / bc1)); sc.bc2_sqrt = (float)sqrt(bc2); sc.lr = lr;
+        sc.inv_bc2_sqrt = 1.0f / sc.bc2_sqrt;
+        const size_t total = (size_t)vocab * dim;
+        hipLaunchKernelGGL(cat_dense_adam_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, table_dev,
+                           exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, total, sc);
+        LAUNCHCHK("bagcsr_dense_adam");
+    } else if (is_max) {
+        p.apply_only = 1;
+        hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, p);
+        LAUNCHCHK("bagcsr_sparse_adam");
     }
     return AAE_OK;
 }

@@ -1,0 +1,307 @@
+// Trainable bag conditions from a resident CSR: cond_bag.h's five reductions, their backward and the optimiser step over the
+// value lists of a corpus that was uploaded once, without the padded [rows][width] rectangle and without the quadratic
+// duplicate scan of cat_update_kernel / bag_update_kernel.
+//
+//   bag CSR   indptr int64 [n_docs + 1], indices int32 (table rows), optionally weights fp32 (per_sample_weights, sum only).
+//             NOT canonical: a row may name a table row several times, and the order of its entries is the order of the value
+//             list.  A step names its rows by row_ids int32 [rows] (a window of the epoch's permutation) or, row_ids NULL, as
+//             row0 .. row0 + rows.  A row id outside [0, n_docs) is an empty row; offsets are clamped into [0, nnz].
+//   entry e   the step's entries numbered in (position of the row in the batch, position in the row) order - the slot order
+//             of the padded route with its padding slots left out.
+//   width     the longest list among the step's rows, dead entries counted, at least 1: what _pad_batch pads to.  It is
+//             computed by bagcsr_rowinfo_kernel and read from the scratch by the launches behind it - the host never sees it.
+//
+// Encode: bagcsr_reduce_col is bag_reduce_col over a row's entries; the slots the padded form would add behind them are dead
+// in every mode, so they change nothing but kBagMeanWidth's divisor (the width) and kBagMaxPad0's candidate of value 0 (one
+// comparison when the row is shorter than the width).  Same operations in the same order: the same bits as aae_bag_encode /
+// aae_cat_encode on the padded form.
+//
+// Update, the grouping: every entry becomes the 64-bit key (table row << 32 | e), a dead entry (padding row, out of range)
+// (0xFFFFFFFF << 32 | e).  The keys are distinct, so their ascending order is unique whatever sorts them, and it lists the
+// entries of a table row next to each other in entry order - the order the padded route sums them in.
+//   bagcsr_rowinfo_kernel   one workgroup: the rows' lengths, their exclusive scan off[rows + 1], E and the width
+//   bagcsr_sort_kernel      a workgroup per run of kBagCsrSort entries: builds the run's keys (the row of entry e by a binary
+//                           search in off) and sorts them in LDS (bitonic, 32 KB: four workgroups a CU)
+//   bagcsr_merge_kernel     one launch per doubling of the run width: a thread per key, its place is its index in its own
+//                           run plus a lower-bound search in the sibling run.  The number of passes follows from the
+//                           caller's entry bound (the host does not know E); a pass whose runs already span E copies.
+//   bagcsr_rowpass_kernel   max modes: the winner of every (row, column), recomputed from the untouched table; kBagMeanCount:
+//                           the live entries of every row.  Once per row, not once per contributing entry.
+//   bagcsr_update_kernel    a wavefront per sorted position (grid-stride): the first key of a table row owns it, walks the
+//                           row's run, sums the contributions in that order (cat_update_kernel's arithmetic) and applies
+//                           SparseAdam or writes the [vocab][dim] gradient scratch, as bag_update_kernel does.
+// Work: O(E) for everything but the sort; the sort is O(E log^2 kBagCsrSort) in LDS plus log2(bound / kBagCsrSort) merge passes
+// of O(E log E) each.  Nothing is quadratic, nothing is proportional to vocab but dense Adam itself, there is no [vocab]
+// marker, no atomic of any kind, and every loop is bounded by a length read once (E, a row's length, the row count).
+// Entries beyond the caller's bound are dropped (hdr[2] is raised), never written.
+#pragma once
+#include "cond_bag.h"
+
+namespace aae {
+
+constexpr int kBagCsrSort = 4096;             // keys a workgroup sorts in LDS in one go; the run length the merges start from
+constexpr int kBagCsrNT = 256;                // threads of the sort and merge workgroups
+constexpr int kBagCsrScanNT = 1024;           // rows bagcsr_rowinfo_kernel scans in one round
+constexpr int kBagCsrMaxGrid = 4096;          // workgroups of the update launch (grid-stride over the sorted keys)
+constexpr int kBagCsrMaxEntries = 1 << 22;    // entries of a step
+constexpr unsigned kBagCsrDead = 0xFFFFFFFFu;
+static_assert((kBagCsrSort & (kBagCsrSort - 1)) == 0, "the bitonic network runs over powers of two");
+
+struct BagCsr {
+    const long long* indptr; const int* indices; const float* weights;      // weights NULL: none
+    long long n_docs, nnz;
+    const int* row_ids; long long row0; int rows;
+    // the scratch (abi_condition.h: bag_csr_carve)
+    unsigned long long* keys_a; unsigned long long* keys_b;                 // [max_entries] each
+    int* hdr;                                                               // [0] E, [1] width, [2] entries were dropped
+    int* off;                                                               // [rows + 1] first entry of every row of the step
+    int* live;                                                              // [rows] kBagMeanCount's divisors
+    int* rowof;                                                             // [max_entries] the row of entry e
+    int* win;                                                               // [rows][dim] max modes: the winning position
+    int max_entries;
+};
+
+// the entries [lo, hi) of row r of the step
+__device__ __forceinline__ void bagcsr_row(const BagCsr& c, int r, long long* lo, long long* hi) {
+    const long long id = c.row_ids ? (long long)c.row_ids[r] : c.row0 + r;
+    long long a = 0, b = 0;
+    if (id >= 0 && id < c.n_docs) { a = c.indptr[id]; b = c.indptr[id + 1]; }
+    a = a < 0 ? 0 : (a > c.nnz ? c.nnz : a);
+    b = b < a ? a : (b > c.nnz ? c.nnz : b);
+    *lo = a; *hi = b;
+}
+
+// bag_reduce_col over the `len` entries ri[] of a row (wt: their weights, kBagSum only) padded to `width` slots.
+__device__ __forceinline__ float bagcsr_reduce_col(const float* __restrict__ table, int vocab, int dim, const int* __restrict__ ri,
+                                                   const float* __restrict__ wt, long long len, int width, int reduce, int pad,
+                                                   int col, int* win, int* cnt) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+    int n = 0, best = -1;
+    bool have = false;
+    for (long long w = 0; w < len; ++w) {
+        const int j = ri[w];
+        const bool live = bag_live(j, vocab, pad);
+        n += live;
+        if (reduce < kBagMaxPad0) {
+            if (live) {
+                const float t = table[(size_t)j * dim + col];
+                acc += wt ? wt[w] * t : t;
+            }
+            continue;
+        }
+        if (!live && reduce == kBagMax) continue;
+        const float t = live ? table[(size_t)j * dim + col] : 0.f;
+        if (!have || t > acc) { acc = t; best = live ? (int)w : -1; have = true; }
+    }
+    // the padding slots behind the entries: dead, so only kBagMaxPad0 sees them, as one candidate of value 0
+    if (reduce == kBagMaxPad0 && len < (long long)width && (!have || 0.f > acc)) { acc = 0.f; best = -1; }
+    *win = best; *cnt = n;
+    if (reduce == kBagMeanWidth) return acc / (float)width;
+    if (reduce == kBagMeanCount) return n ? acc / (float)n : 0.f;
+    return acc;
+}
+
+__global__ void __launch_bounds__(kBagCsrScanNT)
+bagcsr_rowinfo_kernel(BagCsr c) {
+    __shared__ long long part[kBagCsrScanNT / 64];
+    __shared__ long long wmax[kBagCsrScanNT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long carry = 0, longest = 1;
+    for (int base = 0; base < c.rows; base += kBagCsrScanNT) {
+        const int r = base + tid;
+        long long len = 0;
+        if (r < c.rows) { long long lo, hi; bagcsr_row(c, r, &lo, &hi); len = hi - lo; }
+        longest = len > longest ? len : longest;
+        long long x = len;                                          // inclusive scan of the wavefront
+        for (int d = 1; d < 64; d <<= 1) { const long long y = __shfl_up(x, d); if (lane >= d) x += y; }
+        if (lane == 63) part[wave] = x;
+        __syncthreads();
+        long long pre = carry, tot = carry;
+        for (int w = 0; w < kBagCsrScanNT / 64; ++w) { if (w < wave) pre += part[w]; tot += part[w]; }
+        if (r < c.rows) {
+            const long long at = pre + x - len;
+            c.off[r] = (int)(at < (long long)c.max_entries ? at : (long long)c.max_entries);
+        }
+        carry = tot;
+        __syncthreads();
+    }
+    for (int d = 32; d > 0; d >>= 1) { const long long y = __shfl_xor(longest, d); longest = y > longest ? y : longest; }
+    if (lane == 0) wmax[wave] = longest;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kBagCsrScanNT / 64; ++w) longest = wmax[w] > longest ? wmax[w] : longest;
+        const int E = (int)(carry < (long long)c.max_entries ? carry : (long long)c.max_entries);
+        c.off[c.rows] = E;
+        c.hdr[0] = E;
+        c.hdr[1] = (int)(longest < 0x7fffffffll ? longest : 0x7fffffffll);
+        c.hdr[2] = carry > (long long)c.max_entries;
+    }
+}
+
+__global__ void __launch_bounds__(64)
+bagcsr_encode_kernel(BagCsr c, const float* __restrict__ table, int vocab, int dim, int reduce, int pad, float* __restrict__ out,
+                     long long ldo) {
+    const int r = blockIdx.x, col = blockIdx.y * 64 + threadIdx.x;
+    if (col >= dim) return;
+    long long lo, hi;
+    bagcsr_row(c, r, &lo, &hi);
+    const int width = (reduce == kBagMeanWidth || reduce == kBagMaxPad0) ? c.hdr[1] : 1;
+    int win, cnt;
+    out[(size_t)r * ldo + col] = bagcsr_reduce_col(table, vocab, dim, c.indices + lo, c.weights ? c.weights + lo : nullptr, hi - lo,
+                                                   width, reduce, pad, col, &win, &cnt);
+}
+
+// bitonic sort of keys[0, cap) in LDS, ascending; cap a power of two
+__device__ __forceinline__ void bagcsr_bitonic(unsigned long long* keys, int cap, int tid) {
+    for (int k = 2; k <= cap; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (cap >> 1); t += kBagCsrNT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long ki = keys[i], kl = keys[l];
+                if ((ki > kl) == ((i & k) == 0)) { keys[i] = kl; keys[l] = ki; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBagCsrNT)
+bagcsr_sort_kernel(BagCsr c, int vocab, int pad) {
+    __shared__ unsigned long long keys[kBagCsrSort];
+    const int tid = threadIdx.x;
+    const int E = c.hdr[0];
+    const long long e0 = (long long)blockIdx.x * kBagCsrSort;
+    if (e0 >= E) return;
+    const int n = E - e0 < kBagCsrSort ? (int)(E - e0) : kBagCsrSort;
+    int cap = 2;
+    while (cap < n) cap <<= 1;
+    for (int i = tid; i < cap; i += kBagCsrNT) {
+        unsigned long long key = ~0ull;                             // (padding of the network: above every key, never stored)
+        if (i < n) {
+            const int e = (int)e0 + i;
+            int a = 0, b = c.rows;                                  // the row of e: the last one with off[row] <= e
+            while (a < b) {
+                const int m = (a + b) >> 1;
+                if (c.off[m] <= e) a = m + 1; else b = m;
+            }
+            const int row = a - 1;
+            long long lo, hi;
+            bagcsr_row(c, row, &lo, &hi);
+            const int j = c.indices[lo + (e - c.off[row])];
+            c.rowof[e] = row;
+            key = ((unsigned long long)(bag_live(j, vocab, pad) ? (unsigned)j : kBagCsrDead) << 32) | (unsigned)e;
+        }
+        keys[i] = key;
+    }
+    __syncthreads();
+    bagcsr_bitonic(keys, cap, tid);
+    for (int i = tid; i < n; i += kBagCsrNT) c.keys_a[e0 + i] = keys[i];
+}
+
+// runs of w keys in src, merged pairwise into runs of 2 w in dst
+__global__ void __launch_bounds__(kBagCsrNT)
+bagcsr_merge_kernel(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, const int* __restrict__ hdr,
+                    int w) {
+    const long long E = hdr[0];
+    const long long i = (long long)blockIdx.x * kBagCsrNT + threadIdx.x;
+    if (i >= E) return;
+    const long long base = i / (2ll * w) * (2ll * w);
+    const long long mid = base + w < E ? base + w : E;
+    const long long end = base + 2ll * w < E ? base + 2ll * w : E;
+    const unsigned long long key = src[i];
+    // the sibling run, and how many of its keys are smaller (distinct keys: a lower bound on either side)
+    long long a = i < mid ? mid : base, b = i < mid ? end : mid;
+    const long long sib = a;
+    while (a < b) {
+        const long long m = a + ((b - a) >> 1);
+        if (src[m] < key) a = m + 1; else b = m;
+    }
+    dst[base + (i - (i < mid ? base : mid)) + (a - sib)] = key;
+}
+
+__global__ void __launch_bounds__(64)
+bagcsr_rowpass_kernel(BagCsr c, const float* __restrict__ table, int vocab, int dim, int reduce, int pad) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    long long lo, hi;
+    bagcsr_row(c, r, &lo, &hi);
+    const int len = c.off[r + 1] - c.off[r];                        // (the entries the step holds: all of them within the bound)
+    if (reduce == kBagMeanCount) {
+        if (blockIdx.y) return;
+        int n = 0;
+        for (int i = lane; i < len; i += 64) n += bag_live(c.indices[lo + i], vocab, pad);
+        for (int d = 32; d > 0; d >>= 1) n += __shfl_xor(n, d);
+        if (lane == 0) c.live[r] = n;
+        return;
+    }
+    const int col = blockIdx.y * 64 + lane;
+    if (col >= dim) return;
+    int win, cnt;
+    bagcsr_reduce_col(table, vocab, dim, c.indices + lo, nullptr, len, c.hdr[1], reduce, pad, col, &win, &cnt);
+    c.win[(size_t)r * dim + col] = win;
+}
+
+struct BagCsrUpdate {
+    BagUpdate u;                            // u.c.idx / rows / width are unused
+    BagCsr c;
+    const unsigned long long* sorted;
+    int apply_only;                         // SparseAdam of the max modes: the owners apply their row from the scratch and clear it
+};
+
+__global__ void __launch_bounds__(64 * kCatWaves)
+bagcsr_update_kernel(BagCsrUpdate p) {
+#pragma clang fp contract(off)
+    const CatUpdate& a = p.u.c;
+    const BagCsr& c = p.c;
+    const int lane = threadIdx.x & 63;
+    const int E = c.hdr[0], width = c.hdr[1];
+    const int stride = gridDim.x * kCatWaves;
+    for (int k = blockIdx.x * kCatWaves + (threadIdx.x >> 6); k < E; k += stride) {
+        const unsigned j = (unsigned)(p.sorted[k] >> 32);
+        if (j == kBagCsrDead) continue;
+        if (k > 0 && (unsigned)(p.sorted[k - 1] >> 32) == j) continue;        // an earlier entry of the same table row owns it
+        if (p.apply_only) {
+            for (int col = lane; col < a.dim; col += 64) {
+                const size_t o = (size_t)j * a.dim + col;
+                const float gi = a.gdense[o];
+                a.gdense[o] = 0.f;
+                bag_sparse_adam(a, o, gi);
+            }
+            continue;
+        }
+        // gradient of row j: its run of the sorted keys, in entry order
+        float g[kCatMaxDim / 64];
+#pragma unroll
+        for (int q = 0; q < kCatMaxDim / 64; ++q) g[q] = 0.f;
+        for (int k2 = k; k2 < E; ++k2) {
+            const unsigned long long key = p.sorted[k2];
+            if ((unsigned)(key >> 32) != j) break;
+            const int e = (int)(unsigned)key;
+            const int b = c.rowof[e];
+            const int w = e - c.off[b];
+            float wt = 1.f;
+            if (c.weights) { long long lo, hi; bagcsr_row(c, b, &lo, &hi); wt = c.weights[lo + w]; }
+            const int live = p.u.reduce == kBagMeanCount ? c.live[b] : 1;
+#pragma unroll
+            for (int q = 0; q < kCatMaxDim / 64; ++q) {
+                const int col = lane + 64 * q;
+                if (col >= a.dim) continue;
+                const float dv = a.d[(size_t)b * a.ldd + col];
+                if (p.u.reduce == kBagSum) g[q] += c.weights ? wt * dv : dv;
+                else if (p.u.reduce == kBagMeanWidth) g[q] += dv / (float)width;
+                else if (p.u.reduce == kBagMeanCount) g[q] += dv / (float)live;
+                else if (c.win[(size_t)b * a.dim + col] == w) g[q] += dv;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kCatMaxDim / 64; ++q) {
+            const int col = lane + 64 * q;
+            if (col >= a.dim) continue;
+            const size_t o = (size_t)j * a.dim + col;
+            if (a.gdense) a.gdense[o] = g[q];
+            else bag_sparse_adam(a, o, g[q]);
+        }
+    }
+}
+
+}  // namespace aae

@@ -394,6 +394,34 @@ int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int
 int aae_bag_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
                    int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
                    const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream);
+/* The same bags from a RESIDENT CSR (csrc/cond_csr.h): the value lists of the whole corpus are uploaded once, a step names
+ * its rows, nothing is padded and the update's grouping is a sort - no quadratic scan.
+ *   indptr_dev int64 [n_docs + 1], indices_dev int32 [nnz] (table rows), weights_dev float32 [nnz] or NULL
+ *   (per_sample_weights: an entry contributes w * table[j], its gradient is w * dout[row]; AAE_BAG_SUM only).  The CSR is NOT
+ *   canonical: a row may name a table row several times and the order of its entries is kept.
+ *   row_ids_dev int32 [rows] on the device, or NULL for the rows row0 .. row0 + rows.  A row id outside [0, n_docs) is an
+ *   empty row.
+ *   reduce / padding_idx / optimizer / grad_scratch_dev / lr / step: as in aae_bag_encode / aae_bag_update.  The width of
+ *   AAE_BAG_MEAN_WIDTH and AAE_BAG_MAX_PAD0 is the longest list among the step's rows (padding and out-of-range entries
+ *   counted, at least 1), computed on the device inside the call's launches.
+ *   Same bits as aae_bag_encode / aae_bag_update (and aae_cat_*: AAE_BAG_SUM / AAE_BAG_MEAN_WIDTH with padding_idx 0) on
+ *   the same lists padded to that width: the gradient of a table row sums its entries in (row of the batch, position in
+ *   the row) order.  The recompute contract of the max modes holds here too.
+ *   max_entries: a bound on the entries of the step's rows (<= 2^22; e.g. the sum of the `rows` longest lists of the
+ *   corpus).  It sizes the scratch and the number of merge launches; entries beyond it would be dropped.
+ *   scratch_dev: 8-byte aligned, at least aae_bag_csr_scratch_bytes(rows, max_entries) bytes (encode: (rows, 0)); its
+ *   content is meaningless between calls.  aae_bag_csr_scratch_bytes is arithmetic (no GPU needed); AAE_EINVAL for negative sizes.
+ *   Limits: dim <= 256, rows >= 1.  No atomics, no host synchronisation, every launch goes to `stream`. */
+int aae_bag_csr_scratch_bytes(int64_t max_rows, int64_t max_entries, int64_t* bytes_out);
+int aae_bag_csr_encode(const float* table_dev, int32_t vocab, int32_t dim, const int64_t* indptr_dev,
+                       const int32_t* indices_dev, const float* weights_dev, int64_t n_docs, int64_t nnz,
+                       const int32_t* row_ids_dev, int64_t row0, int32_t rows, int32_t reduce, int32_t padding_idx,
+                       float* out_dev, int64_t out_ld, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                       int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev, const float* weights_dev,
+                       int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
+                       int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
+                       int32_t optimizer, double lr, int64_t step, void* scratch_dev, int64_t scratch_bytes, void* stream);
 /* PretrainedWordEmbeddingCondition's preprocessing (condition.py:345-369 -> ub.py:52-57, EmbeddedVectorizer.transform:
  * `sparse_scores @ self.embedding`): out_dev[r][0:dim] = sum over the CSR entries e of row r of
  * values[e] * table_dev[indices[e]][0:dim], accumulated in CSR order.  indptr int64 [n_rows + 1] (absolute offsets
