@@ -423,53 +423,58 @@ class HostRows:
         return self.host.numpy()
 
 
-def _cat_args(table, idx, block):
-    """Argument checks shared by cat_encode / cat_update (operand shapes must match what the kernels index)."""
-    if not (table.is_cuda and idx.is_cuda and block.is_cuda):
-        raise RuntimeError("aaerec: the categorical condition kernels take GPU tensors (there is no CPU path)")
+def _cond_operands(table, block, source, state=()):
+    """Operand checks of the condition kernels (shapes must match what the kernels index): the table, the [rows, dim] block
+    (an encode's out, an update's dout), the source - a padded idx block or a BagWindow - and an update's moments and
+    gradient scratch."""
+    idx = None if isinstance(source, BagWindow) else source
+    rows = source.rows if idx is None else idx.shape[0]
+    if not (table.is_cuda and block.is_cuda and (source.bags.indptr if idx is None else idx).is_cuda):
+        raise RuntimeError("aaerec: the condition kernels take GPU tensors (there is no CPU path)")
     if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2:
         raise TypeError("aaerec: embedding table must be a contiguous float32 [vocab, dim] tensor")
-    if idx.dtype != torch.int32 or idx.dim() != 2 or not idx.is_contiguous():
+    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 2 or not idx.is_contiguous()):
         raise TypeError("aaerec: idx must be a contiguous int32 [rows, width] tensor")
-    if block.dtype != torch.float32 or block.dim() != 2 or block.stride(1) != 1 or block.shape[0] != idx.shape[0] \
+    if block.dtype != torch.float32 or block.dim() != 2 or block.stride(1) != 1 or block.shape[0] != rows \
             or block.shape[1] != table.shape[1]:
         raise TypeError("aaerec: block must be a float32 [rows, dim] view with unit column stride")
+    for t in state[:2] + tuple(t for t in state[2:] if t is not None):          # (the gradient scratch may be absent)
+        if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
+            raise TypeError("aaerec: optimiser state must match the embedding table")
+
+
+def _cond_call(entry, table, *args):
+    """entry(table, *args, stream) on the table's device and current stream; a tensor (None: absent) goes by its address.
+    (Twice a step on a host-bound path: one inline test per argument, not _arg, which measured 4-7 us a call more.)"""
+    args = [_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+    with torch.cuda.device(table.device):
+        _check(entry(_ptr(table), *args, _stream_of(table.device)))
 
 
 def cat_encode(table, idx, out, mean=False):
     """CategoricalCondition.encode on the device: out[r] = sum (or mean over the padded width) of table[idx[r, w]];
     index 0 reads as zero.  `out` may be a column slice of the step's condition block."""
-    _cat_args(table, idx, out)
-    with torch.cuda.device(table.device):
-        _check(load_library().aae_cat_encode(_ptr(table), table.shape[0], table.shape[1], _ptr(idx), idx.shape[0],
-                                             idx.shape[1], CAT_MEAN if mean else CAT_SUM, _ptr(out), out.stride(0),
-                                             C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+    _cond_operands(table, out, idx)
+    _cond_call(load_library().aae_cat_encode, table, table.shape[0], table.shape[1], idx, idx.shape[0], idx.shape[1],
+               CAT_MEAN if mean else CAT_SUM, out, out.stride(0))
 
 
 def cat_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, mean=False, grad_scratch=None):
     """Backward of cat_encode from dout [rows, dim] plus the condition's optimiser step: SparseAdam over the rows the
     batch names, or (grad_scratch given: zeros [vocab, dim]) dense Adam over the whole table.  step counts from 1."""
-    _cat_args(table, idx, dout)
-    for t in (exp_avg, exp_avg_sq) + ((grad_scratch,) if grad_scratch is not None else ()):
-        if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
-            raise TypeError("aaerec: optimiser state must match the embedding table")
-    with torch.cuda.device(table.device):
-        _check(load_library().aae_cat_update(_ptr(table), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(grad_scratch),
-                                             table.shape[0], table.shape[1], _ptr(idx), idx.shape[0], idx.shape[1],
-                                             CAT_MEAN if mean else CAT_SUM, _ptr(dout), dout.stride(0),
-                                             CAT_ADAM if grad_scratch is not None else CAT_SPARSE_ADAM, float(lr), int(step),
-                                             C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+    _cond_operands(table, dout, idx, (exp_avg, exp_avg_sq, grad_scratch))
+    _cond_call(load_library().aae_cat_update, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1], idx,
+               idx.shape[0], idx.shape[1], CAT_MEAN if mean else CAT_SUM, dout, dout.stride(0),
+               CAT_ADAM if grad_scratch is not None else CAT_SPARSE_ADAM, float(lr), int(step))
 
 
 def bag_encode(table, idx, out, reduce=BAG_SUM, padding_idx=-1):
     """A bag of table rows per row of idx, reduced into out [rows, dim] (aae_bag_encode: nn.EmbeddingBag's sum / mean / max
-    and CategoricalCondition's hid.max(1)[0]).  reduce: one of BAG_*; padding_idx -1: no padding row.  `out` may be a
-    column slice of the step's condition block."""
-    _cat_args(table, idx, out)
-    with torch.cuda.device(table.device):
-        _check(load_library().aae_bag_encode(_ptr(table), table.shape[0], table.shape[1], _ptr(idx), idx.shape[0],
-                                             idx.shape[1], int(reduce), int(padding_idx), _ptr(out), out.stride(0),
-                                             C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+    and CategoricalCondition's hid.sum(1) / .mean(1) / .max(1)[0]).  reduce: one of BAG_*; padding_idx -1: no padding row.
+    `out` may be a column slice of the step's condition block."""
+    _cond_operands(table, out, idx)
+    _cond_call(load_library().aae_bag_encode, table, table.shape[0], table.shape[1], idx, idx.shape[0], idx.shape[1],
+               int(reduce), int(padding_idx), out, out.stride(0))
 
 
 def bag_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, reduce=BAG_SUM, padding_idx=-1, grad_scratch=None,
@@ -478,16 +483,10 @@ def bag_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, reduce=BAG_SUM, 
     (sparse=True) SparseAdam over the rows the batch names.  grad_scratch (zeros [vocab, dim], left zero): needed by dense
     Adam and by the two max modes.  The winners of the max modes are recomputed from the table: it must be what bag_encode
     read.  step counts from 1."""
-    _cat_args(table, idx, dout)
-    for t in (exp_avg, exp_avg_sq) + ((grad_scratch,) if grad_scratch is not None else ()):
-        if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
-            raise TypeError("aaerec: optimiser state must match the embedding table")
-    with torch.cuda.device(table.device):
-        _check(load_library().aae_bag_update(_ptr(table), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(grad_scratch),
-                                             table.shape[0], table.shape[1], _ptr(idx), idx.shape[0], idx.shape[1],
-                                             int(reduce), int(padding_idx), _ptr(dout), dout.stride(0),
-                                             CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step),
-                                             C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+    _cond_operands(table, dout, idx, (exp_avg, exp_avg_sq, grad_scratch))
+    _cond_call(load_library().aae_bag_update, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1], idx,
+               idx.shape[0], idx.shape[1], int(reduce), int(padding_idx), dout, dout.stride(0),
+               CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step))
 
 
 # ---- bags from a resident CSR (aae_bag_csr_*; csrc/cond_csr.h) -------------------------------------------------------
@@ -600,46 +599,27 @@ class BagWindow:
         return self.rows
 
 
-def _bag_csr_args(table, view, block):
-    if not (table.is_cuda and block.is_cuda and view.bags.indptr.is_cuda):
-        raise RuntimeError("aaerec: the bag kernels take GPU tensors (there is no CPU path)")
-    if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2:
-        raise TypeError("aaerec: embedding table must be a contiguous float32 [vocab, dim] tensor")
-    if block.dtype != torch.float32 or block.dim() != 2 or block.stride(1) != 1 or block.shape[0] != view.rows \
-            or block.shape[1] != table.shape[1]:
-        raise TypeError("aaerec: block must be a float32 [rows, dim] view with unit column stride")
-
-
 def bag_csr_encode(table, view, out, reduce=BAG_SUM, padding_idx=-1):
     """bag_encode over the rows `view` (a BagWindow) of a resident DeviceBags: the same bits as bag_encode / cat_encode on
     those lists padded to their longest.  `out` may be a column slice of the step's condition block."""
-    _bag_csr_args(table, view, out)
     b = view.bags
+    _cond_operands(table, out, view)
     scratch, nbytes = b.scratch(view.rows)
-    with torch.cuda.device(table.device):
-        _check(load_library().aae_bag_csr_encode(
-            _ptr(table), table.shape[0], table.shape[1], _ptr(b.indptr), _ptr(b.indices), _ptr(b.weights), b.n_docs, b.nnz,
-            _ptr(view.row_ids), view.row0, view.rows, int(reduce), int(padding_idx), _ptr(out), out.stride(0), _ptr(scratch),
-            nbytes, C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+    _cond_call(load_library().aae_bag_csr_encode, table, table.shape[0], table.shape[1], b.indptr, b.indices, b.weights,
+               b.n_docs, b.nnz, view.row_ids, view.row0, view.rows, int(reduce), int(padding_idx), out, out.stride(0), scratch, nbytes)
 
 
 def bag_csr_update(table, exp_avg, exp_avg_sq, view, dout, lr, step, reduce=BAG_SUM, padding_idx=-1, grad_scratch=None,
                    sparse=False):
     """bag_update over the rows `view` of a resident DeviceBags: entries grouped by table row with a sort (no quadratic scan,
     nothing on the host), summed in the padded route's order - the same bits.  Arguments as bag_update."""
-    _bag_csr_args(table, view, dout)
-    for t in (exp_avg, exp_avg_sq) + ((grad_scratch,) if grad_scratch is not None else ()):
-        if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
-            raise TypeError("aaerec: optimiser state must match the embedding table")
     b = view.bags
+    _cond_operands(table, dout, view, (exp_avg, exp_avg_sq, grad_scratch))
     scratch, nbytes = b.scratch(view.rows)
-    with torch.cuda.device(table.device):
-        _check(load_library().aae_bag_csr_update(
-            _ptr(table), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(grad_scratch), table.shape[0], table.shape[1], _ptr(b.indptr),
-            _ptr(b.indices), _ptr(b.weights), b.n_docs, b.nnz, _ptr(view.row_ids), view.row0, view.rows,
-            b.entry_bound(view.rows), int(reduce), int(padding_idx), _ptr(dout), dout.stride(0),
-            CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step), _ptr(scratch), nbytes,
-            C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+    _cond_call(load_library().aae_bag_csr_update, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1],
+               b.indptr, b.indices, b.weights, b.n_docs, b.nnz, view.row_ids, view.row0, view.rows, b.entry_bound(view.rows),
+               int(reduce), int(padding_idx), dout, dout.stride(0), CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step),
+               scratch, nbytes)
 
 
 def csr_embed(csr, table):

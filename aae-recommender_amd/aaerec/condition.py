@@ -239,7 +239,47 @@ class PretrainedWordEmbeddingCondition(ConcatenationBasedConditioning):
         return self.vect.embedding.shape[1]
 
 
-class EmbeddingBagCondition(ConcatenationBasedConditioning):
+class _NativeBags:
+    """The device-native route of a trainable embedding table (libaaerec_hip: aae_bag_encode / aae_bag_update over a padded
+    index block, aae_bag_csr_* over a window of resident bags - _hip.BagWindow): lookup + reduction, its backward and the
+    Adam / SparseAdam step in the library's kernels around the fused step instead of cutting the step at the condition
+    boundary for autograd.  The optimiser state lives in self.optimizer.state in torch's own layout (SparseAdam: step an
+    int; Adam: a tensor), so state_dict(), checkpoints and a later torch-side step see the same tensors.
+    A class contributes _native() -> (weight, reduce - a _hip.BAG_* code -, padding_idx, sparse) and _index_block()."""
+    _idx = _grad_scratch = None
+
+    def encode_into(self, out, inputs, width=None):
+        """encode(inputs) written into `out` ([rows, embedding_dim], may be a column slice of a wider block).  inputs: what
+        _index_block takes, or a window of resident bags.  width: pad to at least this many values (a rank's share of a
+        batch uses the whole batch's width)."""
+        from . import _hip
+        w, reduce, pad, _ = self._native()
+        resident = isinstance(inputs, _hip.BagWindow)
+        self._idx = inputs if resident else self._index_block(inputs, w.device, width)
+        (_hip.bag_csr_encode if resident else _hip.bag_encode)(w.data, self._idx, out, reduce=reduce, padding_idx=pad)
+
+    def update_from(self, dout, inputs=None):
+        """zero_grad + backward + step from dL/d(encoded block) of the rows last handed to encode_into, or of `inputs`
+        (data parallel: every rank applies the gathered gradient of the whole batch).  The winners of the max modes are
+        recomputed from the table, which nothing has touched since encode_into."""
+        from . import _hip
+        w, reduce, pad, sparse = self._native()
+        if inputs is not None:
+            self._idx = inputs if isinstance(inputs, _hip.BagWindow) else self._index_block(inputs, w.device)
+        st = self.optimizer.state[w]
+        if "exp_avg" not in st:
+            st["step"] = 0 if sparse else torch.tensor(0.0)
+            st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(w.data), torch.zeros_like(w.data)
+        scratch = not sparse or reduce in (_hip.BAG_MAX_PAD0, _hip.BAG_MAX)        # dense Adam and the max modes
+        if scratch and self._grad_scratch is None:
+            self._grad_scratch = torch.zeros_like(w.data)
+        st["step"] += 1
+        update = _hip.bag_csr_update if isinstance(self._idx, _hip.BagWindow) else _hip.bag_update
+        update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"], int(st["step"]),
+               reduce=reduce, padding_idx=pad, grad_scratch=self._grad_scratch if scratch else None, sparse=sparse)
+
+
+class EmbeddingBagCondition(_NativeBags, ConcatenationBasedConditioning):
     """Trainable nn.EmbeddingBag + its own Adam (reference 372-394)."""
 
     def __init__(self, num_embeddings, embedding_dim, **kwargs):
@@ -261,11 +301,8 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
     def size_increment(self):
         return self.embedding_dim
 
-    # ---- device-native training path (libaaerec_hip: aae_bag_encode / aae_bag_update) ------------------------
-    # With the table in HBM (nn.EmbeddingBag's own device= keyword, or .embedding_bag.cuda()) the bag reduction, its
-    # backward and the Adam step run in the library's kernels around the fused step, as CategoricalCondition's do.  The
-    # optimiser state lives in self.optimizer.state in torch's own layout (step as a tensor, exp_avg, exp_avg_sq), so
-    # state_dict(), checkpoints and a later torch-side step see the same tensors.
+    # ---- device-native training path (_NativeBags): the table in HBM (nn.EmbeddingBag's own device= keyword, or
+    # .embedding_bag.cuda()), dense Adam, the module's padding_idx
     _BAG_MODES = {"sum": 0, "mean": 2, "max": 4}          # _hip.BAG_SUM / BAG_MEAN_COUNT / BAG_MAX
 
     def device_native(self, device):
@@ -274,7 +311,7 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
         return (w.is_cuda and w.device == torch.device(device) and bag.mode in self._BAG_MODES and bag.max_norm is None
                 and not bag.scale_grad_by_freq and not bag.sparse and self.embedding_dim <= 256)
 
-    def _index_block(self, inputs, device):
+    def _index_block(self, inputs, device, width=None):
         if torch.is_tensor(inputs):
             if inputs.dim() != 2 or inputs.is_floating_point():
                 raise ValueError("EmbeddingBagCondition: the device-native route takes 2-D integer input [rows, width]")
@@ -291,9 +328,9 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
         """Width of a batch: the second dimension of its [rows, width] input (nothing is padded)."""
         return int(inputs.shape[1]) if hasattr(inputs, "shape") else len(inputs[0])
 
-    def _padding_idx(self):
-        p = self.embedding_bag.padding_idx
-        return -1 if p is None else int(p)
+    def _native(self):
+        bag = self.embedding_bag
+        return bag.weight, self._BAG_MODES[bag.mode], -1 if bag.padding_idx is None else int(bag.padding_idx), False
 
     @staticmethod
     def offsets_form(inputs):
@@ -317,42 +354,8 @@ class EmbeddingBagCondition(ConcatenationBasedConditioning):
                                             weights=None if weights is None else host(weights),
                                             include_last_offset=self.embedding_bag.include_last_offset)
 
-    def encode_into(self, out, inputs, width=None):
-        """encode(inputs) written into `out` ([rows, embedding_dim], may be a column slice of a wider block).  width is
-        accepted for the protocol's sake: 2-D input has one width, and no mode divides by it.  inputs: a [rows, width] index
-        block, or a window of resident bags (_hip.BagWindow)."""
-        from . import _hip
-        w = self.embedding_bag.weight
-        if isinstance(inputs, _hip.BagWindow):
-            self._idx = inputs
-            _hip.bag_csr_encode(w.data, inputs, out, reduce=self._BAG_MODES[self.embedding_bag.mode],
-                                padding_idx=self._padding_idx())
-            return
-        self._idx = self._index_block(inputs, w.device)
-        _hip.bag_encode(w.data, self._idx, out, reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx())
 
-    def update_from(self, dout, inputs=None):
-        """zero_grad + backward + step (dense Adam) from dL/d(encoded block) of the rows last handed to encode_into, or
-        of `inputs` (data parallel: every rank applies the gathered gradient of the whole batch).  The winners of
-        mode='max' are recomputed from the table, which nothing has touched since encode_into."""
-        from . import _hip
-        w = self.embedding_bag.weight
-        if inputs is not None:
-            self._idx = inputs if isinstance(inputs, _hip.BagWindow) else self._index_block(inputs, w.device)
-        st = self.optimizer.state[w]
-        if "exp_avg" not in st:
-            st["step"] = torch.tensor(0.0)
-            st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(w.data), torch.zeros_like(w.data)
-        if getattr(self, "_grad_scratch", None) is None:
-            self._grad_scratch = torch.zeros_like(w.data)
-        st["step"] += 1
-        update = _hip.bag_csr_update if isinstance(self._idx, _hip.BagWindow) else _hip.bag_update
-        update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
-               int(st["step"]), reduce=self._BAG_MODES[self.embedding_bag.mode], padding_idx=self._padding_idx(),
-               grad_scratch=self._grad_scratch)
-
-
-class CategoricalCondition(ConcatenationBasedConditioning):
+class CategoricalCondition(_NativeBags, ConcatenationBasedConditioning):
     """Trainable embedding of a categorical attribute; index 0 = padding / out of vocabulary
     (reference 397-508).
 
@@ -423,18 +426,18 @@ class CategoricalCondition(ConcatenationBasedConditioning):
     def size_increment(self):
         return self.embedding_dim
 
-    # ---- device-native training path (libaaerec_hip: aae_cat_encode / aae_cat_update) ------------------------
-    # With the table in HBM the whole condition - lookup + reduction, its backward and its SparseAdam / Adam step -
-    # runs in two small kernels around aae_step instead of cutting the step at the condition boundary for autograd.
-    # The optimiser state lives in self.optimizer.state (torch's own layout), so state_dict() / a later torch-side
-    # step see the same tensors.
+    # ---- device-native training path (_NativeBags): padding row 0, SparseAdam or Adam as `sparse` says; one value a
+    # document (reduce=None) is a bag of one
+    _BAG_MODES = {None: 0, "sum": 0, "mean": 1, "max": 3}         # _hip.BAG_SUM / BAG_MEAN_WIDTH / BAG_MAX_PAD0
+
+    def _native(self):
+        return self.embedding.weight, self._BAG_MODES[self.reduce], self.padding_idx, self.sparse
+
     def device_native(self, device):
         w = self.embedding.weight if self.embedding is not None else None
         return (w is not None and w.is_cuda and w.device == torch.device(device)
-                and self.reduce in (None, "sum", "mean", "max")
+                and self.reduce in self._BAG_MODES
                 and not self.embedding_params and self.embedding_dim <= 256)
-
-    _CSR_MODES = {"sum": 0, "mean": 1, "max": 3}          # _hip.BAG_SUM / BAG_MEAN_WIDTH / BAG_MAX_PAD0
 
     def resident(self, inputs, device):
         """The transformed condition data of a whole corpus in HBM, uploaded once: the value lists as a _hip.DeviceBags
@@ -461,50 +464,6 @@ class CategoricalCondition(ConcatenationBasedConditioning):
     def padded_width(self, inputs):
         """Width the reference pads a batch of value lists to (its longest list); 'mean' divides by it."""
         return 1 if self.reduce is None else max(1, max(len(row) for row in inputs))
-
-    def encode_into(self, out, inputs, width=None):
-        """encode(inputs) written into `out` ([rows, embedding_dim], may be a column slice of a wider block).
-        width: pad to at least this many values (a rank's share of a batch uses the whole batch's width)."""
-        from . import _hip
-        w = self.embedding.weight
-        if isinstance(inputs, _hip.BagWindow):      # resident value lists: the same bits without the padded block
-            self._idx = inputs
-            _hip.bag_csr_encode(w.data, inputs, out, reduce=self._CSR_MODES[self.reduce], padding_idx=self.padding_idx)
-            return
-        self._idx = self._index_block(inputs, w.device, width)
-        if self.reduce == "max":     # hid.max(1)[0]: a padding slot is a candidate of value 0 (aae_bag_*, AAE_BAG_MAX_PAD0)
-            _hip.bag_encode(w.data, self._idx, out, reduce=_hip.BAG_MAX_PAD0, padding_idx=self.padding_idx)
-        else:
-            _hip.cat_encode(w.data, self._idx, out, mean=self.reduce == "mean")
-
-    def update_from(self, dout, inputs=None):
-        """zero_grad + backward + step from dL/d(encoded block) of the rows last handed to encode_into, or of
-        `inputs` (data parallel: every rank applies the gathered gradient of the whole batch)."""
-        from . import _hip
-        w = self.embedding.weight
-        if inputs is not None:
-            self._idx = inputs if isinstance(inputs, _hip.BagWindow) else self._index_block(inputs, w.device)
-        st = self.optimizer.state[w]
-        if "exp_avg" not in st:
-            st["step"] = 0 if self.sparse else torch.tensor(0.0)
-            st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(w.data), torch.zeros_like(w.data)
-        if (not self.sparse or self.reduce == "max") and getattr(self, "_grad_scratch", None) is None:
-            self._grad_scratch = torch.zeros_like(w.data)
-        st["step"] += 1
-        if isinstance(self._idx, _hip.BagWindow):
-            _hip.bag_csr_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
-                                int(st["step"]), reduce=self._CSR_MODES[self.reduce], padding_idx=self.padding_idx,
-                                grad_scratch=self._grad_scratch if (not self.sparse or self.reduce == "max") else None,
-                                sparse=self.sparse)
-            return
-        if self.reduce == "max":        # the winners are recomputed from the table: nothing has touched it since encode_into
-            _hip.bag_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
-                            int(st["step"]), reduce=_hip.BAG_MAX_PAD0, padding_idx=self.padding_idx,
-                            grad_scratch=self._grad_scratch, sparse=self.sparse)
-            return
-        _hip.cat_update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"],
-                        int(st["step"]), mean=self.reduce == "mean",
-                        grad_scratch=None if self.sparse else self._grad_scratch)
 
 
 class Condition(ConditionBase):

@@ -9,7 +9,7 @@ its backward incl. the KL gradient).  Parameter names in the kernels' model: enc
 
 Like the reference, predict() samples eps as well (vae.py:229-266 runs the same forward in eval mode).
 Conditions: constant concatenated blocks (e.g. PretrainedWordEmbeddingCondition) and CategoricalConditions whose
-table lives on this GPU ride in aae_vae_step (encoded and trained by aae_cat_encode / aae_cat_update around the step, as
+table lives on this GPU ride in aae_vae_step (encoded and trained by aae_bag_encode / aae_bag_update around the step, as
 in the AAE - condition.py:397-508); any other plugin runs with torch autograd between the code and the decoder: the step
 is cut at the condition boundary (aae_vae_encode -> encode_impose -> aae_vae_decode_backward -> the plugins' backward and
 step -> aae_vae_encoder_backward).

@@ -5,114 +5,123 @@
 
 extern "C" {
 
-// ---- CategoricalCondition (cond_embed.h): stateless entry points over caller-owned tables --------------------
-static int cat_check(int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce) {
-    if (vocab < 1 || dim < 1 || dim > kCatMaxDim) return fail(AAE_EINVAL, "categorical condition: need vocab >= 1 and 1 <= dim <= 256");
-    if (!idx_dev || rows < 1 || width < 1) return fail(AAE_EINVAL, "categorical condition: empty index block");
-    if ((int64_t)rows * width > (1 << 22)) return fail(AAE_EINVAL, "categorical condition: rows * width > 2^22");
-    if (reduce != AAE_CAT_SUM && reduce != AAE_CAT_MEAN) return fail(AAE_EINVAL, "categorical condition: reduce must be sum or mean");
+// ---- what the entry points of the trainable conditions share (who: the entry point's name) -------------------
+static_assert(AAE_CAT_SUM == AAE_BAG_SUM && AAE_CAT_MEAN == AAE_BAG_MEAN_WIDTH, "aae_cat_* hands its reduce to the bag kernels");
+static_assert(AAE_BAG_SUM == kBagSum && AAE_BAG_MEAN_WIDTH == kBagMeanWidth && AAE_BAG_MEAN_COUNT == kBagMeanCount &&
+              AAE_BAG_MAX_PAD0 == kBagMaxPad0 && AAE_BAG_MAX == kBagMax, "the kernels take the ABI's reduce codes");
+#define COND_FAIL(text) return fail(AAE_EINVAL, std::string(who) + ": " + text)
+
+static int cond_shape_check(const char* who, int32_t vocab, int32_t dim, int32_t reduce, int32_t padding_idx) {
+    if (vocab < 1) COND_FAIL("vocab must be >= 1");
+    if (dim < 1 || dim > kCatMaxDim) COND_FAIL("dim must be within [1, 256]");
+    if (reduce < AAE_BAG_SUM || reduce > AAE_BAG_MAX) COND_FAIL("unknown reduce");
+    if (padding_idx < -1 || padding_idx >= vocab) COND_FAIL("padding_idx must be -1 or a table row");
     return AAE_OK;
 }
 
-int aae_cat_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,
-                   int32_t width, int32_t reduce, float* out_dev, int64_t out_ld, void* stream) {
-    TRY(cat_check(vocab, dim, idx_dev, rows, width, reduce));
-    if (!table_dev || !out_dev || out_ld < dim) return fail(AAE_EINVAL, "aae_cat_encode: table/out is NULL or out_ld < dim");
-    hipLaunchKernelGGL(cat_encode_kernel, dim3(rows, (dim + 63) / 64), dim3(64), 0, S(stream), table_dev, vocab, dim,
-                       idx_dev, width, reduce == AAE_CAT_MEAN, out_dev, (long long)out_ld);
-    LAUNCHCHK("cat_encode");
+static int cond_block_check(const char* who, const int32_t* idx_dev, int32_t rows, int32_t width) {
+    if (!idx_dev || rows < 1 || width < 1) COND_FAIL("empty index block");
+    if ((int64_t)rows * width > (1 << 22)) COND_FAIL("rows * width > 2^22");
     return AAE_OK;
 }
 
-int aae_cat_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
-                   int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce,
-                   const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream) {
-    TRY(cat_check(vocab, dim, idx_dev, rows, width, reduce));
-    if (!table_dev || !exp_avg_dev || !exp_avg_sq_dev || !dout_dev || dout_ld < dim)
-        return fail(AAE_EINVAL, "aae_cat_update: table/state/dout is NULL or dout_ld < dim");
-    if (optimizer != AAE_CAT_SPARSE_ADAM && optimizer != AAE_CAT_ADAM) return fail(AAE_EINVAL, "aae_cat_update: unknown optimizer");
-    if (optimizer == AAE_CAT_ADAM && !grad_scratch_dev) return fail(AAE_EINVAL, "aae_cat_update: dense Adam needs grad_scratch_dev");
-    if (step < 1) return fail(AAE_EINVAL, "aae_cat_update: step counts from 1");
+static bool cond_is_max(int32_t reduce) { return reduce == AAE_BAG_MAX_PAD0 || reduce == AAE_BAG_MAX; }
+
+// What an update's launches take: the table side of the gradient kernels and dense Adam's scalars.
+struct CondUpdate { BagTable a; OptScalars adam; };
+
+// An update in front of its launches: the operand, optimiser and step checks, then the bias corrections into both optimisers' terms.
+static int cond_update_begin(const char* who, CondUpdate& u, float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev,
+                             float* grad_scratch_dev, int32_t vocab, int32_t dim, int32_t reduce, int32_t padding_idx,
+                             const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step) {
+    if (!table_dev || !exp_avg_dev || !exp_avg_sq_dev || !dout_dev || dout_ld < dim) COND_FAIL("table/state/dout is NULL or dout_ld < dim");
+    if (optimizer != AAE_CAT_SPARSE_ADAM && optimizer != AAE_CAT_ADAM) COND_FAIL("unknown optimizer");
+    const bool scratch = optimizer == AAE_CAT_ADAM || cond_is_max(reduce);
+    if (scratch && !grad_scratch_dev) COND_FAIL("dense Adam and the max modes need grad_scratch_dev");
+    if (step < 1) COND_FAIL("step counts from 1");
     const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
-    CatUpdate a;
+    BagTable& a = u.a;
     a.table = table_dev; a.m = exp_avg_dev; a.v = exp_avg_sq_dev;
-    a.gdense = optimizer == AAE_CAT_ADAM ? grad_scratch_dev : nullptr;
-    a.idx = idx_dev; a.d = dout_dev; a.ldd = dout_ld; a.vocab = vocab; a.dim = dim; a.rows = rows; a.width = width;
-    a.mean = reduce == AAE_CAT_MEAN;
+    a.gdense = scratch ? grad_scratch_dev : nullptr;
+    a.d = dout_dev; a.ldd = dout_ld; a.vocab = vocab; a.dim = dim; a.reduce = reduce; a.pad = padding_idx;
     a.neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
-    const int n = rows * width;
-    hipLaunchKernelGGL(cat_update_kernel, dim3((n + kCatWaves - 1) / kCatWaves), dim3(64 * kCatWaves), 0, S(stream), a);
-    LAUNCHCHK("cat_update");
-    if (optimizer == AAE_CAT_ADAM) {
-        OptScalars sc; memset(&sc, 0, sizeof(sc));
-        sc.t = step; sc.neg_step_size = (float)(-(lr / bc1)); sc.bc2_sqrt = (float)sqrt(bc2); sc.lr = lr;
-        sc.inv_bc2_sqrt = 1.0f / sc.bc2_sqrt;
-        const size_t total = (size_t)vocab * dim;
-        hipLaunchKernelGGL(cat_dense_adam_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S(stream), table_dev,
-                           exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, total, sc);
-        LAUNCHCHK("cat_dense_adam");
-    }
+    OptScalars& sc = u.adam;
+    memset(&sc, 0, sizeof(sc));
+    sc.t = step; sc.neg_step_size = (float)(-(lr / bc1)); sc.bc2_sqrt = (float)sqrt(bc2); sc.lr = lr;
+    sc.inv_bc2_sqrt = 1.0f / sc.bc2_sqrt;
     return AAE_OK;
 }
 
-// ---- EmbeddingBagCondition / CategoricalCondition(reduce="max") (cond_bag.h) ---------------------------------
-static int bag_check(int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce,
-                     int32_t padding_idx) {
-    if (vocab < 1 || dim < 1 || dim > kCatMaxDim) return fail(AAE_EINVAL, "embedding bag: need vocab >= 1 and 1 <= dim <= 256");
-    if (!idx_dev || rows < 1 || width < 1) return fail(AAE_EINVAL, "embedding bag: empty index block");
-    if ((int64_t)rows * width > (1 << 22)) return fail(AAE_EINVAL, "embedding bag: rows * width > 2^22");
-    if (reduce < AAE_BAG_SUM || reduce > AAE_BAG_MAX) return fail(AAE_EINVAL, "embedding bag: unknown reduce");
-    if (padding_idx < -1 || padding_idx >= vocab) return fail(AAE_EINVAL, "embedding bag: padding_idx must be -1 or a table row");
+// torch.optim.Adam over the whole table from the gradient scratch the update launch filled
+static int cond_dense_adam(const CondUpdate& u, hipStream_t s) {
+    const BagTable& a = u.a;
+    const size_t total = (size_t)a.vocab * a.dim;
+    hipLaunchKernelGGL(cat_dense_adam_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.table, a.m, a.v, a.gdense,
+                       total, u.adam);
+    LAUNCHCHK("cond_dense_adam");
     return AAE_OK;
 }
 
-int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,
-                   int32_t width, int32_t reduce, int32_t padding_idx, float* out_dev, int64_t out_ld, void* stream) {
-    TRY(bag_check(vocab, dim, idx_dev, rows, width, reduce, padding_idx));
-    if (!table_dev || !out_dev || out_ld < dim) return fail(AAE_EINVAL, "aae_bag_encode: table/out is NULL or out_ld < dim");
+// ---- padded index blocks (cond_bag.h): EmbeddingBagCondition and CategoricalCondition; aae_cat_* is sum / mean at padding row 0
+static int bag_padded_encode(const char* who, const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev,
+                             int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx, float* out_dev, int64_t out_ld,
+                             void* stream) {
+    TRY(cond_shape_check(who, vocab, dim, reduce, padding_idx));
+    TRY(cond_block_check(who, idx_dev, rows, width));
+    if (!table_dev || !out_dev || out_ld < dim) COND_FAIL("table/out is NULL or out_ld < dim");
     hipLaunchKernelGGL(bag_encode_kernel, dim3(rows, (dim + 63) / 64), dim3(64), 0, S(stream), table_dev, vocab, dim,
                        idx_dev, width, reduce, padding_idx, out_dev, (long long)out_ld);
     LAUNCHCHK("bag_encode");
     return AAE_OK;
 }
 
+static int bag_padded_update(const char* who, float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev,
+                             int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce,
+                             int32_t padding_idx, const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr,
+                             int64_t step, void* stream) {
+    TRY(cond_shape_check(who, vocab, dim, reduce, padding_idx));
+    TRY(cond_block_check(who, idx_dev, rows, width));
+    CondUpdate u;
+    TRY(cond_update_begin(who, u, table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, reduce, padding_idx, dout_dev,
+                          dout_ld, optimizer, lr, step));
+    const BagPadded src = {idx_dev, rows, width};
+    const int n = rows * width;
+    const dim3 grid((n + kCatWaves - 1) / kCatWaves), block(64 * kCatWaves);
+    hipLaunchKernelGGL(bag_update_kernel, grid, block, 0, S(stream), u.a, src);
+    LAUNCHCHK("bag_update");
+    if (optimizer == AAE_CAT_ADAM) return cond_dense_adam(u, S(stream));
+    if (cond_is_max(reduce)) {
+        hipLaunchKernelGGL(bag_apply_kernel, grid, block, 0, S(stream), u.a, src);
+        LAUNCHCHK("bag_apply");
+    }
+    return AAE_OK;
+}
+
+int aae_cat_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,
+                   int32_t width, int32_t reduce, float* out_dev, int64_t out_ld, void* stream) {
+    if (reduce != AAE_CAT_SUM && reduce != AAE_CAT_MEAN) return fail(AAE_EINVAL, "aae_cat_encode: reduce must be sum or mean");
+    return bag_padded_encode("aae_cat_encode", table_dev, vocab, dim, idx_dev, rows, width, reduce, 0, out_dev, out_ld, stream);
+}
+
+int aae_cat_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                   int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce,
+                   const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream) {
+    if (reduce != AAE_CAT_SUM && reduce != AAE_CAT_MEAN) return fail(AAE_EINVAL, "aae_cat_update: reduce must be sum or mean");
+    return bag_padded_update("aae_cat_update", table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, idx_dev, rows,
+                             width, reduce, 0, dout_dev, dout_ld, optimizer, lr, step, stream);
+}
+
+int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,
+                   int32_t width, int32_t reduce, int32_t padding_idx, float* out_dev, int64_t out_ld, void* stream) {
+    return bag_padded_encode("aae_bag_encode", table_dev, vocab, dim, idx_dev, rows, width, reduce, padding_idx, out_dev, out_ld,
+                             stream);
+}
+
 int aae_bag_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
                    int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
                    const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream) {
-    TRY(bag_check(vocab, dim, idx_dev, rows, width, reduce, padding_idx));
-    if (!table_dev || !exp_avg_dev || !exp_avg_sq_dev || !dout_dev || dout_ld < dim)
-        return fail(AAE_EINVAL, "aae_bag_update: table/state/dout is NULL or dout_ld < dim");
-    if (optimizer != AAE_CAT_SPARSE_ADAM && optimizer != AAE_CAT_ADAM) return fail(AAE_EINVAL, "aae_bag_update: unknown optimizer");
-    const bool is_max = reduce == AAE_BAG_MAX_PAD0 || reduce == AAE_BAG_MAX;
-    if ((optimizer == AAE_CAT_ADAM || is_max) && !grad_scratch_dev)
-        return fail(AAE_EINVAL, "aae_bag_update: dense Adam and the max modes need grad_scratch_dev");
-    if (step < 1) return fail(AAE_EINVAL, "aae_bag_update: step counts from 1");
-    const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
-    BagUpdate u;
-    CatUpdate& a = u.c;
-    a.table = table_dev; a.m = exp_avg_dev; a.v = exp_avg_sq_dev;
-    a.gdense = (optimizer == AAE_CAT_ADAM || is_max) ? grad_scratch_dev : nullptr;
-    a.idx = idx_dev; a.d = dout_dev; a.ldd = dout_ld; a.vocab = vocab; a.dim = dim; a.rows = rows; a.width = width;
-    a.mean = 0;
-    a.neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
-    u.reduce = reduce; u.pad = padding_idx;
-    const int n = rows * width;
-    const dim3 grid((n + kCatWaves - 1) / kCatWaves), block(64 * kCatWaves);
-    hipLaunchKernelGGL(bag_update_kernel, grid, block, 0, S(stream), u);
-    LAUNCHCHK("bag_update");
-    if (optimizer == AAE_CAT_ADAM) {
-        OptScalars sc; memset(&sc, 0, sizeof(sc));
-        sc.t = step; sc.neg_step_size = (float)(-(lr / bc1)); sc.bc2_sqrt = (float)sqrt(bc2); sc.lr = lr;
-        sc.inv_bc2_sqrt = 1.0f / sc.bc2_sqrt;
-        const size_t total = (size_t)vocab * dim;
-        hipLaunchKernelGGL(cat_dense_adam_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S(stream), table_dev,
-                           exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, total, sc);
-        LAUNCHCHK("bag_dense_adam");
-    } else if (is_max) {
-        hipLaunchKernelGGL(bag_sparse_adam_kernel, grid, block, 0, S(stream), u);
-        LAUNCHCHK("bag_sparse_adam");
-    }
-    return AAE_OK;
+    return bag_padded_update("aae_bag_update", table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, idx_dev, rows,
+                             width, reduce, padding_idx, dout_dev, dout_ld, optimizer, lr, step, stream);
 }
 
 // ---- the same bags from a resident CSR (cond_csr.h) ----------------------------------------------------------
@@ -143,26 +152,21 @@ static void bag_csr_carve(BagCsr& c, void* scratch_dev, int32_t rows, int64_t ma
     c.max_entries = (int)max_entries;
 }
 
-// the checks of both calls (who: the entry point's name); fills c
+// the checks of both calls; fills c
 static int bag_csr_check(const char* who, BagCsr& c, int32_t vocab, int32_t dim, const int64_t* indptr_dev,
                          const int32_t* indices_dev, const float* weights_dev, int64_t n_docs, int64_t nnz,
                          const int32_t* row_ids_dev, int64_t row0, int32_t rows, int64_t max_entries, int32_t reduce,
                          int32_t padding_idx, void* scratch_dev, int64_t scratch_bytes) {
-#define BAG_CSR_FAIL(text) return fail(AAE_EINVAL, std::string(who) + ": " + text)
-    if (vocab < 1) BAG_CSR_FAIL("vocab must be >= 1");
-    if (dim < 1 || dim > kCatMaxDim) BAG_CSR_FAIL("dim must be within [1, 256]");
-    if (rows < 1) BAG_CSR_FAIL("rows must be >= 1");
-    if (!indptr_dev || !indices_dev) BAG_CSR_FAIL("indptr_dev / indices_dev is NULL");
-    if (n_docs < 1 || nnz < 0) BAG_CSR_FAIL("need n_docs >= 1 and nnz >= 0");
-    if (!row_ids_dev && (row0 < 0 || row0 + rows > n_docs)) BAG_CSR_FAIL("row0 .. row0 + rows is not inside [0, n_docs)");
-    if (max_entries < 0) BAG_CSR_FAIL("max_entries must be >= 0");
-    if (max_entries > kBagCsrMaxEntries) BAG_CSR_FAIL("max_entries: a step takes at most 2^22 entries");
-    if (reduce < AAE_BAG_SUM || reduce > AAE_BAG_MAX) BAG_CSR_FAIL("unknown reduce");
-    if (weights_dev && reduce != AAE_BAG_SUM) BAG_CSR_FAIL("weights_dev goes with reduce AAE_BAG_SUM only");
-    if (padding_idx < -1 || padding_idx >= vocab) BAG_CSR_FAIL("padding_idx must be -1 or a table row");
-    if (!scratch_dev || ((uintptr_t)scratch_dev & 7)) BAG_CSR_FAIL("scratch_dev is NULL or not 8-byte aligned");
-    if (scratch_bytes < bag_csr_bytes(rows, max_entries)) BAG_CSR_FAIL("scratch_bytes is smaller than aae_bag_csr_scratch_bytes(rows, max_entries)");
-#undef BAG_CSR_FAIL
+    TRY(cond_shape_check(who, vocab, dim, reduce, padding_idx));
+    if (rows < 1) COND_FAIL("rows must be >= 1");
+    if (!indptr_dev || !indices_dev) COND_FAIL("indptr_dev / indices_dev is NULL");
+    if (n_docs < 1 || nnz < 0) COND_FAIL("need n_docs >= 1 and nnz >= 0");
+    if (!row_ids_dev && (row0 < 0 || row0 + rows > n_docs)) COND_FAIL("row0 .. row0 + rows is not inside [0, n_docs)");
+    if (max_entries < 0) COND_FAIL("max_entries must be >= 0");
+    if (max_entries > kBagCsrMaxEntries) COND_FAIL("max_entries: a step takes at most 2^22 entries");
+    if (weights_dev && reduce != AAE_BAG_SUM) COND_FAIL("weights_dev goes with reduce AAE_BAG_SUM only");
+    if (!scratch_dev || ((uintptr_t)scratch_dev & 7)) COND_FAIL("scratch_dev is NULL or not 8-byte aligned");
+    if (scratch_bytes < bag_csr_bytes(rows, max_entries)) COND_FAIL("scratch_bytes is smaller than aae_bag_csr_scratch_bytes(rows, max_entries)");
     c.indptr = (const long long*)indptr_dev; c.indices = indices_dev; c.weights = weights_dev;
     c.n_docs = n_docs; c.nnz = nnz; c.row_ids = row_ids_dev; c.row0 = row0; c.rows = rows;
     bag_csr_carve(c, scratch_dev, rows, max_entries);
@@ -192,27 +196,14 @@ int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_d
                        int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
                        int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
                        int32_t optimizer, double lr, int64_t step, void* scratch_dev, int64_t scratch_bytes, void* stream) {
-    BagCsrUpdate p;
-    memset(&p, 0, sizeof(p));
-    TRY(bag_csr_check("aae_bag_csr_update", p.c, vocab, dim, indptr_dev, indices_dev, weights_dev, n_docs, nnz, row_ids_dev, row0,
+    BagCsr c;
+    TRY(bag_csr_check("aae_bag_csr_update", c, vocab, dim, indptr_dev, indices_dev, weights_dev, n_docs, nnz, row_ids_dev, row0,
                       rows, max_entries, reduce, padding_idx, scratch_dev, scratch_bytes));
     if (max_entries < 1) return fail(AAE_EINVAL, "aae_bag_csr_update: max_entries must be >= 1");
-    if (!table_dev || !exp_avg_dev || !exp_avg_sq_dev || !dout_dev || dout_ld < dim)
-        return fail(AAE_EINVAL, "aae_bag_csr_update: table/state/dout is NULL or dout_ld < dim");
-    if (optimizer != AAE_CAT_SPARSE_ADAM && optimizer != AAE_CAT_ADAM) return fail(AAE_EINVAL, "aae_bag_csr_update: unknown optimizer");
-    const bool is_max = reduce == AAE_BAG_MAX_PAD0 || reduce == AAE_BAG_MAX;
-    if ((optimizer == AAE_CAT_ADAM || is_max) && !grad_scratch_dev)
-        return fail(AAE_EINVAL, "aae_bag_csr_update: dense Adam and the max modes need grad_scratch_dev");
-    if (step < 1) return fail(AAE_EINVAL, "aae_bag_csr_update: step counts from 1");
-    const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
-    CatUpdate& a = p.u.c;
-    a.table = table_dev; a.m = exp_avg_dev; a.v = exp_avg_sq_dev;
-    a.gdense = (optimizer == AAE_CAT_ADAM || is_max) ? grad_scratch_dev : nullptr;
-    a.d = dout_dev; a.ldd = dout_ld; a.vocab = vocab; a.dim = dim; a.rows = rows;
-    a.neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
-    p.u.reduce = reduce; p.u.pad = padding_idx;
+    CondUpdate u;
+    TRY(cond_update_begin("aae_bag_csr_update", u, table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, reduce,
+                          padding_idx, dout_dev, dout_ld, optimizer, lr, step));
     hipStream_t s = S(stream);
-    const BagCsr& c = p.c;
     hipLaunchKernelGGL(bagcsr_rowinfo_kernel, dim3(1), dim3(kBagCsrScanNT), 0, s, c);
     hipLaunchKernelGGL(bagcsr_sort_kernel, dim3((unsigned)((max_entries + kBagCsrSort - 1) / kBagCsrSort)), dim3(kBagCsrNT), 0, s, c,
                        vocab, padding_idx);
@@ -223,29 +214,22 @@ int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_d
                            src, dst, c.hdr, (int)w);
         unsigned long long* t = src; src = dst; dst = t;
     }
-    p.sorted = src;
     if (reduce >= AAE_BAG_MEAN_COUNT)
         hipLaunchKernelGGL(bagcsr_rowpass_kernel, dim3(rows, reduce == AAE_BAG_MEAN_COUNT ? 1 : (dim + 63) / 64), dim3(64), 0, s, c,
                            table_dev, vocab, dim, reduce, padding_idx);
     const int64_t want = (max_entries + kCatWaves - 1) / kCatWaves;
     const dim3 grid((unsigned)(want < kBagCsrMaxGrid ? want : kBagCsrMaxGrid)), block(64 * kCatWaves);
-    hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, p);
+    hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, u.a, c, (const unsigned long long*)src, 0);
     LAUNCHCHK("bagcsr_update");
-    if (optimizer == AAE_CAT_ADAM) {
-        OptScalars sc; memset(&sc, 0, sizeof(sc));
-        sc.t = step; sc.neg_step_size = (float)(-(lr / bc1)); sc.bc2_sqrt = (float)sqrt(bc2); sc.lr = lr;
-        sc.inv_bc2_sqrt = 1.0f / sc.bc2_sqrt;
-        const size_t total = (size_t)vocab * dim;
-        hipLaunchKernelGGL(cat_dense_adam_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, table_dev,
-                           exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, total, sc);
-        LAUNCHCHK("bagcsr_dense_adam");
-    } else if (is_max) {
-        p.apply_only = 1;
-        hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, p);
-        LAUNCHCHK("bagcsr_sparse_adam");
+    if (optimizer == AAE_CAT_ADAM) return cond_dense_adam(u, s);
+    if (cond_is_max(reduce)) {          // SparseAdam of the max modes: the owners apply their row from the scratch and clear it
+        hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, u.a, c, (const unsigned long long*)src, 1);
+        LAUNCHCHK("bagcsr_apply");
     }
     return AAE_OK;
 }
+
+#undef COND_FAIL
 
 int aae_csr_embed(const int64_t* indptr_dev, const int32_t* indices_dev, const float* values_dev, int32_t n_rows,
                   const float* table_dev, int32_t n_table_rows, int32_t dim, int64_t table_ld, float* out_dev,

@@ -1,6 +1,6 @@
 // Trainable bag conditions from a resident CSR: cond_bag.h's five reductions, their backward and the optimiser step over the
 // value lists of a corpus that was uploaded once, without the padded [rows][width] rectangle and without the quadratic
-// duplicate scan of cat_update_kernel / bag_update_kernel.
+// duplicate scan of bag_update_kernel.  The arithmetic is cond_bag.h's helpers; this file adds the source and the grouping.
 //
 //   bag CSR   indptr int64 [n_docs + 1], indices int32 (table rows), optionally weights fp32 (per_sample_weights, sum only).
 //             NOT canonical: a row may name a table row several times, and the order of its entries is the order of the value
@@ -11,10 +11,9 @@
 //   width     the longest list among the step's rows, dead entries counted, at least 1: what _pad_batch pads to.  It is
 //             computed by bagcsr_rowinfo_kernel and read from the scratch by the launches behind it - the host never sees it.
 //
-// Encode: bagcsr_reduce_col is bag_reduce_col over a row's entries; the slots the padded form would add behind them are dead
-// in every mode, so they change nothing but kBagMeanWidth's divisor (the width) and kBagMaxPad0's candidate of value 0 (one
-// comparison when the row is shorter than the width).  Same operations in the same order: the same bits as aae_bag_encode /
-// aae_cat_encode on the padded form.
+// Encode: bag_reduce_col over a row's entries with the step's width; the slots the padded form would add behind them are the
+// dead slots it accounts for.  Same operations in the same order: the same bits as aae_bag_encode / aae_cat_encode on the
+// padded form.
 //
 // Update, the grouping: every entry becomes the 64-bit key (table row << 32 | e), a dead entry (padding row, out of range)
 // (0xFFFFFFFF << 32 | e).  The keys are distinct, so their ascending order is unique whatever sorts them, and it lists the
@@ -28,8 +27,8 @@
 //   bagcsr_rowpass_kernel   max modes: the winner of every (row, column), recomputed from the untouched table; kBagMeanCount:
 //                           the live entries of every row.  Once per row, not once per contributing entry.
 //   bagcsr_update_kernel    a wavefront per sorted position (grid-stride): the first key of a table row owns it, walks the
-//                           row's run, sums the contributions in that order (cat_update_kernel's arithmetic) and applies
-//                           SparseAdam or writes the [vocab][dim] gradient scratch, as bag_update_kernel does.
+//                           row's run, sums the contributions in that order (bag_grad_add) and hands the row on as
+//                           bag_update_kernel does (bag_write_row; the max modes' second pass: bag_apply_row).
 // Work: O(E) for everything but the sort; the sort is O(E log^2 kBagCsrSort) in LDS plus log2(bound / kBagCsrSort) merge passes
 // of O(E log E) each.  Nothing is quadratic, nothing is proportional to vocab but dense Adam itself, there is no [vocab]
 // marker, no atomic of any kind, and every loop is bounded by a length read once (E, a row's length, the row count).
@@ -69,37 +68,6 @@ __device__ __forceinline__ void bagcsr_row(const BagCsr& c, int r, long long* lo
     a = a < 0 ? 0 : (a > c.nnz ? c.nnz : a);
     b = b < a ? a : (b > c.nnz ? c.nnz : b);
     *lo = a; *hi = b;
-}
-
-// bag_reduce_col over the `len` entries ri[] of a row (wt: their weights, kBagSum only) padded to `width` slots.
-__device__ __forceinline__ float bagcsr_reduce_col(const float* __restrict__ table, int vocab, int dim, const int* __restrict__ ri,
-                                                   const float* __restrict__ wt, long long len, int width, int reduce, int pad,
-                                                   int col, int* win, int* cnt) {
-#pragma clang fp contract(off)
-    float acc = 0.f;
-    int n = 0, best = -1;
-    bool have = false;
-    for (long long w = 0; w < len; ++w) {
-        const int j = ri[w];
-        const bool live = bag_live(j, vocab, pad);
-        n += live;
-        if (reduce < kBagMaxPad0) {
-            if (live) {
-                const float t = table[(size_t)j * dim + col];
-                acc += wt ? wt[w] * t : t;
-            }
-            continue;
-        }
-        if (!live && reduce == kBagMax) continue;
-        const float t = live ? table[(size_t)j * dim + col] : 0.f;
-        if (!have || t > acc) { acc = t; best = live ? (int)w : -1; have = true; }
-    }
-    // the padding slots behind the entries: dead, so only kBagMaxPad0 sees them, as one candidate of value 0
-    if (reduce == kBagMaxPad0 && len < (long long)width && (!have || 0.f > acc)) { acc = 0.f; best = -1; }
-    *win = best; *cnt = n;
-    if (reduce == kBagMeanWidth) return acc / (float)width;
-    if (reduce == kBagMeanCount) return n ? acc / (float)n : 0.f;
-    return acc;
 }
 
 __global__ void __launch_bounds__(kBagCsrScanNT)
@@ -148,7 +116,7 @@ bagcsr_encode_kernel(BagCsr c, const float* __restrict__ table, int vocab, int d
     bagcsr_row(c, r, &lo, &hi);
     const int width = (reduce == kBagMeanWidth || reduce == kBagMaxPad0) ? c.hdr[1] : 1;
     int win, cnt;
-    out[(size_t)r * ldo + col] = bagcsr_reduce_col(table, vocab, dim, c.indices + lo, c.weights ? c.weights + lo : nullptr, hi - lo,
+    out[(size_t)r * ldo + col] = bag_reduce_col(table, vocab, dim, c.indices + lo, c.weights ? c.weights + lo : nullptr, hi - lo,
                                                    width, reduce, pad, col, &win, &cnt);
 }
 
@@ -237,70 +205,42 @@ bagcsr_rowpass_kernel(BagCsr c, const float* __restrict__ table, int vocab, int 
     const int col = blockIdx.y * 64 + lane;
     if (col >= dim) return;
     int win, cnt;
-    bagcsr_reduce_col(table, vocab, dim, c.indices + lo, nullptr, len, c.hdr[1], reduce, pad, col, &win, &cnt);
+    bag_reduce_col(table, vocab, dim, c.indices + lo, nullptr, len, c.hdr[1], reduce, pad, col, &win, &cnt);
     c.win[(size_t)r * dim + col] = win;
 }
 
-struct BagCsrUpdate {
-    BagUpdate u;                            // u.c.idx / rows / width are unused
-    BagCsr c;
-    const unsigned long long* sorted;
-    int apply_only;                         // SparseAdam of the max modes: the owners apply their row from the scratch and clear it
-};
-
 __global__ void __launch_bounds__(64 * kCatWaves)
-bagcsr_update_kernel(BagCsrUpdate p) {
-#pragma clang fp contract(off)
-    const CatUpdate& a = p.u.c;
-    const BagCsr& c = p.c;
+bagcsr_update_kernel(BagTable a, BagCsr c, const unsigned long long* __restrict__ sorted, int apply_only) {
     const int lane = threadIdx.x & 63;
     const int E = c.hdr[0], width = c.hdr[1];
     const int stride = gridDim.x * kCatWaves;
     for (int k = blockIdx.x * kCatWaves + (threadIdx.x >> 6); k < E; k += stride) {
-        const unsigned j = (unsigned)(p.sorted[k] >> 32);
+        const unsigned j = (unsigned)(sorted[k] >> 32);
         if (j == kBagCsrDead) continue;
-        if (k > 0 && (unsigned)(p.sorted[k - 1] >> 32) == j) continue;        // an earlier entry of the same table row owns it
-        if (p.apply_only) {
-            for (int col = lane; col < a.dim; col += 64) {
-                const size_t o = (size_t)j * a.dim + col;
-                const float gi = a.gdense[o];
-                a.gdense[o] = 0.f;
-                bag_sparse_adam(a, o, gi);
-            }
-            continue;
-        }
+        if (k > 0 && (unsigned)(sorted[k - 1] >> 32) == j) continue;          // an earlier entry of the same table row owns it
+        if (apply_only) { bag_apply_row(a, (int)j, lane); continue; }
         // gradient of row j: its run of the sorted keys, in entry order
         float g[kCatMaxDim / 64];
 #pragma unroll
         for (int q = 0; q < kCatMaxDim / 64; ++q) g[q] = 0.f;
         for (int k2 = k; k2 < E; ++k2) {
-            const unsigned long long key = p.sorted[k2];
+            const unsigned long long key = sorted[k2];
             if ((unsigned)(key >> 32) != j) break;
             const int e = (int)(unsigned)key;
             const int b = c.rowof[e];
             const int w = e - c.off[b];
             float wt = 1.f;
             if (c.weights) { long long lo, hi; bagcsr_row(c, b, &lo, &hi); wt = c.weights[lo + w]; }
-            const int live = p.u.reduce == kBagMeanCount ? c.live[b] : 1;
+            const int live = a.reduce == kBagMeanCount ? c.live[b] : 1;
 #pragma unroll
             for (int q = 0; q < kCatMaxDim / 64; ++q) {
                 const int col = lane + 64 * q;
                 if (col >= a.dim) continue;
-                const float dv = a.d[(size_t)b * a.ldd + col];
-                if (p.u.reduce == kBagSum) g[q] += c.weights ? wt * dv : dv;
-                else if (p.u.reduce == kBagMeanWidth) g[q] += dv / (float)width;
-                else if (p.u.reduce == kBagMeanCount) g[q] += dv / (float)live;
-                else if (c.win[(size_t)b * a.dim + col] == w) g[q] += dv;
+                const bool winner = a.reduce >= kBagMaxPad0 && c.win[(size_t)b * a.dim + col] == w;
+                bag_grad_add(g[q], a.reduce, a.d[(size_t)b * a.ldd + col], width, live, winner, c.weights != nullptr, wt);
             }
         }
-#pragma unroll
-        for (int q = 0; q < kCatMaxDim / 64; ++q) {
-            const int col = lane + 64 * q;
-            if (col >= a.dim) continue;
-            const size_t o = (size_t)j * a.dim + col;
-            if (a.gdense) a.gdense[o] = g[q];
-            else bag_sparse_adam(a, o, g[q]);
-        }
+        bag_write_row(a, (int)j, lane, g);
     }
 }
 

@@ -359,7 +359,8 @@ int aae_apply_gathered(aae_handle h, int which_a, int which_b, const float* pack
  *                                       only rows named by the batch move;
  *                  AAE_CAT_ADAM         torch.optim.Adam over the whole table; grad_scratch_dev [vocab][dim] must be
  *                                       zero on the first call and is left zero.
- *                  `step` is the 1-based count of this update (the optimiser's state['step'] after it). */
+ *                  `step` is the 1-based count of this update (the optimiser's state['step'] after it).
+ * Both are aae_bag_encode / aae_bag_update with AAE_BAG_SUM / AAE_BAG_MEAN_WIDTH and padding_idx 0 (the same kernels). */
 enum { AAE_CAT_SUM = 0, AAE_CAT_MEAN = 1 };
 enum { AAE_CAT_SPARSE_ADAM = 0, AAE_CAT_ADAM = 1 };
 int aae_cat_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,

@@ -283,7 +283,7 @@ def test_vae_and_dae_fit_with_resident_conditions_equal_the_padded_route(kind):
 
 
 def test_a_one_value_condition_takes_its_window_on_the_device():
-    """reduce=None: the column is resident as an int32 tensor, a step selects its rows there and keeps aae_cat_*."""
+    """reduce=None: the column is resident as an int32 tensor, a step selects its rows there and hands aae_bag_* a block of width 1."""
     from aaerec.condition import CategoricalCondition
     mk = lambda: CategoricalCondition(8, reduce=None, sparse=True)             # noqa: E731
     one = lambda cond, authors: cond.fit_transform([row[0] if row else "nobody" for row in authors])      # noqa: E731

@@ -149,8 +149,8 @@ def test_condition_plugins_through_autograd_bridge(name):
 
 @pytest.mark.parametrize("name", ["step_cond_categorical"] + CAT_CASES)
 def test_categorical_condition_device_native(name):
-    """A CategoricalCondition with its table on the GPU is trained by the library's own kernels (aae_cat_encode before
-    the fused step, aae_cat_update = backward + SparseAdam / Adam after it) instead of the autograd bridge: same
+    """A CategoricalCondition with its table on the GPU is trained by the library's own kernels (aae_bag_encode before
+    the fused step, aae_bag_update = backward + SparseAdam / Adam after it) instead of the autograd bridge: same
     fixtures from the reference, including the condition's optimiser state."""
     from aaerec.aae import AdversarialAutoEncoder
     from aaerec import condition as C
@@ -946,7 +946,7 @@ def test_conditioned_recommender_through_bags_attributes():
     res = ev([rec, plain])
     mrr_cond, mrr_plain = res[0][0][0], res[1][0][0]
     assert rec.model._is_device_native() and cat.embedding.weight.is_cuda
-    assert float(cat.optimizer.state[cat.embedding.weight]["step"]) > 100          # trained by aae_cat_update
+    assert float(cat.optimizer.state[cat.embedding.weight]["step"]) > 100          # trained by aae_bag_update
     assert mrr_cond > 0.3 and mrr_cond > mrr_plain + 0.05, (mrr_cond, mrr_plain)
 
 
