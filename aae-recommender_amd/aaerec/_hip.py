@@ -63,6 +63,8 @@ T_W1_TSYNC = 103
 CAT_SUM, CAT_MEAN = 0, 1
 CAT_SPARSE_ADAM, CAT_ADAM = 0, 1
 BAG_SUM, BAG_MEAN_WIDTH, BAG_MEAN_COUNT, BAG_MAX_PAD0, BAG_MAX = range(5)
+BAG_NORM_TYPES = {float("inf"): 0, 1.0: 1, 2.0: 2}      # norm_type -> AAE_BAG_NORM_INF / _L1 / _L2: the norms the renorm kernels have
+BAG_SCALE_BY_FREQ = 1                                    # AAE_BAG_SCALE_BY_FREQ
 O_ENC, O_DEC, O_GEN, O_DISC = 0, 1, 2, 3
 MODEL_AAE, MODEL_AE, MODEL_VAE = 0, 1, 3          # cfg.model_kind
 DTYPE_F32, DTYPE_BF16 = 0, 1                      # cfg.dtype
@@ -217,6 +219,17 @@ _PROTOS = {
     "aae_bag_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64,
                                  C.c_void_p]),
+    "aae_bag_update_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                       C.c_int32, C.c_void_p]),
+    "aae_bag_renorm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                 C.c_void_p]),
+    "aae_bag_csr_renorm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_bag_csr_update_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32,
+                                           C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_bag_csr_scratch_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "aae_bag_csr_encode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
@@ -425,18 +438,18 @@ class HostRows:
 
 def _cond_operands(table, block, source, state=()):
     """Operand checks of the condition kernels (shapes must match what the kernels index): the table, the [rows, dim] block
-    (an encode's out, an update's dout), the source - a padded idx block or a BagWindow - and an update's moments and
-    gradient scratch."""
+    (an encode's out, an update's dout; None: a renorm has none), the source - a padded idx block or a BagWindow - and an
+    update's moments and gradient scratch."""
     idx = None if isinstance(source, BagWindow) else source
     rows = source.rows if idx is None else idx.shape[0]
-    if not (table.is_cuda and block.is_cuda and (source.bags.indptr if idx is None else idx).is_cuda):
+    if not (table.is_cuda and (block is None or block.is_cuda) and (source.bags.indptr if idx is None else idx).is_cuda):
         raise RuntimeError("aaerec: the condition kernels take GPU tensors (there is no CPU path)")
     if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2:
         raise TypeError("aaerec: embedding table must be a contiguous float32 [vocab, dim] tensor")
     if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 2 or not idx.is_contiguous()):
         raise TypeError("aaerec: idx must be a contiguous int32 [rows, width] tensor")
-    if block.dtype != torch.float32 or block.dim() != 2 or block.stride(1) != 1 or block.shape[0] != rows \
-            or block.shape[1] != table.shape[1]:
+    if block is not None and (block.dtype != torch.float32 or block.dim() != 2 or block.stride(1) != 1
+                              or block.shape[0] != rows or block.shape[1] != table.shape[1]):
         raise TypeError("aaerec: block must be a float32 [rows, dim] view with unit column stride")
     for t in state[:2] + tuple(t for t in state[2:] if t is not None):          # (the gradient scratch may be absent)
         if t.shape != table.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device:
@@ -478,15 +491,30 @@ def bag_encode(table, idx, out, reduce=BAG_SUM, padding_idx=-1):
 
 
 def bag_update(table, exp_avg, exp_avg_sq, idx, dout, lr, step, reduce=BAG_SUM, padding_idx=-1, grad_scratch=None,
-               sparse=False):
+               sparse=False, scale_by_freq=False):
     """Backward of bag_encode from dout [rows, dim] plus the optimiser step: dense Adam over the whole table, or
     (sparse=True) SparseAdam over the rows the batch names.  grad_scratch (zeros [vocab, dim], left zero): needed by dense
     Adam and by the two max modes.  The winners of the max modes are recomputed from the table: it must be what bag_encode
-    read.  step counts from 1."""
+    read.  step counts from 1.  scale_by_freq (scale_grad_by_freq; dense Adam only): a table row's gradient is divided by
+    the number of times the block names it."""
     _cond_operands(table, dout, idx, (exp_avg, exp_avg_sq, grad_scratch))
-    _cond_call(load_library().aae_bag_update, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1], idx,
+    _cond_call(load_library().aae_bag_update_flags, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1], idx,
                idx.shape[0], idx.shape[1], int(reduce), int(padding_idx), dout, dout.stride(0),
-               CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step))
+               CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step), BAG_SCALE_BY_FREQ if scale_by_freq else 0)
+
+
+def _renorm_operands(table, source, max_norm, norm_type):
+    if float(norm_type) not in BAG_NORM_TYPES:
+        raise ValueError("aaerec: the renorm kernels take norm_type 1, 2 or inf")
+    _cond_operands(table, None, source)
+    return float(max_norm), BAG_NORM_TYPES[float(norm_type)]
+
+
+def bag_renorm(table, idx, max_norm, norm_type=2.0):
+    """nn.Embedding's max_norm on the device (aae_bag_renorm), in front of bag_encode: every distinct table row idx names - a
+    padding row too - whose norm_type-norm exceeds max_norm is scaled onto it, once."""
+    max_norm, code = _renorm_operands(table, idx, max_norm, norm_type)
+    _cond_call(load_library().aae_bag_renorm, table, table.shape[0], table.shape[1], idx, idx.shape[0], idx.shape[1], max_norm, code)
 
 
 # ---- bags from a resident CSR (aae_bag_csr_*; csrc/cond_csr.h) -------------------------------------------------------
@@ -610,16 +638,25 @@ def bag_csr_encode(table, view, out, reduce=BAG_SUM, padding_idx=-1):
 
 
 def bag_csr_update(table, exp_avg, exp_avg_sq, view, dout, lr, step, reduce=BAG_SUM, padding_idx=-1, grad_scratch=None,
-                   sparse=False):
+                   sparse=False, scale_by_freq=False):
     """bag_update over the rows `view` of a resident DeviceBags: entries grouped by table row with a sort (no quadratic scan,
     nothing on the host), summed in the padded route's order - the same bits.  Arguments as bag_update."""
     b = view.bags
     _cond_operands(table, dout, view, (exp_avg, exp_avg_sq, grad_scratch))
     scratch, nbytes = b.scratch(view.rows)
-    _cond_call(load_library().aae_bag_csr_update, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1],
+    _cond_call(load_library().aae_bag_csr_update_flags, table, exp_avg, exp_avg_sq, grad_scratch, table.shape[0], table.shape[1],
                b.indptr, b.indices, b.weights, b.n_docs, b.nnz, view.row_ids, view.row0, view.rows, b.entry_bound(view.rows),
                int(reduce), int(padding_idx), dout, dout.stride(0), CAT_SPARSE_ADAM if sparse else CAT_ADAM, float(lr), int(step),
-               scratch, nbytes)
+               BAG_SCALE_BY_FREQ if scale_by_freq else 0, scratch, nbytes)
+
+
+def bag_csr_renorm(table, view, max_norm, norm_type=2.0):
+    """bag_renorm over the rows `view` of a resident DeviceBags (aae_bag_csr_renorm): the same bits as on those lists padded."""
+    b = view.bags
+    max_norm, code = _renorm_operands(table, view, max_norm, norm_type)
+    scratch, nbytes = b.scratch(view.rows)
+    _cond_call(load_library().aae_bag_csr_renorm, table, table.shape[0], table.shape[1], b.indptr, b.indices, b.n_docs, b.nnz,
+               view.row_ids, view.row0, view.rows, b.entry_bound(view.rows), max_norm, code, scratch, nbytes)
 
 
 def csr_embed(csr, table):

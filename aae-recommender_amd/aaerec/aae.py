@@ -29,7 +29,7 @@ import torch
 
 from . import _hip, ranking
 from .base import Recommender
-from .condition import _check_conditions
+from .condition import _check_conditions, device_native_conditions
 
 torch.manual_seed(42)            # reference aae.py:27
 TINY = 1e-12
@@ -312,8 +312,7 @@ class AdversarialAutoEncoder:
         a CategoricalCondition / EmbeddingBagCondition with its table on this GPU (its own device_native decides)."""
         dev = self.hip.device if self.hip is not None else \
             torch.device(self.device if self.device is not None else "cuda:{}".format(torch.cuda.current_device()))
-        return all(getattr(c, "constant_concat", False) or (hasattr(c, "device_native") and c.device_native(dev))
-                   for c in self.conditions.values())
+        return device_native_conditions(self.conditions, dev, data_parallel=self.data_parallel not in (None, False))
 
     def _native_cond_block(self, c_batch, n_rows, whole_batch=None):
         """[n_rows, size_increment] block of the encoded conditions, in ConditionList order (encode_impose's

@@ -13,7 +13,8 @@ Conditions whose encoded input is a constant block that is concatenated
 fused kernel path instead: their block is copied next to z on the device.  So does a
 `CategoricalCondition` (every `reduce`) or an `EmbeddingBagCondition` (modes sum / mean / max) whose table
 lives on the GPU: its lookup, backward and SparseAdam / Adam step are two small kernels of the library
-around the fused step (`device_native`).
+around the fused step (`device_native`); for a `CategoricalCondition` `max_norm` (a renorm launch in front of
+the lookup) and `scale_grad_by_freq` (a flag of the update) included.
 """
 import itertools as it
 from abc import ABC, abstractmethod
@@ -239,14 +240,42 @@ class PretrainedWordEmbeddingCondition(ConcatenationBasedConditioning):
         return self.vect.embedding.shape[1]
 
 
+def _table_options_native(module, sparse):
+    """max_norm / norm_type / scale_grad_by_freq of a table's nn.Embedding as the kernels have them: max_norm > 0 under
+    norm_type 1, 2 or inf (aae_bag_renorm), scale_grad_by_freq where torch itself accepts it - not with a sparse gradient
+    (embedding_backward raises).  Where torch refuses, the condition stays bridged and the user sees torch's own error."""
+    if module.max_norm is not None:
+        from ._hip import BAG_NORM_TYPES
+        if not float(module.max_norm) > 0 or float(module.norm_type) not in BAG_NORM_TYPES:
+            return False
+    return not (module.scale_grad_by_freq and sparse)
+
+
+def device_native_conditions(conditions, device, data_parallel=False):
+    """The models' decision: every condition is a block the kernels produce and train themselves - a constant concatenated
+    block, or a trainable table whose own device_native(device) agrees.  data_parallel: a rank encodes only its share of a
+    batch, so a max_norm there would scale different rows on different ranks and the replicated tables would drift apart;
+    a table with max_norm or scale_grad_by_freq is then not device-native and the model takes the bridged route."""
+    return all(getattr(c, "constant_concat", False)
+               or (hasattr(c, "device_native") and c.device_native(device)
+                   and not (data_parallel and getattr(c, "has_table_options", lambda: False)()))
+               for c in conditions.values())
+
+
 class _NativeBags:
     """The device-native route of a trainable embedding table (libaaerec_hip: aae_bag_encode / aae_bag_update over a padded
     index block, aae_bag_csr_* over a window of resident bags - _hip.BagWindow): lookup + reduction, its backward and the
     Adam / SparseAdam step in the library's kernels around the fused step instead of cutting the step at the condition
     boundary for autograd.  The optimiser state lives in self.optimizer.state in torch's own layout (SparseAdam: step an
     int; Adam: a tensor), so state_dict(), checkpoints and a later torch-side step see the same tensors.
-    A class contributes _native() -> (weight, reduce - a _hip.BAG_* code -, padding_idx, sparse) and _index_block()."""
+    A class contributes _native() -> (weight, reduce - a _hip.BAG_* code -, padding_idx, sparse), _index_block() and
+    _table_module(), the nn.Embedding / nn.EmbeddingBag whose max_norm, norm_type and scale_grad_by_freq apply."""
     _idx = _grad_scratch = None
+
+    def has_table_options(self):
+        """The table is renormalised by the lookup (max_norm) or its gradient is scaled by frequency."""
+        mod = self._table_module()
+        return mod is not None and (mod.max_norm is not None or bool(mod.scale_grad_by_freq))
 
     def encode_into(self, out, inputs, width=None):
         """encode(inputs) written into `out` ([rows, embedding_dim], may be a column slice of a wider block).  inputs: what
@@ -256,6 +285,11 @@ class _NativeBags:
         w, reduce, pad, _ = self._native()
         resident = isinstance(inputs, _hip.BagWindow)
         self._idx = inputs if resident else self._index_block(inputs, w.device, width)
+        mod = self._table_module()
+        if mod.max_norm is not None:
+            # torch's forward renormalises the named rows first, in training and in eval alike: a launch of its own in front
+            # of the lookup, and nothing touches the table between the lookup and update_from
+            (_hip.bag_csr_renorm if resident else _hip.bag_renorm)(w.data, self._idx, mod.max_norm, mod.norm_type)
         (_hip.bag_csr_encode if resident else _hip.bag_encode)(w.data, self._idx, out, reduce=reduce, padding_idx=pad)
 
     def update_from(self, dout, inputs=None):
@@ -276,7 +310,8 @@ class _NativeBags:
         st["step"] += 1
         update = _hip.bag_csr_update if isinstance(self._idx, _hip.BagWindow) else _hip.bag_update
         update(w.data, st["exp_avg"], st["exp_avg_sq"], self._idx, dout, self.optimizer.param_groups[0]["lr"], int(st["step"]),
-               reduce=reduce, padding_idx=pad, grad_scratch=self._grad_scratch if scratch else None, sparse=sparse)
+               reduce=reduce, padding_idx=pad, grad_scratch=self._grad_scratch if scratch else None, sparse=sparse,
+               scale_by_freq=bool(self._table_module().scale_grad_by_freq))
 
 
 class EmbeddingBagCondition(_NativeBags, ConcatenationBasedConditioning):
@@ -308,8 +343,15 @@ class EmbeddingBagCondition(_NativeBags, ConcatenationBasedConditioning):
     def device_native(self, device):
         bag = self.embedding_bag
         w = bag.weight
+        # max_norm and scale_grad_by_freq are still refused HERE, although _NativeBags and the kernels carry both (they run
+        # for CategoricalCondition): tests/test_cond_bag_cpu.py pins this class's refusal of the two keywords.  Lifting it
+        # is `_table_options_native(bag, False)` in place of the two option terms below, less mode="max" with
+        # scale_grad_by_freq, which nn.EmbeddingBag's own forward refuses.
         return (w.is_cuda and w.device == torch.device(device) and bag.mode in self._BAG_MODES and bag.max_norm is None
                 and not bag.scale_grad_by_freq and not bag.sparse and self.embedding_dim <= 256)
+
+    def _table_module(self):
+        return self.embedding_bag
 
     def _index_block(self, inputs, device, width=None):
         if torch.is_tensor(inputs):
@@ -437,7 +479,13 @@ class CategoricalCondition(_NativeBags, ConcatenationBasedConditioning):
         w = self.embedding.weight if self.embedding is not None else None
         return (w is not None and w.is_cuda and w.device == torch.device(device)
                 and self.reduce in self._BAG_MODES
-                and not self.embedding_params and self.embedding_dim <= 256)
+                and set(self.embedding_params) <= self._NATIVE_PARAMS and self.embedding_dim <= 256
+                and _table_options_native(self.embedding, self.sparse))
+
+    _NATIVE_PARAMS = frozenset(("max_norm", "norm_type", "scale_grad_by_freq"))       # nn.Embedding keywords the kernels have
+
+    def _table_module(self):
+        return self.embedding
 
     def resident(self, inputs, device):
         """The transformed condition data of a whole corpus in HBM, uploaded once: the value lists as a _hip.DeviceBags

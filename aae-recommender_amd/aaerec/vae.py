@@ -21,7 +21,7 @@ import torch
 from . import _hip, ranking
 from .aae import TORCH_OPTIMIZERS, AdversarialAutoEncoder, _take, _validate_targets, loss_targets, resident_condition_data
 from .base import Recommender
-from .condition import _check_conditions
+from .condition import _check_conditions, device_native_conditions
 
 STATUS_FORMAT = "[ R: {:.4f}]"
 # widest decoder input [z | conditions | 1] of a VAE handle: fc3 in up to five k-parts of 208 columns (csrc/abi_model.h
@@ -62,9 +62,7 @@ class VAE:
         dev_probe = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # conditions the kernels produce / train themselves ride in aae_vae_step; any other plugin gets the step cut at
         # the condition boundary and runs with torch autograd in between (aae_vae_encode / _decode_backward / ...)
-        self._cond_native = not conditions or all(
-            getattr(c, "constant_concat", False) or (hasattr(c, "device_native") and c.device_native(dev_probe))
-            for c in conditions.values())
+        self._cond_native = not conditions or device_native_conditions(conditions, dev_probe)
         self._dp = None
         seed = seed if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) \
             if rng_mode == "device" else 0

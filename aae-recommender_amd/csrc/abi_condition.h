@@ -27,13 +27,28 @@ static int cond_block_check(const char* who, const int32_t* idx_dev, int32_t row
 
 static bool cond_is_max(int32_t reduce) { return reduce == AAE_BAG_MAX_PAD0 || reduce == AAE_BAG_MAX; }
 
+static_assert(AAE_BAG_NORM_INF == kBagNormInf && AAE_BAG_NORM_L1 == kBagNormL1 && AAE_BAG_NORM_L2 == kBagNormL2,
+              "the kernels take the ABI's norm codes");
+
+// max_norm as the renorm kernels take it (fp32, as torch's own device kernel holds it)
+static int cond_norm_check(const char* who, double max_norm, int32_t norm_type, float* max_norm_f) {
+    if (!(max_norm > 0.0) || !((float)max_norm > 0.f)) COND_FAIL("max_norm must be > 0");
+    if (norm_type != AAE_BAG_NORM_INF && norm_type != AAE_BAG_NORM_L1 && norm_type != AAE_BAG_NORM_L2)
+        COND_FAIL("norm_type must be AAE_BAG_NORM_L1, AAE_BAG_NORM_L2 or AAE_BAG_NORM_INF");
+    *max_norm_f = (float)max_norm;
+    return AAE_OK;
+}
+
 // What an update's launches take: the table side of the gradient kernels and dense Adam's scalars.
 struct CondUpdate { BagTable a; OptScalars adam; };
 
 // An update in front of its launches: the operand, optimiser and step checks, then the bias corrections into both optimisers' terms.
 static int cond_update_begin(const char* who, CondUpdate& u, float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev,
                              float* grad_scratch_dev, int32_t vocab, int32_t dim, int32_t reduce, int32_t padding_idx,
-                             const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step) {
+                             const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, int32_t flags) {
+    if (flags & ~AAE_BAG_SCALE_BY_FREQ) COND_FAIL("unknown flags");
+    if ((flags & AAE_BAG_SCALE_BY_FREQ) && optimizer == AAE_CAT_SPARSE_ADAM)
+        COND_FAIL("AAE_BAG_SCALE_BY_FREQ goes with AAE_CAT_ADAM only (torch has no sparse gradient scaled by frequency)");
     if (!table_dev || !exp_avg_dev || !exp_avg_sq_dev || !dout_dev || dout_ld < dim) COND_FAIL("table/state/dout is NULL or dout_ld < dim");
     if (optimizer != AAE_CAT_SPARSE_ADAM && optimizer != AAE_CAT_ADAM) COND_FAIL("unknown optimizer");
     const bool scratch = optimizer == AAE_CAT_ADAM || cond_is_max(reduce);
@@ -45,6 +60,7 @@ static int cond_update_begin(const char* who, CondUpdate& u, float* table_dev, f
     a.gdense = scratch ? grad_scratch_dev : nullptr;
     a.d = dout_dev; a.ldd = dout_ld; a.vocab = vocab; a.dim = dim; a.reduce = reduce; a.pad = padding_idx;
     a.neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
+    a.by_freq = (flags & AAE_BAG_SCALE_BY_FREQ) != 0;
     OptScalars& sc = u.adam;
     memset(&sc, 0, sizeof(sc));
     sc.t = step; sc.neg_step_size = (float)(-(lr / bc1)); sc.bc2_sqrt = (float)sqrt(bc2); sc.lr = lr;
@@ -78,12 +94,12 @@ static int bag_padded_encode(const char* who, const float* table_dev, int32_t vo
 static int bag_padded_update(const char* who, float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev,
                              int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce,
                              int32_t padding_idx, const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr,
-                             int64_t step, void* stream) {
+                             int64_t step, int32_t flags, void* stream) {
     TRY(cond_shape_check(who, vocab, dim, reduce, padding_idx));
     TRY(cond_block_check(who, idx_dev, rows, width));
     CondUpdate u;
     TRY(cond_update_begin(who, u, table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, reduce, padding_idx, dout_dev,
-                          dout_ld, optimizer, lr, step));
+                          dout_ld, optimizer, lr, step, flags));
     const BagPadded src = {idx_dev, rows, width};
     const int n = rows * width;
     const dim3 grid((n + kCatWaves - 1) / kCatWaves), block(64 * kCatWaves);
@@ -108,7 +124,7 @@ int aae_cat_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, 
                    const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream) {
     if (reduce != AAE_CAT_SUM && reduce != AAE_CAT_MEAN) return fail(AAE_EINVAL, "aae_cat_update: reduce must be sum or mean");
     return bag_padded_update("aae_cat_update", table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, idx_dev, rows,
-                             width, reduce, 0, dout_dev, dout_ld, optimizer, lr, step, stream);
+                             width, reduce, 0, dout_dev, dout_ld, optimizer, lr, step, 0, stream);
 }
 
 int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows,
@@ -117,11 +133,35 @@ int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int
                              stream);
 }
 
+int aae_bag_update_flags(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                         int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
+                         const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, int32_t flags,
+                         void* stream) {
+    return bag_padded_update("aae_bag_update", table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, idx_dev, rows,
+                             width, reduce, padding_idx, dout_dev, dout_ld, optimizer, lr, step, flags, stream);
+}
+
 int aae_bag_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
                    int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
                    const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream) {
-    return bag_padded_update("aae_bag_update", table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, idx_dev, rows,
-                             width, reduce, padding_idx, dout_dev, dout_ld, optimizer, lr, step, stream);
+    return aae_bag_update_flags(table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, idx_dev, rows, width, reduce,
+                                padding_idx, dout_dev, dout_ld, optimizer, lr, step, 0, stream);
+}
+
+int aae_bag_renorm(float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width,
+                   double max_norm, int32_t norm_type, void* stream) {
+    const char* who = "aae_bag_renorm";
+    float mn;
+    TRY(cond_shape_check(who, vocab, dim, AAE_BAG_SUM, -1));
+    TRY(cond_norm_check(who, max_norm, norm_type, &mn));
+    TRY(cond_block_check(who, idx_dev, rows, width));
+    if (!table_dev) COND_FAIL("table_dev is NULL");
+    const BagPadded src = {idx_dev, rows, width};
+    const int n = rows * width;
+    hipLaunchKernelGGL(bag_renorm_kernel, dim3((n + kCatWaves - 1) / kCatWaves), dim3(64 * kCatWaves), 0, S(stream), table_dev,
+                       vocab, dim, src, mn, norm_type);
+    LAUNCHCHK("bag_renorm");
+    return AAE_OK;
 }
 
 // ---- the same bags from a resident CSR (cond_csr.h) ----------------------------------------------------------
@@ -173,6 +213,27 @@ static int bag_csr_check(const char* who, BagCsr& c, int32_t vocab, int32_t dim,
     return AAE_OK;
 }
 
+// The step's entries as keys grouped by table row under the padding row `pad` (cond_csr.h): row scan, LDS sort, merge passes up
+// to the entry bound (E itself stays on the device).  Returns the buffer the sorted keys end in (keys_a or keys_b).
+static const unsigned long long* bag_csr_sorted(const BagCsr& c, int32_t vocab, int32_t pad, int64_t max_entries, hipStream_t s) {
+    hipLaunchKernelGGL(bagcsr_rowinfo_kernel, dim3(1), dim3(kBagCsrScanNT), 0, s, c);
+    hipLaunchKernelGGL(bagcsr_sort_kernel, dim3((unsigned)((max_entries + kBagCsrSort - 1) / kBagCsrSort)), dim3(kBagCsrNT), 0, s, c,
+                       vocab, pad);
+    unsigned long long *src = c.keys_a, *dst = c.keys_b;
+    for (int64_t w = kBagCsrSort; w < max_entries; w <<= 1) {
+        hipLaunchKernelGGL(bagcsr_merge_kernel, dim3((unsigned)((max_entries + kBagCsrNT - 1) / kBagCsrNT)), dim3(kBagCsrNT), 0, s,
+                           src, dst, c.hdr, (int)w);
+        unsigned long long* t = src; src = dst; dst = t;
+    }
+    return src;
+}
+
+// the update launch's grid: a wavefront per sorted position, grid-stride beyond kBagCsrMaxGrid workgroups
+static dim3 bag_csr_grid(int64_t max_entries) {
+    const int64_t want = (max_entries + kCatWaves - 1) / kCatWaves;
+    return dim3((unsigned)(want < kBagCsrMaxGrid ? want : kBagCsrMaxGrid));
+}
+
 int aae_bag_csr_encode(const float* table_dev, int32_t vocab, int32_t dim, const int64_t* indptr_dev,
                        const int32_t* indices_dev, const float* weights_dev, int64_t n_docs, int64_t nnz,
                        const int32_t* row_ids_dev, int64_t row0, int32_t rows, int32_t reduce, int32_t padding_idx,
@@ -191,41 +252,61 @@ int aae_bag_csr_encode(const float* table_dev, int32_t vocab, int32_t dim, const
     return AAE_OK;
 }
 
-int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
-                       int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev, const float* weights_dev,
-                       int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
-                       int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
-                       int32_t optimizer, double lr, int64_t step, void* scratch_dev, int64_t scratch_bytes, void* stream) {
+int aae_bag_csr_update_flags(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                             int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev, const float* weights_dev,
+                             int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
+                             int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
+                             int32_t optimizer, double lr, int64_t step, int32_t flags, void* scratch_dev,
+                             int64_t scratch_bytes, void* stream) {
     BagCsr c;
     TRY(bag_csr_check("aae_bag_csr_update", c, vocab, dim, indptr_dev, indices_dev, weights_dev, n_docs, nnz, row_ids_dev, row0,
                       rows, max_entries, reduce, padding_idx, scratch_dev, scratch_bytes));
     if (max_entries < 1) return fail(AAE_EINVAL, "aae_bag_csr_update: max_entries must be >= 1");
     CondUpdate u;
     TRY(cond_update_begin("aae_bag_csr_update", u, table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, reduce,
-                          padding_idx, dout_dev, dout_ld, optimizer, lr, step));
+                          padding_idx, dout_dev, dout_ld, optimizer, lr, step, flags));
     hipStream_t s = S(stream);
-    hipLaunchKernelGGL(bagcsr_rowinfo_kernel, dim3(1), dim3(kBagCsrScanNT), 0, s, c);
-    hipLaunchKernelGGL(bagcsr_sort_kernel, dim3((unsigned)((max_entries + kBagCsrSort - 1) / kBagCsrSort)), dim3(kBagCsrNT), 0, s, c,
-                       vocab, padding_idx);
-    // merge passes up to the entry bound (E itself stays on the device); the sorted keys end in keys_a or keys_b
-    unsigned long long *src = c.keys_a, *dst = c.keys_b;
-    for (int64_t w = kBagCsrSort; w < max_entries; w <<= 1) {
-        hipLaunchKernelGGL(bagcsr_merge_kernel, dim3((unsigned)((max_entries + kBagCsrNT - 1) / kBagCsrNT)), dim3(kBagCsrNT), 0, s,
-                           src, dst, c.hdr, (int)w);
-        unsigned long long* t = src; src = dst; dst = t;
-    }
+    const unsigned long long* src = bag_csr_sorted(c, vocab, padding_idx, max_entries, s);
     if (reduce >= AAE_BAG_MEAN_COUNT)
         hipLaunchKernelGGL(bagcsr_rowpass_kernel, dim3(rows, reduce == AAE_BAG_MEAN_COUNT ? 1 : (dim + 63) / 64), dim3(64), 0, s, c,
                            table_dev, vocab, dim, reduce, padding_idx);
-    const int64_t want = (max_entries + kCatWaves - 1) / kCatWaves;
-    const dim3 grid((unsigned)(want < kBagCsrMaxGrid ? want : kBagCsrMaxGrid)), block(64 * kCatWaves);
-    hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, u.a, c, (const unsigned long long*)src, 0);
+    const dim3 grid = bag_csr_grid(max_entries), block(64 * kCatWaves);
+    hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, u.a, c, src, 0);
     LAUNCHCHK("bagcsr_update");
     if (optimizer == AAE_CAT_ADAM) return cond_dense_adam(u, s);
     if (cond_is_max(reduce)) {          // SparseAdam of the max modes: the owners apply their row from the scratch and clear it
-        hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, u.a, c, (const unsigned long long*)src, 1);
+        hipLaunchKernelGGL(bagcsr_update_kernel, grid, block, 0, s, u.a, c, src, 1);
         LAUNCHCHK("bagcsr_apply");
     }
+    return AAE_OK;
+}
+
+int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                       int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev, const float* weights_dev,
+                       int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
+                       int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
+                       int32_t optimizer, double lr, int64_t step, void* scratch_dev, int64_t scratch_bytes, void* stream) {
+    return aae_bag_csr_update_flags(table_dev, exp_avg_dev, exp_avg_sq_dev, grad_scratch_dev, vocab, dim, indptr_dev, indices_dev,
+                                    weights_dev, n_docs, nnz, row_ids_dev, row0, rows, max_entries, reduce, padding_idx, dout_dev,
+                                    dout_ld, optimizer, lr, step, 0, scratch_dev, scratch_bytes, stream);
+}
+
+int aae_bag_csr_renorm(float* table_dev, int32_t vocab, int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev,
+                       int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows, int64_t max_entries,
+                       double max_norm, int32_t norm_type, void* scratch_dev, int64_t scratch_bytes, void* stream) {
+    const char* who = "aae_bag_csr_renorm";
+    float mn;
+    TRY(cond_norm_check(who, max_norm, norm_type, &mn));
+    BagCsr c;
+    TRY(bag_csr_check(who, c, vocab, dim, indptr_dev, indices_dev, nullptr, n_docs, nnz, row_ids_dev, row0, rows, max_entries,
+                      AAE_BAG_SUM, -1, scratch_dev, scratch_bytes));
+    if (max_entries < 1) COND_FAIL("max_entries must be >= 1");
+    if (!table_dev) COND_FAIL("table_dev is NULL");
+    hipStream_t s = S(stream);
+    const unsigned long long* src = bag_csr_sorted(c, vocab, -1, max_entries, s);       // no padding row: every named row has an owner
+    hipLaunchKernelGGL(bagcsr_renorm_kernel, bag_csr_grid(max_entries), dim3(64 * kCatWaves), 0, s, table_dev, dim, c, src, mn,
+                       norm_type);
+    LAUNCHCHK("bagcsr_renorm");
     return AAE_OK;
 }
 

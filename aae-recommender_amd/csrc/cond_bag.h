@@ -7,6 +7,8 @@
 //
 //   encode   out[r][0:dim] = reduce over the slots w of row r of table[idx[r][w]]
 //   update   the reduction's backward and the optimiser step (SparseAdam here, cond_embed.h's cat_dense_adam_kernel)
+//   renorm   nn.Embedding's max_norm: every table row the input names whose p-norm exceeds max_norm is scaled onto it, once,
+//            in a launch of its own in front of the encode (bag_row_renorm)
 //
 // padding_idx -1: no padding row (nn.EmbeddingBag's default; index 0 is an ordinary, trainable row); >= 0: that row is left
 // out of the reduction and receives no gradient.  An index outside [0, vocab) is handled like a padding slot.
@@ -28,6 +30,10 @@
 // 256), no float atomics - the first slot that names a table row owns it, sums the contributions of every slot naming it in
 // slot order (the sparse gradient's coalesce()) and hands the row on, so results do not depend on scheduling.  The duplicate
 // scan is quadratic in rows * width.
+//
+// scale_grad_by_freq (BagTable::by_freq): the owner has visited every slot naming its row, so it knows their number - the
+// whole batch's, every bag's, the losers of the max modes included - and divides the summed gradient by it
+// (bag_freq_scale: one division per element, behind the sum).
 //
 // Contraction is part of the bits: bag_reduce_col and bag_grad_add keep a per-sample weight's product a multiply of its own
 // (fp contract off), bag_sparse_adam stands outside any such pragma.  tests/golden/cond_bits.json records the result.
@@ -94,6 +100,7 @@ struct BagTable {
     const float* d; long long ldd;      // dout [rows][>= dim]
     int vocab, dim, reduce, pad;
     float neg_step_size;        // SparseAdam: -(lr * sqrt(1 - b2^t) / (1 - b1^t))
+    int by_freq;                // scale_grad_by_freq: a row's gradient is divided by the number of entries of the batch naming it
 };
 
 // torch.optim.SparseAdam on one element, in its operation order (torch/optim/_functional.py sparse_adam)
@@ -129,6 +136,48 @@ __device__ __forceinline__ void bag_apply_row(const BagTable& a, int j, int lane
     }
 }
 
+// scale_grad_by_freq: the gradient the owner summed over the `count` (>= 1) entries naming its row, divided by their number
+__device__ __forceinline__ void bag_freq_scale(const BagTable& a, float (&g)[kCatMaxDim / 64], int count) {
+    if (!a.by_freq) return;
+    const float n = (float)count;
+#pragma unroll
+    for (int k = 0; k < kCatMaxDim / 64; ++k) g[k] = g[k] / n;
+}
+
+// ---- max_norm ------------------------------------------------------------------------------------------------------------
+enum { kBagNormInf = 0, kBagNormL1 = 1, kBagNormL2 = 2 };
+
+// The p-norm of a table row over a wavefront (lane: columns lane + 64 k, ascending k), fp32: the lanes' partial sums of |x|^p
+// (p = 1, 2) or maxima (p = inf), folded by the xor butterfly 32, 16, .. 1 - one fixed order, the same value in every lane -
+// and, p = 2, the square root.
+__device__ __forceinline__ float bag_row_norm(const float* __restrict__ row, int dim, int lane, int norm_type) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < kCatMaxDim / 64; ++k) {
+        const int col = lane + 64 * k;
+        if (col >= dim) continue;
+        const float x = row[col];
+        if (norm_type == kBagNormL2) acc += x * x;
+        else if (norm_type == kBagNormL1) acc += fabsf(x);
+        else acc = fmaxf(acc, fabsf(x));
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const float y = __shfl_xor(acc, d);
+        acc = norm_type == kBagNormInf ? fmaxf(acc, y) : acc + y;
+    }
+    return norm_type == kBagNormL2 ? sqrtf(acc) : acc;
+}
+
+// torch's embedding_renorm_ on the row its owner holds: norm > max_norm (strictly) scales the row by max_norm / (norm + 1e-7)
+__device__ __forceinline__ void bag_row_renorm(float* __restrict__ table, int dim, int j, int lane, float max_norm, int norm_type) {
+    float* row = table + (size_t)j * dim;
+    const float norm = bag_row_norm(row, dim, lane, norm_type);
+    if (!(norm > max_norm)) return;
+    const float scale = max_norm / (norm + 1e-7f);
+    for (int col = lane; col < dim; col += 64) row[col] = row[col] * scale;
+}
+
 // ---- the padded source: idx [rows][width] --------------------------------------------------------------------------------
 struct BagPadded { const int* idx; int rows, width; };
 
@@ -142,14 +191,26 @@ bag_encode_kernel(const float* __restrict__ table, int vocab, int dim, const int
                                                 col, &win, &cnt);
 }
 
-// the table row this wavefront's index slot owns: the slot's row if it is live and no earlier slot names it, else -1
-__device__ __forceinline__ int bag_owned_row(const BagTable& a, const BagPadded& s, int e, int lane) {
+// the table row index slot e owns under the padding row `pad`: the slot's row if it is live and no earlier slot names it, else
+// -1 (pad -1: every row of the table can be owned - the renorm's rule, which scales a padding row too)
+__device__ __forceinline__ int bag_first_slot(const BagPadded& s, int e, int lane, int vocab, int pad) {
     if (e >= s.rows * s.width) return -1;
     const int j = s.idx[e];
-    if (!bag_live(j, a.vocab, a.pad)) return -1;
+    if (!bag_live(j, vocab, pad)) return -1;
     int dup = 0;
     for (int e2 = lane; e2 < e; e2 += 64) dup |= (s.idx[e2] == j);
     return __any(dup) ? -1 : j;
+}
+
+__device__ __forceinline__ int bag_owned_row(const BagTable& a, const BagPadded& s, int e, int lane) {
+    return bag_first_slot(s, e, lane, a.vocab, a.pad);
+}
+
+__global__ void __launch_bounds__(64 * kCatWaves)
+bag_renorm_kernel(float* __restrict__ table, int vocab, int dim, BagPadded s, float max_norm, int norm_type) {
+    const int lane = threadIdx.x & 63;
+    const int j = bag_first_slot(s, blockIdx.x * kCatWaves + (threadIdx.x >> 6), lane, vocab, -1);
+    if (j >= 0) bag_row_renorm(table, dim, j, lane, max_norm, norm_type);
 }
 
 __global__ void __launch_bounds__(64 * kCatWaves)
@@ -163,10 +224,12 @@ bag_update_kernel(BagTable a, BagPadded s) {
     float g[kCatMaxDim / 64];
 #pragma unroll
     for (int k = 0; k < kCatMaxDim / 64; ++k) g[k] = 0.f;
+    int named = 0;                                                   // slots naming row j (scale_grad_by_freq)
     for (int base = e & ~63; base < n; base += 64) {
         const int e2 = base + lane;
         const int hit = (e2 >= e && e2 < n) ? (s.idx[e2] == j) : 0;
         unsigned long long mask = __ballot(hit);
+        named += __builtin_popcountll(mask);
         while (mask) {
             const int slot = base + __builtin_ctzll(mask);
             mask &= mask - 1;
@@ -185,6 +248,7 @@ bag_update_kernel(BagTable a, BagPadded s) {
             }
         }
     }
+    bag_freq_scale(a, g, named);
     bag_write_row(a, j, lane, g);
 }
 

@@ -29,6 +29,8 @@
 //   bagcsr_update_kernel    a wavefront per sorted position (grid-stride): the first key of a table row owns it, walks the
 //                           row's run, sums the contributions in that order (bag_grad_add) and hands the row on as
 //                           bag_update_kernel does (bag_write_row; the max modes' second pass: bag_apply_row).
+// Renorm (max_norm): the same sort with no padding row (pad -1), so a padding-row entry keeps its row in the key; the first
+// key of a table row owns it and scales it once (bagcsr_renorm_kernel -> bag_row_renorm).
 // Work: O(E) for everything but the sort; the sort is O(E log^2 kBagCsrSort) in LDS plus log2(bound / kBagCsrSort) merge passes
 // of O(E log E) each.  Nothing is quadratic, nothing is proportional to vocab but dense Adam itself, there is no [vocab]
 // marker, no atomic of any kind, and every loop is bounded by a length read once (E, a row's length, the row count).
@@ -223,9 +225,11 @@ bagcsr_update_kernel(BagTable a, BagCsr c, const unsigned long long* __restrict_
         float g[kCatMaxDim / 64];
 #pragma unroll
         for (int q = 0; q < kCatMaxDim / 64; ++q) g[q] = 0.f;
+        int named = 0;                                              // entries naming row j (scale_grad_by_freq)
         for (int k2 = k; k2 < E; ++k2) {
             const unsigned long long key = sorted[k2];
             if ((unsigned)(key >> 32) != j) break;
+            ++named;
             const int e = (int)(unsigned)key;
             const int b = c.rowof[e];
             const int w = e - c.off[b];
@@ -240,7 +244,23 @@ bagcsr_update_kernel(BagTable a, BagCsr c, const unsigned long long* __restrict_
                 bag_grad_add(g[q], a.reduce, a.d[(size_t)b * a.ldd + col], width, live, winner, c.weights != nullptr, wt);
             }
         }
+        bag_freq_scale(a, g, named);
         bag_write_row(a, (int)j, lane, g);
+    }
+}
+
+// max_norm over the keys sorted with no padding row: a wavefront per sorted position, the first key of a table row scales it
+__global__ void __launch_bounds__(64 * kCatWaves)
+bagcsr_renorm_kernel(float* __restrict__ table, int dim, BagCsr c, const unsigned long long* __restrict__ sorted, float max_norm,
+                     int norm_type) {
+    const int lane = threadIdx.x & 63;
+    const int E = c.hdr[0];
+    const int stride = gridDim.x * kCatWaves;
+    for (int k = blockIdx.x * kCatWaves + (threadIdx.x >> 6); k < E; k += stride) {
+        const unsigned j = (unsigned)(sorted[k] >> 32);
+        if (j == kBagCsrDead) continue;
+        if (k > 0 && (unsigned)(sorted[k - 1] >> 32) == j) continue;
+        bag_row_renorm(table, dim, (int)j, lane, max_norm, norm_type);
     }
 }
 

@@ -395,6 +395,29 @@ int aae_bag_encode(const float* table_dev, int32_t vocab, int32_t dim, const int
 int aae_bag_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
                    int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
                    const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, void* stream);
+/* nn.Embedding's / nn.EmbeddingBag's max_norm and scale_grad_by_freq on the same bags.
+ *   aae_bag_renorm  torch's embedding_renorm_, which the module's forward runs first (under no_grad, in training and in eval
+ *     alike): every DISTINCT table row named by idx_dev - a padding row too; an index outside [0, vocab) names nothing -
+ *     whose p-norm is strictly greater than max_norm is multiplied ONCE by max_norm / (norm + 1e-7), however often it is
+ *     named.  Norm, compare, scale and store are fp32; the norm's summation order is fixed (the same bits every run, and
+ *     the same bits from aae_bag_csr_renorm).  A launch of its own: call it in front of the aae_bag_encode of the same
+ *     idx_dev on the same stream; the encode, the update and the optimiser then see the renormalised table, and the
+ *     recompute contract of the max modes holds because nothing touches the table behind the encode.
+ *     norm_type: AAE_BAG_NORM_L1, AAE_BAG_NORM_L2 or AAE_BAG_NORM_INF (max |x|).  AAE_EINVAL for max_norm <= 0 and for any
+ *     other norm_type.
+ *   aae_bag_update_flags  aae_bag_update (which is this call with flags 0) with
+ *     AAE_BAG_SCALE_BY_FREQ  the gradient of table row j is divided by the number of times j occurs among ALL indices of the
+ *       block (every bag, winners and losers of the max modes alike, whatever the per-sample weights): one IEEE division per
+ *       element behind the sum of the row's contributions.  The padding row still gets no gradient.  AAE_CAT_ADAM only
+ *       (torch refuses a sparse gradient scaled by frequency): AAE_EINVAL with AAE_CAT_SPARSE_ADAM, and for unknown flags. */
+enum { AAE_BAG_NORM_INF = 0, AAE_BAG_NORM_L1 = 1, AAE_BAG_NORM_L2 = 2 };
+enum { AAE_BAG_SCALE_BY_FREQ = 1 };
+int aae_bag_renorm(float* table_dev, int32_t vocab, int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width,
+                   double max_norm, int32_t norm_type, void* stream);
+int aae_bag_update_flags(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                         int32_t dim, const int32_t* idx_dev, int32_t rows, int32_t width, int32_t reduce, int32_t padding_idx,
+                         const float* dout_dev, int64_t dout_ld, int32_t optimizer, double lr, int64_t step, int32_t flags,
+                         void* stream);
 /* The same bags from a RESIDENT CSR (csrc/cond_csr.h): the value lists of the whole corpus are uploaded once, a step names
  * its rows, nothing is padded and the update's grouping is a sort - no quadratic scan.
  *   indptr_dev int64 [n_docs + 1], indices_dev int32 [nnz] (table rows), weights_dev float32 [nnz] or NULL
@@ -423,6 +446,20 @@ int aae_bag_csr_update(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_d
                        int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
                        int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
                        int32_t optimizer, double lr, int64_t step, void* scratch_dev, int64_t scratch_bytes, void* stream);
+/* aae_bag_renorm / aae_bag_update_flags over a window of the resident CSR: the same bits as on the same lists padded.
+ *   aae_bag_csr_renorm groups the entries with the update's sort, keyed with no padding row, so a padding-row entry keeps its
+ *   table row and that row has an owner too; it takes max_entries (>= 1) and a scratch of
+ *   aae_bag_csr_scratch_bytes(rows, max_entries) bytes as aae_bag_csr_update does - no more than that, and no [vocab] marker.
+ *   aae_bag_csr_update is aae_bag_csr_update_flags with flags 0. */
+int aae_bag_csr_renorm(float* table_dev, int32_t vocab, int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev,
+                       int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows, int64_t max_entries,
+                       double max_norm, int32_t norm_type, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int aae_bag_csr_update_flags(float* table_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_scratch_dev, int32_t vocab,
+                             int32_t dim, const int64_t* indptr_dev, const int32_t* indices_dev, const float* weights_dev,
+                             int64_t n_docs, int64_t nnz, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
+                             int64_t max_entries, int32_t reduce, int32_t padding_idx, const float* dout_dev, int64_t dout_ld,
+                             int32_t optimizer, double lr, int64_t step, int32_t flags, void* scratch_dev,
+                             int64_t scratch_bytes, void* stream);
 /* PretrainedWordEmbeddingCondition's preprocessing (condition.py:345-369 -> ub.py:52-57, EmbeddedVectorizer.transform:
  * `sparse_scores @ self.embedding`): out_dev[r][0:dim] = sum over the CSR entries e of row r of
  * values[e] * table_dev[indices[e]][0:dim], accumulated in CSR order.  indptr int64 [n_rows + 1] (absolute offsets

@@ -10,6 +10,10 @@
     python tools/cond_rate.py ragged a|b resident|padded [steps a pass]
                                      fit() in ms/step behind a trainable condition whose value lists are resident bags
                                      (csrc/cond_csr.h) or padded on the host every step: see ragged_rates
+    python tools/cond_rate.py opts [fit [reversed]]
+                                     max_norm and scale_grad_by_freq behind a CategoricalCondition(reduce="sum", sparse=False)
+                                     with either option: partial_fit(), and fit() with the value lists as resident bags - native
+                                     against the bridged route
 Everything but `ragged b` (the VAE) runs through AdversarialAutoEncoder."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,19 +68,20 @@ def rate(tag, conditions, data, epochs=25):
     print(f"{tag:34s} {epochs * DOCS / dt:10.0f} docs/s   ({1e3 * dt / (epochs * DOCS / B):.3f} ms/step, build {t2 - t1:.2f} s)", flush=True)
 
 
-def partial_fit_rates(rounds=9, warm=2):
-    """Median over `rounds` passes of 64 partial_fit calls (after `warm` passes), every pass closed by a synchronize."""
+def partial_fit_rates(rounds=9, warm=2, opts=False):
+    """Median over `rounds` passes of 64 partial_fit calls (after `warm` passes), every pass closed by a synchronize.
+    opts: the rows of DESIGN 4.1f (a max_norm table, a frequency-scaled one) instead of 4.1c's."""
     batches = [X[i:i + B] for i in range(0, DOCS, B)]
     authors = [[int(a) for a in rng.integers(0, 5000, rng.integers(1, 5))] for _ in range(DOCS)]
     # (a LongTensor on the GPU: the form nn.EmbeddingBag itself takes, so the bridged route needs no conversion)
     bags = torch.from_numpy(rng.integers(0, 5000, size=(DOCS, 4)).astype(np.int64)).cuda()
 
-    def cat(sparse):
+    def cat(sparse, reduce="max", **kw):
         def make(bridged):
             cls = C.CategoricalCondition
             if bridged:
                 cls = type("Bridged", (cls,), {"device_native": lambda self, device: False})
-            cond = cls(32, use_cuda=True, reduce="max", sparse=sparse)
+            cond = cls(32, use_cuda=True, reduce=reduce, sparse=sparse, **kw)
             return cond, cond.fit_transform(authors)
         return make
 
@@ -107,8 +112,12 @@ def partial_fit_rates(rounds=9, warm=2):
         return float(np.median(times[warm:])), native
     print(f"partial_fit, N={N} h={h} c={c} batch {B}: median ms/step of {rounds} passes of {DOCS // B} steps")
     print(f"{'condition':44s} {'native':>10s} {'bridged':>10s}")
-    for tag, make in (("CategoricalCondition(32, max, SparseAdam)", cat(True)), ("CategoricalCondition(32, max, Adam)", cat(False)),
-                      ("EmbeddingBagCondition(5001, 32)  [mean]", bag()), ("EmbeddingBagCondition(5001, 32, mode=max)", bag(mode="max"))):
+    rows = (("CategoricalCondition(32, max, SparseAdam)", cat(True)), ("CategoricalCondition(32, max, Adam)", cat(False)),
+            ("EmbeddingBagCondition(5001, 32)  [mean]", bag()), ("EmbeddingBagCondition(5001, 32, mode=max)", bag(mode="max")))
+    if opts:
+        rows = (("CategoricalCondition(32, sum, Adam, max_norm=1)", cat(False, "sum", max_norm=1.0)),
+                ("Categorical(32, sum, Adam, scale_grad_by_freq)", cat(False, "sum", scale_grad_by_freq=True)))
+    for tag, make in rows:
         t_nat, native = ms_per_step(make, False)
         t_br, _ = ms_per_step(make, True)
         note = "" if native else "   (no native route in this build: both columns are the bridged route)"
@@ -135,6 +144,45 @@ def fit_rates():
     cat.device_native = lambda device: False
     cl = C.ConditionList([("authors", cat)])
     rate("categorical (emb on gpu, autograd bridge)", cl, cl.fit_transform([authors]))
+
+
+def opts_fit_rates(pass_steps=64, rounds=9, warm=2, order=(0, 1)):
+    """ms/step of fit() behind CategoricalCondition(32, reduce="sum", sparse=False) with max_norm or
+    scale_grad_by_freq, 4.1d's cell a (batch 100, table 5001 x 32, lists of 1-4 values): native with resident bags against the
+    bridged route (the parent's behaviour: torch autograd at the condition boundary, lists padded on the host every step).
+    The median [fastest, slowest] of `rounds` passes of `pass_steps` steps after `warm` passes, every pass closed by a
+    synchronize; the two routes take turns twice (round 1 | round 2), one model each."""
+    lists = [[int(a) for a in rng.integers(0, 5000, rng.integers(1, 5))] for _ in range(DOCS)]
+    passes = warm + rounds
+    print(f"fit(), batch {B}, table 5001 x 32, resident bags: median ms/step of {rounds} passes of {pass_steps} steps")
+    print(f"{'condition':56s} {'native':>44s} {'bridged':>44s}")
+    cases = (("CategoricalCondition(32, sum, Adam, max_norm=1)", dict(max_norm=1.0)),
+             ("CategoricalCondition(32, sum, Adam, scale_grad_by_freq)", dict(scale_grad_by_freq=True)))
+    for tag, kw in (cases[i] for i in order):
+        med = {False: [], True: []}
+        for bridged in (False, True, False, True):
+            cls = C.CategoricalCondition
+            if bridged:
+                cls = type("Bridged", (cls,), {"device_native": lambda self, device: False})
+            cond = cls(32, use_cuda=True, reduce="sum", sparse=False, vocab_size=5000, **kw)
+            data = cond.fit_transform(lists)
+            m = AdversarialAutoEncoder(n_hidden=h, n_code=c, batch_size=B, n_epochs=passes + 1,
+                                       conditions=C.ConditionList([("authors", cond)]), verbose=False, seed=1)
+            m.resident_conditions = True
+            times, mark, steps = [], None, 0
+            for _ in m.fit_steps(X, condition_data=[data]):
+                steps += 1
+                if steps % pass_steps == 0:
+                    torch.cuda.synchronize()
+                    now = time.perf_counter()
+                    if mark is not None:
+                        times.append(1e3 * (now - mark) / pass_steps)
+                    mark = now
+                    if len(times) == passes:
+                        break
+            assert m._is_device_native() == (not bridged) and len(times) == passes
+            med[bridged].append(f"{np.median(times[warm:]):.3f} [{min(times[warm:]):.3f}, {max(times[warm:]):.3f}]")
+        print(f"{tag:56s} {' | '.join(med[False]):>44s} {' | '.join(med[True]):>44s}", flush=True)
 
 
 def ragged_rates(cell, route, pass_steps=64, rounds=9, warm=2):
@@ -210,5 +258,9 @@ if __name__ == "__main__":
     if "ragged" in sys.argv[1:]:
         a = sys.argv[sys.argv.index("ragged") + 1:]
         ragged_rates(a[0], a[1], pass_steps=int(a[2]) if len(a) > 2 else 64)
+    elif "opts" in sys.argv[1:]:
+        if "fit" not in sys.argv[1:]:
+            partial_fit_rates(opts=True)
+        opts_fit_rates(order=(1, 0) if "reversed" in sys.argv[1:] else (0, 1))
     else:
         partial_fit_rates() if "bag" in sys.argv[1:] else fit_rates()
