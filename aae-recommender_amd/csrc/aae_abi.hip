@@ -116,8 +116,6 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     m->alpha_mode = cfg->activation == AAE_ACT_SELU;
     m->vae = cfg->model_kind == 3; m->vae_cut = false;
     m->bf16 = cfg->dtype == 1;
-    m->blocked_ok = cfg->blocked_output == 1;
-    m->blocked_any = m->opt.blocked_any;
     m->split_any = m->opt.split_any;
     m->x3_gemm = !m->bf16;
     m->noise_next = nullptr; m->noise_ld = 0; m->dense_step = false; m->noise_gen_next = false; m->noise_gen_scale = 0.f;
@@ -162,8 +160,8 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         if (m->x16_ok) each_chain16x3(limit(m->x16_ok, kX16Lds));
         m->force_unfused = cfg->unfused_decoder == 1;   // debugging / A-B switch: unfused_decoder = 1 keeps the 3-kernel path
         if (m->fused_ok) {
-            each_dec_fused(kDecFused, limit(m->fused_ok, maxlds));
-            if (m->bf16) each_dec_fused_bf16(kDecFused, limit(m->fused_ok, maxlds));
+            each_dec_fused(limit(m->fused_ok, maxlds));
+            if (m->bf16) each_dec_fused_bf16(limit(m->fused_ok, maxlds));
             if (!raise_lds_limit(tile_bucket_kernel, maxlds - 2048)) m->fused_ok = false;
             m->bucket_wide_ok = raise_lds_limit(tile_bucket_wide_kernel, maxlds - 16384);
             {   //  the wide bucket builder keeps other workgroups off its CU by its register count (buckets.h: a clobber of
@@ -197,7 +195,7 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
     // runs on the bf16 matrix cores (r3, 116 -> 84 us) the NEXT step waits for this launch; measured at C3, batch 100
     // (r2-r3 sweep of the launch's width, ms/step), with the fp32 deferred kernel: 112 0.306 | 128 0.291 | 144 0.274 | 160 0.274 | 176 0.284
     // | 192 0.285 | 224 0.312; with the bf16-emulated one (dec_opt_x3_kernel: 160 -> 138 us on 128 workgroups): 112 0.279 |
-    // 128 0.273 | 144 0.276 | 160 0.278 | 176 0.286.  Half the CUs again (set below once x3_ok is known; 5/8 without it):
+    // 128 0.273 | 144 0.276 | 160 0.278 | 176 0.286.  Half the CUs again (set below once split_ok is known):
     // beyond that the chain / weight-gradient kernels it runs beside lose more than the launch gains.
     m->split_wgs = std::max(1, (m->n_cu * 5) / 8);
     m->pf_armed = m->pf_built = m->pf_pending = false; m->pf_step = -1; m->hstep = 0; m->flushed_hstep = -1; m->ev_head = m->ev_pf = nullptr;
@@ -222,46 +220,28 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         }
         (void)hipGetLastError();
     }
-    if (side_ok && m->fused_ok && m->bf16 && m->split_wgs > 0 &&
-        (size_t)((m->N + kBU - 1) / kBU) * kBU * bf_stride(4) <= (size_t)m->R * m->ldn) {      // (room for the stored gT images in the G scratch)
-        m->split_ok = true;
-        for (int mode : {kDecCrit, kDecOpt}) each_dec_fused_bf16(mode, limit(m->split_ok, maxlds));
-        (void)hipGetLastError();
-    }
-    // (bf16 mode too: its output layer runs the same kernels with every operand rounded to bf16 - DecFusedArgs::one_term - when
-    //  they are available; dec_fused_bf16.h's own pair otherwise, or with AAE_NO_BF16_X3)
-    if (side_ok && m->fused_ok && m->split_wgs > 0 && 
+    // The split forms of the output layer exist - ONE capability: the side stream and its events, the single launch (the bucket
+    // build and the slab area are its), the stored dL/dlogits tiles of a row block behind one descriptor, and the LDS limit of
+    // every dec_crit_x3.h family this handle's dtype launches: critical, deferred, blocked-deferred.
+    // (a bf16 handle runs the same kernels with every operand rounded to bf16 - DecFusedArgs::one_term - and the critical and
+    //  deferred launch on their one-term instantiations, ONE matrix instruction per product.  Both launches got faster with them -
+    //  critical 35 -> 27 us, deferred 85 -> 74 us at C2 - and for most of r4 the STEP got slower, 0.173 -> 0.186 ms
+    //  (r4's profile of C2 in bf16 under profiles/): the one-term deferred kernel needs 78 VGPRs instead of 126, so six of its waves fit a
+    //  SIMD, its 1024-thread workgroup no longer fills its CU, and the dispatcher deals the step's own weight-gradient / gather
+    //  workgroups onto the CUs where it streams 24 B per parameter (the weight-gradient launch beside it: 32 us instead of 11).
+    //  Its launch now claims 150 KB of LDS (abi_output_layer.h), which no other workgroup of the step fits beside: 0.1648 ms at
+    //  the old width, 0.162-0.164 on 48-64 workgroups (r4 sweep; a claim of 120 KB leaves the 24 KB
+    //  weight-gradient workgroups in: 0.1865).)
+    // (dec_opt_x3_kernel's three-term instantiations take 123 648 bytes - the 58 112 of the tile and 64 KB for the third term of
+    //  dh2's fragments)
+    if (side_ok && m->fused_ok &&
         (size_t)((m->N + kTI - 1) / kTI) * kTI * (size_t)std::min(m->R, 16 * kMB) * sizeof(float) < (size_t)0x7FFFFFF0u) {
-        bool ok = true;
-        for (int mode : {kDecCrit, kDecOpt, kDecOptAcc}) each_dec_fused(mode, limit(ok, maxlds));
-        each_dec_opt_blocks(limit(ok, maxlds));
-        if (!m->bf16) m->split_ok = ok;
-        m->x3_ok = ok;
-        each_dec_crit_x3(false, limit(m->x3_ok, maxlds));
-        each_dec_opt_blocks_x3(limit(m->x3_ok, maxlds));
-        // (dec_opt_x3_kernel: the deferred launch of the fp32 step too.  Its three-term instantiations take 123 648 bytes - the
-        //  58 112 of the tile and 64 KB for the third term of dh2's fragments - and need the raised limit)
-        each_dec_opt_x3(false, limit(m->x3_ok, maxlds));
+        m->split_ok = true;
+        each_dec_crit_x3(m->bf16, limit(m->split_ok, maxlds));
+        each_dec_opt_x3(m->bf16, limit(m->split_ok, maxlds));
+        each_dec_opt_blocks_x3(limit(m->split_ok, maxlds));
         (void)hipGetLastError();
-        if (m->bf16) {
-            m->bf16_x3 = m->x3_ok && ok;
-            if (!m->bf16_x3) m->x3_ok = false;
-            else m->split_ok = true;
-            // The one-term instantiations (first terms only, ONE matrix instruction per product; AAE_NO_BF16_ONE: the three-term
-            // kernels multiplying five zero terms).  Both launches get faster - critical 35 -> 27 us, deferred 85 -> 74 us at C2 -
-            // and for most of r4 the STEP got slower, 0.173 -> 0.186 ms (profiles/r4_c2_bf16_one_term.txt): the one-term deferred
-            // kernel needs 78 VGPRs instead of 126, so six of its waves fit a SIMD, its 1024-thread workgroup no longer fills
-            // its CU, and the dispatcher deals the step's own weight-gradient / gather workgroups onto the CUs where it streams
-            // 24 B per parameter (the weight-gradient launch beside it: 32 us instead of 11).  Its launch now claims 150 KB of
-            // LDS (abi_output_layer.h), which no other workgroup of the step fits beside: 0.1648 ms at the old width, 0.162-0.164
-            // on 48-64 workgroups (tools/debug/bf16_one_sweep.sh; a claim of 120 KB leaves the 24 KB weight-gradient workgroups
-            // in: 0.1865).
-            m->bf16_one = m->bf16_x3;
-            each_dec_crit_x3(true, limit(m->bf16_one, maxlds));
-            each_dec_opt_x3(true, limit(m->bf16_one, maxlds));
-            (void)hipGetLastError();
-        }
-        if (m->x3_ok) {
+        if (m->split_ok) {
             // Workgroups of the deferred launch (batches of one fused launch).  It has to end before the step does (the next
             // step opens behind it), and every CU it holds is one the step's own launches share with it: wide enough to take
             // ~80 us - every shape's step has that much work left behind the critical launch - and never more than 9/16 of
@@ -274,12 +254,12 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
             // 4.11 us at 200, 3.15 at 100, one-term 3.1 at 100; 3.34 / 2.83 / 2.60 on 32 workgroups) - 0.69 of the above, and
             // the targets went down with it (57 / 127 us for 82 / 165), so that a shape nobody swept again keeps its width.
             const int ntiles = (m->N + 31) / 32;
-            const double t_tile = (2.2 + 0.0096 * m->h) * (m->bf16_one ? 0.98 : 1.0);
-            int w = (int)(ntiles * t_tile / (m->bf16_one ? 127.0 : 57.0) / 8.0 + 0.5) * 8;      // (C3's shape in bf16: 0.2230 / 0.2264 / 0.2317 / 0.2374 ms on 96 / 112 / 128 / 144)
+            const double t_tile = (2.2 + 0.0096 * m->h) * (m->bf16 ? 0.98 : 1.0);
+            int w = (int)(ntiles * t_tile / (m->bf16 ? 127.0 : 57.0) / 8.0 + 0.5) * 8;      // (C3's shape in bf16: 0.2230 / 0.2264 / 0.2317 / 0.2374 ms on 96 / 112 / 128 / 144)
             // (C2 in bf16, formula: 32, with the tile-ahead launch, tools/split_width_sweep.py, two passes: 0.1532-0.1534 | 0.1542-
             //  0.1549 | 0.1553-0.1556 | 0.1554-0.1556 | 0.1556-0.1560 | 0.1563-0.1565 | 0.157 | 0.157 | 0.158 ms/step on 40 | 48 | 56 |
             //  64 | 72 | 80 | 88 | 96 | 104-128: the floor of the one-term launch 48 -> 40)
-            w = std::max(w, std::min(ntiles, m->bf16_one ? 40 : 64));
+            w = std::max(w, std::min(ntiles, m->bf16 ? 40 : 64));
             // r4, late join (abi_model.h: the launch may run on into the next step's forward pass, so it need not end with the
             // step): half the chip at most - C3 0.2493 (early join, 144) -> 0.2430 ms/step on 128; 0.2515 / 0.2483 / 0.2497 /
             // 0.2492 on 112 / 120 / 136 / 144 (sharp: 124 -> 0.2459, 132 -> 0.2503); the early join on 128: 0.2608.  C2 (formula:

@@ -570,35 +570,46 @@ void chain_encoder_tail(aae_model* m, ChainBuilder& cb, bool train, const uint8_
 // The fused decoder's tile buckets depend on the batch only: the step's first chain launch carries their builder
 // as one extra workgroup (chain.h), off the critical path.
 static int row_blocks(const aae_model* m) { return m->rows <= 16 * kMB ? 1 : (m->rows + kRowBlock - 1) / kRowBlock; }
-// The fused output-layer kernels address dec.lin3 (and its moments) as  descriptor base + tile's byte offset (a 32-bit scalar
-// register) + the lane's offset inside the tile (vector register; 2^31 for a lane without a cell: dropped by the descriptor's
-// range check).  The range check sees the SUM of both offsets (measured, r5: with a fixed descriptor the tiles beyond byte 2^31
-// of a 2.9 M-item layer read zeros and dropped their stores), so r1-r4 kept these layers below 2^31 bytes - 2.63 M items at
-// hidden 200, while PubMed's and ACM's vocabularies (nmi.txt:68,85 of the reference) are 2.9 M and 2.6 M.  Since r5 the
-// descriptors cover a moving WINDOW of the tensors (X3Window, dec_fused.h) and the scalar offset counts from the window's first
-// tile: the limit is the Gt buffer's and the 32-bit tile arithmetic's, 4 GiB.
-static size_t fused_span_limit(const aae_model* m) {
-    const int bits = out_bf16(m) ? 31 : 32;     // (dec_fused_bf16.h's kernels keep fixed descriptors)
-    return ((size_t)1 << bits) - ((size_t)1 << 24);       // (head room: the padding tiles behind the tensor, the last span of a tile)
+// The form the output layer takes for the running batch: the ONE place that decides it (decode_backward asks once per step;
+// tests/fuzz_cases.py output_form restates the rule).
+//   Three    the three streaming GEMMs through dL/dlogits [B][N] (output_layer_unfused)
+//   Single   one persistent launch: dec_fused_kernel, a bf16 handle's dec_fused_bf16_kernel
+//   Split    critical + deferred launch over one row block: dec_crit_x3_kernel, dec_opt_x3_kernel
+//   Blocked  the same over row blocks of a batch beyond 112 rows: dec_crit_x3_kernel, dh2_frag_kernel, dec_opt_blocks_x3_kernel
+enum class OutForm { Three, Single, Split, Blocked };
+// The fused kernels address dec.lin3 (and its moments) as  descriptor base + tile's byte offset (a 32-bit scalar register) +
+// the lane's offset inside the tile (vector register; 2^31 for a lane without a cell: dropped by the descriptor's range check).
+// The range check sees the SUM of both offsets (measured, r5: with a fixed descriptor the tiles beyond byte 2^31 of a 2.9 M-item
+// layer read zeros and dropped their stores), so r1-r4 kept these layers below 2^31 bytes - 2.63 M items at hidden 200, while
+// PubMed's and ACM's vocabularies (nmi.txt:68,85 of the reference) are 2.9 M and 2.6 M.  Since r5 the descriptors of
+// dec_fused_kernel and of the split forms' kernels cover a moving WINDOW of the tensors (X3Window, dec_fused.h) and the scalar
+// offset counts from the window's first tile: their limit is the Gt buffer's and the 32-bit tile arithmetic's, 4 GiB.
+// dec_fused_bf16_kernel keeps fixed descriptors: 2^31 bytes.
+static bool fused_span_below(const aae_model* m, int bits) {       // (head room: the padding tiles behind the tensor, the last span of a tile)
+    return ((size_t)m->N + 2 * kTI) * m->ldh * sizeof(float) < ((size_t)1 << bits) - ((size_t)1 << 24);
 }
-static bool fused_decoder_applies(const aae_model* m) {
-    const bool one = m->rows <= 16 * kMB;
-    // The row-blocked form pays while its deferred half (2 * rows * N * (h + 1) flop of GEMM2 at the optimiser kernel's
-    // ~30 TFLOP/s) fits beside the rest of the step: 800 rows x 12.5 k items (an item slice at world 8) 0.40 against 0.46 ms
-    // per step, 208 x 100 k 0.64 against 0.70; beyond ~32 M cells the next step waits for it and the three GEMMs win
-    // (512 x 100 k: 1.48 against 1.12 ms; 512 x 275 k, a C5 slice: 3.7 against 2.7 ms).  AAE_BLOCKED_ANY lifts the cap (tests).
-    // r3: with both launches on the emulated product (dec_crit_x3.h: the deferred half of all blocks in ONE launch for any
-    // vocabulary, dec_opt_blocks_x3_kernel) the cap is gone: 512 x 100 k 0.77 ms/step against 0.93 on the three GEMMs.
-    // (bf16 mode on the rounded-operand kernels: only with the one-launch deferred half - the per-block launches are fp32 kernels)
-    const bool bf_blocks_ok = !m->bf16 || (m->x3_ok && m->dh2f.p && true);
-    const bool blocked = !one && m->blocked_ok && !out_bf16(m) && bf_blocks_ok && m->split_ok && m->split_wgs > 0 && m->Gacc.p && row_blocks(m) <= kMaxRowBlocks &&
-                         m->cfg.grad_mode == AAE_GRAD_FUSED &&
-                         (m->blocked_any || (size_t)m->rows * m->N <= ((size_t)32 << 20) || (m->x3_ok && m->dh2f.p));
-    return m->fused_ok && !m->force_unfused && (one || blocked) &&
-           ((size_t)m->N + 2 * kTI) * m->ldh * sizeof(float) < fused_span_limit(m) &&
-           /* (the stored dL/dlogits tiles of a row block, [tiles][rows][32] floats, stay behind ONE fixed descriptor) */
-           ((size_t)m->N + 2 * kTI) * (size_t)((m->rows + row_blocks(m) - 1) / row_blocks(m)) * sizeof(float) < ((size_t)1 << 31) &&
-           (m->bf16 ? dec_fused_bf16_lds_bytes(m->fused_nb) : dec_fused_lds_bytes((m->rows + row_blocks(m) - 1) / row_blocks(m), m->h)) <= 160 * 1024;
+static OutForm output_form(const aae_model* m) {
+    const int nblk = row_blocks(m), Bb = (m->rows + nblk - 1) / nblk, ntiles = (m->N + kTI - 1) / kTI;
+    // what every fused form needs: the kernels, the layer inside 32-bit offsets, the stored dL/dlogits tiles of a row block
+    // ([tiles][rows][32] floats) behind ONE fixed descriptor, and the single launch's LDS image of a row block's dh2 (the rule
+    // of every form: a batch of 110 .. 112 rows on an fp32 handle takes the three GEMMs)
+    if (!m->fused_ok || m->force_unfused || !fused_span_below(m, 32) ||
+        ((size_t)m->N + 2 * kTI) * (size_t)Bb * sizeof(float) >= ((size_t)1 << 31) ||
+        (m->bf16 ? dec_fused_bf16_lds_bytes(m->fused_nb) : dec_fused_lds_bytes(Bb, m->h)) > 160 * 1024) return OutForm::Three;
+    // the split forms: the handle's capability (whole-step gradients: aae_create), not turned off (aae_set_split(h, 0)), and no
+    // diagnostic of the single launch's (DEC_TS other than the split kernels' timelines, a DEC_SKIP bit other than theirs)
+    const char* ts = m->opt.dec_ts;
+    const bool split = m->split_ok && m->split_wgs > 0 && (!ts[0] || strcmp(ts, "x3") == 0 || strcmp(ts, "obk") == 0) && (m->opt.dec_skip & ~(0xF000 | 0x30000)) == 0;
+    // Row blocks (cfg.blocked_output: dh2f is there): the form pays at every size since both launches run on the emulated product,
+    // the deferred half of all blocks in ONE launch - 512 rows x 100 k items 0.77 ms/step against 0.93 on the three GEMMs (r3;
+    // r2's fp32 kernels lost beyond ~32 M cells, where the next step waited for the deferred half).
+    if (nblk > 1) return split && m->dh2f.p && nblk <= kMaxRowBlocks ? OutForm::Blocked : OutForm::Three;
+    // The split pays when the deferred half FITS beside the rest of the step and the layer is big enough to matter:
+    // below ~2 tiles per CU the two event hops cost more than the optimiser pass they hide (C1, N = 1 k: 0.173 -> 0.184
+    // ms/step), and beyond ~32 M parameters the deferred launch on half the CUs outlasts the rest of the step and the
+    // next step waits for it (one rank's C5 share, 442 M parameters: 3.5 -> 4.8 ms/step) - both take the single launch.
+    if (split && (m->split_any || (ntiles >= 2 * m->n_cu && (size_t)m->N * m->ldh <= ((size_t)32 << 20)))) return OutForm::Split;
+    return m->bf16 && !fused_span_below(m, 31) ? OutForm::Three : OutForm::Single;
 }
 // counting sort of the running batch's entries into the fused output layer's 32-item tiles (buckets.h / dec_fused.h)
 static void flip_bucket_set(aae_model* m) {
@@ -683,7 +694,7 @@ static void piggyback_buckets(aae_model* m, ChainBuilder& cb) {
     const int ntiles = (m->N + kTI - 1) / kTI;
     const size_t need = sizeof(int) * ((size_t)ntiles + 1 + kBucketMaxDocs + 1 + 1024);
     if (m->x16_ok && m->rows >= m->x16_rows) return;      // (the wide-batch chain kernel carries no builder; only a forced AAE_X16_ROWS meets a batch this small)
-    if (m->buckets_valid || !fused_decoder_applies(m) || ntiles > kBucketMaxTiles || m->rows > kBucketMaxDocs ||
+    if (m->buckets_valid || output_form(m) == OutForm::Three || ntiles > kBucketMaxTiles || m->rows > kBucketMaxDocs ||
         need > (size_t)kCSlots * kCR * kCL * sizeof(float))
         return;
     flip_bucket_set(m);

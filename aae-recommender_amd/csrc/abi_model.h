@@ -45,7 +45,8 @@ struct aae_options {
     bool no_chain;          // NO_CHAIN: one GEMM launch per hidden layer instead of the layer-chain programs
     bool chain16;           // CHAIN16: the 16-row chain kernel on the fp32 pipe for every program (no 4-row / wide-batch kernel)
     bool split_any;         // SPLIT_ANY: the output layer as critical + deferred launch at every size
-    bool blocked_any;       // BLOCKED_ANY: the row-blocked output layer at every size
+    bool blocked_any;       // BLOCKED_ANY: accepted, without effect - the row-blocked form has had no size cap to lift since both of its launches
+                            // run on the emulated product (output_form, abi_chains.h); the suites set it around their blocked_output handles
     bool early_any;         // EARLY_ANY: the next batch's item list started from the step before, at every batch size
     bool no_late_join;      // NO_LATE_JOIN: a step waits for the deferred launch of the step before at its opening
     bool no_item_lists;     // NO_ITEM_LISTS: the first layer's update collects every item's rows itself (no per-batch row lists, w1_lists.h)
@@ -155,13 +156,12 @@ struct aae_model {
     bool prof_on; unsigned prof_mask;   // bit k: time kernel id k
     std::vector<std::pair<hipEvent_t, hipEvent_t>>* prof_ev;   // [AAE_K_N]
     size_t prof_used[AAE_K_N];
-    // split form of the fused decoder output layer (dec_fused.h, kDecCrit / kDecOpt): the optimiser launch of a step
-    // runs on `side` behind the rest of the step; ev_crit = the critical launch is done (the side stream waits for it),
-    // ev_opt = the optimiser launch is done (join_deferred() makes a caller's stream wait for it)
+    // split forms of the fused decoder output layer (dec_crit_x3.h: critical + deferred launch; a bf16 handle's on the one-term
+    // members, operands rounded to bf16): the optimiser launch of a step runs on `side` behind the rest of the step; ev_crit =
+    // the critical launch is done (the side stream waits for it), ev_opt = the optimiser launch is done (join_deferred() makes
+    // a caller's stream wait for it).  split_ok: the ONE capability - stream, events and every kernel of the forms are there
     bool split_ok; int split_wgs; bool opt_pending;
     hipStream_t side; hipEvent_t ev_crit, ev_opt;
-    bool bf16_one = false;   // ... on their one-term instantiations (AAE_BF16_ONE=1; default: the run-time form, five zero products - see aae_create)
-    bool bf16_x3 = false;    // bf16 mode with the output layer on the dec_crit_x3.h kernels (operands rounded to bf16: DecFusedArgs::one_term)
     float* Gt;               // [ntiles][rows][32] dL/dlogits of the running step (aliases the [R][N] scratch G)
     Ten Xn; const float* noise_next; int64_t noise_ld; bool dense_step;   // cfg.dense_noise: dense noisy encoder input (DenoisingAutoEncoder corrupt='gauss')
     bool noise_gen_next; float noise_gen_scale;   // aae_set_input_noise_gen: the next step draws its noise (stream 14) instead of reading noise_next
@@ -170,11 +170,9 @@ struct aae_model {
     bool split_any = false;        // AAE_SPLIT_ANY at creation: the split form of the output layer at any size (tests: small fixtures through the critical / deferred kernels)
     float* dp_scratch = nullptr; size_t dp_scratch_floats = 0;   // aae_dp_step: the ranks' gathered packets (hipMalloc, owned by the handle)
     bool x3_gemm = false;          // gemm_f32.h gemm_x3_kernel: the streaming GEMMs (batches beyond the fused output layer, predict) likewise
-    bool x3_ok = false;            // dec_crit_x3.h: the critical launch's fp32 products on the bf16 matrix cores (3-term split)
     bool w1_big_lds = false;       // w1_item_update_kernel may take more than 64 KB of LDS (batches beyond ~7 k rows)
-    bool blocked_any = false;      // AAE_BLOCKED_ANY at creation: the row-blocked output layer at any size (tests)
-    Ten dh2f;                      // dec_opt_blocks_x3_kernel: the step's dh2 as split matrix-core fragments (dh2_frag_kernel)
-    bool blocked_ok; Ten Gacc;   // cfg.blocked_output: batches beyond 112 rows as row-blocked launches of the split form; dV3 partial
+    Ten dh2f;                      // cfg.blocked_output (batches beyond 112 rows as row blocks of the split form): the step's dh2 as split matrix-core
+                                   // fragments (dh2_frag_kernel -> dec_opt_blocks_x3_kernel)
     // aae_prefetch_batch: the NEXT step's unique-item list and deferred-Adam catch-up, built on `side` while this step
     // runs, in the second list set (mark2 / ulist2 / ucount2 / stamp2; a step that consumes it swaps the sets)
     int* mark2; int* ulist2; int* ucount2; int* stamp2;
@@ -345,7 +343,8 @@ size_t layout(aae_model* m, char* base, bool dry) {
         int64_t slab_rows = (int64_t)m->max_slabs * R;
         if (fused_width_ok(h, m->ldh)) slab_rows = std::max(slab_rows, (int64_t)(304 + 16) * std::min(R, 16 * kMB));
         // row-blocked form: every workgroup's slab spans the whole batch (each launch fills its rows)
-        if (fused_width_ok(h, m->ldh) && c.blocked_output && R <= kMaxRowBlocks * kRowBlock) slab_rows = std::max(slab_rows, (int64_t)(304 + 16) * R);
+        // (a handle with a larger max_batch still takes it for its batches of up to kMaxRowBlocks row blocks)
+        if (fused_width_ok(h, m->ldh) && c.blocked_output) slab_rows = std::max(slab_rows, (int64_t)(304 + 16) * std::min(R, kMaxRowBlocks * kRowBlock));
         m->slabs = a.mat(slab_rows, h, m->ldh);
     }
     m->gb0 = a.mat(R2, h + 1, m->ldh); m->gb1 = a.mat(R2, h + 1, m->ldh);
@@ -360,11 +359,11 @@ size_t layout(aae_model* m, char* base, bool dry) {
     m->Xn = Ten();
     if (c.dense_noise == 1) m->Xn = a.mat(R, N, m->ldn);
     m->noise_l1 = c.dense_noise == 1 ? a.take((size_t)R * kDaeChunksMax, nullptr) : nullptr;
-    m->Gacc = Ten();
-    if (c.blocked_output && c.grad_mode == AAE_GRAD_FUSED && R > 16 * kMB) m->Gacc = a.mat(N, h + 1, m->ldh, 2 * kTI);
     m->dh2f = Ten();
-    if (c.blocked_output && c.grad_mode == AAE_GRAD_FUSED && R > 16 * kMB && R <= kMaxRowBlocks * kRowBlock)
-        m->dh2f = a.mat((int64_t)((R + kXCH - 1) / kXCH) * 13 * (kXCH / 32) * 3, 256, 256);      // [chunk][column block][k-step][term] x 1 KB
+    if (c.blocked_output && c.grad_mode == AAE_GRAD_FUSED && R > 16 * kMB) {      // (wherever the row-blocked form can run: a blocked batch has at most kMaxRowBlocks row blocks)
+        const int Rb = std::min(R, kMaxRowBlocks * kRowBlock);
+        m->dh2f = a.mat((int64_t)((Rb + kXCH - 1) / kXCH) * 13 * (kXCH / 32) * 3, 256, 256);      // [chunk][column block][k-step][term] x 1 KB
+    }
     if (c.model_kind == 3) {
         m->mulv = a.mat(R, 2 * cc, r4(2 * cc)); m->gmulv = a.mat(R, 2 * cc, r4(2 * cc)); m->veps = a.mat(R, cc, r4(cc));
     }
@@ -468,10 +467,7 @@ bool prof_pair(aae_model* m, int k, hipEvent_t* a, hipEvent_t* b) {
     return true;
 }
 
-// bf16 mode whose output layer runs dec_fused_bf16.h's own kernels (not the rounded-operand form of the dec_crit_x3.h ones)
-static inline bool out_bf16(const aae_model* m) { return m->bf16 && !m->bf16_x3; }
-
-// The previous step's deferred optimiser launch (dec_fused.h kDecOpt on m->side) writes DEC_V3 and its moments and
+// The previous step's deferred optimiser launch (dec_crit_x3.h, on m->side) writes DEC_V3 and its moments and
 // reads dh2 / the G scratch / the decoder's step scalars: everything that touches those waits for it here.
 int join_deferred(aae_model* m, hipStream_t s) {
     // (one side stream, in order: the later record covers the earlier - the prefetch is enqueued in front of the deferred

@@ -1,4 +1,4 @@
-// The step, part 2: the decoder's output layer + BCE + its backward (aae.py:176-177, 693-706) - fused / split / row-blocked / three-GEMM forms.
+// The step, part 2: the decoder's output layer + BCE + its backward (aae.py:176-177, 693-706) in output_form()'s four forms (abi_chains.h).
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
 #pragma once
 
@@ -10,7 +10,6 @@ struct DecLaunch {
     int nblk, Bb;               // row blocks (one launch covers at most 112 rows) and rows per block (the last may be shorter)
     int ntiles, grid;           // 32-item tiles of the layer; workgroups of a launch on the whole chip
     bool win;                   // dec.lin3 beyond 2^31 bytes: the kernels' moving-window instantiations (dec_fused.h)
-    size_t fused_lds;           // LDS of dec_fused.h's / dec_fused_bf16.h's own kernels
     DecodeMode mode;            // of the decode-backward call this launch belongs to
     bool want_ts, ts_obk;       // debug (AAE_DEC_TS): phase timeline of one tile / of dec_opt_blocks_x3_kernel ("obk")
 };
@@ -25,8 +24,8 @@ DecFusedArgs fill_dec_args(const aae_model* m, int B, int nblk, float gscale) {
     fa.te.start = m->tstart; fa.te.eb = m->teb; fa.te.en = m->ten; fa.te.ev = m->tev;
     fa.slabs = m->slabs.p; fa.slab_stride = (size_t)(nblk > 1 ? B : std::min(m->R, 16 * kMB)) * m->ldh; fa.ld_slab = m->ldh;
     fa.partials = m->bce_partials; fa.sc = m->sc + O_DEC;
-    fa.erow0 = 0; fa.acc = nullptr; fa.nblk = 1; fa.Bb = B;
-    fa.one_term = m->bf16_x3 ? 1 : 0; fa.dbg_skip = m->opt.dec_skip;
+    fa.erow0 = 0; fa.dh2f = nullptr; fa.nblk = 1; fa.Bb = B;
+    fa.one_term = m->bf16 ? 1 : 0; fa.dbg_skip = m->opt.dec_skip;
     fa.ts = nullptr; fa.Gt = m->Gt;
     return fa;
 }
@@ -65,7 +64,7 @@ int print_dec_timeline(aae_model* m, bool obk, bool quiet, hipStream_t s) {
                 (t[12] - t[7]) * 0.01);
         return AAE_OK;
     }
-    if (out_bf16(m))
+    if (m->bf16)
         for (int k = 0; k < 5; ++k) {
             fprintf(stderr, "[dec_fused_bf16 arrivals at barrier %d, us after the unit's start]", k);
             for (int w = 0; w < 16; ++w) fprintf(stderr, " %.2f", ((double)t[16 + 16 * k + w] - (double)t[0]) * 0.01);
@@ -75,18 +74,18 @@ int print_dec_timeline(aae_model* m, bool obk, bool quiet, hipStream_t s) {
             (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01, (t[4] - t[3]) * 0.01,
             (t[6] - t[4]) * 0.01, (t[6] - t[0]) * 0.01, (double)(t[9] - t[8]),
             (double)(t[9] - t[8]) / ((t[6] - t[0]) * 10.0));
-    if (out_bf16(m)) fprintf(stderr, "[dec_fused_bf16 S0] barrier A=%.2f work=%.2f barrier B=%.2f us\n", (t[14] - t[0]) * 0.01, (t[15] - t[14]) * 0.01, (t[1] - t[15]) * 0.01);
+    if (m->bf16) fprintf(stderr, "[dec_fused_bf16 S0] barrier A=%.2f work=%.2f barrier B=%.2f us\n", (t[14] - t[0]) * 0.01, (t[15] - t[14]) * 0.01, (t[1] - t[15]) * 0.01);
     fprintf(stderr, "[dec_fused wg 0] prologue=%.2f loop=%.2f (%llu tiles, %.2f each) epilogue=%.2f us\n",
             (t[11] - t[10]) * 0.01, (t[7] - t[11]) * 0.01, t[13], (t[7] - t[11]) * 0.01 / (double)(t[13] ? t[13] : 1),
             (t[12] - t[7]) * 0.01);
     return AAE_OK;
 }
 
-// ---- split form, the critical launch: ONE launch for all row blocks - workgroup w works on block w % nblk with its block
-// of dh2 in LDS and takes every (grid / nblk)-th tile (dec_fused.h); 8 launches of 1.5 tile rounds each (-> 2, plus an 84 KB
-// prologue per workgroup and launch) cost 8 x 26.5 us on a 12.5 k-item slice, one launch of 12.2 rounds what the 100-row
-// step's critical launch costs.
-// late join (abi_model.h): dec_crit_x3_kernel sets the deferred launch's dh2 and step scalars aside.
+// ---- split forms, the critical launch (dec_crit_x3_kernel): ONE launch for all row blocks - workgroup w works on block
+// w % nblk with its block of dh2 in LDS and takes every (grid / nblk)-th tile; 8 launches of 1.5 tile rounds each (-> 2, plus
+// an 84 KB prologue per workgroup and launch) cost 8 x 26.5 us on a 12.5 k-item slice, one launch of 12.2 rounds what the
+// 100-row step's critical launch costs.
+// late join (abi_model.h): the kernel sets the deferred launch's dh2 and step scalars aside.
 int launch_output_critical(aae_model* m, const DecLaunch& L, bool late, int grid, hipStream_t s) {
     DecFusedArgs b = L.fa;
     b.nblk = L.nblk; b.Bb = L.Bb;
@@ -97,45 +96,27 @@ int launch_output_critical(aae_model* m, const DecLaunch& L, bool late, int grid
     hipEvent_t start = nullptr, stop = m->ev_crit;
     (void)prof_pair(m, AAE_K_DEC_CRIT, &start, &stop);
     const int nb = m->fused_nb;
-    DecKernel kernel; int threads = kNT; uint32_t lds = (uint32_t)L.fused_lds;
-    if (out_bf16(m)) { kernel = pick_dec_fused_bf16(nb, kDecCrit); threads = kBT; }
-    else if (m->x3_ok) {
-        // (bf16 mode: the one-term instantiation, one matrix instruction per product; the timeline exists for <13> three-term alone)
-        const bool ts = b.ts && !m->bf16_one && nb == 13;
-        kernel = pick_dec_crit_x3(nb, ts, m->bf16_one, L.win && !ts);
-        lds = (uint32_t)dec_crit_x3_lds_bytes(nb);
-    } else kernel = pick_dec_fused(nb, kDecCrit, L.win);
-    if (!kernel) return no_kernel("dec_fused (critical launch)");
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, start, stop, 0, b);
-    LAUNCHCHK("dec_fused (critical launch)");
+    // (a bf16 handle: the one-term instantiation, one matrix instruction per product; the timeline exists for <13> three-term alone)
+    const bool ts = b.ts && !m->bf16 && nb == 13;
+    const DecKernel kernel = pick_dec_crit_x3(nb, ts, m->bf16, L.win && !ts);
+    if (!kernel) return no_kernel("dec_crit_x3");
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kNT), (uint32_t)dec_crit_x3_lds_bytes(nb), s, start, stop, 0, b);
+    LAUNCHCHK("dec_crit_x3");
     HIPCHK(hipStreamWaitEvent(m->side, stop, 0));
     return AAE_OK;
 }
 
-// one launch of the deferred half on the side stream, timed as AAE_K_DEC_OPT
-int launch_deferred(aae_model* m, DecKernel kernel, const char* what, int grid, int threads, uint32_t lds, const DecFusedArgs& b) {
-    if (!kernel) return no_kernel(what);
-    hipEvent_t start = nullptr, stop = nullptr;
-    (void)prof_pair(m, AAE_K_DEC_OPT, &start, &stop);
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, m->side, start, stop, 0, b);
-    LAUNCHCHK(what);
-    return AAE_OK;
-}
-
-// ---- split form, the optimiser launch(es) on the side stream behind the rest of the step.  nblk > 1: the deferred half of
-// every block in ONE launch - dec_opt_blocks_x3_kernel on the emulated product (r3, any vocabulary size), dec_opt_blocks_kernel
-// with at most kOBT tiles per workgroup on the chip - else one launch per block that adds its dV3 to the partial of the
-// blocks before it (through Gacc); the last one runs the optimiser.
-int launch_output_deferred(aae_model* m, const DecLaunch& L, bool late, bool* late_launched) {
-    const DecFusedArgs& fa = L.fa;
-    const int nblk = L.nblk, Bb = L.Bb, ntiles = L.ntiles, nb = m->fused_nb, B = fa.B;
-    const int g2 = std::min(ntiles, std::min(m->split_wgs, m->n_cu));
-    DecFusedArgs b = fa;          // every row block in one launch
-    b.nblk = nblk; b.Bb = Bb;
-    if (nblk > 1 && !out_bf16(m) && m->x3_ok && m->dh2f.p) {
+// ---- split forms, the deferred launch on the side stream behind the rest of the step, timed as AAE_K_DEC_OPT: dec_opt_x3_kernel
+// over one row block, dec_opt_blocks_x3_kernel over every row block of a batch beyond one launch (any vocabulary size)
+int launch_output_deferred(aae_model* m, const DecLaunch& L, bool late) {
+    const int ntiles = L.ntiles, nb = m->fused_nb, B = L.fa.B;
+    DecFusedArgs b = L.fa;
+    b.nblk = L.nblk; b.Bb = L.Bb;
+    DecKernel kernel; const char* what; int grid; uint32_t lds; bool ts = false;
+    if (L.nblk > 1) {
         hipLaunchKernelGGL(dh2_frag_kernel, dim3((B + kXCH - 1) / kXCH, m->fused_nb), dim3(128), 0, m->side, m->dh2.p, m->ldh, B,
                            reinterpret_cast<u32x4_t*>(m->dh2f.p), b.one_term);
-        b.acc = m->dh2f.p;                      // (this kernel's reading of the field: the fragment image)
+        b.dh2f = m->dh2f.p;
         // tile groups of at most kXBT tiles, the same number (+-1 tile) for every workgroup and round
         // Workgroups: one per ~16 tiles, between half and three quarters of the CUs (tools/debug/sweep_obk_wgs*.sh, late r3,
         // ms per step): 100 k items x 512 rows 0.774 / 0.725 / 0.710 / 0.703 / 0.690 / 0.755 / 0.749 on 128 / 144 / 160 /
@@ -150,61 +131,48 @@ int launch_output_deferred(aae_model* m, const DecLaunch& L, bool late, bool* la
         //  0.3493 | 0.3489 | 0.3486 | 0.3524 ms/step on 128 | 32 | 48 | 64 | 96 workgroups, tools/debug/c4_obk_sweep.sh)
         const int by_tiles = ntiles < 384 ? std::max(32, std::min(m->n_cu / 2, ntiles / 3))
                                           : std::max(m->n_cu / 2, std::min(wg_cap, (int)(ntiles / 16.3 / 8.0 + 0.5) * 8));
-        const int g3 = std::max(1, std::min(by_tiles, std::min(ntiles, m->n_cu)));
-        const int rounds = (ntiles + g3 * kXBT - 1) / (g3 * kXBT);
-        b.tpp = g3 * rounds;
-        const uint32_t lds3 = (uint32_t)dec_opt_blocks_x3_lds_bytes();
-        const bool ts = L.ts_obk && nb == 13;
-        TRY(launch_deferred(m, pick_dec_opt_blocks_x3(nb, ts, L.win && !ts), "dec_opt_blocks_x3", g3, kNT, lds3, b));
-        return ts ? print_dec_timeline(m, true, false, m->side) : AAE_OK;
+        grid = std::max(1, std::min(by_tiles, std::min(ntiles, m->n_cu)));
+        const int rounds = (ntiles + grid * kXBT - 1) / (grid * kXBT);
+        b.tpp = grid * rounds;
+        ts = L.ts_obk && nb == 13;
+        kernel = pick_dec_opt_blocks_x3(nb, ts, L.win && !ts); what = "dec_opt_blocks_x3";
+        lds = (uint32_t)dec_opt_blocks_x3_lds_bytes();
+    } else {
+        // (the 3-term bf16 emulation of dV3 = G^T dh2, dec_crit_x3.h)
+        // (one-term instantiation: 78 VGPRs - six of its waves fit a SIMD, so the step's own launches would be dealt onto
+        //  its CUs and run beside its streams; its LDS claim is raised until no other workgroup of the step fits there)
+        // (the three-term instantiations keep dh2's third term in a 64 KB block of LDS behind the tile: ~124 KB)
+        lds = (uint32_t)dec_opt_x3_lds_bytes(!m->bf16);
+        if (m->bf16) lds = std::max(lds, 150u * 1024u);
+        // (late join: dec_opt_x3_kernel reads the copies the critical launch set aside)
+        if (late) { b.dh2 = m->dh2s.p; b.sc = m->sc_snap; }
+        grid = std::min(ntiles, std::min(m->split_wgs, m->n_cu));
+        kernel = pick_dec_opt_x3(nb, m->bf16, L.win); what = "dec_opt_x3";
     }
-    if (nblk > 1 && !out_bf16(m) && ntiles <= kOBT * m->n_cu && dec_opt_blocks_lds_bytes(Bb) <= 160 * 1024) {
-        const int g3 = std::max(std::min(g2, ntiles), (ntiles + kOBT - 1) / kOBT);
-        return launch_deferred(m, pick_dec_opt_blocks(nb), "dec_opt_blocks", g3, kNT, (uint32_t)dec_opt_blocks_lds_bytes(Bb), b);
-    }
-    for (int r = 0; r < nblk; ++r) {
-        b = fa;
-        const int r0 = r * Bb;
-        b.B = std::min(Bb, B - r0); b.erow0 = r0;
-        b.dh2 = fa.dh2 + (size_t)r0 * m->ldh;
-        b.slabs = fa.slabs + (size_t)r0 * m->ldh;
-        b.partials = fa.partials + (size_t)r * L.grid;
-        b.Gt = fa.Gt + (size_t)r * ntiles * Bb * kTI;
-        if (nblk > 1) { b.acc = m->Gacc.p; b.gradV3 = r == nblk - 1 ? nullptr : m->Gacc.p; }
-        const char* what = "dec_fused (optimiser launch)";
-        if (out_bf16(m)) TRY(launch_deferred(m, pick_dec_fused_bf16(nb, kDecOpt), what, g2, kBT, (uint32_t)L.fused_lds, b));
-        else if (nblk == 1 && m->x3_ok) {
-            // (the 3-term bf16 emulation of dV3 = G^T dh2, dec_crit_x3.h)
-            // (one-term instantiation: 78 VGPRs - six of its waves fit a SIMD, so the step's own launches would be dealt onto
-            //  its CUs and run beside its streams; its LDS claim is raised until no other workgroup of the step fits there)
-            // (the three-term instantiations keep dh2's third term in a 64 KB block of LDS behind the tile: ~124 KB)
-            const uint32_t lds_nat = (uint32_t)dec_opt_x3_lds_bytes(!m->bf16_one);
-            const uint32_t lds3 = m->bf16_one ? std::max(lds_nat, 150u * 1024u) : lds_nat;
-            // (late join: dec_opt_x3_kernel reads the copies the critical launch set aside)
-            if (late) { b.dh2 = m->dh2s.p; b.sc = m->sc_snap; *late_launched = true; }
-            TRY(launch_deferred(m, pick_dec_opt_x3(nb, m->bf16_one, L.win), what, g2, kNT, lds3, b));
-        } else TRY(launch_deferred(m, pick_dec_fused(nb, r == 0 ? kDecOpt : kDecOptAcc, L.win), what, g2, kNT, (uint32_t)L.fused_lds, b));
-    }
-    return AAE_OK;
+    if (!kernel) return no_kernel(what);
+    hipEvent_t start = nullptr, stop = nullptr;
+    (void)prof_pair(m, AAE_K_DEC_OPT, &start, &stop);
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kNT), lds, m->side, start, stop, 0, b);
+    LAUNCHCHK(what);
+    return ts ? print_dec_timeline(m, true, false, m->side) : AAE_OK;
 }
 
-// ---- split form: the critical launch here, the optimiser launch(es) on the side stream
+// ---- split forms: the critical launch here, the deferred launch on the side stream
 int output_layer_split(aae_model* m, const DecLaunch& L, int* n_loss_partials, int* crit_slabs, hipStream_t s) {
     if (m->opt_pending) TRY(join_deferred(m, s));   // (never: every step-opening entry point joins)
-    // late join (abi_model.h): single row block on the emulated product
+    // late join (abi_model.h): single row block
     const int nblk = L.nblk;
-    const bool late = m->late_enabled && nblk == 1 && m->x3_ok && !out_bf16(m) && !L.want_ts &&
+    const bool late = m->late_enabled && nblk == 1 && !L.want_ts &&
                       m->dh2s.p && m->sc_snap && L.fa.B <= m->dh2s.rows && L.grid >= L.fa.B;
     const int wgs = nblk > 1 ? std::max(1, m->n_cu / nblk) : L.grid;
     const int crit_grid = nblk > 1 ? wgs * nblk : L.grid;
     *n_loss_partials = crit_grid;
     *crit_slabs = wgs;
     TRY(launch_output_critical(m, L, late, crit_grid, s));
-    bool late_launched = false;
-    TRY(launch_output_deferred(m, L, late, &late_launched));
+    TRY(launch_output_deferred(m, L, late));
     TRY(side_done(m, m->ev_opt));
     m->opt_pending = true;
-    m->late_ok = late_launched;
+    m->late_ok = late;
     m->last_out_split = true; m->side_ordered = true;
     // an item slice's next batch (named ahead): its distinct items and their deferred-Adam catch-up behind the
     // deferred launch on the same stream (ordered behind this step's head by ev_crit; rows of the running batch
@@ -213,14 +181,13 @@ int output_layer_split(aae_model* m, const DecLaunch& L, int* n_loss_partials, i
     return AAE_OK;
 }
 
-// ---- the single launch (dec_fused.h): logits, BCE, dV3 + dec_optim and dA2 in one persistent kernel
+// ---- the single launch (dec_fused.h; a bf16 handle's: dec_fused_bf16.h): logits, BCE, dV3 + dec_optim and dA2 in one persistent kernel
 int launch_output_single(aae_model* m, const DecLaunch& L, hipStream_t s) {
     m->last_out_split = false; m->side_ordered = false;
     ProfScope ps(m, AAE_K_DEC_FUSED, s);
-    // (the single launch of bf16 mode is always dec_fused_bf16.h's own kernel: there is no rounded-operand form of it)
-    const DecKernel kernel = m->bf16 ? pick_dec_fused_bf16(m->fused_nb, kDecFused) : pick_dec_fused(m->fused_nb, kDecFused, L.win);
+    const DecKernel kernel = m->bf16 ? pick_dec_fused_bf16(m->fused_nb) : pick_dec_fused(m->fused_nb, L.win);
     if (!kernel) return no_kernel("dec_fused");
-    const size_t lds = m->bf16 ? dec_fused_bf16_lds_bytes(m->fused_nb) : L.fused_lds;
+    const size_t lds = m->bf16 ? dec_fused_bf16_lds_bytes(m->fused_nb) : dec_fused_lds_bytes(L.fa.B, m->h);
     hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(m->bf16 ? kBT : kNT), lds, s, L.fa);
     return AAE_OK;
 }
@@ -257,8 +224,8 @@ int reduce_slabs(aae_model* m, const DecLaunch& L, int crit_slabs, int n_loss_pa
     return AAE_OK;
 }
 
-// ---- fused path (dec_fused.h), single or split launch, then the slab reduction
-int output_layer_fused(aae_model* m, const DecodeMode& mode, int B, float gscale, const DropSpec& d2, const float** chain_part, size_t* chain_stride, hipStream_t s) {
+// ---- fused forms (form: Single, Split or Blocked), then the slab reduction
+int output_layer_fused(aae_model* m, OutForm form, const DecodeMode& mode, int B, float gscale, const DropSpec& d2, const float** chain_part, size_t* chain_stride, hipStream_t s) {
     if (m->bk_pending) {            // built on the side stream while this step's forward ran (aae_first_layer_forward)
         HIPCHK(hipStreamWaitEvent(s, m->ev_bk, 0));
         m->bk_pending = false;
@@ -266,12 +233,11 @@ int output_layer_fused(aae_model* m, const DecodeMode& mode, int B, float gscale
     if (!m->buckets_valid) TRY(build_tile_buckets(m, s));   // (else: the extra workgroup of this step's first chain launch did)
     DecLaunch L;
     L.mode = mode;
-    // row blocks of the fused output layer: one launch covers at most 112 rows; larger batches (cfg.blocked_output) run as
-    // nblk launches of the split form over equal row blocks
-    L.nblk = m->have_batch ? row_blocks(m) : 1; L.Bb = (B + L.nblk - 1) / L.nblk;
+    // row blocks of the fused output layer: a row block covers at most 112 rows; larger batches (cfg.blocked_output) run as
+    // nblk equal row blocks of the split form
+    L.nblk = form == OutForm::Blocked ? row_blocks(m) : 1; L.Bb = (B + L.nblk - 1) / L.nblk;
     L.ntiles = (m->N + kTI - 1) / kTI; L.grid = std::min(L.ntiles, m->n_cu);
     L.win = x3_big_span(m->N, m->ldh);
-    L.fused_lds = out_bf16(m) ? dec_fused_bf16_lds_bytes(m->fused_nb) : dec_fused_lds_bytes(L.Bb, m->h);
     L.fa = fill_dec_args(m, B, L.nblk, gscale);
     L.want_ts = m->opt.dec_ts[0] != 0;
     if (L.want_ts) {
@@ -279,17 +245,11 @@ int output_layer_fused(aae_model* m, const DecodeMode& mode, int B, float gscale
         L.fa.ts = dec_ts_dev;
     }
     int n_loss_partials = L.grid, crit_slabs = L.grid;
-    // The split pays when the deferred half FITS beside the rest of the step and the layer is big enough to matter:
-    // below ~2 tiles per CU the two event hops cost more than the optimiser pass they hide (C1, N = 1 k: 0.173 -> 0.184
-    // ms/step), and beyond ~32 M parameters the deferred launch on half the CUs outlasts the rest of the step and the
-    // next step waits for it (one rank's C5 share, 442 M parameters: 3.5 -> 4.8 ms/step) - both take the single launch.
-    const bool split_fits = L.nblk > 1 || m->split_any || (L.ntiles >= 2 * m->n_cu && (size_t)m->N * m->ldh <= ((size_t)32 << 20));
-    // (AAE_DEC_TS: the timeline of the single launch - or, AAE_DEC_TS=x3, of the split form's critical launch dec_crit_x3.h)
-    const bool ts_x3 = L.want_ts && strcmp(m->opt.dec_ts, "x3") == 0;
+    // (AAE_DEC_TS: the timeline of the single launch - or, AAE_DEC_TS=x3 / obk, of the split forms' dec_crit_x3_kernel /
+    // dec_opt_blocks_x3_kernel)
     L.ts_obk = L.want_ts && strcmp(m->opt.dec_ts, "obk") == 0;
-    if (m->split_ok && m->split_wgs > 0 && split_fits && L.fa.gradV3 == nullptr && (!L.want_ts || ((ts_x3 || L.ts_obk) && m->x3_ok && !out_bf16(m))) && (L.fa.dbg_skip & ~(256 | 0xF000 | 0x30000)) == 0)
-        TRY(output_layer_split(m, L, &n_loss_partials, &crit_slabs, s));
-    else TRY(launch_output_single(m, L, s));
+    if (form == OutForm::Single) TRY(launch_output_single(m, L, s));
+    else TRY(output_layer_split(m, L, &n_loss_partials, &crit_slabs, s));
     LAUNCHCHK("dec_fused");
     if (L.want_ts) TRY(print_dec_timeline(m, false, m->last_out_split && L.ts_obk, s));
     *chain_stride = L.fa.slab_stride;
@@ -423,8 +383,9 @@ int decode_backward(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_
     DropSpec d1 = make_drop(m, 0, true, mk2, nullptr, B, h, 2);
     DropSpec d2 = make_drop(m, 1, true, mk3, nullptr, B, h, 3);
     const float* chain_part = nullptr; size_t chain_stride = 0;
-    if (fused_decoder_applies(m)) TRY(output_layer_fused(m, mode, B, gscale, d2, &chain_part, &chain_stride, s));
-    else TRY(output_layer_unfused(m, mode, B, gscale, d2, s));
+    const OutForm form = output_form(m);
+    if (form == OutForm::Three) TRY(output_layer_unfused(m, mode, B, gscale, d2, s));
+    else TRY(output_layer_fused(m, form, mode, B, gscale, d2, &chain_part, &chain_stride, s));
     if (!mode.only_output_layer) TRY(decoder_hidden_backward(m, mode, chain_part, chain_stride, d1, dzc_out, s));
     m->phase = 2;
     return AAE_OK;

@@ -128,7 +128,7 @@ static int ae_encode_impl(aae_handle m, const aae_batch* batch, const aae_rng_in
     // rows the builder rides in the step's first chain launch.)  The side stream is in order behind the previous step's
     // deferred launch, which waited for that step's output layer - the alternate bucket set's last readers are older.
     // (Not on the three-GEMM path: there the side stream holds the previous step's dV3 GEMM for most of this step.)
-    if (m->side && m->ev_bk && m->last_out_split && m->rows > 16 * kMB && !m->buckets_valid && fused_decoder_applies(m))
+    if (m->side && m->ev_bk && m->last_out_split && m->rows > 16 * kMB && !m->buckets_valid && output_form(m) != OutForm::Three)
         TRY(build_tile_buckets_aside(m));
     const bool pf = m->pf_armed && m->side && m->mark2 && m->lazy && m->use_chain;
     if (m->pf_armed && !pf) m->pf_armed = false;

@@ -230,7 +230,7 @@ int aae_first_layer_forward(aae_handle m, const aae_batch* batch, const float* b
         // handle's list building and gather (and the caller's forward pass) instead of in front of the critical launch.
         // The side stream is in order behind the last deferred launch, which waited for the last critical launch - the
         // last reader of the bucket arrays; without such a launch to order it the build stays where it was.
-        if (m->side && m->ev_bk && m->last_out_split && fused_decoder_applies(m)) TRY(build_tile_buckets_aside(m));
+        if (m->side && m->ev_bk && m->last_out_split && output_form(m) != OutForm::Three) TRY(build_tile_buckets_aside(m));
         // (a batch named with aae_prefetch_batch stays armed: its list and catch-up are enqueued behind this step's
         //  deferred optimiser launch - aae_output_layer_step - where they need no mark on this stream; a mark riding on
         //  the gather below cost the stream more than the 16 us it moved away)

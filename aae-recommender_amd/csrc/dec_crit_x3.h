@@ -1,4 +1,4 @@
-// Critical launch of the fused decoder output layer (dec_fused.h, MODE kDecCrit: logits, BCE, dL/d(hidden), the stored
+// Critical launch of the split output layer (dec_fused.h's S0 GEMM1 S2 GEMM3: logits, BCE, dL/d(hidden), and the stored
 // dL/dlogits tiles) with its fp32 products EMULATED on the bf16 matrix cores.
 //
 // gfx950 has no TF32 and its fp32 MFMA (v_mfma_f32_16x16x4_f32) runs at 1/16 of the bf16 rate.  Every fp32 operand
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(kNT) void dec_crit_x3_kernel(DecFusedArgs a) {
 namespace aae {
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The DEFERRED launch of the split output layer (dec_fused.h MODE kDecOpt: dV3 = G^T dh2 from the stored dL/dlogits tiles,
+// The DEFERRED launch of the split output layer (dec_fused.h's GEMM2 S5: dV3 = G^T dh2 from the stored dL/dlogits tiles,
 // then dec_optim on the tile) with the same 3-term bf16 emulation of its fp32 product.  Since r3 the next step waits for
 // this launch (the critical launch got 30 % shorter), and a third of a tile's time was the fp32 matrix pipe (26 blocks x
 // 28 v_mfma_f32_16x16x4_f32) fed by k-strided 4-byte LDS reads of a 95 KB dh2 image.  Here:
@@ -513,8 +513,9 @@ namespace aae {
 //        kernel (4 k-steps x 3 terms = 48 VGPRs; no LDS image of it);
 //   G   (the tile's stored dL/dlogits, fp32 [B][32]) -> three bf16 images gB[t][b][n]; the A operand G^T[n][k = b] is their
 //        transpose: ds_read_b64_tr_b16;
-//   dV3 tile -> os [32][kSO] (fp32) -> the optimiser exactly as in dec_fused.h (S5), V3a / m / v streamed non-temporally,
-//        V3a kept in registers between its load and its update (no LDS copy);
+//   dV3 tile -> os [32][kSO] (fp32) -> the optimiser exactly as in dec_fused.h (S5), V3a / m / v and the stored tiles streamed non-temporally
+//        (with plain loads / stores the 0.5 GB pass evicted the hidden layers' weights from L2 under the layer-chain kernels it
+//        runs beside: +25 % on each of them), V3a kept in registers between its load and its update (no LDS copy);
 //   the NEXT tile's G, V3a, m and v are requested while this tile multiplies, one request per k-step, into a second
 //        register set; the three-term instantiations pay for it with the third term of dh2's fragments, which lives in a
 //        64 KB block of LDS (one ds_read_b128 per k-step) instead of 16 registers.
@@ -747,7 +748,7 @@ __global__ __launch_bounds__(kNT) void dec_opt_x3_kernel(DecFusedArgs a) {
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The deferred half for ALL row blocks of a row-blocked step in one launch (dec_fused.h's dec_opt_blocks_kernel) on the
+// The deferred half for ALL row blocks of a row-blocked step in one launch, on the
 // emulated product, for any vocabulary: dV3 = G^T dh2 over the WHOLE batch from the tiles the critical launch stored,
 // then dec_optim.  dh2 cannot stay resident (512 rows x 208 columns in three bf16 terms: 640 KB against a 512 KB register
 // file), so a workgroup takes a GROUP of up to kXBT consecutive tiles (256 items) per pass, keeps their dV3 in registers
@@ -996,7 +997,7 @@ __global__ __launch_bounds__(kNT) void dec_opt_blocks_x3_kernel(DecFusedArgs a) 
         for (int ch = 0; ch < nch; ++ch) {
             // the chunk's dh2 fragments (dh2_frag_kernel's image)
             if (mult && (ch == 0 || !(a.dbg_skip & 0x4000))) {
-                const u32x4_t* F = reinterpret_cast<const u32x4_t*>(a.acc) + (((size_t)ch * NB + cb) * KR * 3) * 64 + lane;
+                const u32x4_t* F = reinterpret_cast<const u32x4_t*>(a.dh2f) + (((size_t)ch * NB + cb) * KR * 3) * 64 + lane;
 #pragma unroll
                 for (int kc = 0; kc < KR; ++kc)
 #pragma unroll

@@ -40,23 +40,17 @@ bool raise_lds_limit(K kernel, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
-// ---- dec_fused.h: every MODE with its moving-window form; dec_fused_bf16.h: no kDecOptAcc, no window form
-inline DecKernel pick_dec_fused(int nb, int mode, bool win) {
-    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_of<DecKernel, kDecFused, kDecCrit, kDecOpt, kDecOptAcc>(mode, [&](auto MODE) {
-        return pick_flags<DecKernel>([](auto WIN) -> DecKernel { return dec_fused_kernel<NB_, decltype(MODE)::value, WIN()>; }, win); }); });
+// ---- the single launch of the output layer: dec_fused.h with its moving-window form; dec_fused_bf16.h (no window form)
+inline DecKernel pick_dec_fused(int nb, bool win) {
+    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_flags<DecKernel>([](auto WIN) -> DecKernel { return dec_fused_kernel<NB_, WIN()>; }, win); });
 }
-inline DecKernel pick_dec_fused_bf16(int nb, int mode) {
-    return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_of<DecKernel, kDecFused, kDecCrit, kDecOpt>(mode, [](auto MODE) -> DecKernel {
-        return dec_fused_bf16_kernel<NB_, MODE()>; }); });
+inline DecKernel pick_dec_fused_bf16(int nb) {
+    return pick_nb<DecKernel>(nb, [](auto NB) -> DecKernel { return dec_fused_bf16_kernel<NB_>; });
 }
-inline DecKernel pick_dec_opt_blocks(int nb) {
-    return pick_nb<DecKernel>(nb, [](auto NB) -> DecKernel { return dec_opt_blocks_kernel<NB_>; });
-}
-template <class F> void each_dec_fused(int mode, F&& f) { for (int nb : kPickNb) for (int win = 0; win < 2; ++win) f(pick_dec_fused(nb, mode, win)); }
-template <class F> void each_dec_fused_bf16(int mode, F&& f) { for (int nb : kPickNb) f(pick_dec_fused_bf16(nb, mode)); }
-template <class F> void each_dec_opt_blocks(F&& f) { for (int nb : kPickNb) f(pick_dec_opt_blocks(nb)); }
+template <class F> void each_dec_fused(F&& f) { for (int nb : kPickNb) for (int win = 0; win < 2; ++win) f(pick_dec_fused(nb, win)); }
+template <class F> void each_dec_fused_bf16(F&& f) { for (int nb : kPickNb) f(pick_dec_fused_bf16(nb)); }
 
-// ---- dec_crit_x3.h.  TS (the debug timelines) exists for NB == 13 alone, three-term, no window
+// ---- dec_crit_x3.h: the split forms.  ONE = the handle is a bf16 one; TS (the debug timelines) exists for NB == 13 alone, three-term, no window
 inline DecKernel pick_dec_crit_x3(int nb, bool ts, bool one, bool win) {
     return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_flags<DecKernel>([](auto TS, auto ONE, auto WIN) -> DecKernel {
         if constexpr (TS() && (NB_ != 13 || ONE() || WIN())) return nullptr; else return dec_crit_x3_kernel<NB_, TS(), ONE(), WIN()>; }, ts, one, win); });
@@ -69,7 +63,7 @@ inline DecKernel pick_dec_opt_blocks_x3(int nb, bool ts, bool win) {
     return pick_nb<DecKernel>(nb, [&](auto NB) { return pick_flags<DecKernel>([](auto TS, auto WIN) -> DecKernel {
         if constexpr (TS() && (NB_ != 13 || WIN())) return nullptr; else return dec_opt_blocks_x3_kernel<NB_, TS(), WIN()>; }, ts, win); });
 }
-// (ONE: the one-term members are a bf16 handle's, prepared apart from the three-term ones)
+// (ONE: the handle's dtype - a bf16 handle launches the one-term members, an fp32 handle the three-term ones)
 template <class F> void each_dec_crit_x3(bool one, F&& f) {
     for (int nb : kPickNb) for (int i = 0; i < 4; ++i) if (DecKernel k = pick_dec_crit_x3(nb, i & 1, one, i & 2)) f(k);
 }

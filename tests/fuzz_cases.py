@@ -32,8 +32,8 @@ FUSED_ROWS, LAUNCH_ROWS, ROW_BLOCK = 109, 112, 104
 
 def output_form(path, rows):
     """The form an fp32 handle of the fuzz's sizes (hidden width below 208, fewer than 16384 items, whole-step gradients) takes
-    for a batch of `rows` rows, restating csrc/abi_chains.h fused_decoder_applies and csrc/abi_output_layer.h
-    output_layer_fused: 'split' (critical + deferred launch; row-blocked beyond 112 rows), 'single' or 'three' (the three
+    for a batch of `rows` rows, restating csrc/abi_chains.h output_form (the library's one decision; its Split and Blocked are
+    'split' here): 'split' (critical + deferred launch; row-blocked beyond 112 rows), 'single' or 'three' (the three
     GEMMs).  The single-launch LDS image of dh2 fits up to 109 rows; a batch of 110 .. 112 rows is one row block that does not
     fit; beyond 112 rows only a blocked_output handle - the fuzz creates one on BLOCKED_ANY - stays on the fused kernels, as
     row blocks of ceil(rows / ceil(rows / 104)) rows."""
@@ -187,11 +187,12 @@ def bf16_param_stats(got, want, lr, n_steps):
 SGD_TOL = 5e-5        # (the fp32 fuzz's; tests/bf16_cases.py has the measurement that keeps it for bf16 mode)
 
 
-def check_configuration(cfg, r, seed, bf16=False, path="default", counters=None):
+def check_configuration(cfg, r, seed, bf16=False, path="default", counters=None, max_batch=None):
     """Three steps of the device against the oracle, the parameters after them, and predict where the configuration asks, on
     a handle forced onto `path`.  bf16: a dtype = 'bf16' handle against OracleAAE(bf16=True) at the tolerances of
     tests/test_bf16_gpu.py; returns the observed (share, maximum) per tensor.  counters: a list that receives, per step,
-    (rows, launches of OUT_KERNELS) from the handle's profile."""
+    (rows, launches of OUT_KERNELS) from the handle's profile.  max_batch: the handle's, where it is to be larger than the
+    configuration's batch."""
     import pytest
     import torch
     from aaerec import _hip
@@ -201,12 +202,13 @@ def check_configuration(cfg, r, seed, bf16=False, path="default", counters=None)
     N, h, c, B, inc = cfg["N"], cfg["h"], cfg["c"], cfg["B"], cfg["inc"]
     params = init_params(N, h, c, cond_inc=inc, seed=seed)
     kw, p, lr = model_kwargs(cfg)
+    R = max_batch or B
     if bf16:
-        dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", dtype="bf16", blocked_output=blocked, **kw))
+        dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=R, rng_mode="inject", dtype="bf16", blocked_output=blocked, **kw))
     elif path != "default":
-        dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", blocked_output=blocked, **kw))
+        dev = _forced_handle(path, lambda blocked: HipAAE(N, h, c, cond_inc=inc, max_batch=R, rng_mode="inject", blocked_output=blocked, **kw))
     else:
-        dev = HipAAE(N, h, c, cond_inc=inc, max_batch=B, rng_mode="inject", **kw)
+        dev = HipAAE(N, h, c, cond_inc=inc, max_batch=R, rng_mode="inject", **kw)
     dev.load_params(params)
     if counters is not None:
         dev.profile_enable(True, kernels=OUT_KERNELS)

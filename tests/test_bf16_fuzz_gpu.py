@@ -13,7 +13,10 @@ Three steps, the last one shorter; the cut at the output layer where the configu
 (AAE_ESTATE: hidden layers that run layer by layer) the test asserts the status and the message and takes the whole step.
 Tolerances: tests/test_bf16_gpu.py's, and tests/bf16_cases.py for the two it has none for; tests/test_bf16_fuzz_cpu.py shows
 that the reference alone stays inside a quarter of each.  Every case prints the observed share and maximum per tensor
-(BF16FUZZ lines; DESIGN.md's table holds the worst per group)."""
+(BF16FUZZ lines; DESIGN.md's table holds the worst per group).
+
+  corner    the first regular BLOCKED_ANY case above 112 rows once more on a handle created with max_batch = 1700 (more than 16 row
+            blocks of 104 rows): its batches run the row-blocked form, not the three GEMMs - the launch counters say so."""
 import pytest
 
 import bf16_cases as C
@@ -31,6 +34,21 @@ def _report(group, cid, path, stats):
 def test_bf16_random_configuration_matches_the_rounded_oracle(seed, path):
     cfg, r = C.regular_config(seed)
     _report("regular", seed, path, F.check_configuration(cfg, r, seed, bf16=True, path=path))
+
+
+CORNER = [(seed, path) for seed, path in C.REGULAR if path == "blocked_any" and C.regular_config(seed)[0]["B"] > F.LAUNCH_ROWS][:1]
+
+
+@pytest.mark.parametrize("seed,path", CORNER)
+def test_bf16_row_blocked_batch_on_a_handle_with_a_larger_max_batch_matches_the_rounded_oracle(seed, path):
+    assert len(CORNER) == 1         # (test_bf16_fuzz_cpu.py: the lists hold a BLOCKED_ANY batch above 112 rows)
+    cfg, r = C.regular_config(seed)
+    counters = []
+    _report("corner", seed, path, F.check_configuration(cfg, r, seed, bf16=True, path=path, counters=counters, max_batch=1700))
+    # (a bf16 handle's single launch keeps no LDS image of dh2: every batch above 112 rows of at most 16 row blocks is row-blocked)
+    for step, (rows, counts) in enumerate(counters):
+        assert rows > F.LAUNCH_ROWS and tuple(min(n, 1) for n in counts) == (0, 0, 1, 1), (f"step {step}, {rows} rows: launches of (bce_fwd, "
+                                                                                           f"single, critical, deferred) {counts}")
 
 
 @pytest.mark.parametrize("seed,path", C.TINY)

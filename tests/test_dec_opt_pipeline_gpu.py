@@ -9,7 +9,7 @@ Widths: 1 (one workgroup walks every tile: the steady state and the final iterat
 with two tiles, two with one), 6 (the prologue's requests only) and 64 (more workgroups than tiles).  Shapes: 167 items
 (6 tiles, the last with 7 items) and 32 (one tile); hidden 200 (13 column blocks: waves 10..15 split the item halves) and
 100 (7); batches of 1, 100, 109 and 112 rows: 112 is the kernels' row block, 109 the largest batch the library sends through
-them (csrc/abi_chains.h fused_decoder_applies: the single-launch form's LDS image of dh2 has to fit 160 KB, at any hidden
+them (csrc/abi_chains.h output_form: the single-launch form's LDS image of dh2 has to fit 160 KB, at any hidden
 width) - a batch of 112 takes the three-kernel path, where the width must change nothing either.  Three consecutive aae_output_layer_step calls on
 seeded parameters with non-zero Adam moments loaded, so that the moments, the late join and the operand copies are live."""
 import functools

@@ -24,6 +24,11 @@ def _maxdiff(a, b):
     return float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
 
 
+# seconds: test_bf16_layer_beyond_two_gib_takes_the_three_gemms allocates and fills what ONE of the two handles of
+# test_fused_output_layer_beyond_two_gib[100] does (DESIGN.md 4.3 has both run times on one box)
+BF16_TWO_GIB_LIMIT = 60         # (measured: 1.65 s beside the twin's 2.30 s; most of either is the host's random fill of the layer)
+
+
 def test_c3_full_size_step_fused_equals_three_kernel_path_equals_oracle():
     from aaerec._hip import HipAAE, DeviceCSR
     from oracle import aae_oracle as O
@@ -292,6 +297,43 @@ def test_fused_output_layer_beyond_two_gib(B):
         assert d <= tol + 1e-4 * float(b.abs().max().item()), (tid, d)
         # ... and the rows beyond byte 2^31 did move (an update dropped by a range check would leave them at their start values)
         assert float(a[-1000:].abs().sum().item()) > 0
+
+
+@pytest.mark.timeout(BF16_TWO_GIB_LIMIT)
+def test_bf16_layer_beyond_two_gib_takes_the_three_gemms():
+    """The bf16 twin of test_fused_output_layer_beyond_two_gib[100] (its shape and its generator): one row block, a layer too big
+    to split, so the form would be the single launch - and dec_fused_bf16_kernel keeps FIXED descriptors of 2^31 bytes: beyond
+    them its loads return zero and its stores are dropped.  output_form (csrc/abi_chains.h) sends a bf16 handle's single launch
+    beyond 2^31 bytes to the three GEMMs: the profile counters say which kernels ran, and the last 1000 rows of dec.lin3 - beyond
+    byte 2^31 - are finite and have moved from their loaded values after two steps.  No numeric tolerance is involved."""
+    from aaerec._hip import HipAAE, DeviceCSR, T_DEC_V3, K_DEC_CRIT, K_DEC_FUSED, K_DEC_BCE_FWD
+    from tools.synth import throughput_corpus
+    Ns, h, c, B = 2900000, 200, 50, 100
+    assert 2 ** 31 < (Ns + 64) * 204 * 4 < 2 ** 32
+    rng = np.random.default_rng(Ns + B)
+    k = 1.0 / np.sqrt(h)
+    full = {"dec.lin3.weight": ((rng.random((Ns, h), dtype=np.float32) * 2 - 1) * np.float32(k)),
+            "dec.lin3.bias": ((rng.random(Ns, dtype=np.float32) * 2 - 1) * np.float32(k))}
+    X = throughput_corpus(2 * B, Ns, median_len=30, seed=Ns)
+    m = HipAAE(Ns, h, c, max_batch=B, max_nnz=B * 256, rng_mode="inject", dtype="bf16")
+    m.load_params(full)
+    m.set_grad_scale(0.25)
+    del full
+    loaded = m.tensor(T_DEC_V3)[-1000:].clone()
+    m.profile_enable(True, kernels=(K_DEC_CRIT, K_DEC_FUSED, K_DEC_BCE_FWD))
+    csr = DeviceCSR(X, m.device)
+    for s in range(2):
+        dh2 = np.abs(rng.standard_normal((B, h + 1))).astype(np.float32) * 0.5
+        dh2[rng.random((B, h + 1)) < 0.4] = 0.0
+        dh2[:, h] = 1.0
+        m.dh2_rows(B)[:, :h + 1].copy_(torch.from_numpy(dh2))
+        m.output_layer_step(csr, s * B, B)
+    torch.cuda.synchronize()
+    assert m.profile_read(K_DEC_BCE_FWD)[1] == 2, "the three-kernel path did not run"
+    assert m.profile_read(K_DEC_FUSED)[1] == 0 and m.profile_read(K_DEC_CRIT)[1] == 0, "a fused launch ran beyond its descriptors"
+    last = m.tensor(T_DEC_V3)[-1000:]
+    assert bool(torch.isfinite(last).all().item())
+    assert bool((last != loaded).any(dim=1).all().item()), "rows beyond byte 2^31 kept their loaded values"
 
 
 @pytest.mark.parametrize("N,B", [(6000, 150), (40000, 224), (100000, 512)])

@@ -62,7 +62,7 @@ def test_the_lists_hold_what_the_gpu_test_is_meant_to_run():
 
 
 def test_output_form_restates_the_library_rule():
-    """fused_decoder_applies / output_layer_fused for an fp32 handle of the fuzz's sizes, at the row counts where the form changes."""
+    """output_form (csrc/abi_chains.h) for an fp32 handle of the fuzz's sizes, at the row counts where the form changes."""
     for rows, split_any, blocked_any in ((1, "split", "single"), (109, "split", "single"), (110, "three", "three"), (112, "three", "three"),
                                          (113, "three", "split"), (208, "three", "split"), (209, "three", "split"), (1664, "three", "split"),
                                          (1665, "three", "three")):

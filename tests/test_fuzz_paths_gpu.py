@@ -15,7 +15,11 @@ dec_opt_x3_kernel and dec_opt_blocks_x3_kernel.  A forced path can fall back sil
 profile's launch counters after each step: a batch of at most 109 rows on SPLIT_ANY and a batch above 112 rows on BLOCKED_ANY must
 have run the critical and the deferred launch and neither the single launch nor the three-kernel path's first GEMM; the cases
 that legitimately take another form are named in fuzz_path_cases.FALLBACK with the reason, and assert that form
-(fuzz_cases.output_form).  tests/test_fuzz_paths_cpu.py shows that the reference alone stays inside a quarter of each tolerance."""
+(fuzz_cases.output_form).  tests/test_fuzz_paths_cpu.py shows that the reference alone stays inside a quarter of each tolerance.
+
+  corner    the regular BLOCKED_ANY cases above 112 rows once more on a handle created with max_batch = 1700 - more than the 16 row
+            blocks of 104 rows a row-blocked batch can have: its batches of 113 .. 1664 rows run the row-blocked form like any
+            other blocked_output handle's (dec_opt_blocks_x3_kernel), at the same tolerances."""
 import pytest
 
 import fuzz_cases as F
@@ -39,6 +43,22 @@ def _check(group, cid, cfg, r, seed, path):
 def test_fp32_random_configuration_on_a_forced_path_matches_oracle(seed, path):
     cfg, r = F.config(seed)
     _check("regular", f"{seed}-{path}", cfg, r, seed, path)
+
+
+CORNER_MAX_BATCH = 1700      # > 16 row blocks x 104 rows
+CORNER = [(seed, path) for seed, path in P.REGULAR if path == "blocked_any" and F.config(seed)[0]["B"] > F.LAUNCH_ROWS]
+
+
+@pytest.mark.parametrize("seed,path", CORNER)
+def test_fp32_row_blocked_batch_on_a_handle_with_a_larger_max_batch_matches_oracle(seed, path):
+    assert len(CORNER) >= 2         # (fuzz_path_cases.regular_ok)
+    cfg, r = F.config(seed)
+    counters = []
+    F.check_configuration(cfg, r, seed, path=path, counters=counters, max_batch=CORNER_MAX_BATCH)
+    F.assert_output_form(path, counters, f"corner {seed}")
+    forms = [F.output_form(path, rows) for rows, _ in counters]
+    print(f"FUZZPATH corner {seed}: rows {[rows for rows, _ in counters]} forms {forms} launches (bce_fwd, single, critical, deferred) {[c for _, c in counters]}")
+    assert forms == ["split"] * 3, forms
 
 
 @pytest.mark.parametrize("seed,path", P.TINY)
