@@ -29,6 +29,8 @@ FINALS = {"linear": 0, "softmax": 1, "sigmoid": 2}
 OPTIMIZERS = {"adam": 0, "sgd": 1}
 PRIORS = {"gauss": 0, "categorical": 1, "bernoulli": 2}
 RNG_INJECT, RNG_DEVICE = 0, 1
+VAE_CHAIN_HIDDEN_MAX, VAE_CHAIN_CODE2_MAX = 207, 208      # a VAE handle without cfg.vae_wide: n_hidden, 2 * n_code (one chain slot)
+VAE_WIDE_HIDDEN_MAX, VAE_WIDE_CODE_MAX = 1024, 512        # ... with it (csrc/abi_model.h kVaeWideHiddenMax / kVaeWideCodeMax)
 RANK_K_MAX = 1024         # longest list of predict_topk / decode_topk (aaerec_hip.h; beyond 32: csrc/rank_long.h)
 COOC_TILE = 16384         # items per LDS tile of the co-occurrence score kernel (AAE_COOC_TILE; csrc/cooc.h kCoocTile)
 SPGEMM_HASH_PRODUCTS = 4096   # most products of a row the sparse product keeps in an LDS hash table (AAE_SPGEMM_HASH_PRODUCTS; csrc/spgemm.h)
@@ -80,7 +82,7 @@ class AaeConfig(C.Structure):
                 ("prior_scale", C.c_float), ("has_prior_scale", C.c_int32), ("seed", C.c_uint64),
                 ("unfused_decoder", C.c_int32), ("dp_world", C.c_int32), ("model_kind", C.c_int32),
                 ("dtype", C.c_int32), ("blocked_output", C.c_int32), ("dense_noise", C.c_int32),
-                ("reserved", C.c_int32 * 2)]
+                ("vae_wide", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class AaeBatch(C.Structure):
@@ -321,6 +323,7 @@ _PROTOS = {
 }
 K_ENC_GATHER, K_DEC_BCE_FWD, K_DEC_DA2, K_DEC_DV3_ADAM, K_ENC_W1_ADAM, K_DEC_FUSED, K_CHAIN, K_DEC_CRIT, K_DEC_OPT, K_RANK, K_COLLECTIVE = range(11)
 K_UNIQ_ITEMS, K_W1_CATCHUP = 11, 12
+K_VAE_REPARAM = 13        # the reparametrisation kernels of a VAE handle on the per-layer route (csrc/vae_layers.h)
 
 _lib = None
 
@@ -1423,7 +1426,8 @@ class HipAAE:
                  activation="ReLU", prior="gauss", prior_scale=None, optimizer="adam",
                  normalize_inputs=True, dropout=(.2, .2), gen_lr=1e-3, reg_lr=1e-3,
                  rng_mode="device", seed=0, grad_mode="fused", device=None, unfused_decoder=False,
-                 dp_world=1, w1_cap=None, ae_only=False, vae=False, dtype="f32", blocked_output=False, dense_noise=False):
+                 dp_world=1, w1_cap=None, ae_only=False, vae=False, dtype="f32", blocked_output=False, dense_noise=False,
+                 vae_wide=False):
         lib = load_library()
         if not torch.cuda.is_available():
             raise AaeHipError("no HIP device: the AAE step has no CPU fallback")
@@ -1463,6 +1467,9 @@ class HipAAE:
         cfg.blocked_output = 1 if (blocked_output and grad_mode != "export") else 0
         # DenoisingAutoEncoder(corrupt='gauss'): room for the dense noisy encoder input (set_input_noise before a step)
         cfg.dense_noise = 1 if dense_noise else 0
+        # a VAE handle's wide bounds (n_hidden <= VAE_WIDE_HIDDEN_MAX, n_code <= VAE_WIDE_CODE_MAX): beyond a chain slot - or under the
+        # NO_CHAIN option - its hidden half runs one launch per layer; at sizes that fit a slot it is the handle of vae_wide=False
+        cfg.vae_wide = 1 if vae_wide else 0
         self.dtype = dtype
         self.ae_only, self.vae = bool(ae_only or vae), bool(vae)
         self.dp_world = int(dp_world)

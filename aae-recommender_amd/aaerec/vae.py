@@ -27,6 +27,11 @@ STATUS_FORMAT = "[ R: {:.4f}]"
 # widest decoder input [z | conditions | 1] of a VAE handle: fc3 in up to five k-parts of 208 columns (csrc/abi_model.h
 # kVaeDecInMax, include/aaerec_hip.h) - the reference drivers' CONDITIONS need 383 and, eval/mpd/mpd.py, 983
 DEC_IN_MAX = 1040
+# widest hidden layer and code (csrc/abi_model.h kVaeWideHiddenMax / kVaeWideCodeMax, include/aaerec_hip.h): beyond a chain
+# slot - n_hidden > 207 or 2 * n_code > 208, the reference's own grid point (300, 100) - the handle is asked for cfg.vae_wide
+# and runs its hidden half one launch per layer
+HIDDEN_MAX, CODE_MAX = _hip.VAE_WIDE_HIDDEN_MAX, _hip.VAE_WIDE_CODE_MAX
+assert (HIDDEN_MAX, CODE_MAX) == (1024, 512)
 
 
 def log_losses(loss):
@@ -59,6 +64,11 @@ class VAE:
             raise ValueError("the VAE's decoder input [z | conditions | 1] is n_code + conditions.size_increment() + 1 = "
                              "{} + {} + 1 columns: the kernels take at most {} (five parts of 208)".format(
                                  n_code, code_inc, DEC_IN_MAX))
+        if n_hidden > HIDDEN_MAX or n_code > CODE_MAX:
+            raise ValueError("the VAE's kernels take n_hidden <= {} and n_code <= {}: got n_hidden = {}, n_code = {}".format(
+                HIDDEN_MAX, CODE_MAX, n_hidden, n_code))
+        # a model that fits a chain slot creates the handle it always did
+        vae_wide = n_hidden > _hip.VAE_CHAIN_HIDDEN_MAX or 2 * n_code > _hip.VAE_CHAIN_CODE2_MAX
         dev_probe = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # conditions the kernels produce / train themselves ride in aae_vae_step; any other plugin gets the step cut at
         # the condition boundary and runs with torch autograd in between (aae_vae_encode / _decode_backward / ...)
@@ -70,7 +80,7 @@ class VAE:
                                activation=activation, optimizer=optimizer.lower(), normalize_inputs=normalize_inputs,
                                dropout=(0.0, 0.0), gen_lr=lr, reg_lr=lr,
                                rng_mode="device" if rng_mode == "device" else "inject", seed=seed, device=device,
-                               vae=True)
+                               vae=True, **({"vae_wide": True} if vae_wide else {}))
         self.device = self.hip.device
         # nn.Linear default initialisation in the reference's construction order: fc1, fc21, fc22, fc3, fc4
         fc1, fc21, fc22 = torch.nn.Linear(inp, n_hidden), torch.nn.Linear(n_hidden, n_code), torch.nn.Linear(n_hidden, n_code)

@@ -47,6 +47,7 @@
 #include "chain.h"
 #include "chain4.h"
 #include "chain16x3.h"
+#include "vae_layers.h"
 #include "cond_embed.h"
 #include "cond_bag.h"
 #include "cond_csr.h"
@@ -139,6 +140,7 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         //  kVaeInParts parts on the 16-row kernel, abi_chains.h)
         m->use_chain = (m->h + 1 <= 208) && (m->c + 1 <= 208) && (m->cp + 1 <= (m->vae ? kVaeDecInMax : 2 * 208)) &&
                        !m->opt.no_chain;      // (the code itself has to fit a slot: only the condition block may exceed it)
+        if (m->vae && !vae_fits_chain(m->h, m->c)) m->use_chain = false;      // (cfg.vae_wide: [mu | logvar] has to fit a slot as well)
         const size_t chain_lds = kCSlots * kCR * kCL * sizeof(float);
         if (m->use_chain) each_chain(false, limit(m->use_chain, chain_lds));
         // (the r6 activation classes live in chain_kernel<.., true> alone: device_common.h act_fwd)
@@ -147,6 +149,17 @@ int aae_create(const aae_config* cfg, void* arena_dev, size_t arena_bytes, void*
         m->use_chain4 = m->use_chain && !m->act_nm && !m->opt.chain16;
         if (m->use_chain4) each_chain4(limit(m->use_chain4, chain_lds));
         if (m->use_chain && m->cp + 1 > 208 && !m->use_chain4 && !m->vae) m->use_chain = false;      // (the AAE's two k-parts: chain4.h alone)
+        // a cfg.vae_wide handle off the chain programs (its sizes, or NO_CHAIN): the per-layer route.  What launch_gather asks of
+        // enc_gather_kernel_t<16> for a row's image (gather_lds_bytes; + the kernel's 64 bytes of static LDS) passes the default
+        // 64 KB at the widest hidden layer: the limit is raised to that request here, the only place that does so for this kernel
+        // (the four-wave form of batches from 512 rows on asks for a quarter and stays below)
+        m->vae_layers = m->vae && cfg->vae_wide == 1 && !m->use_chain;
+        if (m->vae_layers && gather_lds_bytes(m->h) + 64 > 64 * 1024) {
+            bool ok = true;
+            limit(ok, gather_lds_bytes(m->h))(enc_gather_kernel_t<16>);
+            (void)hipGetLastError();
+            if (!ok) { delete m; return fail(AAE_EHIP, "the first layer's gather cannot take the LDS of this n_hidden"); }
+        }
         m->x16_rows = m->opt.x16_rows;
         m->dw_ksplit_rows = 256;                       // (the handle is zero-filled after construction: no default member values)
         if (m->opt.dw_ksplit_rows >= 0) m->dw_ksplit_rows = m->opt.dw_ksplit_rows;
@@ -454,7 +467,7 @@ int aae_tensor_info(aae_handle h, int id, aae_tensor* out) {
     else if (id == AAE_T_ACT_DA2) t = &h->da2;
     // (ga1x: the LAST rows hold the batch; the per-layer path - NO_CHAIN, or a model too wide for the chain programs - leaves
     //  dL/d(a1) in gb1: abi_layers.h encoder_backward)
-    else if (id == AAE_T_ACT_GA1) t = (h->ext_first && h->ga1x.p) ? &h->ga1x : h->use_chain ? &h->gb3 : &h->gb1;
+    else if (id == AAE_T_ACT_GA1) t = (h->ext_first && h->ga1x.p) ? &h->ga1x : (h->use_chain || h->vae_layers) ? &h->gb3 : &h->gb1;
     else if (id == AAE_T_ACT_DZC) { tmp = h->gzc; tmp.cols = h->cp; t = &tmp; }
     else if (id == AAE_T_ACT_LOSSES) {
         tmp.rows = 1; tmp.cols = 4; tmp.ld = 4; tmp.off = (size_t)((char*)h->losses - h->base); t = &tmp;

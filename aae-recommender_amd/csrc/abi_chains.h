@@ -944,7 +944,7 @@ int encoder_first_layer_update(aae_model* m, const float* ga1, int which, hipStr
 int launch_gather(aae_model* m, const float* bias, float* act_out, const DropSpec& d, bool head, bool open_step, const char* what,
                   hipStream_t s, bool bump_next = false) {
     ProfScope ps(m, AAE_K_ENC_GATHER, s);
-    const size_t shm = (size_t)16 * r4(m->h) * sizeof(float);
+    const size_t shm = gather_lds_bytes(m->h);
     // wide batches: four waves per document (eight documents per CU instead of two; a document is ~20 entries: five per wave;
     // an item slice holds 1 / world of a document's entries).
     // ms/step, 16 | 4 waves: C3 at batch 512 0.651 | 0.646, C4 (1 000 rows) 0.389 | 0.381; C2's shape at batch 500 0.327 | 0.331,

@@ -22,6 +22,8 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 namespace {
 
 inline int r4(int x) { return (x + 3) & ~3; }
+// dynamic LDS of the first layer's gather in its 16-wave form: the waves' partial sums of a row, [16][round4(n_hidden)] floats
+inline size_t gather_lds_bytes(int h) { return (size_t)16 * r4(h) * sizeof(float); }
 
 struct Ten {
     float* p = nullptr; size_t off = 0; int64_t rows = 0, cols = 0, ld = 0;
@@ -115,6 +117,8 @@ struct aae_model {
     bool bf16;               // cfg.dtype = 1: bf16 matrix-core inputs for the GEMM-shaped products (fp32 accumulate / master / Adam)
     bool vae_cut;            // the VAE step is cut at the condition boundary (aae_vae_encode / _decode_backward / _encoder_backward)
     Ten mulv, gmulv, veps;   // VAE: [mu | logvar], its gradient, eps of the step
+    bool vae_layers;         // a cfg.vae_wide handle off the chain programs: the VAE's hidden half one launch per layer (abi_output_layer.h)
+    unsigned* kl_ticket;     // ... the hand-off word of its KL sum (vae_layers.h), zero between launches
     bool use_chain;          // row-blocked layer chains (chain.h) instead of one GEMM launch per layer
     bool use_chain4;         // ... with 4 rows per workgroup (chain4.h) where a program allows it
     bool act_nm;             // cfg.activation is one of the r6 classes (AAE_ACT_SOFTPLUS ..): its layer programs run on chain_kernel<.., true> only
@@ -239,6 +243,13 @@ inline bool fused_width_ok(int h, int ldh) {
 // every program of the step, predict and the rank calls is still one launch of at most kCMaxOps ops (the forward: 6 + 2 (n - 1))
 constexpr int kVaeInParts = 5, kVaeDecInMax = kVaeInParts * kCWide;      // 1040: mpd.py's 50 + 932 + 1 = 983 columns
 static_assert(kVaeDecInMax == 1040, "validate()'s message, include/aaerec_hip.h, README.md and aaerec/vae.py name this bound");
+// ... with cfg.vae_wide = 1: the hidden width and the code of the per-layer route (abi_output_layer.h vae_*_layers).  Its kernels
+// are the wide AAE's; the narrowest of them is the opening gather's 16 x round4(n_hidden) floats of LDS - 64 KB at 1024, which
+// aae_create asks for - and vae_layers.h's two take any code a wavefront walks
+constexpr int kVaeWideHiddenMax = 1024, kVaeWideCodeMax = 512;
+static_assert(kVaeWideHiddenMax == 1024 && kVaeWideCodeMax == 512, "validate()'s message, include/aaerec_hip.h, README.md, DESIGN.md and aaerec/vae.py name these bounds");
+// a VAE handle whose sizes fit the layer-chain programs (one slot for the hidden layer and for [mu | logvar])
+inline bool vae_fits_chain(int n_hidden, int n_code) { return n_hidden + 1 <= 208 && 2 * n_code <= 208; }
 int validate(const aae_config* c) {
     if (!c) return fail(AAE_EINVAL, "cfg is NULL");
     if (c->abi_version != AAE_ABI_VERSION) return fail(AAE_EINVAL, "abi_version mismatch");
@@ -254,7 +265,9 @@ int validate(const aae_config* c) {
     if (c->grad_mode != AAE_GRAD_FUSED && c->grad_mode != AAE_GRAD_EXPORT) return fail(AAE_EINVAL, "unknown grad_mode");
     if (!(c->dropout1 >= 0.f && c->dropout1 < 1.f && c->dropout2 >= 0.f && c->dropout2 < 1.f))
         return fail(AAE_EINVAL, "dropout must be in [0,1)");
-    if (c->reserved[0] || c->reserved[1]) return fail(AAE_EINVAL, "reserved fields must be zero");
+    if (c->reserved[0]) return fail(AAE_EINVAL, "reserved fields must be zero");
+    if (c->vae_wide != 0 && c->vae_wide != 1) return fail(AAE_EINVAL, "vae_wide must be 0 or 1 (the VAE's wide bounds)");
+    if (c->vae_wide == 1 && c->model_kind != 3) return fail(AAE_EINVAL, "vae_wide = 1 needs VAE mode (model_kind = 3)");
     if (c->dense_noise != 0 && c->dense_noise != 1) return fail(AAE_EINVAL, "dense_noise must be 0 or 1 (dense noisy encoder input)");
     if (c->dense_noise == 1 && (c->model_kind != 1 || c->grad_mode != AAE_GRAD_FUSED || c->dtype != 0))
         return fail(AAE_EINVAL, "dense_noise = 1 (dense noisy encoder input) needs the plain autoencoder (model_kind = 1), fp32, fused optimiser");
@@ -263,8 +276,11 @@ int validate(const aae_config* c) {
     if (c->dtype == 1 && c->model_kind == 3) return fail(AAE_EINVAL, "bf16 arithmetic is not available in VAE mode");
     if (c->model_kind < 0 || c->model_kind > 3 || c->model_kind == 2)
         return fail(AAE_EINVAL, "model_kind must be 0 (AAE), 1 (plain autoencoder) or 3 (VAE)");
-    if (c->model_kind == 3 && (c->n_hidden + 1 > 208 || c->n_code + c->cond_inc + 1 > kVaeDecInMax || 2 * c->n_code > 208))
-        return fail(AAE_EINVAL, "VAE mode needs n_hidden <= 207, n_code + cond_inc + 1 <= 1040 (the decoder input in up to five parts of 208 columns), 2 * n_code <= 208");
+    if (c->model_kind == 3 && c->vae_wide == 0 && (!vae_fits_chain(c->n_hidden, c->n_code) || c->n_code + c->cond_inc + 1 > kVaeDecInMax))
+        return fail(AAE_EINVAL, "VAE mode needs n_hidden <= 207, n_code + cond_inc + 1 <= 1040 (the decoder input in up to five parts of 208 columns), 2 * n_code <= 208"
+                                " (cfg.vae_wide = 1 lifts the first and the last: n_hidden <= 1024, n_code <= 512)");
+    if (c->model_kind == 3 && c->vae_wide == 1 && (c->n_hidden > kVaeWideHiddenMax || c->n_code > kVaeWideCodeMax || c->n_code + c->cond_inc + 1 > kVaeDecInMax))
+        return fail(AAE_EINVAL, "VAE mode with vae_wide = 1 needs n_hidden <= 1024, n_code <= 512, n_code + cond_inc + 1 <= 1040");
     if (c->dp_world < 0 || c->dp_world > 64) return fail(AAE_EINVAL, "dp_world (data-parallel world size) out of range");
     if (c->unfused_decoder != 0 && c->unfused_decoder != 1) return fail(AAE_EINVAL, "unfused_decoder must be 0 or 1");
     return AAE_OK;
@@ -367,6 +383,7 @@ size_t layout(aae_model* m, char* base, bool dry) {
     if (c.model_kind == 3) {
         m->mulv = a.mat(R, 2 * cc, r4(2 * cc)); m->gmulv = a.mat(R, 2 * cc, r4(2 * cc)); m->veps = a.mat(R, cc, r4(cc));
     }
+    m->kl_ticket = c.vae_wide == 1 ? reinterpret_cast<unsigned*>(a.take(4, nullptr)) : nullptr;
     m->bce_partials_cap = std::max(512 * (c.blocked_output ? kMaxRowBlocks : 1), ((N + 31) / 32) * ((R + 31) / 32));
     m->bce_partials = a.take(m->bce_partials_cap, nullptr);
     m->fix_partials = a.take((size_t)R * 64, nullptr);

@@ -316,25 +316,136 @@ int output_layer_unfused(aae_model* m, const DecodeMode& mode, int B, float gsca
     return AAE_OK;
 }
 
+// ---- the VAE's hidden half (reference vae.py:111-130 and its backward), one dispatcher per half: the layer-chain programs
+// (abi_chains.h chain_vae_*) where the handle has them, else - a cfg.vae_wide handle wider than a chain slot, or under NO_CHAIN -
+// one launch per layer: the wide AAE's products and epilogues (abi_layers.h) around vae_layers.h's two kernels.  A backward
+// dispatcher ends with the weight gradients and optimiser updates of its half.
+// (any other VAE handle off the chain programs: the refusal of before, for the entry points to hand on)
+inline bool vae_route(const aae_model* m) { return m->use_chain || m->vae_layers; }
+int vae_route_check(const aae_model* m) {
+    if (vae_route(m)) return AAE_OK;
+    return fail(AAE_ESTATE, "VAE mode needs the layer-chain kernels (a handle created with cfg.vae_wide = 1 runs layer by layer without them)");
+}
+
+int launch_vae_reparam_fwd(aae_model* m, const float* cond_dev, const float* eps_dev, float* z_out, bool tail, int rows, int grow0, hipStream_t s) {
+    VaeReparamFwd a;
+    a.mulv = m->mulv.p; a.ldm = (int)m->mulv.ld; a.eps_in = eps_dev; a.ldi = m->c;
+    a.veps = m->veps.p; a.lde = (int)m->veps.ld; a.zc = m->zc.p; a.ldzc = m->ldc; a.z_out = z_out;
+    a.cond = cond_dev; a.cond_inc = m->cfg.cond_inc; a.tail = tail ? 1 : 0;
+    a.rows = rows; a.c = m->c; a.cp = m->cp;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    a.vec = (m->c & 3) == 0 && al16(eps_dev) && al16(z_out);
+    a.vec_cond = (m->c & 3) == 0 && (a.cond_inc & 3) == 0 && al16(cond_dev);
+    a.seed = m->cfg.seed; a.step_ctr = m->step_ctr; a.stream_id = 12; a.grow0 = grow0;
+    ProfScope ps(m, AAE_K_VAE_REPARAM, s);
+    hipLaunchKernelGGL(pick_vae_reparam_fwd(), dim3((rows + 3) / 4), dim3(256), 0, s, a);
+    LAUNCHCHK("vae_reparam_fwd");
+    return AAE_OK;
+}
+// [mu | logvar] = [fc21; fc22] eh1 -> z (and the constant condition block, the bias column: tail)
+int vae_encode_layers(aae_model* m, const float* cond_dev, const float* eps_dev, float* z_out, bool tail, int rows, int grow0, hipStream_t s) {
+    EpiStore e; e.out = m->mulv.p; e.ld = (int)m->mulv.ld;
+    TRY(linear_fwd(m->eh1.p, m->ldh, rows, m->P[P_W3], e, s, gmode(m)));
+    return launch_vae_reparam_fwd(m, cond_dev, eps_dev, z_out, tail, rows, grow0, s);
+}
+// dh2 = act(fc3 zc)
+int vae_dec_hidden_layers(aae_model* m, int rows, hipStream_t s) {
+    EpiDropAct e; e.out = m->dh2.p; e.ld = m->ldh; e.act = m->cfg.activation; memset(&e.d, 0, sizeof(e.d));      // (no dropout in the VAE)
+    e.seed = m->cfg.seed; e.step_ctr = m->step_ctr;
+    return linear_fwd(m->zc.p, m->ldc, rows, m->P[P_V1], e, s, gmode(m));
+}
+// from gb0 = dL/d(pre-activation of fc3), which both forms of the output layer leave there off the chain programs (reduce_slabs,
+// output_layer_unfused): dL/d(decoder input) -> gzc (and the caller), fc3's weight gradient + optimiser
+int vae_backward_dec_layers(aae_model* m, float* dzc_out, hipStream_t s) {
+    const int B = m->rows, cp = m->cp;
+    EpiStore ez; ez.out = m->gzc.p; ez.ld = m->ldc;
+    TRY(linear_dx(m->gb0.p, m->ldh, B, m->P[P_V1], cp, ez, s, gmode(m)));
+    if (dzc_out) {
+        hipLaunchKernelGGL(copy2d_kernel, dim3(grid1d((size_t)B * cp)), dim3(256), 0, s, m->gzc.p, m->ldc, dzc_out, cp, B, cp, 1.0f);
+        LAUNCHCHK("copy dzc");
+    }
+    return linear_dw(m, m->gb0.p, m->ldh, B, m->zc.p, m->ldc, P_V1, O_DEC, s);
+}
+// from dL/dz: (dL/dmu, dL/dlogvar) with the KL gradient and the KL sum -> [fc21; fc22] -> dL/d(a1) in gb3, their weight
+// gradients + optimiser, the first layer's bias and rows (as encoder_backward ends)
+int vae_backward_enc_layers(aae_model* m, const float* dz_dev, int ld_dz, hipStream_t s) {
+    const int B = m->rows, h = m->h;
+    {
+        VaeReparamBwd a;
+        a.dz = dz_dev; a.lddz = ld_dz; a.mulv = m->mulv.p; a.ldm = (int)m->mulv.ld; a.veps = m->veps.p; a.lde = (int)m->veps.ld;
+        a.gmulv = m->gmulv.p; a.ldg = (int)m->gmulv.ld; a.rows = B; a.c = m->c;
+        a.vec = (m->c & 3) == 0 && (ld_dz & 3) == 0 && (reinterpret_cast<uintptr_t>(dz_dev) & 15) == 0;
+        a.scale = m->grad_scale; a.row_kl = m->adv_terms; a.ticket = m->kl_ticket; a.loss_out = m->losses + 1;
+        ProfScope ps(m, AAE_K_VAE_REPARAM, s);
+        hipLaunchKernelGGL(pick_vae_reparam_bwd(), dim3((B + 3) / 4), dim3(256), 0, s, a);
+        LAUNCHCHK("vae_reparam_bwd");
+    }
+    EpiActBwd b; b.out = m->gb3.p; b.ld = m->ldh; b.y = m->eh1.p; b.ldy = m->ldh; b.act = m->cfg.activation; memset(&b.d, 0, sizeof(b.d));
+    b.seed = m->cfg.seed; b.step_ctr = m->step_ctr;
+    TRY(linear_dx(m->gmulv.p, (int)m->gmulv.ld, B, m->P[P_W3], h, b, s, gmode(m)));
+    TRY(linear_dw(m, m->gmulv.p, (int)m->gmulv.ld, B, m->eh1.p, m->ldh, P_W3, O_ENC, s));
+    return encoder_first_layer_update(m, m->gb3.p, O_ENC, s);      // (nothing rode in a grouped launch: colsum_adam_kernel, then the item rows)
+}
+
+// (grow0: the generator row of row 0 - chain_vae_forward)
+int vae_forward(aae_model* m, const float* cond_dev, const float* eps_dev, int rows, hipStream_t s, int grow0 = 0) {
+    if (m->use_chain) return chain_vae_forward(m, cond_dev, eps_dev, rows, s, grow0);
+    TRY(vae_route_check(m));
+    TRY(vae_encode_layers(m, cond_dev, eps_dev, nullptr, true, rows, grow0, s));
+    return vae_dec_hidden_layers(m, rows, s);
+}
+int vae_encode(aae_model* m, const float* eps_dev, float* z_out, int rows, hipStream_t s) {
+    if (m->use_chain) return chain_vae_encode(m, eps_dev, z_out, rows, s);
+    TRY(vae_route_check(m));
+    return vae_encode_layers(m, nullptr, eps_dev, z_out, false, rows, 0, s);
+}
+int vae_dec_hidden(aae_model* m, int rows, hipStream_t s) {
+    if (m->use_chain) return chain_vae_dec_hidden(m, rows, s);
+    TRY(vae_route_check(m));
+    return vae_dec_hidden_layers(m, rows, s);
+}
+// the cut step's first half: down to dL/d(decoder input), fc3's update (part_slabs: the fused output layer's partial slabs for
+// the chain program to sum, NULL behind the three GEMMs)
+int vae_backward_dec(aae_model* m, const float* part_slabs, size_t slab_stride, float* dzc_out, hipStream_t s) {
+    if (!m->use_chain) { TRY(vae_route_check(m)); return vae_backward_dec_layers(m, dzc_out, s); }
+    TRY(chain_vae_backward_dec(m, part_slabs, slab_stride, dzc_out, s));
+    DwBuilder dw;
+    dw.add(m, m->gb0.p, m->ldh, m->zc.p, m->ldc, m->rows, P_V1, O_DEC);
+    return dw.launch(s);
+}
+// ... its second half, from the caller's dL/dz
+int vae_backward_enc(aae_model* m, const float* dz_dev, int ld_dz, hipStream_t s) {
+    if (!m->use_chain) { TRY(vae_route_check(m)); return vae_backward_enc_layers(m, dz_dev, ld_dz, s); }
+    TRY(chain_vae_backward_enc(m, dz_dev, ld_dz, s));
+    DwBuilder dw;
+    dw.add(m, m->gmulv.p, (int)m->gmulv.ld, m->eh1.p, m->ldh, m->rows, P_W3, O_ENC);
+    TRY(dw.add_first_layer(m, m->gb3.p, O_ENC, s)); m->w1_merged = true;
+    TRY(dw.launch(s));
+    return encoder_first_layer_update(m, m->gb3.p, O_ENC, s, m->w1_merged);
+}
+// the whole backward below the output layer (aae_vae_step)
+int vae_backward(aae_model* m, const float* part_slabs, size_t slab_stride, hipStream_t s) {
+    if (!m->use_chain) {
+        TRY(vae_route_check(m));
+        TRY(vae_backward_dec_layers(m, nullptr, s));
+        return vae_backward_enc_layers(m, m->gzc.p, m->ldc, s);
+    }
+    TRY(chain_vae_backward(m, part_slabs, slab_stride, s));
+    DwBuilder dw;
+    dw.add(m, m->gb0.p, m->ldh, m->zc.p, m->ldc, m->rows, P_V1, O_DEC);
+    dw.add(m, m->gmulv.p, (int)m->gmulv.ld, m->eh1.p, m->ldh, m->rows, P_W3, O_ENC);
+    TRY(dw.add_first_layer(m, m->gb3.p, O_ENC, s)); m->w1_merged = true;
+    TRY(dw.launch(s));
+    return encoder_first_layer_update(m, m->gb3.p, O_ENC, s, m->w1_merged);
+}
+
 // ---- the decoder's hidden layers, backward (VAE cut / VAE / chain program / per-layer GEMMs)
 int decoder_hidden_backward(aae_model* m, const DecodeMode& mode, const float* chain_part, size_t chain_stride, const DropSpec& d1, float* dzc_out, hipStream_t s) {
     const int B = m->rows, h = m->h, cp = m->cp;
-    if (m->use_chain && mode.vae && m->vae_cut) {
-        // cut at the condition boundary: stop at dL/d(decoder input); fc3's weight gradient + optimiser here, the rest
-        // of the backward pass comes with the caller's dL/dz (aae_vae_encoder_backward)
-        TRY(chain_vae_backward_dec(m, chain_part, chain_stride, dzc_out, s));
-        DwBuilder dw;
-        dw.add(m, m->gb0.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);
-        return dw.launch(s);
-    }
-    if (m->use_chain && mode.vae) {
-        TRY(chain_vae_backward(m, chain_part, chain_stride, s));
-        DwBuilder dw;
-        dw.add(m, m->gb0.p, m->ldh, m->zc.p, m->ldc, B, P_V1, O_DEC);
-        dw.add(m, m->gmulv.p, (int)m->gmulv.ld, m->eh1.p, m->ldh, B, P_W3, O_ENC);
-        TRY(dw.add_first_layer(m, m->gb3.p, O_ENC, s)); m->w1_merged = true;
-        return dw.launch(s);
-    }
+    // cut at the condition boundary: stop at dL/d(decoder input); fc3's weight gradient + optimiser here, the rest
+    // of the backward pass comes with the caller's dL/dz (aae_vae_encoder_backward)
+    if (mode.vae && m->vae_cut) return vae_backward_dec(m, chain_part, chain_stride, dzc_out, s);
+    if (mode.vae) return vae_backward(m, chain_part, chain_stride, s);
     if (m->use_chain) {
         // decoder hidden backward (+ the encoder backward when called from aae_step) in one program,
         // then every small weight gradient + optimiser update in one grouped launch
@@ -375,7 +486,7 @@ int decode_backward(aae_model* m, const float* zc_dev, int64_t zc_ld, const aae_
     if (zc_dev) TRY(stage_zc(m, zc_dev, zc_ld, B, s));
     const uint8_t* mk2 = m->inj.masks_dev[2];
     const uint8_t* mk3 = m->inj.masks_dev[3];
-    if (mode.only_output_layer) { /* ACT_DH2 is the input */ }
+    if (mode.only_output_layer || mode.vae) { /* ACT_DH2 is the input / the VAE's entry points ran its one hidden layer */ }
     else if (m->use_chain) { if (!m->dec_hidden_done) TRY(chain_dec_hidden(m, true, B, s)); }
     else TRY(decoder_hidden_forward(m, true, mk2, mk3, B, s));
     TRY(join_output_layer(m, s));       // a deferred launch of the step before that was left running at this step's opening (late join)

@@ -35,7 +35,7 @@ int aae_encode(aae_handle m, const aae_batch* batch, float* z_out, void* stream)
 namespace {
 // the decoder's hidden layers of the rows staged in zc -> m->dh2, eval mode
 int dec_hidden_rows(aae_model* m, int n_rows, hipStream_t s) {
-    if (m->vae) return chain_vae_dec_hidden(m, n_rows, s);       // (VAE: one hidden layer, fc3)
+    if (m->vae) return vae_dec_hidden(m, n_rows, s);       // (VAE: one hidden layer, fc3)
     if (m->use_chain) return chain_dec_hidden(m, false, n_rows, s);
     return decoder_hidden_forward(m, false, nullptr, nullptr, n_rows, s);
 }
@@ -150,7 +150,7 @@ int logits_to_scratch(aae_model* m, const RankInput& in, void* stream) {
         TRY(join_deferred(m, s));
         if (m->lazy) TRY(lazy_prepare(m, 0, true, s));
         TRY(gather_first_layer(m, false, nullptr, 0, s));
-        TRY(chain_vae_forward(m, in.cond, in.eps, m->rows, s, in.grow0));
+        TRY(vae_forward(m, in.cond, in.eps, m->rows, s, in.grow0));
     } else {
         TRY(aae_encode(m, &in.batch, nullptr, stream));
         if (m->cfg.cond_inc > 0) {

@@ -443,7 +443,7 @@ int rank_check_call(const char* who, const aae_model* m, bool vae, int form, boo
                     const float* eps_dev, int64_t zc_ld, const aae_batch* batch, const aae_batch* truth) {
     const std::string w(who);
     if (!m || !ptrs) return fail(AAE_EINVAL, w + ": NULL argument");
-    if (vae && (!m->vae || !m->use_chain)) return fail(AAE_ESTATE, w + ": model was not created in VAE mode (cfg.model_kind = 3)");
+    if (vae && (!m->vae || !(m->use_chain || m->vae_layers))) return fail(AAE_ESTATE, w + ": model was not created in VAE mode (cfg.model_kind = 3)");
     auto predict_args = [&]() {
         if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, w + ": cond_inc > 0 needs cond_dev");
         if (vae && m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, w + ": rng_mode inject needs eps_dev");

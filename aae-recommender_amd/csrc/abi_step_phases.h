@@ -22,18 +22,17 @@ int aae_decoder_step(aae_handle m, const aae_batch* batch, const float* zin_dev,
 int aae_vae_step(aae_handle m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, void* stream) {
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
     if (!m->vae) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
-    if (!m->use_chain) return fail(AAE_ESTATE, "VAE mode needs the layer-chain kernels");
+    TRY(vae_route_check(m));
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
     hipStream_t s = S(stream);
     TRY(open_step_plain(m, batch, nullptr, s));
     if (m->lazy) TRY(lazy_prepare(m, -1, false, s));
     TRY(gather_first_layer(m, false, nullptr, 0, s));                 // eh1 = act(fc1(normalize(x))), vae.py:111-113
-    TRY(chain_vae_forward(m, cond_dev, eps_dev, m->rows, s));
+    TRY(vae_forward(m, cond_dev, eps_dev, m->rows, s));
     m->dec_hidden_done = true; m->vae_cut = false; m->phase = 1;
     DecodeMode mode; mode.vae = true;
-    TRY(decode_backward(m, nullptr, 0, nullptr, nullptr, mode, s));
-    TRY(encoder_first_layer_update(m, m->gb3.p, O_ENC, s, m->w1_merged));
+    TRY(decode_backward(m, nullptr, 0, nullptr, nullptr, mode, s));      // (ends with vae_backward: every update below the output layer)
     m->phase = 0;
     return AAE_OK;
 }
@@ -42,7 +41,7 @@ int aae_vae_step(aae_handle m, const aae_batch* batch, const float* cond_dev, co
 int aae_vae_predict(aae_handle m, const aae_batch* batch, const float* cond_dev, const float* eps_dev, float* out_dev,
                     int64_t out_ld, void* stream) {
     if (!m || !out_dev) return fail(AAE_EINVAL, "handle/out is NULL");
-    if (!m->vae || !m->use_chain) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
+    if (!m->vae || !vae_route(m)) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
     if (m->cfg.cond_inc > 0 && !cond_dev) return fail(AAE_EINVAL, "cond_inc > 0 needs cond_dev");
     if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
     if (out_ld < m->N || (out_ld & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
@@ -52,7 +51,7 @@ int aae_vae_predict(aae_handle m, const aae_batch* batch, const float* cond_dev,
     TRY(join_deferred(m, s));
     if (m->lazy) TRY(lazy_prepare(m, 0, true, s));
     TRY(gather_first_layer(m, false, nullptr, 0, s));
-    TRY(chain_vae_forward(m, cond_dev, eps_dev, m->rows, s));
+    TRY(vae_forward(m, cond_dev, eps_dev, m->rows, s));
     EpiSigmoid e; e.out = out_dev; e.ld = (int)out_ld;
     TRY(linear_fwd(m->dh2.p, m->ldh, m->rows, m->P[P_V3], e, s, gmode(m)));
     m->phase = 0;
@@ -68,7 +67,7 @@ int aae_vae_predict(aae_handle m, const aae_batch* batch, const float* cond_dev,
 //   aae_vae_encoder_backward  reparametrize' + KL gradient -> [fc21; fc22] -> fc1, their updates
 int aae_vae_encode(aae_handle m, const aae_batch* batch, const float* eps_dev, float* z_out_dev, int32_t train, void* stream) {
     if (!m) return fail(AAE_EINVAL, "handle is NULL");
-    if (!m->vae || !m->use_chain) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
+    if (!m->vae || !vae_route(m)) return fail(AAE_ESTATE, "model was not created in VAE mode (cfg.model_kind = 3)");
     if (m->cfg.rng_mode == AAE_RNG_INJECT && !eps_dev) return fail(AAE_EINVAL, "rng_mode inject needs eps_dev");
     hipStream_t s = S(stream);
     if (train) {
@@ -83,7 +82,7 @@ int aae_vae_encode(aae_handle m, const aae_batch* batch, const float* eps_dev, f
         m->enc_bwd_done = false;
     }
     TRY(gather_first_layer(m, false, nullptr, 0, s));
-    TRY(chain_vae_encode(m, eps_dev, z_out_dev, m->rows, s));
+    TRY(vae_encode(m, eps_dev, z_out_dev, m->rows, s));
     m->dec_hidden_done = false;
     m->phase = train ? 1 : 0; m->vae_cut = train != 0;
     return AAE_OK;
@@ -95,7 +94,7 @@ int aae_vae_decode_backward(aae_handle m, const float* zc_dev, int64_t zc_ld, fl
     if (zc_ld < m->cp) return fail(AAE_EINVAL, "zc_ld < n_code + cond_inc");
     hipStream_t s = S(stream);
     TRY(stage_zc(m, zc_dev, zc_ld, m->rows, s));
-    TRY(chain_vae_dec_hidden(m, m->rows, s));
+    TRY(vae_dec_hidden(m, m->rows, s));
     m->dec_hidden_done = true;
     DecodeMode mode; mode.vae = true;
     return decode_backward(m, nullptr, 0, nullptr, dzc_out_dev, mode, s);
@@ -106,13 +105,7 @@ int aae_vae_encoder_backward(aae_handle m, const float* dz_dev, int64_t dz_ld, v
     if (!m->vae || m->phase != 2 || !m->vae_cut) return fail(AAE_ESTATE, "aae_vae_encoder_backward without aae_vae_decode_backward");
     if (dz_ld < m->c) return fail(AAE_EINVAL, "dz_ld < n_code");
     hipStream_t s = S(stream);
-    const int B = m->rows;
-    TRY(chain_vae_backward_enc(m, dz_dev, (int)dz_ld, s));
-    DwBuilder dw;
-    dw.add(m, m->gmulv.p, (int)m->gmulv.ld, m->eh1.p, m->ldh, B, P_W3, O_ENC);
-    TRY(dw.add_first_layer(m, m->gb3.p, O_ENC, s)); m->w1_merged = true;
-    TRY(dw.launch(s));
-    TRY(encoder_first_layer_update(m, m->gb3.p, O_ENC, s, m->w1_merged));
+    TRY(vae_backward_enc(m, dz_dev, (int)dz_ld, s));
     m->phase = 0; m->vae_cut = false;
     return AAE_OK;
 }

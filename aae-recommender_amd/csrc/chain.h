@@ -549,14 +549,8 @@ __global__ __launch_bounds__(kCT) void chain_kernel(ChainProgram P) {
                     const int j = col < n ? col : col - n;
                     const float mu = ml[lrow * kCL + j], lv = ml[lrow * kCL + n + j];
                     const float gz = src[lrow * kCL + j];
-                    const float ev = expf(lv);
-                    if (col < n) {
-                        o = gz + op.scale * mu;
-                        kl += -0.5f * (1.f + lv - mu * mu - ev);
-                    } else {
-                        const float eps = op.aux_ptr[(size_t)(r0 + lrow) * op.aux_ld + j];
-                        o = gz * eps * 0.5f * expf(0.5f * lv) + op.scale * 0.5f * (ev - 1.f);
-                    }
+                    const float eps = col < n ? 0.f : op.aux_ptr[(size_t)(r0 + lrow) * op.aux_ld + j];
+                    o = reparam_bwd_cell(col < n, gz, mu, lv, eps, op.scale, kl);
                 }
                 dst[lrow * kCL + col] = o;
             }

@@ -25,6 +25,17 @@ __device__ __forceinline__ float chain_actbwd_factor(const EpiCtx& c, int grow, 
 
 // ---- VAE (vae.py:115-118): z = mu + eps * exp(logvar / 2); eps injected, or draw_gauss on the stream the op names
 __device__ __forceinline__ float reparam_cell(float mu, float logvar, float eps) { return mu + eps * expf(0.5f * logvar); }
+// its backward with the KL term's gradient (vae.py:132-145), one cell of [dL/dmu | dL/dlogvar]: gz = dL/dz of the cell's code
+// column, scale = the step's gradient scale on the KL sum.  mu_half: the cell is dL/dmu - it also adds the column's KL term
+// to kl; else it is dL/dlogvar (eps: the forward's draw, read by this half alone).
+__device__ __forceinline__ float reparam_bwd_cell(bool mu_half, float gz, float mu, float lv, float eps, float scale, float& kl) {
+    const float ev = expf(lv);
+    if (mu_half) {
+        kl += -0.5f * (1.f + lv - mu * mu - ev);
+        return gz + scale * mu;
+    }
+    return gz * eps * 0.5f * expf(0.5f * lv) + scale * 0.5f * (ev - 1.f);
+}
 
 // ---- encoder output activation (PRIOR_ACTIVATIONS, aae.py:97-101), one wave per row of n <= 256 columns: a lane holds
 // columns lane + 64 j, j < 4 (cells at columns >= n: any finite value, left as they are by kind 1).

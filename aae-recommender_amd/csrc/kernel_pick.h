@@ -146,6 +146,10 @@ template <class F> void each_chain4(F&& f) { for (int i = 0; i < 8; ++i) if (Cha
 template <class F> void each_chain4_vae(F&& f) { f(pick_chain4(false, false, false, true)); }      // (a VAE handle's rank programs)
 template <class F> void each_chain16x3(F&& f) { for (int i = 0; i < 4; ++i) if (ChainKernel k = pick_chain16x3(i & 1, i & 2)) f(k); }
 
+// ---- vae_layers.h: the reparametrisation of a VAE handle on the per-layer route, forward and backward.  Static LDS: no limit to raise
+inline auto pick_vae_reparam_fwd() { return vae_reparam_fwd_kernel; }
+inline auto pick_vae_reparam_bwd() { return vae_reparam_bwd_kernel; }
+
 // ---- gemm_f32.h for lowrank.h: the reconstruction scores = hidden . Vt^T on the fp32 matrix pipe - both operands k-contiguous
 // (AT = 0, BT = 1), the streaming tile (16-deep slabs, 64 x 64), a plain store.  Static LDS: no limit to raise
 using LowRankGemmKernel = void (*)(GemmShape, EpiStore);

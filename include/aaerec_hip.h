@@ -103,7 +103,9 @@ typedef struct aae_config {
     int32_t blocked_output;   /* 1: batches beyond 112 rows run the fused output layer over row blocks */
     int32_t dense_noise;      /* 1: room for aae_set_input_noise (DenoisingAutoEncoder corrupt='gauss'; needs
                                * model_kind = AAE_MODEL_AE, fp32, fused optimiser) */
-    int32_t reserved[2];      /* must be zero */
+    int32_t vae_wide;         /* 1 (model_kind = AAE_MODEL_VAE alone): the VAE's wide bounds - n_hidden <= 1024, n_code <= 512 -
+                               * with the per-layer route beyond a chain slot (see aae_vae_step); 0: n_hidden <= 207, 2 * n_code <= 208 */
+    int32_t reserved[1];      /* must be zero */
 } aae_config;
 
 typedef struct aae_model* aae_handle;
@@ -272,6 +274,12 @@ int aae_decoder_step(aae_handle h, const aae_batch* batch, const float* zin_dev,
  * Sizes (aae_arena_bytes / aae_create answer AAE_EINVAL beyond them): n_hidden <= 207, 2 * n_code <= 208 and
  * n_code + cond_inc + 1 <= 1040 - the decoder input [z | condition | 1] runs through fc3 in up to five parts of 208 columns,
  * which holds the reference drivers' conditions (50 + 332 + 1 and, mpd.py, 50 + 932 + 1 columns).
+ * cfg.vae_wide = 1 lifts the first two: n_hidden <= 1024, n_code <= 512 (the reference's own grid, vae.py main(): (300, 100)).
+ * Such a handle whose sizes fit a chain slot (n_hidden <= 207, 2 * n_code <= 208) is the handle cfg.vae_wide = 0 creates, bit
+ * for bit; any other - or any under the NO_CHAIN option - runs its hidden half one launch per layer: every
+ * aae_vae_* call works, the ranking and loss calls in their dense form (the *_max_rows calls answer max_batch), and the KL sum is
+ * added in a fixed order (the same inputs give the same losses[1] bits).  Every AAE_ACT_* class runs there (none has parameters
+ * of its own to train); fp32 only, as every VAE handle.
  *   cond_dev constant concatenated condition block [rows][cond_inc] or NULL
  *   eps_dev   [rows][n_code] standard-normal draws of reparametrize() (vae.py:115-118); NULL = counter generator
  *             (required when cfg.rng_mode == AAE_RNG_INJECT).  The reference samples eps in predict as well. */
@@ -1062,6 +1070,8 @@ enum { AAE_K_ENC_GATHER = 0,   /* sparse row gather of the first encoder layer *
        AAE_K_UNIQ_ITEMS,       /* uniq_items_kernel as a launch of its own: a batch's distinct-item list (a list built by workgroups of
                                 * a layer-chain launch is no launch and is not counted) */
        AAE_K_W1_CATCHUP,       /* w1_catchup_kernel as a launch of its own: the deferred first-layer Adam replayed on listed (or all) rows */
+       AAE_K_VAE_REPARAM,      /* vae_reparam_fwd_kernel / vae_reparam_bwd_kernel: the reparametrisation of a VAE handle on the per-layer
+                                * route (cfg.vae_wide; a layer-chain program carries it as an op and is counted as AAE_K_CHAIN) */
        AAE_K_N };
 /* on = 0: off; 1: every kernel id above; otherwise a selection: bit (k + 1) of `on` times kernel id k
  * (an event pair costs a few microseconds of stream time, so a timed run selects only what it reports) */

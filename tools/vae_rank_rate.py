@@ -17,6 +17,11 @@
    timed runs of --steps steps behind --warmup steps, the rank call's ms per call of --batch rows beside it.  A decoder
    input n_code + cond_inc + 1 beyond 208 columns runs fc3 in k-parts of 208 (csrc/abi_chains.h): 0 and 150 are one slot,
    332 two parts (the reference's main.py), 932 five (mpd.py).
+5. (--hidden a,b,.. --code x,y,..: this part alone) aae_vae_step by the width of the hidden layer and of the code, one handle
+   per (hidden, code) pair, cfg.vae_wide on: a pair beyond a chain slot (hidden > 207 or 2 code > 208) runs the per-layer route
+   (csrc/abi_output_layer.h vae_*_layers), a narrow one the chain programs - unless its entry of --layer-route (0 / 1 per pair)
+   forces the per-layer route (option NO_CHAIN), which makes a narrow pair the A/B of the two routes.  All handles are built
+   first and take turns inside every repeat; ms/step as in part 4, and aae_vae_predict_topk(k = 10) in rows/s beside it.
 VR_PARTS=1,2,3 selects the parts."""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +29,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aae-recommender
 import numpy as np
 import scipy.sparse as sp
 import torch
+from aaerec import _hip
 from aaerec._hip import DeviceCSR, HipAAE, K_CHAIN
 from aaerec.evaluation import Evaluation, argtopk, remove_non_missing
 from aaerec.vae import VAERecommender
@@ -33,12 +39,15 @@ N, h, c, B = int(os.environ.get("VR_ITEMS", 100000)), int(os.environ.get("VR_HID
 DOCS, REPS = int(os.environ.get("VR_DOCS", 10000)), int(os.environ.get("VR_REPEATS", 3))
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--cond-inc", default="", help="comma-separated condition widths: time aae_vae_step at each (part 4 alone)")
+_ap.add_argument("--hidden", default="", help="comma-separated hidden widths: time aae_vae_step at each (hidden, code) pair (part 5 alone)")
+_ap.add_argument("--code", default="", help="comma-separated code widths, one per --hidden entry")
+_ap.add_argument("--layer-route", default="", help="comma-separated 0 / 1 per pair: 1 forces the per-layer route at a narrow size")
 _ap.add_argument("--batch", type=int, default=1000)
 _ap.add_argument("--steps", type=int, default=50)
 _ap.add_argument("--warmup", type=int, default=20)
 _ap.add_argument("--repeats", type=int, default=7)
 ARGS = _ap.parse_args()
-PARTS = [4] if ARGS.cond_inc else [int(x) for x in os.environ.get("VR_PARTS", "1,2,3").split(",")]
+PARTS = [5] if ARGS.hidden else [4] if ARGS.cond_inc else [int(x) for x in os.environ.get("VR_PARTS", "1,2,3").split(",")]
 med = lambda t: sorted(t)[len(t) // 2]                                                                  # noqa: E731
 
 
@@ -175,3 +184,39 @@ if 4 in PARTS:
               f"{ARGS.repeats} runs of {ARGS.steps}) | aae_vae_predict_topk(k=10), {rows} rows: median {med(t_rank):.3f} ms "
               f"(min {min(t_rank):.3f}, max {max(t_rank):.3f}); vae_rank_max_rows(10) = {dev.vae_rank_max_rows(10)}", flush=True)
         dev.close()
+
+if 5 in PARTS:
+    Bt = ARGS.batch
+    hs, cs = [int(x) for x in ARGS.hidden.split(",")], [int(x) for x in ARGS.code.split(",")]
+    forced = [int(x) for x in ARGS.layer_route.split(",")] if ARGS.layer_route else [0] * len(hs)
+    assert len(hs) == len(cs) == len(forced), "--hidden, --code and --layer-route name one entry per pair"
+    Xt = throughput_corpus(Bt * 8, N, seed=77)
+    runs = []
+    for hh, cc, f in zip(hs, cs, forced):
+        if f:
+            _hip.set_option("NO_CHAIN", "1")
+        try:
+            dev = HipAAE(N, hh, cc, max_batch=Bt, rng_mode="device", seed=1, dropout=(0.0, 0.0), vae=True, vae_wide=True)
+        finally:
+            _hip.set_option("NO_CHAIN", None)
+        tcsr = DeviceCSR(Xt, dev.device)
+        it = [0]
+
+        def one_step(dev=dev, tcsr=tcsr, it=it):
+            dev.vae_step(tcsr, (it[0] % 8) * Bt, Bt)
+            it[0] += 1
+        rows = min(Bt, dev.vae_rank_max_rows(10))
+        rank = lambda dev=dev, tcsr=tcsr, rows=rows: dev.vae_predict_topk(tcsr, 0, rows, 10)      # noqa: E731
+        region(one_step, ARGS.warmup)
+        region(rank, 3)
+        layer = bool(f) or hh > 207 or 2 * cc > 208
+        runs.append(dict(h=hh, c=cc, layer=layer, step=one_step, rank=rank, rows=rows, t_step=[], t_rank=[]))
+    for _ in range(ARGS.repeats):
+        for q in runs:
+            q["t_step"].append(region(q["step"], ARGS.steps))
+            q["t_rank"].append(region(q["rank"], 10))
+    for q in runs:
+        print(f"hidden {q['h']:4d} code {q['c']:3d} on the {'per-layer' if q['layer'] else 'chain'} route, {N} items, batch {Bt}: aae_vae_step median "
+              f"{med(q['t_step']):.4f} ms/step (min {min(q['t_step']):.4f}, max {max(q['t_step']):.4f}, {ARGS.repeats} runs of {ARGS.steps}) | "
+              f"aae_vae_predict_topk(k=10), {q['rows']} rows: median {med(q['t_rank']):.3f} ms = {q['rows'] / med(q['t_rank']) * 1e3:.0f} rows/s "
+              f"(min {min(q['t_rank']):.3f}, max {max(q['t_rank']):.3f})", flush=True)
