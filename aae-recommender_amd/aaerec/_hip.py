@@ -113,6 +113,11 @@ class AaeCooc(C.Structure):
     _fields_ = [("indptr_dev", C.c_void_p), ("indices_dev", C.c_void_p), ("values_dev", C.c_void_p), ("n_rows", C.c_int32)]
 
 
+class AaeCondSrc(C.Structure):
+    """aae_cond_src: one resident constant condition block of an aae_cond_gather call."""
+    _fields_ = [("base_dev", C.c_void_p), ("ld", C.c_int64), ("n_docs", C.c_int64), ("width", C.c_int32), ("col0", C.c_int32)]
+
+
 class AaePopular(C.Structure):
     _fields_ = [("counts_dev", C.c_void_p), ("order_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("n_items", C.c_int32)]
 
@@ -242,6 +247,8 @@ _PROTOS = {
                                      C.c_void_p]),
     "aae_csr_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "aae_cond_gather": (C.c_int, [C.POINTER(AaeCondSrc), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                  C.c_void_p]),
     "aae_cooc_scores": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_void_p, C.c_int64, C.c_void_p]),
     "aae_cooc_topk": (C.c_int, [C.POINTER(AaeCooc), C.c_int32, C.POINTER(AaeBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -662,14 +669,126 @@ def bag_csr_renorm(table, view, max_norm, norm_type=2.0):
                view.row_ids, view.row0, view.rows, b.entry_bound(view.rows), max_norm, code, scratch, nbytes)
 
 
-def csr_embed(csr, table):
+# ---- constant condition blocks resident in HBM (aae_cond_gather; csrc/cond_gather.h) -----------------------------------
+COND_SRC_MAX = 8                 # AAE_COND_SRC_MAX: blocks of one aae_cond_gather call
+
+
+class DeviceBlock:
+    """The dense counterpart of DeviceBags: the [n_docs, width] float32 matrix of a constant condition (the document vectors
+    of a PretrainedWordEmbeddingCondition) resident in HBM - uploaded once, or wrapped around a CUDA tensor without a copy.
+    window() names the rows of a step; cond_gather copies the windows of up to COND_SRC_MAX blocks into a condition block."""
+
+    def __init__(self, data, device=None):
+        if torch.is_tensor(data) and data.is_cuda:
+            if data.dtype != torch.float32 or data.dim() != 2 or (data.shape[1] > 1 and data.stride(1) != 1) or data.stride(0) < data.shape[1]:
+                raise TypeError("aaerec: a resident condition block is a float32 [n_docs, width] tensor with unit column stride")
+            self.data = data
+        else:
+            if np.ndim(data) != 2:
+                raise TypeError("aaerec: a resident condition block is a [n_docs, width] matrix")
+            if device is None:
+                raise ValueError("aaerec: DeviceBlock of host data needs the device to upload it to")
+            self.data = upload(data, device, torch.float32)
+        if self.data.shape[1] < 1:
+            raise ValueError("aaerec: a resident condition block has at least one column")
+        self.device = self.data.device
+        self.n_docs, self.width = int(self.data.shape[0]), int(self.data.shape[1])
+
+    def __len__(self):
+        return self.n_docs
+
+    def window(self, row_ids=None, row0=0, rows=None):
+        """The rows of a step, named as DeviceBags.window names them: a device int32 tensor of row ids (a window of the
+        epoch's permutation), or the contiguous rows row0 .. row0 + rows."""
+        return BlockWindow(self, row_ids, int(row0), int(row_ids.numel() if row_ids is not None else rows))
+
+
+class BlockWindow:
+    """(DeviceBlock, rows of a step): what cond_gather takes."""
+    __slots__ = ("block", "row_ids", "row0", "rows")
+
+    def __init__(self, block, row_ids, row0, rows):
+        if row_ids is not None and (row_ids.dtype != torch.int32 or row_ids.dim() != 1 or not row_ids.is_contiguous()
+                                    or row_ids.device != block.device):
+            raise TypeError("aaerec: row_ids must be a contiguous int32 vector on the block's device")
+        self.block, self.row_ids, self.row0, self.rows = block, row_ids, row0, rows
+
+    def __len__(self):
+        return self.rows
+
+
+def _cond_col0s(widths, col0s):
+    if col0s is None:
+        return [int(c) for c in np.cumsum([0] + list(widths[:-1]))]
+    if len(col0s) != len(widths):
+        raise ValueError("aaerec: cond_gather takes one col0 per window")
+    return [int(c) for c in col0s]
+
+
+def cond_gather(windows, out=None, col0s=None):
+    """The rows the windows name - BlockWindows of up to COND_SRC_MAX DeviceBlocks, all naming the SAME rows - copied into
+    `out` [rows, >= the columns named] at the column offsets col0s (None: one block behind the other from column 0), in one
+    launch (aae_cond_gather).  out None: a new [rows, sum of the widths] tensor.  Columns no window names keep their content;
+    a row id outside a block gives a row of zeros.  Returns out."""
+    windows = list(windows)
+    if not 1 <= len(windows) <= COND_SRC_MAX:
+        raise ValueError("aaerec: cond_gather takes 1 to %d windows" % COND_SRC_MAX)
+    w0 = windows[0]
+    for w in windows[1:]:
+        if w.rows != w0.rows or w.row0 != w0.row0 or (w.row_ids is None) != (w0.row_ids is None) or \
+                (w.row_ids is not None and w.row_ids.data_ptr() != w0.row_ids.data_ptr()) or w.block.device != w0.block.device:
+            raise ValueError("aaerec: the windows of one cond_gather name the same rows on one device")
+    col0s = _cond_col0s([w.block.width for w in windows], col0s)
+    dev = w0.block.device
+    if out is None:
+        out = torch.empty(w0.rows, max(c + w.block.width for c, w in zip(col0s, windows)), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.device != dev or out.shape[0] != w0.rows or \
+            (out.shape[1] > 1 and out.stride(1) != 1):
+        raise TypeError("aaerec: out must be a float32 [rows, columns] view with unit column stride on the blocks' device")
+    if any(c < 0 or c + w.block.width > out.shape[1] for c, w in zip(col0s, windows)):
+        raise ValueError("aaerec: a window's columns lie outside out")
+    srcs = (AaeCondSrc * len(windows))(*(AaeCondSrc(w.block.data.data_ptr(), w.block.data.stride(0), w.block.n_docs,
+                                                    w.block.width, c) for c, w in zip(col0s, windows)))
+    with torch.cuda.device(dev):
+        _check(load_library().aae_cond_gather(srcs, len(windows), _ptr(w0.row_ids), w0.row0, w0.rows, _ptr(out),
+                                              out.stride(0) if w0.rows > 1 else max(out.stride(0), out.shape[1]), _stream_of(dev)))
+    return out
+
+
+def cond_gather_host(tables, row_ids=None, row0=0, rows=None, out=None, col0s=None):
+    """cond_gather restated in NumPy (the tests' oracle): tables are float32 [n_docs, width] arrays (any row stride), row_ids
+    an integer vector or None for row0 .. row0 + rows, out a float32 [rows, columns] array (None: a new one of zeros, as wide
+    as the columns named).  Words move as uint32, so every bit arrives."""
+    tables = [np.asarray(t) for t in tables]
+    if any(t.dtype != np.float32 or t.ndim != 2 for t in tables):
+        raise TypeError("aaerec: cond_gather_host takes float32 [n_docs, width] arrays")
+    ids = np.arange(row0, row0 + rows, dtype=np.int64) if row_ids is None else np.asarray(row_ids, dtype=np.int64).reshape(-1)
+    col0s = _cond_col0s([t.shape[1] for t in tables], col0s)
+    if out is None:
+        out = np.zeros((len(ids), max(c + t.shape[1] for c, t in zip(col0s, tables))), dtype=np.float32)
+    bits = out.view(np.uint32)
+    for c, t in zip(col0s, tables):
+        live = (ids >= 0) & (ids < t.shape[0])
+        part = np.zeros((len(ids), t.shape[1]), dtype=np.uint32)
+        if live.any():
+            part[live] = np.ascontiguousarray(t[ids[live]]).view(np.uint32)
+        bits[:, c:c + t.shape[1]] = part
+    return out
+
+
+def csr_embed(csr, table, out=None):
     """[rows, dim] device tensor: row r = sum of csr.values[e] * table[csr.indices[e]] over the entries of row r
-    (EmbeddedVectorizer.transform's `sparse_scores @ embedding`, reference ub.py:52-57)."""
+    (EmbeddedVectorizer.transform's `sparse_scores @ embedding`, reference ub.py:52-57).  out: a float32 [rows, dim] view
+    with unit column stride on the table's device to write into (rows of a larger matrix); None: a new tensor."""
     if not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2 or table.stride(1) != 1:
         raise TypeError("aaerec: table must be a float32 [vocab, dim] GPU tensor with unit column stride")
     if csr.shape[1] > table.shape[0]:
         raise ValueError("aaerec: the sparse matrix has more columns than the table has rows")
-    out = torch.empty(csr.shape[0], table.shape[1], dtype=torch.float32, device=table.device)
+    if out is None:
+        out = torch.empty(csr.shape[0], table.shape[1], dtype=torch.float32, device=table.device)
+    elif out.dtype != torch.float32 or out.device != table.device or tuple(out.shape) != (csr.shape[0], table.shape[1]) \
+            or (out.shape[1] > 1 and out.stride(1) != 1) or (out.shape[0] > 1 and out.stride(0) < out.shape[1]):
+        raise TypeError("aaerec: out must be a float32 [rows, dim] view with unit column stride on the table's device")
     with torch.cuda.device(table.device):
         _check(load_library().aae_csr_embed(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.values), csr.shape[0],
                                             _ptr(table), table.shape[0], table.shape[1], table.stride(0), _ptr(out),

@@ -97,9 +97,10 @@ class _OptimView:
 
 class AdversarialAutoEncoder:
     """ Adversarial Autoencoder """
-    # True: device-native trainable conditions read their data from HBM, uploaded once per fit / ranking call
-    # (resident_condition_data below: same bits as the padded per-step route).  Opt-in: with lists of a few values the
-    # two extra launches cost 0.01 ms a step, with long-tailed lists the step is twice as fast (DESIGN 4.1d)
+    # True: the conditions of a device-native list read their data from HBM, uploaded once per fit / ranking call
+    # (resident_condition_data below: same bits as the per-step route) - a trainable table its value lists, a constant block
+    # its document vectors, gathered into the step's condition block by one launch (DESIGN 3.7c, 4.1h).  Opt-in: with lists
+    # of a few values the two extra launches cost 0.01 ms a step, with long-tailed lists the step is twice as fast (DESIGN 4.1d)
     resident_conditions = False
 
     def __init__(self, n_hidden=100, n_code=50, gen_lr=0.001, reg_lr=0.001, prior="gauss", prior_scale=None,
@@ -318,30 +319,12 @@ class AdversarialAutoEncoder:
         """[n_rows, size_increment] block of the encoded conditions, in ConditionList order (encode_impose's
         concatenation order, condition.py:90-99).  whole_batch: the condition inputs of the global batch this is a
         share of (data parallel) - value lists are padded to ITS width, as the single process would."""
-        dev = self.hip.device
-        block = torch.empty(n_rows, self.hip.cond_inc, dtype=torch.float32, device=dev)
-        off = 0
-        for j, (cond, x) in enumerate(zip(self.conditions.values(), c_batch)):
-            w = cond.size_increment()
-            if getattr(cond, "constant_concat", False):
-                block[:, off:off + w] = _hip.upload(cond.encode(x), dev)
-            else:
-                cond.encode_into(block[:, off:off + w], x,
-                                 width=None if whole_batch is None else cond.padded_width(whole_batch[j]))
-            off += w
-        return block
+        return native_cond_block(self.conditions, c_batch, n_rows, self.hip.cond_inc, self.hip.device, whole_batch)
 
     def _native_cond_update(self, n_rows, dblock=None, whole_batch=None):
         """conditions.zero_grad / backward / step (aae.py:699-709) from the step's dL/d(condition block); data
         parallel: from the gathered gradient of the whole batch and its inputs, identically on every rank."""
-        if dblock is None:
-            dblock = self.hip.cond_grad(n_rows)
-        off = 0
-        for j, cond in enumerate(self.conditions.values()):
-            w = cond.size_increment()
-            if not getattr(cond, "constant_concat", False):
-                cond.update_from(dblock[:, off:off + w], None if whole_batch is None else whole_batch[j])
-            off += w
+        native_cond_update(self.conditions, self.hip.cond_grad(n_rows) if dblock is None else dblock, whole_batch)
 
     def _run_step(self, csr, row_start, n_rows, rows, c_batch):
         """One partial_fit on rows of a device-resident CSR."""
@@ -374,6 +357,10 @@ class AdversarialAutoEncoder:
                           cond_fn=cond_fn, masks=masks, z_real=z_real)
         elif not use_condition:
             hip.step(csr, row_start, n_rows, rows=rows, masks=masks, z_real=z_real)
+        elif self._is_constant_concat() and any_resident_block(c_batch):
+            # resident constant blocks (resident_conditions): the batch's rows by one gather launch, nothing from the host
+            hip.step(csr, row_start, n_rows, rows=rows, cond=self._native_cond_block(c_batch, n_rows), masks=masks,
+                     z_real=z_real)
         elif self._is_constant_concat():
             blocks = [_hip.upload(c.encode(x), hip.device) for c, x in zip(self.conditions.values(), c_batch)]
             # (one block: as it is - torch.cat of a single tensor is a copy launch of its own, every step)
@@ -584,7 +571,7 @@ class AdversarialAutoEncoder:
             self._dp.gather_output_layer()              # (a no-op after fit(); collective otherwise)
         fused = (not use_condition) or self._is_constant_concat()
         native = use_condition and not fused and self._is_device_native()
-        if native:
+        if use_condition and (fused or native):
             condition_data = resident_condition_data(self, condition_data)
         pred = _hip.HostRows(Xs.shape[0], Xs.shape[1], self.hip.device)
         with torch.no_grad():
@@ -597,7 +584,9 @@ class AdversarialAutoEncoder:
                     dcsr, dstart = csr, start
                 if fused:
                     cond = None
-                    if use_condition:
+                    if use_condition and any_resident_block(c_batch):
+                        cond = self._native_cond_block(c_batch, n)
+                    elif use_condition:
                         cond = torch.cat([_hip.upload(c.encode(x), self.hip.device)
                                           for c, x in zip(self.conditions.values(), c_batch)], 1)
                     out = self.hip.predict(dcsr, dstart, n, cond=cond)
@@ -648,7 +637,7 @@ def _rank_chunks(self, Xs, condition_data, chunk, fused, decode):
     concat = (not use_condition) or self._is_constant_concat()
     native = use_condition and not concat and self._is_device_native()
     csr = _hip.DeviceCSR(Xs, self.hip.device)
-    if native:
+    if use_condition and (concat or native):
         condition_data = resident_condition_data(self, condition_data)
     self._dp_settle()
     if self._slice is not None:
@@ -657,7 +646,9 @@ def _rank_chunks(self, Xs, condition_data, chunk, fused, decode):
     for start, n in ranking.row_chunks(Xs.shape[0], chunk):
         cond = None
         c_batch = [_take(c, slice(start, start + n)) for c in condition_data] if use_condition else None
-        if use_condition and concat:
+        if use_condition and concat and any_resident_block(c_batch):
+            cond = self._native_cond_block(c_batch, n)
+        elif use_condition and concat:
             cond = torch.cat([_hip.upload(c.encode(x), self.hip.device) for c, x in zip(self.conditions.values(), c_batch)], 1)
         elif native:
             cond = self._native_cond_block(c_batch, n)
@@ -747,11 +738,12 @@ AdversarialAutoEncoder.eval_loss = _eval_loss
 
 
 def resident_condition_data(model, condition_data):
-    """condition_data with the data of every device-native trainable condition made resident in HBM (the condition's
-    resident(): a _hip.DeviceBags of its value lists, or the int32 column of a one-value condition), once per fit / per
-    ranking call - _take then hands every step or chunk a window of it, and nothing of the condition crosses the host again.
-    On with model.resident_conditions = True, never under data parallelism (the padded route); nn.EmbeddingBag's
-    (input, offsets) call form has no padded form, so it is made resident either way."""
+    """condition_data with the data of every condition of a device-native list made resident in HBM (the condition's
+    resident(): a _hip.DeviceBags of a trainable condition's value lists, the int32 column of a one-value condition, a
+    _hip.DeviceBlock of a constant block's document vectors), once per fit / per ranking call - _take then hands every step
+    or chunk a window of it, and nothing of the condition crosses the host again.  A condition without a resident() stays
+    as it is.  On with model.resident_conditions = True, never under data parallelism (the per-step route);
+    nn.EmbeddingBag's (input, offsets) call form has no padded form, so it is made resident either way."""
     if not condition_data or not model.conditions or not model._is_device_native():
         return condition_data
     out = []
@@ -760,18 +752,68 @@ def resident_condition_data(model, condition_data):
         res = None
         if offsets_form and getattr(model, "_dp", None) is not None:
             raise NotImplementedError("(input, offsets) condition data is not available under data parallelism")
-        if hasattr(cond, "resident") and not getattr(cond, "constant_concat", False) \
+        if hasattr(cond, "resident") \
                 and (offsets_form or (model.resident_conditions and getattr(model, "_dp", None) is None)):
             res = cond.resident(c, model.hip.device)
         out.append(c if res is None else res)
     return out
 
 
+def any_resident_block(c_batch):
+    """A batch's condition inputs hold a window of a resident constant block."""
+    return any(isinstance(x, _hip.BlockWindow) for x in c_batch)
+
+
+def gather_resident_blocks(conditions, c_batch, block):
+    """The rows of every resident constant block of a batch (_hip.BlockWindow entries of c_batch) into `block` at the
+    conditions' column offsets, ConditionList order: one launch for up to _hip.COND_SRC_MAX of them - no upload, no cat, no
+    slice assignment."""
+    windows, col0s, off = [], [], 0
+    for cond, x in zip(conditions.values(), c_batch):
+        if isinstance(x, _hip.BlockWindow):
+            windows.append(x)
+            col0s.append(off)
+        off += cond.size_increment()
+    for i in range(0, len(windows), _hip.COND_SRC_MAX):
+        _hip.cond_gather(windows[i:i + _hip.COND_SRC_MAX], out=block, col0s=col0s[i:i + _hip.COND_SRC_MAX])
+
+
+def native_cond_block(conditions, c_batch, n_rows, width, device, whole_batch=None):
+    """[n_rows, width] block of the encoded conditions of a device-native list, one behind the other in ConditionList order:
+    resident constant blocks by one gather launch, a host-fed constant block uploaded, a trainable table through its
+    encode_into.  whole_batch: see AdversarialAutoEncoder._native_cond_block."""
+    block = torch.empty(n_rows, width, dtype=torch.float32, device=device)
+    gather_resident_blocks(conditions, c_batch, block)
+    off = 0
+    for j, (cond, x) in enumerate(zip(conditions.values(), c_batch)):
+        w = cond.size_increment()
+        if isinstance(x, _hip.BlockWindow):
+            pass                                        # (a resident constant block: the gather above wrote its columns)
+        elif getattr(cond, "constant_concat", False):
+            block[:, off:off + w] = _hip.upload(cond.encode(x), device)
+        else:
+            cond.encode_into(block[:, off:off + w], x,
+                             width=None if whole_batch is None else cond.padded_width(whole_batch[j]))
+        off += w
+    return block
+
+
+def native_cond_update(conditions, dblock, whole_batch=None):
+    """Every trainable table's update_from with its columns of dL/d(condition block), ConditionList order."""
+    off = 0
+    for j, cond in enumerate(conditions.values()):
+        w = cond.size_increment()
+        if not getattr(cond, "constant_concat", False):
+            cond.update_from(dblock[:, off:off + w], None if whole_batch is None else whole_batch[j])
+        off += w
+
+
 def _take(c, idx, rows_dev=None):
-    """Row selection on whatever a condition's transform produced (ndarray, sparse, list, tensor, resident bags).  rows_dev:
-    the same selection as a device tensor - condition data that already lives in HBM is then selected there (indexing a
-    device tensor with a host array is a blocking copy on the compute stream: host and GPU in lock-step, every step)."""
-    if isinstance(c, _hip.DeviceBags):
+    """Row selection on whatever a condition's transform produced (ndarray, sparse, list, tensor, resident bags or block).
+    rows_dev: the same selection as a device tensor - condition data that already lives in HBM is then selected there
+    (indexing a device tensor with a host array is a blocking copy on the compute stream: host and GPU in lock-step, every
+    step)."""
+    if isinstance(c, (_hip.DeviceBags, _hip.DeviceBlock)):
         if rows_dev is not None:
             return c.window(rows_dev)
         if isinstance(idx, slice):
@@ -792,8 +834,13 @@ def _take(c, idx, rows_dev=None):
 class DecodingRecommender(Recommender):
     """ Only the decoder part of the AAE, basically 2-MLP (reference aae.py:461-584): the encoded conditions
     (the first one as is, the others imposed on it) -> Decoder -> BCE against the item rows.  The decoder runs
-    on the HIP kernels (aae_decoder_step / aae_decode); the condition plugins stay torch modules and receive
-    dL/d(inputs) through autograd, then take their own optimiser step. """
+    on the HIP kernels (aae_decoder_step / aae_decode); by default the condition plugins stay torch modules and receive
+    dL/d(inputs) through autograd, then take their own optimiser step (resident_conditions below: the kernels' route). """
+    # True, with a list of device-native conditions (condition.device_native_conditions): the decoder input is built by the
+    # kernels - resident constant blocks by one gather launch, trainable tables by their encode_into - and a trainable table
+    # gets its columns of dL/d(inputs) through update_from, the AAE's route; fit() and the ranking calls upload the condition
+    # data once.  False (the default), or any other condition in the list: the torch route below
+    resident_conditions = False
 
     def __init__(self, conditions, n_epochs=100, batch_size=100, optimizer='adam', n_hidden=100, lr=0.001,
                  verbose=True, device=None, rng_mode="device", seed=None, **mlp_params):
@@ -853,9 +900,23 @@ class DecodingRecommender(Recommender):
     def _dp_settle(self):
         return None      # single device: nothing travels
 
-    def _inputs(self, condition_data):
+    def _is_device_native(self):
+        dev = self.hip.device if self.hip is not None else \
+            torch.device(self.device if self.device is not None else "cuda:{}".format(torch.cuda.current_device()))
+        return device_native_conditions(self.conditions, dev)
+
+    def _native_route(self):
+        """The kernels build the decoder input and train the tables: the opt-in, over a device-native list."""
+        return bool(self.resident_conditions) and self._is_device_native()
+
+    def _inputs(self, condition_data, native=None):
         """ Encode ALL condition data with the respective condition, start with the first encoded condition
         and impose all remaining ones (aae.py:494-502, 570-576) """
+        if self._native_route() if native is None else native:
+            # concatenating conditions one behind the other: the block the torch route below produces, in ConditionList order
+            x = condition_data[0]
+            return native_cond_block(self.conditions, condition_data, x.shape[0] if hasattr(x, "shape") else len(x),
+                                     self.hip.c, self.hip.device)
         encoded = self.conditions.encode(condition_data)
         inputs = encoded[0]
         for cond, cdata in zip(list(self.conditions.values())[1:], encoded[1:]):
@@ -870,8 +931,15 @@ class DecodingRecommender(Recommender):
 
     def _step(self, csr, n_rows, rows, condition_data):
         self.conditions.train()
-        inputs = self._inputs(condition_data)
+        native = self._native_route()
+        inputs = self._inputs(condition_data, native)
         masks = self._masks(n_rows)
+        if native:
+            trainable = not all(getattr(c, "constant_concat", False) for c in self.conditions.values())
+            dz = self.hip.decoder_step(csr, 0, n_rows, inputs, rows=rows, masks=masks, want_grad=trainable)
+            if trainable:
+                native_cond_update(self.conditions, dz)        # zero_grad / backward / step of every table, in the kernels
+            return
         dz = self.hip.decoder_step(csr, 0, n_rows, inputs, rows=rows, masks=masks, want_grad=inputs.requires_grad)
         self.conditions.zero_grad()
         if inputs.requires_grad:
@@ -899,6 +967,9 @@ class DecodingRecommender(Recommender):
         row_nnz = Y.getnnz(1)
         self._build(Y.shape[1], max_row_nnz=max(int(row_nnz.max()) if Y.shape[0] else 1, 4096))
         csr = _hip.DeviceCSR(Y, self.hip.device)       # the targets stay resident in HBM
+        native = self._native_route()
+        if native:                                      # ... and so does the condition data: a step takes windows of perm_dev
+            condition_data = resident_condition_data(self, condition_data)
         n_docs = Y.shape[0]
         step = 0
         for __epoch in range(self.n_epochs):
@@ -908,8 +979,9 @@ class DecodingRecommender(Recommender):
             perm_dev = torch.as_tensor(perm.astype(np.int32), device=self.hip.device)
             for start in range(0, n_docs, self.batch_size):
                 idx = perm[start:start + self.batch_size]
-                c_batch = [_take(c, idx) for c in condition_data]
-                self._step(csr, len(idx), perm_dev[start:start + len(idx)], c_batch)
+                rows = perm_dev[start:start + len(idx)]
+                c_batch = [_take(c, idx, rows if native else None) for c in condition_data]
+                self._step(csr, len(idx), rows, c_batch)
                 if self.verbose:
                     self.last_loss = self.hip.losses()[0]
                     print("\rLoss: {}".format(self.last_loss), flush=True, end='')
@@ -928,11 +1000,14 @@ class DecodingRecommender(Recommender):
 
     def _predict_conditions(self, condition_data, n_users):
         self.conditions.eval()
+        native = self._native_route()
+        if native:
+            condition_data = resident_condition_data(self, condition_data)
         batch_results = _hip.HostRows(n_users, self.hip.N, self.hip.device)
         with torch.no_grad():
             for start in range(0, n_users, self.batch_size):
                 c_batch = [_take(c, slice(start, start + self.batch_size)) for c in condition_data]
-                batch_results.put(start, self.hip.decode(self._inputs(c_batch)))
+                batch_results.put(start, self.hip.decode(self._inputs(c_batch, native)))
         return batch_results.numpy()
 
     def predict(self, test_set):
@@ -948,11 +1023,14 @@ class DecodingRecommender(Recommender):
         X = test_set.tocsr()
         csr = _hip.DeviceCSR(X, self.hip.device)
         self.conditions.eval()
+        native = self._native_route()
+        if native:
+            condition_data = resident_condition_data(self, condition_data)
         out = []
         with torch.no_grad():
             for start, n in ranking.row_chunks(X.shape[0], chunk):
                 c_batch = [_take(c, slice(start, start + n)) for c in condition_data]
-                out.append(call(self._inputs(c_batch), csr, start))
+                out.append(call(self._inputs(c_batch, native), csr, start))
         return out
 
     def predict_topk(self, test_set, k=10, y_true=None, metrics=None):

@@ -203,10 +203,15 @@ class PretrainedWordEmbeddingCondition(ConcatenationBasedConditioning):
     """Fixed document vectors (TF-IDF weighted mean of pre-trained word vectors) concatenated to
     the code (reference 345-369).  `vectors` is either a gensim-KeyedVectors-like object (needs
     the optional aaerec.ub vectoriser) or any object with fit/transform/fit_transform and an
-    `embedding` array of shape [vocab, dim]."""
+    `embedding` array of shape [vocab, dim].
+
+    keep_on_device: with a vectoriser that has transform_device (aaerec.ub's), transform / fit_transform return the
+    [docs, D] CUDA tensor the product was formed in instead of a host copy of it; resident() then wraps it without an
+    upload.  Off by default: the reference's transform returns a host array."""
     constant_concat = True
 
-    def __init__(self, vectors, dim=1, use_cuda=None, **tfidf_params):
+    def __init__(self, vectors, dim=1, use_cuda=None, keep_on_device=False, **tfidf_params):
+        self.keep_on_device = bool(keep_on_device)
         if all(hasattr(vectors, a) for a in ("fit", "transform", "embedding")):
             self.vect = vectors
         else:
@@ -225,10 +230,32 @@ class PretrainedWordEmbeddingCondition(ConcatenationBasedConditioning):
         return self
 
     def transform(self, raw_inputs):
+        if self.keep_on_device and hasattr(self.vect, "transform_device"):
+            return self.vect.transform_device(raw_inputs)
         return self.vect.transform(raw_inputs)
 
     def fit_transform(self, raw_inputs):
+        if self.keep_on_device and hasattr(self.vect, "transform_device"):
+            return self.fit(raw_inputs).transform(raw_inputs)
         return self.vect.fit_transform(raw_inputs)
+
+    def resident(self, inputs, device):
+        """The document vectors of a whole corpus in HBM as a _hip.DeviceBlock: a host matrix uploaded once (as float32, the
+        cast encode() gives every batch), a CUDA tensor (keep_on_device) wrapped as it is.  A step then names its rows and
+        one gather launch copies them into the condition block.  The gather stands for this class's encode(), a cast to
+        float32: a subclass with an encode() of its own (a normalisation, say) gets None - the per-step route, through its
+        encode() - unless it brings its own resident()."""
+        from . import _hip
+        if type(self).encode is not PretrainedWordEmbeddingCondition.encode:
+            return None
+        if torch.is_tensor(inputs) and inputs.is_cuda and inputs.device == torch.device(device) \
+                and inputs.dtype == torch.float32 and inputs.dim() == 2 and inputs.stride(1) == 1:
+            return _hip.DeviceBlock(inputs)
+        if torch.is_tensor(inputs):
+            return _hip.DeviceBlock(_hip.upload(inputs, device, torch.float32).contiguous())
+        if sp.issparse(inputs) or np.ndim(inputs) != 2:
+            return None                                  # (nothing the gather takes: the per-step route)
+        return _hip.DeviceBlock(inputs, device)
 
     def encode(self, inputs):
         if self.device.type == "cuda":

@@ -56,6 +56,16 @@ class EmbeddedVectorizer:
     def fit_transform(self, raw_documents, y=None):
         return self.fit(raw_documents, y).transform(raw_documents, y)
 
+    def transform_device(self, raw_documents):
+        """transform() without its copy to the host: the [docs, D] float32 CUDA tensor the product was formed in, bit for bit
+        what transform() returns (PretrainedWordEmbeddingCondition(keep_on_device=True) keeps it resident)."""
+        scores = self.tfidf.transform(raw_documents)
+        table = self._device_table()
+        out = torch.empty(scores.shape[0], self.embedding.shape[1], dtype=torch.float32, device=table.device)
+        for _ in self._embed_chunks(scores, table, out):           # (every chunk lands in its rows: the vectors are held once)
+            pass
+        return out
+
     @property
     def vocabulary_(self):
         return self.tfidf.vocabulary_
@@ -65,20 +75,32 @@ class EmbeddedVectorizer:
 
     # -----------------------------------------------------------------------------------------------------
     def _times_embedding(self, scores):
+        table = self._device_table()
+        out = np.empty((scores.shape[0], self.embedding.shape[1]), dtype=np.float32)
+        for start, part in self._embed_chunks(scores, table):
+            out[start:start + part.shape[0]] = part.cpu().numpy()
+        return out
+
+    def _device_table(self):
+        """The embedding matrix on the GPU, uploaded once."""
         if not torch.cuda.is_available():
             raise RuntimeError("EmbeddedVectorizer.transform multiplies on the GPU (libaaerec_hip aae_csr_embed); "
                                "no GPU is visible and there is no CPU path")
         dev = torch.device(self.device if self.device is not None else ("cuda:%d" % torch.cuda.current_device()))
         if self._table is None or self._table.device != dev:
             self._table = torch.from_numpy(self.embedding).to(dev)
+        return self._table
+
+    def _embed_chunks(self, scores, table, out=None):
+        """(first document, [documents, D] device tensor) of the product, `step` documents per launch, one at a time; with
+        `out` ([docs, D] on the device) each chunk is written into its rows of it."""
         scores = sp.csr_matrix(scores, dtype=np.float32)
         scores.sort_indices()                                      # accumulate in column order, as scipy does
-        out = np.empty((scores.shape[0], self.embedding.shape[1]), dtype=np.float32)
         step = 1 << 16                                             # documents per launch
         for start in range(0, scores.shape[0], step):
             part = scores[start:start + step]
-            out[start:start + step] = _hip.csr_embed(_hip.DeviceCSR(part, dev), self._table).cpu().numpy()
-        return out
+            yield start, _hip.csr_embed(_hip.DeviceCSR(part, table.device), table,
+                                        out=None if out is None else out[start:start + part.shape[0]])
 
 
 class GensimEmbeddedVectorizer(EmbeddedVectorizer):

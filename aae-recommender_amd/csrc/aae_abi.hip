@@ -51,6 +51,7 @@
 #include "cond_embed.h"
 #include "cond_bag.h"
 #include "cond_csr.h"
+#include "cond_gather.h"
 #include "w1_update.h"
 #include "dae_corrupt.h"
 

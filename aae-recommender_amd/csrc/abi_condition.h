@@ -1,5 +1,5 @@
 // Entry points of the trainable categorical and embedding-bag conditions and of the CSR helpers (cond_embed.h, cond_bag.h,
-// cond_csr.h, kernels.h).
+// cond_csr.h, kernels.h), and the gather of the constant condition blocks (cond_gather.h).
 // (one of the parts of aae_abi.hip's translation unit: included there in order, not on its own)
 #pragma once
 
@@ -323,6 +323,41 @@ int aae_csr_embed(const int64_t* indptr_dev, const int32_t* indices_dev, const f
     hipLaunchKernelGGL(csr_embed_kernel, dim3(n_rows), dim3(256), 0, S(stream), (const long long*)indptr_dev, indices_dev,
                        values_dev, table_dev, n_table_rows, dim, (long long)table_ld, out_dev, (long long)out_ld);
     LAUNCHCHK("csr_embed");
+    return AAE_OK;
+}
+
+// ---- constant condition blocks resident in HBM (cond_gather.h) ------------------------------------------------
+static_assert(AAE_COND_SRC_MAX == kCondSrcMax, "the kernel's argument block holds the ABI's number of sources");
+
+int aae_cond_gather(const aae_cond_src* srcs, int32_t n_srcs, const int32_t* row_ids_dev, int64_t row0, int32_t rows,
+                    float* out_dev, int64_t out_ld, void* stream) {
+    const char* who = "aae_cond_gather";
+#define COND_FAIL(text) return fail(AAE_EINVAL, std::string(who) + ": " + text)
+    if (!srcs || !out_dev) COND_FAIL("srcs / out_dev is NULL");
+    if (n_srcs < 1 || n_srcs > AAE_COND_SRC_MAX) COND_FAIL("n_srcs must be within [1, AAE_COND_SRC_MAX]");
+    if (rows < 0) COND_FAIL("rows must be >= 0");
+    CondGatherArgs a;
+    memset(&a, 0, sizeof(a));
+    // 16-byte loads and stores where both sides allow them: the output's part of the rule is the call's, the rest a source's
+    const bool out16 = ((uintptr_t)out_dev & 15) == 0 && out_ld % 4 == 0;
+    for (int i = 0; i < n_srcs; ++i) {
+        const aae_cond_src& s = srcs[i];
+        if (!s.base_dev) COND_FAIL("a source's base_dev is NULL");
+        if (s.width < 1) COND_FAIL("a source's width must be >= 1");
+        if (s.ld < s.width) COND_FAIL("a source's ld is smaller than its width");
+        if (s.n_docs < 0) COND_FAIL("a source's n_docs must be >= 0");
+        if (s.col0 < 0) COND_FAIL("a source's col0 must be >= 0");
+        if ((int64_t)s.col0 + s.width > out_ld) COND_FAIL("a source's col0 + width passes out_ld");
+        const bool vec = out16 && ((uintptr_t)s.base_dev & 15) == 0 && s.ld % 4 == 0 && s.col0 % 4 == 0;
+        a.src[i] = {reinterpret_cast<const unsigned*>(s.base_dev), (long long)s.ld, (long long)s.n_docs, s.width, s.col0,
+                    vec ? s.width / 4 : 0, 0};
+    }
+#undef COND_FAIL
+    if (rows == 0) return AAE_OK;
+    a.row_ids = row_ids_dev; a.row0 = row0; a.out = reinterpret_cast<unsigned*>(out_dev); a.out_ld = out_ld; a.rows = rows;
+    hipLaunchKernelGGL(pick_cond_gather(), dim3((unsigned)(((int64_t)rows + kCondGatherWaves - 1) / kCondGatherWaves), (unsigned)n_srcs),
+                       dim3(64, kCondGatherWaves), 0, S(stream), a);
+    LAUNCHCHK("cond_gather");
     return AAE_OK;
 }
 

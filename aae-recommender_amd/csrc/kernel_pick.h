@@ -205,5 +205,9 @@ inline auto pick_vae_kl_rows() { return vae_kl_rows_kernel; }
 using SpmmKernel = void (*)(LowRankView, BatchView, float*, long long);
 inline SpmmKernel pick_lowrank_project() { return lowrank_project_kernel; }
 
+// ---- cond_gather.h: the rows of the resident constant condition blocks.  One kernel - 16-byte or scalar is a per-block value
+// of its argument, not a template flag.  No LDS
+inline auto pick_cond_gather() { return cond_gather_kernel; }
+
 #undef NB_
 }  // namespace

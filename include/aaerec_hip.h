@@ -475,6 +475,25 @@ int aae_bag_csr_update_flags(float* table_dev, float* exp_avg_dev, float* exp_av
 int aae_csr_embed(const int64_t* indptr_dev, const int32_t* indices_dev, const float* values_dev, int32_t n_rows,
                   const float* table_dev, int32_t n_table_rows, int32_t dim, int64_t table_ld, float* out_dev,
                   int64_t out_ld, void* stream);
+/* The constant condition blocks of a batch from matrices RESIDENT in HBM (csrc/cond_gather.h): the document vectors of every
+ * PretrainedWordEmbeddingCondition are uploaded once, a step names its rows, and one launch copies them into the step's
+ * condition block - nothing of a condition crosses the host inside the loop.  Handle-free like aae_csr_embed and
+ * aae_bag_csr_encode: one launch on `stream`, no synchronisation.  For each source s and each row r of the call
+ *     out_dev[r * out_ld + col0_s + j] = base_dev_s[id_r * ld_s + j],   0 <= j < width_s
+ *   id_r = row_ids_dev[r] (int32 [rows] on the device), or row0 + r when row_ids_dev is NULL: aae_bag_csr_encode's row naming,
+ *   so one window of an epoch's permutation serves both.  An id outside [0, n_docs_s) gives a row of zeros (an empty row) and
+ *   reads nothing.  Columns of out_dev no source names are not written.  A copy: bit-exact, NaN payloads and -0.0 included.
+ *   A source goes by 16-byte loads and stores where both sides allow it - base_dev_s and out_dev on 16 bytes, ld_s, col0_s and
+ *   out_ld multiples of 4 -, the columns behind its last full quad one at a time; any other source takes the scalar path.  No
+ *   load touches an address outside a source row's [0, width): with ld == width the last row may end with the allocation.
+ *   Offsets are 64-bit (id * ld passes 2^31 at a few million documents).
+ *   AAE_EINVAL (checked before any HIP call) for n_srcs outside [1, AAE_COND_SRC_MAX], a NULL srcs / out_dev / base_dev,
+ *   width < 1, ld < width, n_docs < 0, col0 < 0, col0 + width > out_ld, rows < 0.  rows == 0: nothing is launched.
+ *   Sources that overlap in out_dev's columns are the caller's mistake: the order of their stores is not defined. */
+#define AAE_COND_SRC_MAX 8
+typedef struct { const float* base_dev; int64_t ld; int64_t n_docs; int32_t width; int32_t col0; } aae_cond_src;
+int aae_cond_gather(const aae_cond_src* srcs, int32_t n_srcs, const int32_t* row_ids_dev, int64_t row0,
+                    int32_t rows, float* out_dev, int64_t out_ld, void* stream);
 /* The reference's call form: partial_fit(X) / predict(X) take the DENSE [rows][n_cols] batch that
  * X_shuf[start:end].toarray() produced (aae.py:745-754, 823, 848-853) and upload it whole.  aae_dense_to_csr compacts
  * such a matrix, already on the device as float32 (elem_bytes = 4) or float64 (8), into the CSR form aae_batch takes:

@@ -14,7 +14,11 @@
                                      max_norm and scale_grad_by_freq behind a CategoricalCondition(reduce="sum", sparse=False)
                                      with either option: partial_fit(), and fit() with the value lists as resident bags - native
                                      against the bridged route
-Everything but `ragged b` (the VAE) runs through AdversarialAutoEncoder."""
+    python tools/cond_rate.py const  fit() in ms/step behind constant 300-column blocks with resident_conditions False against True
+                                     (DESIGN 4.1h): AdversarialAutoEncoder and DecodingRecommender, see const_rates
+    python tools/cond_rate.py const split
+                                     the AAE's MPD cell of that table taken apart (blocks, table, a synchronize per step)
+Everything but `ragged b` (the VAE) and `const`'s DecodingRecommender rows runs through AdversarialAutoEncoder."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aae-recommender_amd"))
@@ -254,8 +258,117 @@ def ragged_rates(cell, route, pass_steps=64, rounds=9, warm=2):
           f"{sum(len(r) for r in lists) / docs:.1f} values a list", flush=True)
 
 
+class _Vect:
+    """A vectoriser whose documents already are their vectors (what EmbeddedVectorizer.transform hands a condition)."""
+
+    def __init__(self, width):
+        self.embedding = np.zeros((1, width), dtype=np.float32)
+
+    def fit(self, raw):
+        return self
+
+    def transform(self, raw):
+        return raw
+
+
+def const_rates(pass_steps=32, rounds=7, warm=2, split=False):
+    """ms/step of fit() behind constant condition blocks (PretrainedWordEmbeddingCondition, 300 columns each) with
+    resident_conditions False - the per-step route: rows picked on the host and uploaded, or index_select on a CUDA tensor -
+    against True - one upload per fit(), one gather launch per step -, same process, same data, one model per run, the two
+    routes taking turns twice (round 1 | round 2).  Models: AdversarialAutoEncoder and DecodingRecommender.  Cells: one block at
+    batch 100, one block at batch 1000, MPD's list (3 blocks + CategoricalCondition(32, sum)) at batch 1000.  Feeds: the host
+    numpy array train() produces, and the CUDA tensor keep_on_device=True keeps.  The median [fastest, slowest] of `rounds`
+    passes of `pass_steps` steps after `warm` passes, every pass closed by a synchronize.
+    split: instead, the AAE's MPD cell (host feed) taken apart - the three blocks without the table, the table alone, the list
+    with the table kept on the per-step padded route under the flag, the whole list, and the whole list with a synchronize
+    after every step (the host cannot enqueue ahead: what a step's host round trip costs when nothing hides it)."""
+    from aaerec.aae import DecodingRecommender
+    passes = warm + rounds
+    big = 1000 * 64
+    Xb = throughput_corpus(big, N, seed=4321)
+    vecs = [rng.standard_normal((big, 300)).astype(np.float32) for _ in range(3)]
+    lists = [[int(a) for a in rng.integers(0, 5000, rng.integers(1, 5))] for _ in range(big)]
+
+    class Done(Exception):
+        pass
+
+    def run(model, batch, n_blocks, with_cat, on_device, flag, cat_resident=True, sync=False):
+        docs = batch * 64
+        items, data = [], []
+        for j in range(n_blocks):
+            items.append((f"title{j}", C.PretrainedWordEmbeddingCondition(_Vect(300), use_cuda=True)))
+            data.append(torch.from_numpy(vecs[j][:docs]).cuda() if on_device else vecs[j][:docs])
+        if with_cat:
+            cat = C.CategoricalCondition(32, use_cuda=True, reduce="sum", vocab_size=5000)
+            data.append(cat.fit_transform(lists[:docs]))
+            if not cat_resident:
+                cat.resident = lambda inputs, device: None        # (the value lists padded on the host every step)
+            items.append(("playlist", cat))
+        conds = C.ConditionList(items)
+        Xc = X if batch == B else Xb
+        times, mark = [], [None, 0]
+
+        def tick():
+            mark[1] += 1
+            if mark[1] % pass_steps == 0:
+                torch.cuda.synchronize()
+                now = time.perf_counter()
+                if mark[0] is not None:
+                    times.append(1e3 * (now - mark[0]) / pass_steps)
+                mark[0] = now
+            if len(times) == passes:
+                raise Done
+        epochs = 1 + (passes + 1) * pass_steps // 64
+        if model == "AAE":
+            m = AdversarialAutoEncoder(n_hidden=h, n_code=c, batch_size=batch, n_epochs=epochs, conditions=conds, verbose=False, seed=1)
+        else:
+            m = DecodingRecommender(conds, n_epochs=epochs, batch_size=batch, n_hidden=h, verbose=False, seed=1)
+        m.resident_conditions = flag
+        step = m._run_step if model == "AAE" else m._step
+
+        def timed(*a, **k):
+            step(*a, **k)
+            if sync:
+                torch.cuda.synchronize()
+            tick()
+        setattr(m, "_run_step" if model == "AAE" else "_step", timed)
+        try:
+            m.fit(Xc, condition_data=data) if model == "AAE" else m.fit(data, Xc)
+        except Done:
+            pass
+        assert len(times) == passes, len(times)
+        t = times[warm:]
+        return float(np.median(t)), f"{np.median(t):.3f} [{min(t):.3f}, {max(t):.3f}]"
+
+    print(f"fit(), N={N} h={h}: median ms/step of {rounds} passes of {pass_steps} steps; resident_conditions False | True, two rounds each")
+    if split:
+        parts = (("3 blocks, no table", 3, False, True, False), ("the table alone", 0, True, True, False),
+                 ("MPD, the table padded per step", 3, True, False, False), ("MPD", 3, True, True, False),
+                 ("MPD, a synchronize after every step", 3, True, True, True))
+        for tag, n_blocks, with_cat, cat_resident, sync in parts:
+            med = {False: [], True: []}
+            for flag in (False, True, False, True):
+                med[flag].append(run("AAE", 1000, n_blocks, with_cat, False, flag, cat_resident, sync)[1])
+            print(f"AAE      {tag:44s} host     {' | '.join(med[False]):>44s} {' | '.join(med[True]):>44s}", flush=True)
+        return
+    print(f"{'model':8s} {'cell':44s} {'feed':8s} {'False':>44s} {'True':>44s} {'False/True':>10s}")
+    cells = (("1 x 300, batch 100", B, 1, False), ("1 x 300, batch 1000", 1000, 1, False),
+             ("MPD: 3 x 300 + Categorical(32, sum), batch 1000", 1000, 3, True))
+    for model in ("AAE", "Decoding"):
+        for tag, batch, n_blocks, with_cat in cells:
+            for on_device in (False, True):
+                med = {False: [], True: []}
+                for flag in (False, True, False, True):
+                    med[flag].append(run(model, batch, n_blocks, with_cat, on_device, flag))
+                ratio = np.mean([v for v, _ in med[False]]) / np.mean([v for v, _ in med[True]])
+                print(f"{model:8s} {tag:44s} {'device' if on_device else 'host':8s} {' | '.join(s for _, s in med[False]):>44s} "
+                      f"{' | '.join(s for _, s in med[True]):>44s} {ratio:10.2f}", flush=True)
+
+
 if __name__ == "__main__":
-    if "ragged" in sys.argv[1:]:
+    if "const" in sys.argv[1:]:
+        const_rates(split="split" in sys.argv[1:])
+    elif "ragged" in sys.argv[1:]:
         a = sys.argv[sys.argv.index("ragged") + 1:]
         ragged_rates(a[0], a[1], pass_steps=int(a[2]) if len(a) > 2 else 64)
     elif "opts" in sys.argv[1:]:
